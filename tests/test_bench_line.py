@@ -93,3 +93,36 @@ def test_sortformer_flops_formula(bench):
     # linear part scales with T, the attention part with T^2
     f1, f2 = bench.sortformer_step_flops(d, 100, 0), bench.sortformer_step_flops(d, 200, 0)
     assert 2.0 < f2 / f1 < 2.2
+
+
+def test_dumped_outputs_are_float_arrays_a_caller_can_read_back(bench, tmp_path):
+    """--dump-outputs: per session the committed words (call, start, end), their text and the decode decisions behind
+    them, float arrays only, named by the session's audio seed."""
+    class Model:
+        decision_log = [[100, [(50257, 3), (1000, 7)]], [150, []], [200, [(2000, 9)]]]
+
+    class Proc:
+        model = Model()
+
+    calls = [(0.1, 0.0, [], 0.5, []), (0.1, 0.0, [1.0], 1.0, [(0.2, 1.0, " hello")]),
+             (0.1, 0.0, [1.4, 1.5], 1.5, [(1.0, 1.4, " wörld"), (1.4, 1.5, "!")])]
+    bench.dump_outputs(str(tmp_path), [3], [Proc()], [calls])
+    assert sorted(os.listdir(tmp_path)) == ["s3_decisions.npy", "s3_text.npy", "s3_words.npy"]
+    import numpy as np
+    words = np.load(tmp_path / "s3_words.npy")
+    text = np.load(tmp_path / "s3_text.npy")
+    dec = np.load(tmp_path / "s3_decisions.npy")
+    assert words.dtype == np.float64 and text.dtype == np.float32 and dec.dtype == np.float64
+    assert words.tolist() == [[1, 0.2, 1.0], [2, 1.0, 1.4], [2, 1.4, 1.5]]
+    assert text.astype(np.uint8).tobytes().decode("utf-8").split("\0")[:-1] == [" hello", " wörld", "!"]
+    assert dec.tolist() == [[0, 100, 50257, 3], [0, 100, 1000, 7], [1, 150, -1, -1], [2, 200, 2000, 9]]
+
+
+def test_plain_run_options(bench, monkeypatch):
+    """--full is off by default and --steps sets the number of timed steps (at least one)."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse_args()
+    assert (args.steps, args.warmup, args.full, args.dump_outputs) == (7, 2, False, "")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()

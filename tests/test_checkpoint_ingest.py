@@ -144,7 +144,7 @@ def _bench_on_checkpoint(path, model_name, seconds, chunks):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     full = os.path.join(tempfile.mkdtemp(prefix="wlk_bench_ckpt_"), "full.json")
     env = {k: v for k, v in os.environ.items() if k not in ("WLK_SYNTHETIC_VOCAB", "WLK_VOCAB_DIR")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--checkpoint", path, "--model", model_name, "--seconds", str(seconds),
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--checkpoint", path, "--model", model_name, "--seconds", str(seconds),
                         "--steps", "1", "--warmup", "1", "--no-diarization", "--cpu-chunks", str(chunks), "--cpu-seconds", "240",
                         "--full-out", full], capture_output=True, text=True, timeout=1500, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

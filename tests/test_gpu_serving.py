@@ -188,7 +188,7 @@ def test_bench_checks_its_own_outputs_against_the_reference():
     """bench.py replays the reference's golden decisions on the sessions it times (1-stream headline + the 8-stream
     leg) and prints parity_checked; nothing it reports may come from unverified outputs."""
     full_path = os.path.join(tempfile.mkdtemp(prefix="wlk_bench_"), "full.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1",
                         "--no-cpu-baseline", "--no-diarization", "--no-large-v3", "--full-out", full_path], capture_output=True,
                        text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -228,6 +228,31 @@ def test_bench_checks_its_own_outputs_against_the_reference():
         json.dump(line, fh)
 
 
+def test_plain_bench_run_times_the_headline_and_dumps_what_it_computed():
+    """A plain run (no --full) prints the contract's line for exactly --steps timed steps and, with --dump-outputs, the
+    last timed step's outputs: the dumped decisions of the seed-0 stream are the reference's golden ones."""
+    tmp = tempfile.mkdtemp(prefix="wlk_bench_")
+    dump = os.path.join(tmp, "out")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", dump], capture_output=True, text=True, timeout=600, cwd=tmp)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["unit"] == "audio_s/s"
+    assert line["ms_per_step"] > 0 and abs(line["value"] - 30.0 / (line["ms_per_step"] / 1e3)) < 0.01 * line["value"]
+    assert line["roofline"] is None and line["parity_checked"] is None and line["full"] is None and "eight_streams" not in line
+    assert sorted(os.listdir(dump)) == ["s0_decisions.npy", "s0_text.npy", "s0_words.npy"]
+    dec = np.load(os.path.join(dump, "s0_decisions.npy"))
+    log = []
+    for i, cml, tok, fr in dec.astype(np.int64).tolist():
+        if not log or log[-1][0] != i:
+            log.append((i, [cml, []]))
+        if tok >= 0:
+            log[-1][1][1].append((tok, fr))
+    res = H.compare_decisions(H.golden_json("stream_bench_base_30s_s0.json"), [e for _, e in log])
+    assert res["mismatch"] is None and res["tie_divergence"] is None and res["identical"] == res["decisions"] > 100, res
+    assert len(np.load(os.path.join(dump, "s0_words.npy"))) > 0
+
+
 def test_bench_multi_rank_code_path_rehearsal():
     """The N > 1 path of bench.py end to end on ONE GPU: `--gpus 2` re-executes itself under torch.distributed.run, both
     ranks share device 0 and talk over gloo (WLK_BENCH_REHEARSAL=1; RCCL refuses two ranks per device).  Exercises the
@@ -236,7 +261,7 @@ def test_bench_multi_rank_code_path_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["WLK_BENCH_REHEARSAL"] = "1"
     tmp = tempfile.mkdtemp(prefix="wlk_bench_")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "0",
                         "--no-cpu-baseline", "--no-large-v3", "--full-out", os.path.join(tmp, "weak.json")], capture_output=True,
                        text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -254,7 +279,7 @@ def test_bench_multi_rank_code_path_rehearsal():
     pc = line["parity_checked"]
     assert pc["sessions"] == 2 + 8 + 8 and pc["mismatches"] == [] and not pc["missing_golden"], pc
     assert pc["identical"] == pc["decisions"] and pc["unchecked_calls"] == 0, pc
-    r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--streams", "8", "--steps", "1",
+    r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--streams", "8", "--steps", "1",
                          "--warmup", "0", "--no-cpu-baseline", "--no-diarization", "--no-eight-streams",
                          "--full-out", os.path.join(tmp, "strong.json")],
                         capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
