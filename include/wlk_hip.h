@@ -264,7 +264,8 @@ int wlk_melspec_destroy(wlk_melspec* m);
  * attention) -> Linear -> 18 post-LN Transformer blocks -> sigmoid speaker head.  NeMo is a third-party
  * dependency that is not in the reference tree: packed tensor names/layout are defined by wlk_sf_tensor_name /
  * wlk_sf_tensor_lookup, the host shim (whisperlivekit_amd/sortformer.py) maps NeMo state-dict names onto them.
- * The streaming speaker-cache / FIFO bookkeeping (SortformerModules.streaming_update_async) is host logic. */
+ * The streaming speaker-cache / FIFO bookkeeping (SortformerModules.streaming_update_async) is host logic, unless the
+ * session is device-resident (wlk_sf_session_*, below). */
 typedef struct wlk_sortformer wlk_sortformer;
 typedef struct wlk_sf_dims {
     int32_t n_mels;        /* 128 */
@@ -306,7 +307,45 @@ int wlk_sf_step_pcm(wlk_sortformer* m, wlk_melspec* mel, const float* pcm_host, 
 int wlk_sf_stats(wlk_sortformer* m, uint64_t* stacked_steps, uint64_t* session_steps, uint64_t* rows);
 /* parity/debug export of the last step (its first session): "fc_out" [T, fc_d_model] (Conformer output), "tf_out" [T, tf_d_model] */
 int wlk_sf_export(wlk_sortformer* m, const char* what, float* host, uint64_t capacity, uint64_t* n_written);
+/* WLK_ERR_STATE (and nothing freed) while sessions of the model are alive */
 int wlk_sf_destroy(wlk_sortformer* m);
+
+/* Device-resident diarizer sessions (opt-in): the streaming state of forward_streaming_step - speaker cache, FIFO, their
+ * activities, the silence profile, the three lengths - and the last keep_feat_rows log-mel rows of the previous chunk live in
+ * device buffers of the session.  A step runs the front end, the network over [spkcache | fifo | chunk] read from those buffers
+ * and the state update (SortformerModules.streaming_update_async / _compress_spkcache, fp32 op for op as the numpy restatement
+ * in whisperlivekit_amd/sortformer.py) in one launch chain; only the chunk's activities come back.  Session steps stack with
+ * host-state steps (wlk_sf_step*) of the same model.  A session is used by one thread at a time: a call while another call of
+ * the same session is in flight returns WLK_ERR_STATE. */
+typedef struct wlk_sf_session wlk_sf_session;
+typedef struct wlk_sf_cache_params {   /* SpkCacheParams (sortformer.py) */
+    int32_t spkcache_len, fifo_len, spkcache_update_period, subsampling_factor, spkcache_sil_frames_per_spk;
+    float pred_score_threshold, scores_boost_latest, sil_threshold, strong_boost_rate, weak_boost_rate, min_pos_scores_rate;
+    int32_t max_index;
+} wlk_sf_cache_params;
+/* host view of a session's state: full buffers (spkcache [spkcache_len][d], spkcache_preds [spkcache_len][n_spk], fifo
+ * [fifo_len][d], fifo_preds [fifo_len][n_spk], mean_sil_emb [d], kept_feats [keep_feat_rows][n_mels]) plus the lengths */
+typedef struct wlk_sf_state {
+    float *spkcache, *spkcache_preds, *fifo, *fifo_preds, *mean_sil_emb, *kept_feats;
+    int32_t spkcache_len, fifo_len, n_sil_frames, n_kept;
+} wlk_sf_state;
+/* everything zeroed (new_state()); WLK_ERR_CAPACITY when the geometry does not fit the state kernels */
+int wlk_sf_session_create(wlk_sortformer* m, const wlk_sf_cache_params* params, int keep_feat_rows, wlk_sf_session** out);
+int wlk_sf_session_destroy(wlk_sf_session* s);
+/* forward_streaming_step with the front end inside: pcm [n_pcm] -> log-mel rows behind the session's kept rows -> network ->
+ * state update; chunk_preds_out receives the chunk's [*n_out][n_spk] activities; the chunk's last keep_feat_rows feature rows
+ * become the kept rows.  left/right offsets in feature frames (converted with subsampling_factor like the host path). */
+int wlk_sf_session_step_pcm(wlk_sf_session* s, wlk_melspec* mel, const float* pcm_host, int n_pcm, int valid_frames,
+                            int left_offset, int right_offset, float* chunk_preds_out, int capacity_rows, int* n_out);
+/* the same with the caller's feature rows [n_feat][n_mels] (forward_streaming_step); the kept rows are left as they are */
+int wlk_sf_session_step(wlk_sf_session* s, const float* feats_host, int n_feat, int left_offset, int right_offset,
+                        float* chunk_preds_out, int capacity_rows, int* n_out);
+/* the state update alone on host-supplied chunk embeddings [Tc][d] and activities [T][n_spk] (T = spkcache_len + fifo_len
+ * + Tc); lc / rc in embedding rows (streaming_update's arguments) */
+int wlk_sf_session_update(wlk_sf_session* s, const float* chunk_embs, int Tc, const float* preds, int T, int lc, int rc,
+                          float* chunk_preds_out, int capacity_rows, int* n_out);
+int wlk_sf_session_get_state(wlk_sf_session* s, wlk_sf_state* st);
+int wlk_sf_session_set_state(wlk_sf_session* s, const wlk_sf_state* st);
 
 /* ---- (f-next, rank 3) Silero VAD gate -------------------------------------------------------------------
  * Replaces the TorchScript model the reference evaluates on the CPU once per 512-sample window

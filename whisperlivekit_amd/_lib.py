@@ -33,6 +33,21 @@ class SfDims(C.Structure):
         ("xscale", C.c_float)]
 
 
+class SfCacheParams(C.Structure):
+    """wlk_sf_cache_params (include/wlk_hip.h): sortformer.SpkCacheParams field by field"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "spkcache_len", "fifo_len", "spkcache_update_period", "subsampling_factor", "spkcache_sil_frames_per_spk")] + [
+        (n, C.c_float) for n in ("pred_score_threshold", "scores_boost_latest", "sil_threshold", "strong_boost_rate",
+                                 "weak_boost_rate", "min_pos_scores_rate")] + [("max_index", C.c_int32)]
+
+
+class SfState(C.Structure):
+    """wlk_sf_state (include/wlk_hip.h): host buffers of a device session's state + its lengths"""
+    _fields_ = [(n, C.POINTER(C.c_float)) for n in (
+        "spkcache", "spkcache_preds", "fifo", "fifo_preds", "mean_sil_emb", "kept_feats")] + [
+        (n, C.c_int32) for n in ("spkcache_len", "fifo_len", "n_sil_frames", "n_kept")]
+
+
 class NllbDims(C.Structure):
     """wlk_nllb_dims (include/wlk_hip.h)"""
     _fields_ = [(n, C.c_int32) for n in (
@@ -158,6 +173,13 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_sf_stats": (cint, [p, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "wlk_sf_export": (cint, [p, C.c_char_p, p, u64, C.POINTER(u64)]),
         "wlk_sf_destroy": (cint, [p]),
+        "wlk_sf_session_create": (cint, [p, C.POINTER(SfCacheParams), cint, C.POINTER(p)]),
+        "wlk_sf_session_destroy": (cint, [p]),
+        "wlk_sf_session_step_pcm": (cint, [p, p, p, cint, cint, cint, cint, p, cint, C.POINTER(cint)]),
+        "wlk_sf_session_step": (cint, [p, p, cint, cint, cint, p, cint, C.POINTER(cint)]),
+        "wlk_sf_session_update": (cint, [p, p, cint, p, cint, cint, cint, p, cint, C.POINTER(cint)]),
+        "wlk_sf_session_get_state": (cint, [p, C.POINTER(SfState)]),
+        "wlk_sf_session_set_state": (cint, [p, C.POINTER(SfState)]),
         "wlk_nllb_arena_floats": (cint, [C.POINTER(NllbDims), C.POINTER(u64)]),
         "wlk_nllb_tensor_lookup": (cint, [C.POINTER(NllbDims), C.c_char_p, C.POINTER(u64), C.POINTER(u64)]),
         "wlk_nllb_tensor_name": (cint, [C.POINTER(NllbDims), cint, C.POINTER(C.c_char_p)]),
@@ -233,6 +255,8 @@ EXPORTED_SYMBOLS = (
     "wlk_prof_end", "wlk_melspec_create", "wlk_melspec_run", "wlk_melspec_destroy",
     "wlk_sf_arena_floats", "wlk_sf_tensor_lookup", "wlk_sf_tensor_name", "wlk_sf_create", "wlk_sf_upload",
     "wlk_sf_finalize", "wlk_sf_step", "wlk_sf_step_pcm", "wlk_sf_stats", "wlk_sf_export", "wlk_sf_destroy",
+    "wlk_sf_session_create", "wlk_sf_session_destroy", "wlk_sf_session_step_pcm", "wlk_sf_session_step",
+    "wlk_sf_session_update", "wlk_sf_session_get_state", "wlk_sf_session_set_state",
     "wlk_vad_weights_floats", "wlk_vad_tensor_lookup", "wlk_vad_tensor_name", "wlk_vad_create", "wlk_vad_destroy",
     "wlk_vad_stream_create", "wlk_vad_stream_reset", "wlk_vad_stream_run", "wlk_vad_stream_state",
     "wlk_vad_stream_destroy",

@@ -532,6 +532,34 @@ void launch_sf_head(const LaunchCtx& ctx, const float* x, const float* w1t, cons
                     const float* b2, float* out, int T, int d, int n_spk);
 void launch_sf_transpose(const LaunchCtx& ctx, const float* src, float* dst, int rows, int cols);
 
+// ---- sortformer_state.hip (device-resident streaming state: FIFO / speaker-cache update, compression) --------------
+constexpr int kSfStateMaxKeys = 4096;  // (cache rows + popped rows + silence slots) x n_spk the compression kernel holds in LDS
+constexpr int kSfStateMaxRows = 1024;  // FIFO + chunk rows the update kernel flags in LDS
+struct SfStateParams {                 // SpkCacheParams, with the derived integers / fp32 constants computed on the host
+    int S = 0, F = 0, sil_per_spk = 0, max_index = 0, d = 0, n_spk = 0;
+    int strong_k = 0, weak_k = 0, min_pos = 0;
+    float thr = 0.f, boost_latest = 0.f, sil_thr = 0.f, log_half = 0.f, strong_boost = 0.f, weak_boost = 0.f;
+};
+struct SfStateJob {                    // one device session's update: inputs (current buffers) -> outputs (the other buffers)
+    SfStateParams p;
+    const float* chunk = nullptr;      // [Tc][d] the step's pre-encode embeddings
+    const float* preds = nullptr;      // [s_len + f_len + Tc][n_spk] the network's activities
+    const float *cache_in = nullptr, *cache_p_in = nullptr, *fifo_in = nullptr, *mean_in = nullptr;
+    const int* lens_in = nullptr;      // [3] spkcache_len, fifo_len, n_sil_frames
+    float *cache_out = nullptr, *cache_p_out = nullptr, *fifo_out = nullptr, *fifo_p_out = nullptr, *mean_out = nullptr;
+    int* lens_out = nullptr;
+    float *up = nullptr, *up_p = nullptr;   // [N][d] / [N][n_spk]: the cache before compression (compressing sessions only)
+    int s_len = 0, f_len = 0, lc = 0, chunk_len = 0, pop = 0, N = 0, compress = 0;
+};
+struct SfStateBatch {
+    int n = 0;
+    SfStateJob job[kSfMaxSegments];
+};
+// one workgroup per job: FIFO append / pop, silence profile, FIFO shift, cache append (into up / cache_out)
+void launch_sf_state_update(const LaunchCtx& ctx, const SfStateBatch& b);
+// one workgroup per job with compress != 0: SortformerModules._compress_spkcache over up / up_p -> cache_out / cache_p_out
+void launch_sf_state_compress(const LaunchCtx& ctx, const SfStateBatch& b);
+
 // ---- select.hip -----------------------------------------------------------------------------
 // adjustments (may be n_adj = 0) are applied to the logits in place before the reduction
 void launch_logsoftmax_topk(const LaunchCtx& ctx, float* logits, int n_vocab, int n_rows, int k,

@@ -1,5 +1,7 @@
 // C ABI of the streaming Sortformer diarizer network (include/wlk_hip.h, "a12 network"): packed weight arena,
 // workspace, and the launch sequence of one streaming step.  Kernels: sortformer.hip, gemm_f32.hip, layernorm.hip.
+#include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
@@ -26,6 +28,8 @@ static int sf_guarded(F&& f) {
         return f();
     } catch (const HipError& e) {
         return sf_fail(WLK_ERR_HIP, e.what());
+    } catch (const std::length_error& e) {
+        return sf_fail(WLK_ERR_CAPACITY, e.what());
     } catch (const std::invalid_argument& e) {
         return sf_fail(WLK_ERR_ARG, e.what());
     } catch (const std::exception& e) {
@@ -121,6 +125,12 @@ struct SfTfLayer {
 
 using namespace wlk;
 
+// The state-update plan of one device-session step: every length is a function of the lengths before it and of the chunk
+// geometry (never of data), so the host knows the row counts of the chain without reading anything back
+struct SfPlan {
+    int s_len = 0, f_len = 0, Tc = 0, lc = 0, max_chunk = 0, chunk_len = 0, pop = 0, N = 0, compress = 0, s_after = 0, f_after = 0;
+};
+
 // One caller's step on its way through the model: inputs and outputs in PINNED host memory (the caller copies its numpy
 // rows in and out itself, in parallel with other callers; the lane's copies are then truly asynchronous).
 struct SfRequest {
@@ -133,6 +143,9 @@ struct SfRequest {
     float* chunk = nullptr;     // [max chunk rows][d]      (out)
     float* preds = nullptr;     // [max_frames][n_spk]      (out)
     int n_feat = 0, n_ctx = 0, Tc = 0, T = 0;
+    wlk_sf_session* sess = nullptr;   // device-resident session: context / kept rows / state update on the device
+    SfPlan plan;
+    int keep_new = 0;                 // kept feature rows the step leaves in the session (PCM steps)
     bool in_use = false, queued = false, done = false;
     int rc = WLK_OK;
     std::string err;
@@ -181,6 +194,7 @@ struct wlk_sortformer {
     float* head_w1t = nullptr;            // head.h.w transposed ([in][out]) at finalize: coalesced rows for sf_head_kernel
     std::vector<float*> owned;
     std::vector<float*> pinned;
+    std::atomic<int> live_sessions{0};   // wlk_sf_session_create / _destroy; wlk_sf_destroy refuses while > 0
     const float* P(const std::string& n) const {
         auto it = index.find(n);
         if (it == index.end()) throw std::invalid_argument("unknown packed tensor " + n);
@@ -197,7 +211,85 @@ struct wlk_sortformer {
     }
 };
 
+// A device-resident session: its streaming state in two buffer sets (ping-pong: a step reads set `cur` and writes set
+// 1 - cur, so a failed step leaves the state it started from), lengths mirrored on the host (SfPlan).
+struct wlk_sf_session {
+    wlk_sortformer* m = nullptr;
+    wlk_sf_cache_params cp{};
+    wlk::SfStateParams sp;
+    int keep = 0, N_cap = 0, Tc_cap = 0;
+    float *cache[2] = {}, *cache_p[2] = {}, *fifo[2] = {}, *fifo_p[2] = {}, *mean[2] = {}, *kept[2] = {};
+    int* lens[2] = {};
+    float *up = nullptr, *up_p = nullptr;          // the cache before compression, [N_cap][d] / [N_cap][n_spk]
+    float *in_chunk = nullptr, *in_preds = nullptr;   // wlk_sf_session_update's inputs
+    hipStream_t stream = nullptr;                  // wlk_sf_session_update / get / set
+    int cur = 0, kcur = 0;                         // current state set / kept-rows set
+    int s_len = 0, f_len = 0, n_kept = 0;          // host mirror of the lengths
+    std::atomic<bool> busy{false};
+    std::vector<void*> owned;
+    ~wlk_sf_session() {
+        (void)hipSetDevice(m->device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (void* p : owned)
+            if (p) (void)hipFree(p);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
 namespace wlk {
+// one call of a session at a time
+struct SfSessionHold {
+    wlk_sf_session* s;
+    bool ok;
+    explicit SfSessionHold(wlk_sf_session* s_) : s(s_) {
+        bool expect = false;
+        ok = s->busy.compare_exchange_strong(expect, true);
+    }
+    ~SfSessionHold() {
+        if (ok) s->busy.store(false);
+    }
+};
+
+static SfPlan sf_plan(const wlk_sf_session* s, int Tc, int lc, int rc) {
+    // streaming_update (sortformer.py): the chunk's own rows join the FIFO, an overflowing FIFO pops to the cache
+    const wlk_sf_cache_params& c = s->cp;
+    SfPlan p;
+    p.s_len = s->s_len; p.f_len = s->f_len; p.Tc = Tc; p.lc = lc;
+    p.max_chunk = Tc - lc - rc;
+    p.chunk_len = std::max(0, std::min(Tc - lc, p.max_chunk));
+    const int new_f = p.f_len + p.chunk_len;
+    if (new_f > c.fifo_len) p.pop = std::min(std::max(c.spkcache_update_period, p.max_chunk - c.fifo_len + p.f_len), new_f);
+    p.N = c.spkcache_len + std::min(std::max(c.spkcache_update_period, p.max_chunk), p.max_chunk + c.fifo_len);
+    p.compress = p.s_len + p.pop > c.spkcache_len ? 1 : 0;
+    p.s_after = p.compress ? c.spkcache_len : p.s_len + p.pop;
+    p.f_after = new_f - p.pop;
+    return p;
+}
+
+static void sf_check_plan(const wlk_sf_session* s, const SfPlan& p) {
+    if (p.lc < 0 || p.max_chunk < 0) throw std::invalid_argument("chunk offsets leave no chunk rows");
+    if (p.Tc > s->Tc_cap || p.N > s->N_cap) throw std::length_error("chunk longer than the session's buffers");
+}
+
+static SfStateJob sf_job(wlk_sf_session* s, const SfPlan& p, const float* chunk, const float* preds) {
+    SfStateJob j;
+    j.p = s->sp;
+    j.chunk = chunk; j.preds = preds;
+    const int a = s->cur, b = 1 - s->cur;
+    j.cache_in = s->cache[a]; j.cache_p_in = s->cache_p[a]; j.fifo_in = s->fifo[a]; j.mean_in = s->mean[a]; j.lens_in = s->lens[a];
+    j.cache_out = s->cache[b]; j.cache_p_out = s->cache_p[b]; j.fifo_out = s->fifo[b]; j.fifo_p_out = s->fifo_p[b];
+    j.mean_out = s->mean[b]; j.lens_out = s->lens[b];
+    j.up = s->up; j.up_p = s->up_p;
+    j.s_len = p.s_len; j.f_len = p.f_len; j.lc = p.lc; j.chunk_len = p.chunk_len; j.pop = p.pop; j.N = p.N; j.compress = p.compress;
+    return j;
+}
+
+static void sf_commit(wlk_sf_session* s, const SfPlan& p) {
+    s->cur = 1 - s->cur;
+    s->s_len = p.s_after;
+    s->f_len = p.f_after;
+}
+
 static float* sf_alloc(wlk_sortformer* m, size_t n) {
     float* p = nullptr;
     WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(float)));
@@ -327,8 +419,17 @@ static void sf_run_batch(wlk_sortformer* m, wlk_sortformer::Lane* w_, const std:
         SfRequest& q = m->slots[batch[b]];
         rows.start[b] = r0; rows.len[b] = q.T;
         chunks.start[b] = c0; chunks.len[b] = q.Tc;
-        if (q.n_ctx > 0)
+        wlk_sf_session* ss = q.sess;
+        if (ss) {        // the session's own rows, device to device: [spkcache[:s_len] | fifo[:f_len]]
+            if (q.plan.s_len > 0)
+                WLK_HIP(hipMemcpyAsync(w_->ctxbuf + (size_t)r0 * d, ss->cache[ss->cur], (size_t)q.plan.s_len * d * sizeof(float),
+                                       hipMemcpyDeviceToDevice, w_->stream));
+            if (q.plan.f_len > 0)
+                WLK_HIP(hipMemcpyAsync(w_->ctxbuf + (size_t)(r0 + q.plan.s_len) * d, ss->fifo[ss->cur], (size_t)q.plan.f_len * d * sizeof(float),
+                                       hipMemcpyDeviceToDevice, w_->stream));
+        } else if (q.n_ctx > 0) {
             WLK_HIP(hipMemcpyAsync(w_->ctxbuf + (size_t)r0 * d, q.ctx, (size_t)q.n_ctx * d * sizeof(float), hipMemcpyHostToDevice, w_->stream));
+        }
         if (q.n_feat > 0) {
             float* frows = w_->feats + (size_t)f0 * D.n_mels;
             if (q.n_pcm > 0) {
@@ -340,7 +441,10 @@ static void sf_run_batch(wlk_sortformer* m, wlk_sortformer::Lane* w_, const std:
                 const wlk_melspec* me = q.mel;
                 const int n_new = q.n_feat - q.n_prev;
                 float* au = w_->audio + (size_t)b * m->max_pcm;
-                if (q.n_prev > 0)
+                if (q.n_prev > 0 && ss)
+                    WLK_HIP(hipMemcpyAsync(frows, ss->kept[ss->kcur], (size_t)q.n_prev * D.n_mels * sizeof(float), hipMemcpyDeviceToDevice,
+                                           w_->stream));
+                else if (q.n_prev > 0)
                     WLK_HIP(hipMemcpyAsync(frows, q.feats, (size_t)q.n_prev * D.n_mels * sizeof(float), hipMemcpyHostToDevice, w_->stream));
                 WLK_HIP(hipMemcpyAsync(au, q.pcm, (size_t)q.n_pcm * sizeof(float), hipMemcpyHostToDevice, w_->stream));
                 MelSpecArgs a;
@@ -351,8 +455,14 @@ static void sf_run_batch(wlk_sortformer* m, wlk_sortformer::Lane* w_, const std:
                 if (q.zero_from < n_new)
                     WLK_HIP(hipMemsetAsync(frows + (size_t)(q.n_prev + q.zero_from) * D.n_mels, 0,
                                            (size_t)(n_new - q.zero_from) * D.n_mels * sizeof(float), w_->stream));
-                WLK_HIP(hipMemcpyAsync(q.feats + (size_t)q.n_prev * D.n_mels, frows + (size_t)q.n_prev * D.n_mels,
-                                       (size_t)n_new * D.n_mels * sizeof(float), hipMemcpyDeviceToHost, w_->stream));
+                if (ss) {    // the chunk's last rows stay on the device for the session's next chunk
+                    if (q.keep_new > 0)
+                        WLK_HIP(hipMemcpyAsync(ss->kept[1 - ss->kcur], frows + (size_t)(q.n_feat - q.keep_new) * D.n_mels,
+                                               (size_t)q.keep_new * D.n_mels * sizeof(float), hipMemcpyDeviceToDevice, w_->stream));
+                } else {
+                    WLK_HIP(hipMemcpyAsync(q.feats + (size_t)q.n_prev * D.n_mels, frows + (size_t)q.n_prev * D.n_mels,
+                                           (size_t)n_new * D.n_mels * sizeof(float), hipMemcpyDeviceToHost, w_->stream));
+                }
             } else {
                 WLK_HIP(hipMemcpyAsync(frows, q.feats, (size_t)q.n_feat * D.n_mels * sizeof(float), hipMemcpyHostToDevice, w_->stream));
             }
@@ -379,7 +489,7 @@ static void sf_run_batch(wlk_sortformer* m, wlk_sortformer::Lane* w_, const std:
         sf_linear(c, w_->ca, (long)F3 * C, m->P("pre.out.w"), m->P("pre.out.b"), w_->chunk_tmp, d, c0, d, F3 * C, 0, nullptr, 0, "sf_pre_out");
         for (int b = 0; b < nb; ++b) {
             SfRequest& q = m->slots[batch[b]];
-            if (q.Tc > 0)
+            if (q.Tc > 0 && !q.sess)
                 WLK_HIP(hipMemcpyAsync(q.chunk, w_->chunk_tmp + (size_t)chunks.start[b] * d, (size_t)q.Tc * d * sizeof(float),
                                        hipMemcpyDeviceToHost, w_->stream));
         }
@@ -387,10 +497,26 @@ static void sf_run_batch(wlk_sortformer* m, wlk_sortformer::Lane* w_, const std:
     launch_sf_assemble(c, w_->ctxbuf, w_->chunk_tmp, w_->x, rows, chunks, d, D.xscale);
     sf_network(m, w_, c, rows);
     w_->last_T = rows.len[0];
+    // the device sessions' state updates: one update launch and (if any cache overflowed) one compression launch per batch
+    SfStateBatch sb;
     for (int b = 0; b < nb; ++b) {
         SfRequest& q = m->slots[batch[b]];
-        WLK_HIP(hipMemcpyAsync(q.preds, w_->preds + (size_t)rows.start[b] * D.n_spk, (size_t)q.T * D.n_spk * sizeof(float),
-                               hipMemcpyDeviceToHost, w_->stream));
+        if (q.sess)
+            sb.job[sb.n++] = sf_job(q.sess, q.plan, w_->chunk_tmp + (size_t)chunks.start[b] * d, w_->preds + (size_t)rows.start[b] * D.n_spk);
+    }
+    launch_sf_state_update(c, sb);
+    launch_sf_state_compress(c, sb);
+    for (int b = 0; b < nb; ++b) {
+        SfRequest& q = m->slots[batch[b]];
+        if (q.sess) {    // only the chunk's own activities come back
+            const SfPlan& p = q.plan;
+            if (p.chunk_len > 0)
+                WLK_HIP(hipMemcpyAsync(q.preds, w_->preds + (size_t)(rows.start[b] + p.s_len + p.f_len + p.lc) * D.n_spk,
+                                       (size_t)p.chunk_len * D.n_spk * sizeof(float), hipMemcpyDeviceToHost, w_->stream));
+        } else {
+            WLK_HIP(hipMemcpyAsync(q.preds, w_->preds + (size_t)rows.start[b] * D.n_spk, (size_t)q.T * D.n_spk * sizeof(float),
+                                   hipMemcpyDeviceToHost, w_->stream));
+        }
     }
     WLK_HIP(hipStreamSynchronize(w_->stream));
 }
@@ -583,13 +709,20 @@ struct SfPcmIn {                 // wlk_sf_step_pcm's front-end arguments (mel =
     int n_pcm = 0, n_prev = 0, zero_from = 0;
     float* feats_out = nullptr;
 };
+struct SfSessIn {                // a device session's step: the session, its offsets (embedding rows), the chunk activities out
+    wlk_sf_session* s = nullptr;
+    int lc = 0, rc = 0;
+    float* out = nullptr;
+    int cap = 0;
+    int* n_out = nullptr;
+};
 }  // namespace wlk
 static int sf_step_impl(wlk_sortformer* m, const float* feats_host, int n_feat, const wlk::SfPcmIn& pin, const float* ctx_embs_host,
                         int n_ctx, float* chunk_embs_host, int chunk_capacity_rows, int* n_chunk, float* preds_host,
-                        int preds_capacity_rows) {
-    if (!m || !preds_host) return sf_fail(WLK_ERR_ARG, "NULL argument");
+                        int preds_capacity_rows, const wlk::SfSessIn* si = nullptr) {
+    if (!m || (!preds_host && !si)) return sf_fail(WLK_ERR_ARG, "NULL argument");
     if (!m->finalized) return sf_fail(WLK_ERR_STATE, "wlk_sf_finalize has not been called");
-    if (n_feat < 0 || n_ctx < 0 || (n_feat > 0 && (!feats_host || !chunk_embs_host)) || (n_ctx > 0 && !ctx_embs_host))
+    if (n_feat < 0 || n_ctx < 0 || (n_feat > 0 && (!feats_host || (!chunk_embs_host && !si))) || (n_ctx > 0 && !ctx_embs_host && !si))
         return sf_fail(WLK_ERR_ARG, "bad step arguments");
     if (n_feat > m->D.max_feat_frames) return sf_fail(WLK_ERR_CAPACITY, "feature chunk longer than max_feat_frames");
     return sf_guarded([&]() {
@@ -597,11 +730,19 @@ static int sf_step_impl(wlk_sortformer* m, const float* feats_host, int n_feat, 
         const int d = D.fc_d_model;
         int Tc = 0;
         if (n_feat > 0) Tc = sf_sub_len(sf_sub_len(sf_sub_len(n_feat)));
+        SfPlan plan;
+        if (si) {        // the context is the session's own [spkcache | fifo] (lengths mirrored on the host)
+            plan = sf_plan(si->s, Tc, si->lc, si->rc);
+            sf_check_plan(si->s, plan);
+            n_ctx = plan.s_len + plan.f_len;
+            if (si->n_out) *si->n_out = plan.max_chunk;
+            if (plan.max_chunk > si->cap) return sf_fail(WLK_ERR_CAPACITY, "chunk activity buffer too small");
+        }
         const int T = n_ctx + Tc;
         if (n_chunk) *n_chunk = Tc;
         if (T < 1) return sf_fail(WLK_ERR_ARG, "empty step");
         if (T > D.max_frames) return sf_fail(WLK_ERR_CAPACITY, "sequence longer than max_frames");
-        if (Tc > chunk_capacity_rows || T > preds_capacity_rows) return sf_fail(WLK_ERR_CAPACITY, "output buffer too small");
+        if (!si && (Tc > chunk_capacity_rows || T > preds_capacity_rows)) return sf_fail(WLK_ERR_CAPACITY, "output buffer too small");
         // 1. a request slot; the inputs go into its pinned blocks (this thread's own memcpy, outside the lock)
         int me = -1;
         {
@@ -615,13 +756,16 @@ static int sf_step_impl(wlk_sortformer* m, const float* feats_host, int n_feat, 
         mine.n_feat = n_feat; mine.n_ctx = n_ctx; mine.Tc = Tc; mine.T = T;
         mine.mel = pin.mel; mine.n_pcm = pin.mel ? pin.n_pcm : 0; mine.n_prev = pin.n_prev; mine.zero_from = pin.zero_from;
         mine.done = false; mine.rc = WLK_OK; mine.err.clear();
+        mine.sess = si ? si->s : nullptr;
+        mine.plan = plan;
+        mine.keep_new = si && pin.mel ? std::min(si->s->keep, n_feat - pin.n_prev) : 0;
         if (pin.mel) {
-            if (pin.n_prev > 0) memcpy(mine.feats, feats_host, (size_t)pin.n_prev * D.n_mels * sizeof(float));
+            if (pin.n_prev > 0 && !si) memcpy(mine.feats, feats_host, (size_t)pin.n_prev * D.n_mels * sizeof(float));
             memcpy(mine.pcm, pin.pcm, (size_t)pin.n_pcm * sizeof(float));
         } else if (n_feat > 0) {
             memcpy(mine.feats, feats_host, (size_t)n_feat * D.n_mels * sizeof(float));
         }
-        if (n_ctx > 0) memcpy(mine.ctx, ctx_embs_host, (size_t)n_ctx * d * sizeof(float));
+        if (n_ctx > 0 && !si) memcpy(mine.ctx, ctx_embs_host, (size_t)n_ctx * d * sizeof(float));
         // 2. queue; whoever finds a free lane while requests wait runs the oldest ones as ONE stacked step (its own may or
         //    may not be among them) - no dispatcher thread, no gather window
         std::unique_lock<std::mutex> lock(m->mu);
@@ -656,8 +800,14 @@ static int sf_step_impl(wlk_sortformer* m, const float* feats_host, int n_feat, 
             } catch (const std::invalid_argument& e) {
                 rc = WLK_ERR_ARG; err = e.what();
                 (void)hipStreamSynchronize(lane->stream);
+            } catch (const std::length_error& e) {
+                rc = WLK_ERR_CAPACITY; err = e.what();
+                (void)hipStreamSynchronize(lane->stream);
             } catch (const std::exception& e) {
                 rc = WLK_ERR_STATE; err = e.what();
+                (void)hipStreamSynchronize(lane->stream);
+            } catch (...) {          // whatever ends the chain, the lane is released and the batch marked done below
+                rc = WLK_ERR_STATE; err = "sortformer: unknown failure in a stacked step";
                 (void)hipStreamSynchronize(lane->stream);
             }
             lock.lock();
@@ -677,10 +827,24 @@ static int sf_step_impl(wlk_sortformer* m, const float* feats_host, int n_feat, 
         // 3. results out of the pinned blocks, slot back
         const int rc = mine.rc;
         const std::string err = mine.err;
-        if (rc == WLK_OK) {
+        if (rc == WLK_OK && si) {
+            const size_t got = (size_t)plan.chunk_len * D.n_spk;
+            if (got) memcpy(si->out, mine.preds, got * sizeof(float));
+            if (plan.max_chunk > plan.chunk_len)
+                memset(si->out + got, 0, (size_t)(plan.max_chunk - plan.chunk_len) * D.n_spk * sizeof(float));
+            sf_commit(si->s, plan);
+            if (pin.mel) {
+                si->s->kcur = 1 - si->s->kcur;
+                si->s->n_kept = mine.keep_new;
+            }
+        } else if (rc == WLK_OK) {
             if (Tc > 0) memcpy(chunk_embs_host, mine.chunk, (size_t)Tc * d * sizeof(float));
             memcpy(preds_host, mine.preds, (size_t)T * D.n_spk * sizeof(float));
             if (pin.mel) memcpy(pin.feats_out, mine.feats + (size_t)pin.n_prev * D.n_mels, (size_t)(n_feat - pin.n_prev) * D.n_mels * sizeof(float));
+        }
+        {
+            std::lock_guard<std::mutex> g(m->mu);
+            mine.sess = nullptr;
         }
         {
             std::lock_guard<std::mutex> g(m->mu);
@@ -754,8 +918,225 @@ int wlk_sf_export(wlk_sortformer* m, const char* what, float* host, uint64_t cap
 }
 
 int wlk_sf_destroy(wlk_sortformer* m) {
+    if (m && m->live_sessions.load() > 0) return sf_fail(WLK_ERR_STATE, "the model still has live sessions (wlk_sf_session_destroy first)");
     delete m;          // ~wlk_sortformer frees the arena, the lanes' buffers and streams, the pinned request blocks
     return WLK_OK;
+}
+
+// ---- device-resident sessions ------------------------------------------------------------------------------------
+int wlk_sf_session_create(wlk_sortformer* m, const wlk_sf_cache_params* params, int keep_feat_rows, wlk_sf_session** out) {
+    if (!m || !params || !out) return sf_fail(WLK_ERR_ARG, "NULL argument");
+    const wlk_sf_dims& D = m->D;
+    const wlk_sf_cache_params& c = *params;
+    if (c.spkcache_len < 1 || c.fifo_len < 0 || c.spkcache_update_period < 0 || c.subsampling_factor < 1 ||
+        c.spkcache_sil_frames_per_spk < 0 || c.max_index < 0 || keep_feat_rows < 0)
+        return sf_fail(WLK_ERR_ARG, "bad speaker-cache parameters");
+    const int per_spk = c.spkcache_len / D.n_spk - c.spkcache_sil_frames_per_spk;
+    if (per_spk < 0) return sf_fail(WLK_ERR_ARG, "spkcache_len leaves no frames per speaker");
+    // the longest chunk a step can bring (the stem of max_feat_frames rows) bounds the FIFO rows and the compression keys
+    const int Tc_cap = sf_sub_len(sf_sub_len(sf_sub_len(D.max_feat_frames)));
+    const int N_cap = c.spkcache_len + std::min(std::max(c.spkcache_update_period, Tc_cap), Tc_cap + c.fifo_len);
+    if (c.spkcache_len > kSfMaxFrames || c.fifo_len + Tc_cap > kSfStateMaxRows ||
+        (int64_t)(N_cap + c.spkcache_sil_frames_per_spk) * D.n_spk > kSfStateMaxKeys || keep_feat_rows > D.max_feat_frames)
+        return sf_fail(WLK_ERR_CAPACITY, "speaker-cache geometry does not fit the state kernels' LDS budget");
+    return sf_guarded([&]() {
+        WLK_HIP(hipSetDevice(m->device));
+        auto s = std::make_unique<wlk_sf_session>();
+        s->m = m;
+        s->cp = c;
+        s->keep = keep_feat_rows;
+        s->Tc_cap = Tc_cap;
+        s->N_cap = N_cap;
+        SfStateParams& p = s->sp;
+        p.S = c.spkcache_len; p.F = c.fifo_len; p.sil_per_spk = c.spkcache_sil_frames_per_spk; p.max_index = c.max_index;
+        p.d = D.fc_d_model; p.n_spk = D.n_spk;
+        // compress_spkcache's integers and fp32 constants, computed as the host does (Python floats, then np.float32)
+        p.strong_k = (int)std::floor(per_spk * (double)c.strong_boost_rate);
+        p.weak_k = (int)std::floor(per_spk * (double)c.weak_boost_rate);
+        p.min_pos = (int)std::floor(per_spk * (double)c.min_pos_scores_rate);
+        p.thr = c.pred_score_threshold; p.boost_latest = c.scores_boost_latest; p.sil_thr = c.sil_threshold;
+        p.log_half = (float)std::log(0.5);
+        p.strong_boost = (float)(2.0 * std::log(0.5));
+        p.weak_boost = (float)(1.0 * std::log(0.5));
+        const size_t d = D.fc_d_model, ns = D.n_spk, S = c.spkcache_len, F = c.fifo_len;
+        auto alloc = [&](size_t bytes) {
+            void* q = nullptr;
+            WLK_HIP(hipMalloc(&q, std::max<size_t>(bytes, 16)));
+            s->owned.push_back(q);
+            return q;
+        };
+        for (int b = 0; b < 2; ++b) {
+            s->cache[b] = (float*)alloc(S * d * sizeof(float));
+            s->cache_p[b] = (float*)alloc(S * ns * sizeof(float));
+            s->fifo[b] = (float*)alloc(F * d * sizeof(float));
+            s->fifo_p[b] = (float*)alloc(F * ns * sizeof(float));
+            s->mean[b] = (float*)alloc(d * sizeof(float));
+            s->kept[b] = (float*)alloc((size_t)keep_feat_rows * D.n_mels * sizeof(float));
+            s->lens[b] = (int*)alloc(3 * sizeof(int));
+        }
+        s->up = (float*)alloc((size_t)N_cap * d * sizeof(float));
+        s->up_p = (float*)alloc((size_t)N_cap * ns * sizeof(float));
+        s->in_chunk = (float*)alloc((size_t)Tc_cap * d * sizeof(float));
+        s->in_preds = (float*)alloc((size_t)D.max_frames * ns * sizeof(float));
+        WLK_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+        for (int b = 0; b < 2; ++b) {
+            WLK_HIP(hipMemsetAsync(s->cache[b], 0, S * d * sizeof(float), s->stream));
+            WLK_HIP(hipMemsetAsync(s->cache_p[b], 0, S * ns * sizeof(float), s->stream));
+            WLK_HIP(hipMemsetAsync(s->fifo[b], 0, F * d * sizeof(float), s->stream));
+            WLK_HIP(hipMemsetAsync(s->fifo_p[b], 0, F * ns * sizeof(float), s->stream));
+            WLK_HIP(hipMemsetAsync(s->mean[b], 0, d * sizeof(float), s->stream));
+            WLK_HIP(hipMemsetAsync(s->kept[b], 0, (size_t)keep_feat_rows * D.n_mels * sizeof(float), s->stream));
+            WLK_HIP(hipMemsetAsync(s->lens[b], 0, 3 * sizeof(int), s->stream));
+        }
+        WLK_HIP(hipStreamSynchronize(s->stream));
+        m->live_sessions.fetch_add(1);
+        *out = s.release();
+        return WLK_OK;
+    });
+}
+
+int wlk_sf_session_destroy(wlk_sf_session* s) {
+    if (!s) return WLK_OK;
+    SfSessionHold hold(s);
+    if (!hold.ok) return sf_fail(WLK_ERR_STATE, "the session has a call in flight");
+    wlk_sortformer* m = s->m;
+    hold.ok = false;          // the session goes away with the hold
+    delete s;
+    m->live_sessions.fetch_sub(1);
+    return WLK_OK;
+}
+
+static int sf_session_offsets(const wlk_sf_session* s, int left_offset, int right_offset, int* lc, int* rc) {
+    // forward_streaming_step: round(left / sf) (half to even, like Python's round) and ceil(right / sf)
+    const double sf = s->cp.subsampling_factor;
+    *lc = (int)std::nearbyint(left_offset / sf);
+    *rc = (int)std::ceil(right_offset / sf);
+    return WLK_OK;
+}
+
+int wlk_sf_session_step_pcm(wlk_sf_session* s, wlk_melspec* mel, const float* pcm_host, int n_pcm, int valid_frames,
+                            int left_offset, int right_offset, float* chunk_preds_out, int capacity_rows, int* n_out) {
+    if (!s || !mel || !pcm_host || !chunk_preds_out) return sf_fail(WLK_ERR_ARG, "NULL argument");
+    wlk_sortformer* m = s->m;
+    if (n_pcm < 1 || n_pcm > m->max_pcm || n_pcm > mel->cap) return sf_fail(WLK_ERR_CAPACITY, "audio chunk does not fit the step's buffer");
+    if (mel->n_mels != m->D.n_mels || mel->device != m->device) return sf_fail(WLK_ERR_ARG, "the extractor does not match the model (mel bins / device)");
+    SfSessionHold hold(s);
+    if (!hold.ok) return sf_fail(WLK_ERR_STATE, "the session has a call in flight");
+    const int n_new = n_pcm / mel->hop + 1;
+    if (s->n_kept + n_new > m->D.max_feat_frames) return sf_fail(WLK_ERR_CAPACITY, "feature chunk longer than max_feat_frames");
+    wlk::SfPcmIn pin;
+    pin.mel = mel; pin.pcm = pcm_host; pin.n_pcm = n_pcm; pin.n_prev = s->n_kept;
+    pin.zero_from = valid_frames < 0 ? n_new : std::min(valid_frames, n_new);
+    wlk::SfSessIn si;
+    si.s = s; si.out = chunk_preds_out; si.cap = capacity_rows; si.n_out = n_out;
+    sf_session_offsets(s, left_offset, right_offset, &si.lc, &si.rc);
+    return sf_step_impl(m, pcm_host, s->n_kept + n_new, pin, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, &si);
+}
+
+int wlk_sf_session_step(wlk_sf_session* s, const float* feats_host, int n_feat, int left_offset, int right_offset,
+                        float* chunk_preds_out, int capacity_rows, int* n_out) {
+    if (!s || !chunk_preds_out) return sf_fail(WLK_ERR_ARG, "NULL argument");
+    SfSessionHold hold(s);
+    if (!hold.ok) return sf_fail(WLK_ERR_STATE, "the session has a call in flight");
+    wlk::SfSessIn si;
+    si.s = s; si.out = chunk_preds_out; si.cap = capacity_rows; si.n_out = n_out;
+    sf_session_offsets(s, left_offset, right_offset, &si.lc, &si.rc);
+    return sf_step_impl(s->m, feats_host, n_feat, wlk::SfPcmIn{}, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, &si);
+}
+
+int wlk_sf_session_update(wlk_sf_session* s, const float* chunk_embs, int Tc, const float* preds, int T, int lc, int rc,
+                          float* chunk_preds_out, int capacity_rows, int* n_out) {
+    if (!s || !chunk_preds_out || (Tc > 0 && !chunk_embs) || !preds) return sf_fail(WLK_ERR_ARG, "NULL argument");
+    SfSessionHold hold(s);
+    if (!hold.ok) return sf_fail(WLK_ERR_STATE, "the session has a call in flight");
+    return sf_guarded([&]() {
+        const wlk_sf_dims& D = s->m->D;
+        if (Tc < 0) return sf_fail(WLK_ERR_ARG, "negative chunk length");
+        const SfPlan plan = sf_plan(s, Tc, lc, rc);
+        sf_check_plan(s, plan);
+        if (n_out) *n_out = plan.max_chunk;
+        if (T != plan.s_len + plan.f_len + Tc) return sf_fail(WLK_ERR_ARG, "activity rows != spkcache_len + fifo_len + Tc");
+        if (T > D.max_frames) return sf_fail(WLK_ERR_CAPACITY, "sequence longer than max_frames");
+        if (plan.max_chunk > capacity_rows) return sf_fail(WLK_ERR_CAPACITY, "chunk activity buffer too small");
+        WLK_HIP(hipSetDevice(s->m->device));
+        const size_t d = D.fc_d_model, ns = D.n_spk;
+        if (Tc > 0) WLK_HIP(hipMemcpyAsync(s->in_chunk, chunk_embs, (size_t)Tc * d * sizeof(float), hipMemcpyHostToDevice, s->stream));
+        WLK_HIP(hipMemcpyAsync(s->in_preds, preds, (size_t)T * ns * sizeof(float), hipMemcpyHostToDevice, s->stream));
+        SfStateBatch sb;
+        sb.job[sb.n++] = sf_job(s, plan, s->in_chunk, s->in_preds);
+        LaunchCtx c{s->stream, nullptr};
+        launch_sf_state_update(c, sb);
+        launch_sf_state_compress(c, sb);
+        if (plan.chunk_len > 0)
+            WLK_HIP(hipMemcpyAsync(chunk_preds_out, s->in_preds + (size_t)(plan.s_len + plan.f_len + plan.lc) * ns,
+                                   (size_t)plan.chunk_len * ns * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        WLK_HIP(hipStreamSynchronize(s->stream));
+        if (plan.max_chunk > plan.chunk_len)
+            memset(chunk_preds_out + (size_t)plan.chunk_len * ns, 0, (size_t)(plan.max_chunk - plan.chunk_len) * ns * sizeof(float));
+        sf_commit(s, plan);
+        return WLK_OK;
+    });
+}
+
+int wlk_sf_session_get_state(wlk_sf_session* s, wlk_sf_state* st) {
+    if (!s || !st) return sf_fail(WLK_ERR_ARG, "NULL argument");
+    SfSessionHold hold(s);
+    if (!hold.ok) return sf_fail(WLK_ERR_STATE, "the session has a call in flight");
+    return sf_guarded([&]() {
+        const wlk_sf_dims& D = s->m->D;
+        const size_t d = D.fc_d_model, ns = D.n_spk, S = s->cp.spkcache_len, F = s->cp.fifo_len;
+        const int a = s->cur;
+        int lens[3] = {0, 0, 0};
+        WLK_HIP(hipSetDevice(s->m->device));
+        auto get = [&](void* dst, const void* src, size_t bytes) {
+            if (dst && bytes) WLK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s->stream));
+        };
+        get(st->spkcache, s->cache[a], S * d * sizeof(float));
+        get(st->spkcache_preds, s->cache_p[a], S * ns * sizeof(float));
+        get(st->fifo, s->fifo[a], F * d * sizeof(float));
+        get(st->fifo_preds, s->fifo_p[a], F * ns * sizeof(float));
+        get(st->mean_sil_emb, s->mean[a], d * sizeof(float));
+        get(st->kept_feats, s->kept[s->kcur], (size_t)s->n_kept * D.n_mels * sizeof(float));
+        get(lens, s->lens[a], sizeof(lens));
+        WLK_HIP(hipStreamSynchronize(s->stream));
+        if (lens[0] != s->s_len || lens[1] != s->f_len)
+            return sf_fail(WLK_ERR_STATE, "device lengths disagree with the host mirror");
+        st->spkcache_len = lens[0]; st->fifo_len = lens[1]; st->n_sil_frames = lens[2]; st->n_kept = s->n_kept;
+        return WLK_OK;
+    });
+}
+
+int wlk_sf_session_set_state(wlk_sf_session* s, const wlk_sf_state* st) {
+    if (!s || !st || !st->spkcache || !st->spkcache_preds || !st->fifo || !st->fifo_preds || !st->mean_sil_emb ||
+        (st->n_kept > 0 && !st->kept_feats))
+        return sf_fail(WLK_ERR_ARG, "NULL argument");
+    if (st->spkcache_len < 0 || st->spkcache_len > s->cp.spkcache_len || st->fifo_len < 0 || st->fifo_len > s->cp.fifo_len ||
+        st->n_sil_frames < 0 || st->n_kept < 0 || st->n_kept > s->keep)
+        return sf_fail(WLK_ERR_ARG, "state lengths out of range");
+    SfSessionHold hold(s);
+    if (!hold.ok) return sf_fail(WLK_ERR_STATE, "the session has a call in flight");
+    return sf_guarded([&]() {
+        const wlk_sf_dims& D = s->m->D;
+        const size_t d = D.fc_d_model, ns = D.n_spk, S = s->cp.spkcache_len, F = s->cp.fifo_len;
+        const int a = s->cur;
+        const int lens[3] = {st->spkcache_len, st->fifo_len, st->n_sil_frames};
+        WLK_HIP(hipSetDevice(s->m->device));
+        auto put = [&](void* dst, const void* src, size_t bytes) {
+            if (bytes) WLK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s->stream));
+        };
+        put(s->cache[a], st->spkcache, S * d * sizeof(float));
+        put(s->cache_p[a], st->spkcache_preds, S * ns * sizeof(float));
+        put(s->fifo[a], st->fifo, F * d * sizeof(float));
+        put(s->fifo_p[a], st->fifo_preds, F * ns * sizeof(float));
+        put(s->mean[a], st->mean_sil_emb, d * sizeof(float));
+        put(s->kept[s->kcur], st->kept_feats, (size_t)st->n_kept * D.n_mels * sizeof(float));
+        put(s->lens[a], lens, sizeof(lens));
+        WLK_HIP(hipStreamSynchronize(s->stream));
+        s->s_len = st->spkcache_len;
+        s->f_len = st->fifo_len;
+        s->n_kept = st->n_kept;
+        return WLK_OK;
+    });
 }
 
 }  // extern "C"

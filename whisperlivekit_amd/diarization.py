@@ -184,7 +184,11 @@ class HipSortformerDiarizationOnline:
         self.buffer_audio = self.buffer_audio[threshold:]
         left_offset = 8 if self._chunk_index > 0 else 0                  # :290-291
         fused = getattr(self.model, "forward_streaming_step_pcm", None)
-        if fused is not None:
+        if getattr(self.streaming_state, "on_device", False):
+            # device-resident state (sortformer.DeviceSortformerState): the audio goes in, the chunk's activities come out;
+            # the kept log-mel rows, the speaker cache and the FIFO never leave the GPU
+            chunk_preds = self.model.forward_streaming_step_session_pcm(audio, self.streaming_state, left_offset, 8)
+        elif fused is not None:
             # the HIP model takes the audio itself: log-mel, stem and network in ONE launch chain / ONE synchronisation
             # (same kernels, same values as the three calls below)
             prev = self._previous_chunk_features[-99:] if self._previous_chunk_features is not None else None   # :279-283
@@ -241,3 +245,5 @@ class HipSortformerDiarizationOnline:
     def close(self):
         with self.segment_lock:
             self.diarization_segments.clear()
+        if getattr(self.streaming_state, "on_device", False):
+            self.streaming_state.close()

@@ -19,8 +19,10 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
+import weakref
 from dataclasses import dataclass, field
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 
@@ -367,6 +369,116 @@ def streaming_update(sp: SpkCacheParams, st: SortformerState, chunk: np.ndarray,
     return chunk_preds
 
 
+# ---- device-resident state ------------------------------------------------------------------------------------
+def resolve_device_state(device_state: Optional[bool]) -> bool:
+    """``HipSortformerModel(device_state=...)``: an explicit bool wins; ``None`` reads ``WLK_SF_DEVICE_STATE`` (default off)."""
+    if device_state is not None:
+        return bool(device_state)
+    return os.environ.get("WLK_SF_DEVICE_STATE", "0").strip().lower() in ("1", "true", "yes", "on")
+
+
+def cache_params_struct(cp: SpkCacheParams) -> "_lib.SfCacheParams":
+    return _lib.SfCacheParams(cp.spkcache_len, cp.fifo_len, cp.spkcache_update_period, cp.subsampling_factor,
+                              cp.spkcache_sil_frames_per_spk, cp.pred_score_threshold, cp.scores_boost_latest,
+                              cp.sil_threshold, cp.strong_boost_rate, cp.weak_boost_rate, cp.min_pos_scores_rate,
+                              cp.max_index)
+
+
+def _fptr(a: Optional[np.ndarray]):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+class DeviceSortformerState:
+    """A diarizer session whose streaming state - speaker cache, FIFO, their activities, the silence profile, the lengths -
+    and the last ``keep_feat_rows`` log-mel rows of its previous chunk live on the GPU (``wlk_sf_session_*``).  A step then
+    uploads only the new audio and reads back only the chunk's activities; the update rule is ``streaming_update`` computed
+    by the state kernels (csrc/sortformer_state.hip), fp32 op for op.  One thread at a time per state."""
+
+    on_device = True
+
+    def __init__(self, model: "HipSortformerModel", keep_feat_rows: int = 99):
+        self.model, self.lib = model, model.lib
+        self.keep_feat_rows = keep_feat_rows
+        self._h = C.c_void_p()
+        cp = cache_params_struct(model.cache)
+        _lib.check(self.lib.wlk_sf_session_create(model._h, C.byref(cp), keep_feat_rows, C.byref(self._h)))
+
+    def _lengths(self):
+        st = _lib.SfState()
+        _lib.check(self.lib.wlk_sf_session_get_state(self._handle(), C.byref(st)))
+        return st.spkcache_len, st.fifo_len, st.n_sil_frames, st.n_kept
+
+    def _handle(self):
+        if not self._h:
+            raise _lib.WlkError("the device state is closed")
+        return self._h
+
+    @property
+    def spkcache_len(self) -> int:
+        return self._lengths()[0]
+
+    @property
+    def fifo_len(self) -> int:
+        return self._lengths()[1]
+
+    @property
+    def n_sil_frames(self) -> int:
+        return self._lengths()[2]
+
+    def to_host(self) -> Tuple[SortformerState, np.ndarray]:
+        """-> (the state as a host ``SortformerState``, the kept feature rows [n_kept, n_mels])."""
+        m, c = self.model, self.model.cache
+        d, ns = m.dims.fc_d_model, m.n_spk
+        bufs = dict(spkcache=np.zeros((c.spkcache_len, d), np.float32), spkcache_preds=np.zeros((c.spkcache_len, ns), np.float32),
+                    fifo=np.zeros((c.fifo_len, d), np.float32), fifo_preds=np.zeros((c.fifo_len, ns), np.float32),
+                    mean_sil_emb=np.zeros(d, np.float32))
+        kept = np.zeros((self.keep_feat_rows, m.dims.n_mels), np.float32)
+        st = _lib.SfState(*[_fptr(bufs[k]) for k in ("spkcache", "spkcache_preds", "fifo", "fifo_preds", "mean_sil_emb")],
+                          _fptr(kept))
+        _lib.check(self.lib.wlk_sf_session_get_state(self._handle(), C.byref(st)))
+        return (SortformerState(**bufs, spkcache_len=st.spkcache_len, fifo_len=st.fifo_len, n_sil_frames=st.n_sil_frames),
+                kept[: st.n_kept].copy())
+
+    def load(self, state: SortformerState, kept_rows: Optional[np.ndarray] = None) -> None:
+        """Replace the device state by a host ``SortformerState`` (and the kept feature rows, if given)."""
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+        bufs = [f(state.spkcache), f(state.spkcache_preds), f(state.fifo), f(state.fifo_preds), f(state.mean_sil_emb)]
+        c, m = self.model.cache, self.model
+        shapes = [(c.spkcache_len, m.dims.fc_d_model), (c.spkcache_len, m.n_spk), (c.fifo_len, m.dims.fc_d_model),
+                  (c.fifo_len, m.n_spk), (m.dims.fc_d_model,)]
+        if [b.shape for b in bufs] != shapes:
+            raise ValueError(f"state buffers {[b.shape for b in bufs]} do not match the session's {shapes}")
+        kept = None if kept_rows is None or len(kept_rows) == 0 else f(kept_rows)
+        if kept is not None and kept.shape[1:] != (m.dims.n_mels,):
+            raise ValueError("kept feature rows must be [n, n_mels]")
+        st = _lib.SfState(*[_fptr(b) for b in bufs], _fptr(kept), state.spkcache_len, state.fifo_len, state.n_sil_frames,
+                          0 if kept is None else kept.shape[0])
+        _lib.check(self.lib.wlk_sf_session_set_state(self._handle(), C.byref(st)))
+
+    def update(self, chunk: np.ndarray, preds: np.ndarray, lc: int, rc: int) -> np.ndarray:
+        """``streaming_update`` on the device with host-supplied embeddings / activities (the state kernels alone)."""
+        e = np.ascontiguousarray(chunk, np.float32)
+        p = np.ascontiguousarray(preds, np.float32)
+        out = np.empty((max(e.shape[0], 1), self.model.n_spk), np.float32)
+        n = C.c_int()
+        _lib.check(self.lib.wlk_sf_session_update(self._handle(), e.ctypes.data_as(C.c_void_p), e.shape[0],
+                                                  p.ctypes.data_as(C.c_void_p), p.shape[0], lc, rc,
+                                                  out.ctypes.data_as(C.c_void_p), out.shape[0], C.byref(n)))
+        return out[: n.value].copy()
+
+    def close(self) -> None:
+        if self._h:
+            _lib.check(self.lib.wlk_sf_session_destroy(self._h))
+            self._h = C.c_void_p()
+            self.model._states.discard(self)
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---- the model handle --------------------------------------------------------------------------------------
 class HipSortformerModel:
     """Shared (per GPU) Sortformer network + feature extractor; implements ``diarization.SortformerBackend``.
@@ -376,7 +488,11 @@ class HipSortformerModel:
 
     def __init__(self, dims: SortformerDims, state_dict: Dict[str, np.ndarray], device: int = 0,
                  params: SortformerStreamingParams = SortformerStreamingParams(),
-                 cache: SpkCacheParams = SpkCacheParams(), max_feat_frames: int = 256):
+                 cache: SpkCacheParams = SpkCacheParams(), max_feat_frames: int = 256,
+                 device_state: Optional[bool] = None):
+        self._h = C.c_void_p()
+        self._states: "weakref.WeakSet[DeviceSortformerState]" = weakref.WeakSet()
+        self.device_state = resolve_device_state(device_state)
         self.lib = _lib.load()
         if _lib.device_count() <= 0:
             raise _lib.WlkError("no HIP device visible: the Sortformer HIP backend has no CPU fallback")
@@ -389,7 +505,6 @@ class HipSortformerModel:
                                dims.conv_kernel, dims.tf_d_model, dims.tf_layers, dims.tf_heads, dims.tf_inner,
                                dims.n_spk, self.max_frames, max_feat_frames,
                                math.sqrt(dims.fc_d_model) if dims.xscaling else 1.0)
-        self._h = C.c_void_p()
         _lib.check(self.lib.wlk_sf_create(C.byref(self._cd), device, C.byref(self._h)))
         packed = pack_sortformer_state_dict(dims, state_dict, self.max_frames)
         for name in packed_sortformer_names(self._cd):
@@ -415,7 +530,18 @@ class HipSortformerModel:
             self._mel = HipMelSpectrogram(device=self.device, n_mels=self.dims.n_mels)
         return self._mel(pcm)
 
-    def new_state(self) -> SortformerState:
+    def new_device_state(self, keep_feat_rows: int = 99) -> DeviceSortformerState:
+        """A device-resident session (always available; no host fallback).  ``keep_feat_rows``: log-mel rows of the previous
+        chunk prepended to the next one (sortformer_backend.py:279-285 keeps 99)."""
+        st = DeviceSortformerState(self, keep_feat_rows)
+        self._states.add(st)
+        return st
+
+    def new_state(self):
+        """A host ``SortformerState``, or a ``DeviceSortformerState`` when the model was built with device_state on
+        (``WLK_SF_DEVICE_STATE=1``): callers that only pass the state back to this model need no change."""
+        if self.device_state:
+            return self.new_device_state()
         d, c = self.dims.fc_d_model, self.cache
         return SortformerState(np.zeros((c.spkcache_len, d), np.float32), np.zeros((c.spkcache_len, self.n_spk), np.float32),
                                np.zeros((c.fifo_len, d), np.float32), np.zeros((c.fifo_len, self.n_spk), np.float32),
@@ -472,10 +598,44 @@ class HipSortformerModel:
         sf = self.cache.subsampling_factor
         return streaming_update(self.cache, state, chunk, preds, round(left_offset / sf), math.ceil(right_offset / sf)), feats
 
-    def forward_streaming_step(self, features: np.ndarray, state: SortformerState, left_offset: int,
-                               right_offset: int) -> np.ndarray:
+    def _own(self, state: DeviceSortformerState) -> DeviceSortformerState:
+        if state.model is not self:
+            raise _lib.WlkError("the device state belongs to another model")
+        return state
+
+    def _ensure_mel(self) -> HipMelSpectrogram:
+        if self._mel is None:
+            self._mel = HipMelSpectrogram(device=self.device, n_mels=self.dims.n_mels)
+        return self._mel
+
+    def forward_streaming_step_session_pcm(self, pcm: np.ndarray, state: DeviceSortformerState, left_offset: int,
+                                           right_offset: int, mel: Optional[HipMelSpectrogram] = None) -> np.ndarray:
+        """``forward_streaming_step_pcm`` for a device state: the audio goes in, the chunk's activities come out; the
+        log-mel rows kept for the next chunk, the context and the state update stay on the device (one launch chain)."""
+        st = self._own(state)
+        mel = mel if mel is not None else self._ensure_mel()
+        a = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        cap = (st.keep_feat_rows + a.shape[0] // mel.hop + 1) // 8 + 2
+        out = np.empty((cap, self.n_spk), np.float32)
+        n = C.c_int()
+        valid = -1 if mel.seq_len_plus_one else a.shape[0] // mel.hop
+        _lib.check(self.lib.wlk_sf_session_step_pcm(st._handle(), mel._h, a.ctypes.data_as(C.c_void_p), a.shape[0], valid,
+                                                    left_offset, right_offset, out.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+        return out[: n.value].copy()
+
+    def forward_streaming_step(self, features: np.ndarray, state, left_offset: int, right_offset: int) -> np.ndarray:
         """SortformerEncLabelModel.forward_streaming_step for one stream: pre-encode the chunk, run the network over
-        [spkcache | fifo | chunk], update ``state`` in place, return the chunk's activities."""
+        [spkcache | fifo | chunk], update ``state`` in place, return the chunk's activities.  A ``DeviceSortformerState``
+        is updated on the device (the features are the caller's; its kept rows are left as they are)."""
+        if isinstance(state, DeviceSortformerState):
+            st = self._own(state)
+            f = np.ascontiguousarray(features, np.float32)
+            cap = f.shape[0] // 8 + 2
+            out = np.empty((cap, self.n_spk), np.float32)
+            n = C.c_int()
+            _lib.check(self.lib.wlk_sf_session_step(st._handle(), f.ctypes.data_as(C.c_void_p), f.shape[0], left_offset,
+                                                    right_offset, out.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+            return out[: n.value].copy()
         ctx = np.concatenate([state.spkcache[: state.spkcache_len], state.fifo[: state.fifo_len]], axis=0)
         chunk, preds = self.step(features, ctx if ctx.shape[0] else None)
         sf = self.cache.subsampling_factor
@@ -496,11 +656,13 @@ class HipSortformerModel:
         return buf.reshape(-1)[: n.value].reshape(-1, width).copy()
 
     def close(self):
+        for st in list(self._states):     # device states still open: their buffers go before the model's
+            st.close()
         if self._mel is not None:
             self._mel.close()
             self._mel = None
         if self._h:
-            self.lib.wlk_sf_destroy(self._h)
+            _lib.check(self.lib.wlk_sf_destroy(self._h))
             self._h = C.c_void_p()
 
     def __del__(self):  # pragma: no cover
