@@ -427,6 +427,36 @@ int wlk_nllb_topk(wlk_nllb_session* s, int32_t k, float* logprobs, int32_t* ids)
 int wlk_nllb_export(wlk_nllb_session* s, const char* what, float* host, uint64_t capacity, uint64_t* n_written);
 int wlk_nllb_sync(wlk_nllb_session* s);
 
+/* ---- NLLB: up to 8 DIFFERENT sentences per launch chain (csrc/nllb_batch.hip) ---------------------------------------
+ * A session above holds ONE sentence (its rows are hypotheses of it).  A batch holds `n_slots` (1..8) slots, each one
+ * sentence in flight with its own encoder output, cross K/V, self-attention cache, source length and target length; the
+ * stacked work buffers, the row table, the stream and the step graphs belong to the batch.  Greedy decoding of several
+ * sentences shares every weight pass: whisperlivekit_amd.nllb.generate_batch.  One caller at a time per batch.  Like
+ * sessions, batches are destroyed before their model. */
+typedef struct wlk_nllb_batch wlk_nllb_batch;
+int wlk_nllb_batch_create(wlk_nllb* m, int n_slots, wlk_nllb_batch** out);
+int wlk_nllb_batch_destroy(wlk_nllb_batch* b);
+/* Stacked ragged encode of n sentences into the n different slots named: sentence i is src_ids[src_offsets[i] ..
+ * src_offsets[i + 1]) (host int64, unpadded, 1..max_src ids each; src_offsets[0] = 0).  One launch chain over all
+ * sum(S_i) rows; attention never crosses a sentence.  Each slot's target length returns to 0.  Slots not named keep
+ * their state - they may be in the middle of a decode. */
+int wlk_nllb_batch_encode(wlk_nllb_batch* b, const int32_t* slots, const int64_t* src_ids, const int32_t* src_offsets, int32_t n);
+/* One decoder step over n_rows (slot, token) pairs - at most one row per slot, any subset, any order - as ONE graph
+ * replay, with the read-out: row r feeds tokens[r] at its slot's own position against its slot's own caches and source
+ * length, and receives the k (<= 8) best log-probabilities / ids, descending: [n_rows][k].  The first step of a slot
+ * after its encode feeds the decoder start token at position 0.  Synchronous. */
+int wlk_nllb_batch_step(wlk_nllb_batch* b, const int32_t* slots, const int64_t* tokens, int32_t n_rows, int32_t k, float* logprobs,
+                        int32_t* ids);
+/* the slot's sentence is done: the slot must be encoded again before its next step */
+int wlk_nllb_batch_release(wlk_nllb_batch* b, int32_t slot);
+/* parity exports of one slot: "enc" [src_len][d_model], "logits" [vocab] of the slot's row in the latest step */
+int wlk_nllb_batch_export(wlk_nllb_batch* b, int32_t slot, const char* what, float* host, uint64_t capacity, uint64_t* n_written);
+/* diagnostics: the ragged cross-attention kernel alone - queries q_host [n_rows][d_model] (pre-scaled) against decoder
+ * layer `layer`'s cross K/V of the encoded slots named, out_host [n_rows][d_model] */
+int wlk_nllb_batch_cross_attention(wlk_nllb_batch* b, const int32_t* slots, int32_t n_rows, int32_t layer, const float* q_host,
+                                   float* out_host);
+int wlk_nllb_batch_sync(wlk_nllb_batch* b);
+
 /* ---- word-timestamp alignment ------------------------------------------------------------------
  * Dynamic time warping of a [n_rows tokens, n_cols frames] fp32 cost matrix on `device`: replaces `dtw_cpu`
  * (whisperlivekit/whisper/timing.py:82-105; CUDA counterpart `dtw_cuda` :108-138) under `find_alignment` (:163-243).

@@ -196,6 +196,14 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_nllb_topk": (cint, [p, i32, p, p]),
         "wlk_nllb_export": (cint, [p, C.c_char_p, p, u64, C.POINTER(u64)]),
         "wlk_nllb_sync": (cint, [p]),
+        "wlk_nllb_batch_create": (cint, [p, cint, C.POINTER(p)]),
+        "wlk_nllb_batch_destroy": (cint, [p]),
+        "wlk_nllb_batch_encode": (cint, [p, p, p, p, i32]),
+        "wlk_nllb_batch_step": (cint, [p, p, p, i32, i32, p, p]),
+        "wlk_nllb_batch_release": (cint, [p, i32]),
+        "wlk_nllb_batch_export": (cint, [p, i32, C.c_char_p, p, u64, C.POINTER(u64)]),
+        "wlk_nllb_batch_cross_attention": (cint, [p, p, i32, i32, p, p]),
+        "wlk_nllb_batch_sync": (cint, [p]),
         "wlk_vad_weights_floats": (cint, [C.POINTER(u64)]),
         "wlk_vad_tensor_lookup": (cint, [C.c_char_p, C.POINTER(u64), C.POINTER(u64)]),
         "wlk_vad_tensor_name": (cint, [cint, C.POINTER(C.c_char_p)]),
@@ -264,6 +272,8 @@ EXPORTED_SYMBOLS = (
     "wlk_nllb_arena_floats", "wlk_nllb_tensor_lookup", "wlk_nllb_tensor_name", "wlk_nllb_create", "wlk_nllb_upload",
     "wlk_nllb_finalize", "wlk_nllb_destroy", "wlk_nllb_session_create", "wlk_nllb_session_destroy", "wlk_nllb_encode",
     "wlk_nllb_decode", "wlk_nllb_step", "wlk_nllb_kv_reorder", "wlk_nllb_topk", "wlk_nllb_export", "wlk_nllb_sync",
+    "wlk_nllb_batch_create", "wlk_nllb_batch_destroy", "wlk_nllb_batch_encode", "wlk_nllb_batch_step", "wlk_nllb_batch_release",
+    "wlk_nllb_batch_export", "wlk_nllb_batch_cross_attention", "wlk_nllb_batch_sync",
     "wlk_diag_last_error", "wlk_diag_linear", "wlk_diag_linear_time", "wlk_diag_linear_ln", "wlk_diag_layernorm",
     "wlk_diag_encoder_attention", "wlk_diag_encoder_attention_time", "wlk_diag_wave_ops", "wlk_diag_env_refresh",
     "wlk_diag_linear_x3", "wlk_diag_linear_x3_time", "wlk_diag_layernorm_x3",

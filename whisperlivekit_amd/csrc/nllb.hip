@@ -23,30 +23,9 @@
 
 #include "../../include/wlk_hip.h"
 #include "common.h"
+#include "nllb_internal.h"
 
 namespace wlk {
-
-static int nl_fail(int code, const std::string& msg) {
-    set_last_error(msg);
-    return code;
-}
-template <typename F>
-static int nl_guarded(F&& f) {
-    try {
-        return f();
-    } catch (const HipError& e) {
-        return nl_fail(WLK_ERR_HIP, e.what());
-    } catch (const std::invalid_argument& e) {
-        return nl_fail(WLK_ERR_ARG, e.what());
-    } catch (const std::exception& e) {
-        return nl_fail(WLK_ERR_STATE, e.what());
-    }
-}
-
-struct NlSlot {
-    std::string name;
-    uint64_t offset, numel;
-};
 
 static std::vector<NlSlot> nl_layout(const wlk_nllb_dims& D, uint64_t* total) {
     std::vector<NlSlot> v;
@@ -94,11 +73,6 @@ static int nl_check_dims(const wlk_nllb_dims* d) {
     return WLK_OK;
 }
 
-struct NlLayer {
-    const float *ln1w, *ln1b, *qkvw, *qkvb, *outw, *outb, *lnxw, *lnxb, *xqw, *xqb, *xkvw, *xkvb, *xoutw, *xoutb, *ln2w, *ln2b,
-        *fc1w, *fc1b, *fc2w, *fc2b;
-};
-
 // x[r][:] = emb[tokens[r]][:] * scale + pos[pos0 + *offset + (r % n_tok)][:]
 __global__ __launch_bounds__(256) void nllb_embed_kernel(const int* __restrict__ tokens, const float* __restrict__ emb,
                                                          const float* __restrict__ pos, float scale, int pos0,
@@ -127,27 +101,6 @@ __global__ __launch_bounds__(256) void nllb_embed_step_kernel(const int* __restr
 }  // namespace wlk
 
 using namespace wlk;
-
-struct wlk_nllb {
-    wlk_nllb_dims D{};
-    int device = 0;
-    float* arena = nullptr;
-    uint64_t arena_floats = 0;
-    std::vector<NlSlot> layout;
-    std::map<std::string, const NlSlot*> index;
-    bool finalized = false;
-    std::vector<NlLayer> enc, dec;
-    const float *emb = nullptr, *pos = nullptr, *enc_lnw = nullptr, *enc_lnb = nullptr, *dec_lnw = nullptr, *dec_lnb = nullptr;
-    const float* P(const std::string& n) const {
-        auto it = index.find(n);
-        if (it == index.end()) throw std::invalid_argument("unknown packed tensor " + n);
-        return arena + it->second->offset;
-    }
-    ~wlk_nllb() {
-        (void)hipSetDevice(device);
-        if (arena) (void)hipFree(arena);
-    }
-};
 
 struct wlk_nllb_session {
     wlk_nllb* m = nullptr;
@@ -202,20 +155,6 @@ struct wlk_nllb_session {
 };
 
 namespace wlk {
-
-static void nl_linear(const LaunchCtx& c, const float* A, long lda, const float* W, const float* b, float* C, long ldc, int M,
-                      int N, int K, int flags, const float* R, long ldr, const char* tag, float scale = 1.f, int scale_cols = 0) {
-    GemmArgs g;
-    g.A = A; g.lda = lda; g.W = W; g.bias = b; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-    g.flags = flags; g.R = R; g.ldr = ldr; g.scale = scale; g.scale_cols = scale_cols;
-    launch_linear(c, g, tag);
-}
-
-static void nl_ffn(const LaunchCtx& c, const NlLayer& L, float* x, float* h, float* wide, int R, int d, int f) {
-    launch_layernorm(c, x, d, L.ln2w, L.ln2b, h, d, R, d, "nllb_ln2");
-    nl_linear(c, h, d, L.fc1w, L.fc1b, wide, f, R, f, d, kGemmRelu, nullptr, 0, "nllb_fc1");
-    nl_linear(c, wide, f, L.fc2w, L.fc2b, x, d, R, d, f, kGemmResidual, x, d, "nllb_fc2");
-}
 
 static void nl_encode(wlk_nllb_session* s, int S) {
     wlk_nllb* m = s->m;
@@ -430,7 +369,7 @@ int wlk_nllb_finalize(wlk_nllb* m) {
 }
 
 int wlk_nllb_destroy(wlk_nllb* m) {
-    delete m;        // sessions of the model must be destroyed first (they hold pointers into its arena)
+    delete m;        // sessions and batches (nllb_batch.hip) of the model must be destroyed first (they hold pointers into its arena)
     return WLK_OK;
 }
 

@@ -1,0 +1,590 @@
+// NLLB-200 / M2M-100: up to 8 DIFFERENT sentences in one launch chain (config 5 runs 8 translation sessions; a single-token
+// step streams the decoder's layer weights and the tied vocabulary matrix once per call, so 8 sentences stepped one after
+// another stream them 8 times).  nllb.hip's session holds one sentence - its rows are hypotheses of that sentence and all
+// read one cross K/V and one source length.  Here a batch owns `n_slots` SLOTS, each one sentence in flight with
+//
+//   enc_out   [max_src][d]                      cross_kv  [max_src][dec_layers][k | v]   (the session's layout)
+//   kcache / vcache  [dec_layers][max_tgt][d]    src_len, self_len
+//
+// and the batch owns the stacked work buffers, the row table, the stream and the step graphs.
+//
+//   encode(slots, ids, offsets)  the named slots' sentences concatenated: ONE embedding launch (positions restart inside
+//                                every sentence), LayerNorm / GEMM / FFN once over all sum(S_i) rows, self-attention per
+//                                segment (launch_sf_attention's n_seg: no score crosses a sentence), cross K/V projected
+//                                over all rows and copied into each slot's own buffer.  Slots not named are untouched -
+//                                they may be in the middle of a decode; that is what lets a new sentence take a freed slot.
+//   step((slot, token) x R)      one decoder pass over R rows, any subset of the slots in any order: nl_decode's fused
+//                                branch (LayerNorm-fused weight-streaming GEMVs, the cache append riding in the qkv GEMV
+//                                through GemmArgs::kv_rows, launch_decoder_self_attention_rows) with every per-row scalar
+//                                (token, position, caches, cross K/V, SOURCE LENGTH) in a row table.  The host writes the
+//                                table into a host-coherent block; the chain's first kernel reads it over the bus and
+//                                leaves a device copy for the kernels behind it; the top-k kernel writes its results into
+//                                host-coherent memory.  The chain is one graph per row count - and because no launch
+//                                carries a length or an offset by value, a recording serves every later mix of sentences
+//                                (the session's step graph carries the source length and is re-recorded per length:
+//                                wlk_nllb_session::step_exec_src).
+//
+// Two kernels are new: the row-table embedding and the RAGGED cross-attention (every row its own key count, 1..512, read
+// from the table).  The row table is common.h's StepRow - the type the GEMV's cache append and the self-attention
+// launcher already index - with `content_len` holding the row's source length (its meaning for Whisper rows as well: the
+// number of valid encoder positions).  fp32 throughout.
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/wlk_hip.h"
+#include "common.h"
+#include "nllb_internal.h"
+#include "wave_ops.h"
+
+namespace wlk {
+
+constexpr int kNlBatchMaxRows = 8;         // rows of a stacked step = the weight-streaming GEMV's limit (gemv_applicable)
+constexpr int kNlCrossMaxT = 512;          // == kSfMaxFrames, the bound nl_check_dims puts on max_src
+static_assert(kNlCrossMaxT == kSfMaxFrames, "the encoder's attention and the ragged cross-attention share the source bound");
+static_assert(kNlBatchMaxRows == kSfMaxSegments, "a stacked encode is one attention segment per slot");
+static_assert(sizeof(StepRow) % 16 == 0, "the row table is copied in 4-byte words, rows stay 16-byte aligned");
+
+struct NlSegTable {                         // by-value table of a stacked encode (never replayed from a graph)
+    int n = 0;
+    int start[kNlBatchMaxRows] = {0};       // first stacked row of segment s
+};
+
+// stacked ragged encode: x[r][:] = emb[tokens[r]][:] * scale + pos[pos0 + (r - start of r's sentence)][:]
+__global__ __launch_bounds__(256) void nllb_embed_segments_kernel(const int* __restrict__ tokens, const float* __restrict__ emb,
+                                                                  const float* __restrict__ pos, float scale, int pos0,
+                                                                  NlSegTable sg, int d, float* __restrict__ x) {
+    const int r = blockIdx.x;
+    int first = 0;
+#pragma unroll
+    for (int s = 1; s < kNlBatchMaxRows; ++s) first = (s < sg.n && r >= sg.start[s]) ? sg.start[s] : first;
+    const float4* e = reinterpret_cast<const float4*>(emb + (long)tokens[r] * d);
+    const float4* p = reinterpret_cast<const float4*>(pos + (long)(pos0 + r - first) * d);
+    float4* o = reinterpret_cast<float4*>(x + (long)r * d);
+    for (int c = threadIdx.x; c < d / 4; c += 256) {
+        const float4 ev = e[c], pv = p[c];
+        o[c] = make_float4(ev.x * scale + pv.x, ev.y * scale + pv.y, ev.z * scale + pv.z, ev.w * scale + pv.w);
+    }
+}
+
+// First kernel of a stacked step: workgroup r pulls row r of the table out of the host-coherent block (one uncached
+// 4-byte read per lane, all in flight together), leaves it in the device copy for the kernels behind this one, and
+// writes x[r][:] = emb[token_r][:] * scale + pos[pos0 + offset_r][:].
+__global__ __launch_bounds__(256) void nllb_embed_rows_step_kernel(const StepRow* __restrict__ host_rows,
+                                                                   StepRow* __restrict__ dev_rows, const float* __restrict__ emb,
+                                                                   const float* __restrict__ pos, float scale, int pos0, int d,
+                                                                   float* __restrict__ x) {
+    constexpr int kRowWords = sizeof(StepRow) / 4;
+    __shared__ __attribute__((aligned(16))) unsigned mine[kRowWords];
+    const int tid = threadIdx.x, row = blockIdx.x;
+    if (tid < kRowWords) {
+        const unsigned w = __hip_atomic_load(reinterpret_cast<const unsigned*>(host_rows + row) + tid, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_SYSTEM);
+        mine[tid] = w;
+        reinterpret_cast<unsigned*>(dev_rows + row)[tid] = w;
+    }
+    __syncthreads();
+    const StepRow* sr = reinterpret_cast<const StepRow*>(mine);
+    const float4* e = reinterpret_cast<const float4*>(emb + (long)sr->token * d);
+    const float4* p = reinterpret_cast<const float4*>(pos + (long)(pos0 + sr->offset) * d);
+    float4* o = reinterpret_cast<float4*>(x + (long)row * d);
+    for (int c = tid; c < d / 4; c += 256) {
+        const float4 ev = e[c], pv = p[c];
+        o[c] = make_float4(ev.x * scale + pv.x, ev.y * scale + pv.y, ev.z * scale + pv.z, ev.w * scale + pv.w);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Ragged decoder cross-attention of a stacked step: one 256-thread workgroup per (row, head); row r attends to the
+// T_r = rows[r].content_len keys / values of ITS sentence (rows[r].cross_kv + kv_off, key stride ldkv), 1 <= T_r <= 512.
+// launch_decoder_cross_attention takes one T by value and is shaped for Whisper's 1500 keys (key-parallel split + merge);
+// a translation source is 5 .. 60 tokens and differs per row, so the whole head fits one workgroup pass:
+//   scores   a 16-lane group reads one 256-byte key row (float4 per lane), a wave covers 4 keys per instruction, the 4
+//            waves 16; 8 instructions (128 keys - every usual sentence) are in flight before the first dot is folded
+//   softmax  scores in LDS, wave reductions + one LDS exchange (decoder_self_attention_kernel's order)
+//   values   the same row mapping, the weights from LDS, 16 partial head rows merged through LDS
+// Nothing is read at or past key T_r: lanes beyond it re-read key 0 and their scores are never stored.  A workgroup
+// touches only its own row's operands, so a row's output bits do not depend on which other rows share the launch.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void nllb_cross_attention_ragged_kernel(const float* __restrict__ q,
+                                                                          const StepRow* __restrict__ rows, long kv_off,
+                                                                          long ldkv, int d, float* __restrict__ out) {
+    __shared__ float sc[kNlCrossMaxT];
+    __shared__ float red[8];
+    __shared__ __attribute__((aligned(16))) float part[16 * 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int sub = lane & 15, kq = lane >> 4;
+    const int row = blockIdx.x, head = blockIdx.y;
+    const float4 q4 = *reinterpret_cast<const float4*>(q + (long)row * d + head * 64 + sub * 4);
+    int T = rows[row].content_len;
+    T = T < 1 ? 1 : (T > kNlCrossMaxT ? kNlCrossMaxT : T);      // the host checks it; a bad table must not leave the LDS rows
+    const gcf_ptr kb = to_global(rows[row].cross_kv) + kv_off + head * 64 + sub * 4;
+    const gcf_ptr vb = kb + d;
+
+    float4 kk0[8], vv0[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int j = wave * 4 + 16 * u + kq;
+        kk0[u] = ldg4(kb + (long)(j < T ? j : 0) * ldkv);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int j = wave * 4 + 16 * u + kq;
+        vv0[u] = ldg4(vb + (long)(j < T ? j : 0) * ldkv);
+    }
+
+    float mx = -INFINITY;
+    for (int base = wave * 4; base < T; base += 16 * 8) {
+        float4 kk[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int j = base + 16 * u + kq;
+            if (base == wave * 4) kk[u] = kk0[u];
+            else kk[u] = ldg4(kb + (long)(j < T ? j : 0) * ldkv);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int j = base + 16 * u + kq;
+            float acc = 0.f;
+            acc = fmaf(q4.x, kk[u].x, acc);
+            acc = fmaf(q4.y, kk[u].y, acc);
+            acc = fmaf(q4.z, kk[u].z, acc);
+            acc = fmaf(q4.w, kk[u].w, acc);
+            acc = row16_sum_1248(acc);
+            if (j < T) {
+                if (sub == 0) sc[j] = acc;
+                mx = fmaxf(mx, acc);
+            }
+        }
+    }
+    mx = wave_max(mx);
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));      // (a wave without keys contributes -inf)
+    float sum = 0.f;
+    for (int j = tid; j < T; j += 256) {
+        const float e = expf(sc[j] - mx);
+        sc[j] = e;
+        sum += e;
+    }
+    sum = wave_sum(sum);
+    if (lane == 0) red[4 + wave] = sum;
+    __syncthreads();
+    sum = (red[4] + red[5]) + (red[6] + red[7]);
+    for (int j = tid; j < T; j += 256) sc[j] = sc[j] / sum;
+    __syncthreads();
+
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int base = wave * 4; base < T; base += 16 * 8) {
+        float4 vv[8];
+        float ww[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int j = base + 16 * u + kq;
+            const bool ok = j < T;
+            if (base == wave * 4) vv[u] = vv0[u];
+            else vv[u] = ldg4(vb + (long)(ok ? j : 0) * ldkv);
+            ww[u] = ok ? sc[j] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            o.x = fmaf(ww[u], vv[u].x, o.x);
+            o.y = fmaf(ww[u], vv[u].y, o.y);
+            o.z = fmaf(ww[u], vv[u].z, o.z);
+            o.w = fmaf(ww[u], vv[u].w, o.w);
+        }
+    }
+    reinterpret_cast<float4*>(part)[(wave * 4 + kq) * 16 + sub] = o;
+    __syncthreads();
+    if (tid < 64) {
+        float acc = 0.f;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) acc += part[s * 64 + tid];
+        out[(long)row * d + head * 64 + tid] = acc;
+    }
+}
+
+static void launch_nllb_cross_attention_ragged(const LaunchCtx& ctx, const float* q, const StepRow* rows, long kv_off, long ldkv,
+                                               float* out, int n_rows, int d, int n_head) {
+    KernelScope ks(ctx, "nllb_cross_attention_ragged");
+    hipLaunchKernelGGL(nllb_cross_attention_ragged_kernel, dim3(n_rows, n_head), dim3(256), 0, ctx.stream, q, rows, kv_off, ldkv,
+                       d, out);
+    WLK_HIP(hipGetLastError());
+}
+
+struct NlBatchSlot {
+    float *enc_out = nullptr, *cross_kv = nullptr, *kcache = nullptr, *vcache = nullptr;
+    int src_len = 0, self_len = 0;
+    bool encoded = false;
+    int logits_row = -1;       // row of the latest step's logits that is this slot's, -1: the slot was not in it
+};
+
+}  // namespace wlk
+
+using namespace wlk;
+
+struct wlk_nllb_batch {
+    wlk_nllb* m = nullptr;
+    int n_slots = 0;
+    hipStream_t stream = nullptr;
+    std::vector<void*> owned;
+    std::vector<NlBatchSlot> slots;
+    // stacked encode (n_slots x max_src rows)
+    float *ex = nullptr, *eh = nullptr, *eqkv = nullptr, *eatt = nullptr, *ewide = nullptr, *enc_stack = nullptr, *xkv_stack = nullptr;
+    int* enc_tokens = nullptr;
+    // stacked step (up to 8 rows)
+    float *dx = nullptr, *dqkv = nullptr, *datt = nullptr, *dq = nullptr, *dwide = nullptr, *logits = nullptr;
+    void* topk_scratch = nullptr;
+    StepRow* rows_dev = nullptr;         // the device copy of the row table, written by the chain's first kernel
+    StepRow* probe_rows_dev = nullptr;   // wlk_nllb_batch_cross_attention's own table
+    StepRow* rows_host = nullptr;        // pinned + mapped: [8] rows
+    StepRow* rows_host_dev = nullptr;    // the same block as the device sees it
+    float* vals_host = nullptr;          // pinned + mapped: top-k results written by the top-k kernel itself
+    int* ids_host = nullptr;
+    float* vals_dev = nullptr;
+    int* ids_dev = nullptr;
+    int step_k = 1;
+    hipGraphExec_t exec[kNlBatchMaxRows + 1] = {nullptr};     // by row count
+    int exec_k[kNlBatchMaxRows + 1] = {0};
+    template <typename T>
+    T* alloc(size_t n) {
+        void* p = nullptr;
+        WLK_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+        owned.push_back(p);
+        return static_cast<T*>(p);
+    }
+    LaunchCtx ctx() const { return LaunchCtx{stream, nullptr}; }
+    ~wlk_nllb_batch() {          // also the clean-up of a half-built batch
+        if (m) (void)hipSetDevice(m->device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (void* p : owned) (void)hipFree(p);
+        for (auto& e : exec) if (e) (void)hipGraphExecDestroy(e);
+        if (rows_host) (void)hipHostFree(rows_host);
+        if (vals_host) (void)hipHostFree(vals_host);
+        if (ids_host) (void)hipHostFree(ids_host);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace wlk {
+
+static void nlb_encode(wlk_nllb_batch* b, const NlSegTable& sg, const int* len, int total) {
+    wlk_nllb* m = b->m;
+    const wlk_nllb_dims& D = m->D;
+    const LaunchCtx c = b->ctx();
+    const int d = D.d_model, H = D.heads, f = D.ffn, S = total;
+    const float q_scale = 0.125f;                      // 64^-0.5, exact
+    hipLaunchKernelGGL(nllb_embed_segments_kernel, dim3(S), dim3(256), 0, b->stream, b->enc_tokens, m->emb, m->pos, D.embed_scale,
+                       D.pad_id + 1, sg, d, b->ex);
+    WLK_HIP(hipGetLastError());
+    int longest = 0;
+    for (int s = 0; s < sg.n; ++s) longest = std::max(longest, len[s]);
+    for (int l = 0; l < D.enc_layers; ++l) {
+        const NlLayer& L = m->enc[l];
+        launch_layernorm(c, b->ex, d, L.ln1w, L.ln1b, b->eh, d, S, d, "nllb_ln1");
+        nl_linear(c, b->eh, d, L.qkvw, L.qkvb, b->eqkv, 3 * d, S, 3 * d, d, kGemmScaleCols, nullptr, 0, "nllb_enc_qkv", q_scale, d);
+        SfAttnArgs a;
+        a.q = b->eqkv; a.k = b->eqkv + d; a.v = b->eqkv + 2 * d; a.ldq = a.ldk = a.ldv = 3 * d;
+        a.out = b->eatt; a.ldo = d; a.T = longest; a.n_head = H; a.dh = 64; a.scale = 1.f;
+        a.n_seg = sg.n;
+        for (int s = 0; s < sg.n; ++s) { a.seg_start[s] = sg.start[s]; a.seg_T[s] = len[s]; }
+        launch_sf_attention(c, a);
+        nl_linear(c, b->eatt, d, L.outw, L.outb, b->ex, d, S, d, d, kGemmResidual, b->ex, d, "nllb_enc_out");
+        nl_ffn(c, L, b->ex, b->eh, b->ewide, S, d, f);
+    }
+    launch_layernorm(c, b->ex, d, m->enc_lnw, m->enc_lnb, b->enc_stack, d, S, d, "nllb_enc_ln");
+    // cross-attention keys / values of every decoder layer over all stacked rows: [S][dec_layers][k | v]
+    const long ld = (long)D.dec_layers * 2 * d;
+    for (int l = 0; l < D.dec_layers; ++l) {
+        const NlLayer& L = m->dec[l];
+        nl_linear(c, b->enc_stack, d, L.xkvw, L.xkvb, b->xkv_stack + (size_t)l * 2 * d, ld, S, 2 * d, d, 0, nullptr, 0, "nllb_xkv");
+    }
+}
+
+// embed .. logits .. top-k of R stacked rows; every per-row scalar comes from the row table
+static void nlb_step_chain(wlk_nllb_batch* b, int R) {
+    wlk_nllb* m = b->m;
+    const wlk_nllb_dims& D = m->D;
+    const LaunchCtx c = b->ctx();
+    const int d = D.d_model, H = D.heads, f = D.ffn, ctx_len = D.max_tgt;
+    const float q_scale = 0.125f;
+    hipLaunchKernelGGL(nllb_embed_rows_step_kernel, dim3(R), dim3(256), 0, b->stream, b->rows_host_dev, b->rows_dev, m->emb,
+                       m->pos, D.embed_scale, D.pad_id + 1, d, b->dx);
+    WLK_HIP(hipGetLastError());
+    const long ldkv = (long)D.dec_layers * 2 * d;
+    for (int l = 0; l < D.dec_layers; ++l) {
+        const NlLayer& L = m->dec[l];
+        const long layer_off = (long)l * ctx_len * d;       // a slot's caches: [dec_layers][max_tgt][d]
+        GemmArgs g;
+        g.A = b->dx; g.lda = d; g.W = L.qkvw; g.bias = L.qkvb; g.C = b->dqkv; g.ldc = 3 * d; g.M = R; g.N = 3 * d; g.K = d;
+        g.flags = kGemmScaleCols; g.scale = q_scale; g.scale_cols = d;
+        g.ln_gamma = L.ln1w; g.ln_beta = L.ln1b;
+        g.kv_rows = b->rows_dev; g.kv_layer_off = layer_off; g.kv_d = d; g.kv_ctx = ctx_len;
+        launch_gemv(c, g, "nllb_ln1_qkv_kv");
+        launch_decoder_self_attention_rows(c, b->dqkv, b->rows_dev, layer_off, b->datt, R, d, H, ctx_len);
+        nl_linear(c, b->datt, d, L.outw, L.outb, b->dx, d, R, d, d, kGemmResidual, b->dx, d, "nllb_dec_out");
+        GemmArgs q;
+        q.A = b->dx; q.lda = d; q.W = L.xqw; q.bias = L.xqb; q.C = b->dq; q.ldc = d; q.M = R; q.N = d; q.K = d;
+        q.flags = kGemmScaleCols; q.scale = q_scale; q.scale_cols = d; q.ln_gamma = L.lnxw; q.ln_beta = L.lnxb;
+        launch_gemv(c, q, "nllb_lnx_xq");
+        launch_nllb_cross_attention_ragged(c, b->dq, b->rows_dev, (long)l * 2 * d, ldkv, b->datt, R, d, H);
+        nl_linear(c, b->datt, d, L.xoutw, L.xoutb, b->dx, d, R, d, d, kGemmResidual, b->dx, d, "nllb_dec_xout");
+        GemmArgs g1;
+        g1.A = b->dx; g1.lda = d; g1.W = L.fc1w; g1.bias = L.fc1b; g1.C = b->dwide; g1.ldc = f; g1.M = R; g1.N = f; g1.K = d;
+        g1.flags = kGemmRelu; g1.ln_gamma = L.ln2w; g1.ln_beta = L.ln2b;
+        launch_gemv(c, g1, "nllb_ln2_fc1");
+        nl_linear(c, b->dwide, f, L.fc2w, L.fc2b, b->dx, d, R, d, f, kGemmResidual, b->dx, d, "nllb_fc2");
+    }
+    GemmArgs lg;
+    lg.A = b->dx; lg.lda = d; lg.W = m->emb; lg.C = b->logits; lg.ldc = D.vocab; lg.M = R; lg.N = D.vocab; lg.K = d;
+    lg.ln_gamma = m->dec_lnw; lg.ln_beta = m->dec_lnb;
+    launch_gemv(c, lg, "nllb_lnf_logits");
+    // results straight into the host-coherent block: no copy node behind the graph
+    launch_logsoftmax_topk(c, b->logits, D.vocab, R, b->step_k, b->vals_dev, b->ids_dev, b->topk_scratch, nullptr, nullptr, nullptr, 0);
+}
+
+static StepRow nlb_row(const wlk_nllb_batch* b, int slot, int token) {
+    const NlBatchSlot& s = b->slots[slot];
+    StepRow r{};
+    r.kcache = s.kcache; r.vcache = s.vcache; r.cross_kv = s.cross_kv; r.ring = nullptr;
+    r.token = token; r.offset = s.self_len; r.content_len = s.src_len;
+    return r;
+}
+
+// slots[n] in range and pairwise different
+static int nlb_check_slots(const wlk_nllb_batch* b, const int32_t* slots, int n) {
+    unsigned seen = 0;
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= b->n_slots) return nl_fail(WLK_ERR_ARG, "NLLB batch: slot index out of range");
+        if (seen & (1u << slots[i])) return nl_fail(WLK_ERR_ARG, "NLLB batch: a slot is named twice in one call");
+        seen |= 1u << slots[i];
+    }
+    return WLK_OK;
+}
+
+}  // namespace wlk
+
+extern "C" {
+
+int wlk_nllb_batch_create(wlk_nllb* m, int n_slots, wlk_nllb_batch** out) {
+    if (!m || !out) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    if (!m->finalized) return nl_fail(WLK_ERR_STATE, "NLLB model not finalized");
+    if (n_slots < 1 || n_slots > kNlBatchMaxRows) return nl_fail(WLK_ERR_ARG, "NLLB batch: 1..8 slots");
+    if (!gemv_applicable(std::min(n_slots, kNlBatchMaxRows), m->D.d_model))
+        return nl_fail(WLK_ERR_ARG, "NLLB batch: the model is too wide for that many stacked single-token rows");
+    return nl_guarded([&]() {
+        WLK_HIP(hipSetDevice(m->device));
+        auto b = std::make_unique<wlk_nllb_batch>();
+        b->m = m;
+        b->n_slots = n_slots;
+        WLK_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+        const wlk_nllb_dims& D = m->D;
+        const size_t d = D.d_model, f = D.ffn, S = D.max_src, Tt = D.max_tgt, L = D.dec_layers, Smax = S * n_slots, R = kNlBatchMaxRows;
+        b->slots.resize(n_slots);
+        for (auto& s : b->slots) {
+            s.enc_out = b->alloc<float>(S * d);
+            s.cross_kv = b->alloc<float>(S * L * 2 * d);
+            s.kcache = b->alloc<float>(L * Tt * d);
+            s.vcache = b->alloc<float>(L * Tt * d);
+        }
+        b->ex = b->alloc<float>(Smax * d); b->eh = b->alloc<float>(Smax * d); b->eqkv = b->alloc<float>(Smax * 3 * d);
+        b->eatt = b->alloc<float>(Smax * d); b->ewide = b->alloc<float>(Smax * f); b->enc_stack = b->alloc<float>(Smax * d);
+        b->xkv_stack = b->alloc<float>(Smax * L * 2 * d);
+        b->enc_tokens = b->alloc<int>(Smax);
+        b->dx = b->alloc<float>(R * d); b->dqkv = b->alloc<float>(R * 3 * d); b->datt = b->alloc<float>(R * d);
+        b->dq = b->alloc<float>(R * d); b->dwide = b->alloc<float>(R * f);
+        b->logits = b->alloc<float>(R * D.vocab);
+        b->topk_scratch = b->alloc<char>(topk_scratch_bytes(R));
+        b->rows_dev = b->alloc<StepRow>(R);
+        b->probe_rows_dev = b->alloc<StepRow>(R);
+        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->rows_host), R * sizeof(StepRow), hipHostMallocMapped));
+        WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->rows_host_dev), b->rows_host, 0));
+        std::memset(b->rows_host, 0, R * sizeof(StepRow));
+        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->vals_host), R * 8 * sizeof(float), hipHostMallocMapped));
+        WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->vals_dev), b->vals_host, 0));
+        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->ids_host), R * 8 * sizeof(int), hipHostMallocMapped));
+        WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->ids_dev), b->ids_host, 0));
+        *out = b.release();
+        return WLK_OK;
+    });
+}
+
+int wlk_nllb_batch_destroy(wlk_nllb_batch* b) {
+    delete b;        // ~wlk_nllb_batch releases the stream, graphs and buffers
+    return WLK_OK;
+}
+
+int wlk_nllb_batch_encode(wlk_nllb_batch* b, const int32_t* slots, const int64_t* src_ids, const int32_t* src_offsets, int32_t n) {
+    if (!b || !slots || !src_ids || !src_offsets) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    if (n < 1 || n > b->n_slots) return nl_fail(WLK_ERR_ARG, "NLLB batch encode: 1..n_slots sentences per call");
+    if (int rc = nlb_check_slots(b, slots, n)) return rc;
+    const wlk_nllb_dims& D = b->m->D;
+    if (src_offsets[0] != 0) return nl_fail(WLK_ERR_ARG, "NLLB batch encode: src_offsets must start at 0");
+    NlSegTable sg;
+    int len[kNlBatchMaxRows] = {0};
+    sg.n = n;
+    for (int i = 0; i < n; ++i) {
+        const long li = (long)src_offsets[i + 1] - src_offsets[i];
+        if (li < 1 || li > D.max_src) return nl_fail(WLK_ERR_CAPACITY, "source length out of range");
+        sg.start[i] = src_offsets[i];
+        len[i] = (int)li;
+    }
+    const int total = src_offsets[n];
+    std::vector<int> stage(total);
+    for (int i = 0; i < total; ++i) {
+        if (src_ids[i] < 0 || src_ids[i] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
+        if (src_ids[i] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sentence is not supported (sentences are stacked, not padded)");
+        stage[i] = (int)src_ids[i];
+    }
+    return nl_guarded([&]() {
+        WLK_HIP(hipSetDevice(b->m->device));
+        WLK_HIP(hipStreamSynchronize(b->stream));
+        WLK_HIP(hipMemcpyAsync(b->enc_tokens, stage.data(), (size_t)total * sizeof(int), hipMemcpyHostToDevice, b->stream));
+        WLK_HIP(hipStreamSynchronize(b->stream));           // `stage` is pageable
+        for (int i = 0; i < n; ++i) b->slots[slots[i]].encoded = false;      // a failure below leaves them unusable, not stale
+        nlb_encode(b, sg, len, total);
+        const size_t d = D.d_model, ld = (size_t)D.dec_layers * 2 * d;
+        for (int i = 0; i < n; ++i) {
+            NlBatchSlot& s = b->slots[slots[i]];
+            WLK_HIP(hipMemcpyAsync(s.enc_out, b->enc_stack + (size_t)sg.start[i] * d, (size_t)len[i] * d * sizeof(float),
+                                   hipMemcpyDeviceToDevice, b->stream));
+            WLK_HIP(hipMemcpyAsync(s.cross_kv, b->xkv_stack + (size_t)sg.start[i] * ld, (size_t)len[i] * ld * sizeof(float),
+                                   hipMemcpyDeviceToDevice, b->stream));
+        }
+        for (int i = 0; i < n; ++i) {
+            NlBatchSlot& s = b->slots[slots[i]];
+            s.src_len = len[i];
+            s.self_len = 0;
+            s.encoded = true;
+            s.logits_row = -1;
+        }
+        return WLK_OK;
+    });
+}
+
+int wlk_nllb_batch_step(wlk_nllb_batch* b, const int32_t* slots, const int64_t* tokens, int32_t n_rows, int32_t k, float* logprobs,
+                        int32_t* ids) {
+    if (!b || !slots || !tokens || !logprobs || !ids) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    if (n_rows < 1 || n_rows > kNlBatchMaxRows || n_rows > b->n_slots)
+        return nl_fail(WLK_ERR_ARG, "NLLB batch step: 1..min(8, n_slots) rows, at most one per slot");
+    if (k < 1 || k > 8) return nl_fail(WLK_ERR_ARG, "k must be 1..8 (the top-k kernel's limit)");
+    if (int rc = nlb_check_slots(b, slots, n_rows)) return rc;
+    const wlk_nllb_dims& D = b->m->D;
+    for (int r = 0; r < n_rows; ++r) {
+        const NlBatchSlot& s = b->slots[slots[r]];
+        if (!s.encoded) return nl_fail(WLK_ERR_STATE, "NLLB batch step on a slot that is not encoded");
+        if (s.self_len + 1 > D.max_tgt) return nl_fail(WLK_ERR_CAPACITY, "target context exceeded");
+        if (tokens[r] < 0 || tokens[r] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
+        if (tokens[r] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sequence is not supported");
+    }
+    return nl_guarded([&]() {
+        WLK_HIP(hipSetDevice(b->m->device));
+        WLK_HIP(hipStreamSynchronize(b->stream));           // the previous step's readers of the host block are done
+        for (int r = 0; r < n_rows; ++r) b->rows_host[r] = nlb_row(b, slots[r], (int)tokens[r]);
+        hipGraphExec_t& exec = b->exec[n_rows];
+        if (!exec || b->exec_k[n_rows] != k) {
+            if (exec) { WLK_HIP(hipGraphExecDestroy(exec)); exec = nullptr; }
+            b->step_k = k;
+            hipGraph_t graph = nullptr;
+            WLK_HIP(hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal));
+            try {
+                nlb_step_chain(b, n_rows);
+            } catch (...) {
+                (void)hipStreamEndCapture(b->stream, &graph);
+                if (graph) (void)hipGraphDestroy(graph);
+                throw;
+            }
+            WLK_HIP(hipStreamEndCapture(b->stream, &graph));
+            const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(graph);
+            WLK_HIP(e);
+            b->exec_k[n_rows] = k;
+        }
+        WLK_HIP(hipGraphLaunch(exec, b->stream));
+        WLK_HIP(hipStreamSynchronize(b->stream));
+        std::memcpy(logprobs, b->vals_host, (size_t)n_rows * k * sizeof(float));
+        std::memcpy(ids, b->ids_host, (size_t)n_rows * k * sizeof(int));
+        for (auto& s : b->slots) s.logits_row = -1;
+        for (int r = 0; r < n_rows; ++r) {
+            NlBatchSlot& s = b->slots[slots[r]];
+            s.self_len += 1;
+            s.logits_row = r;
+        }
+        return WLK_OK;
+    });
+}
+
+int wlk_nllb_batch_release(wlk_nllb_batch* b, int32_t slot) {
+    if (!b) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    if (slot < 0 || slot >= b->n_slots) return nl_fail(WLK_ERR_ARG, "NLLB batch: slot index out of range");
+    NlBatchSlot& s = b->slots[slot];
+    s.encoded = false;
+    s.src_len = s.self_len = 0;
+    s.logits_row = -1;
+    return WLK_OK;
+}
+
+int wlk_nllb_batch_export(wlk_nllb_batch* b, int32_t slot, const char* what, float* host, uint64_t capacity, uint64_t* n_written) {
+    if (!b || !what || !host || !n_written) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    if (slot < 0 || slot >= b->n_slots) return nl_fail(WLK_ERR_ARG, "NLLB batch: slot index out of range");
+    return nl_guarded([&]() {
+        const wlk_nllb_dims& D = b->m->D;
+        const NlBatchSlot& s = b->slots[slot];
+        const std::string w = what;
+        const float* src = nullptr;
+        uint64_t n = 0;
+        if (!s.encoded) return nl_fail(WLK_ERR_STATE, "slot not encoded");
+        if (w == "logits") {
+            if (s.logits_row < 0) return nl_fail(WLK_ERR_STATE, "the slot was not in the latest step: no logits");
+            src = b->logits + (size_t)s.logits_row * D.vocab; n = (uint64_t)D.vocab;
+        } else if (w == "enc") {
+            src = s.enc_out; n = (uint64_t)s.src_len * D.d_model;
+        } else {
+            return nl_fail(WLK_ERR_ARG, "unknown export " + w);
+        }
+        if (n > capacity) return nl_fail(WLK_ERR_CAPACITY, "export buffer too small");
+        WLK_HIP(hipSetDevice(b->m->device));
+        WLK_HIP(hipMemcpyAsync(host, src, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+        WLK_HIP(hipStreamSynchronize(b->stream));
+        *n_written = n;
+        return WLK_OK;
+    });
+}
+
+int wlk_nllb_batch_cross_attention(wlk_nllb_batch* b, const int32_t* slots, int32_t n_rows, int32_t layer, const float* q_host,
+                                   float* out_host) {
+    if (!b || !slots || !q_host || !out_host) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    if (n_rows < 1 || n_rows > kNlBatchMaxRows || n_rows > b->n_slots) return nl_fail(WLK_ERR_ARG, "NLLB batch: 1..min(8, n_slots) rows");
+    if (int rc = nlb_check_slots(b, slots, n_rows)) return rc;
+    const wlk_nllb_dims& D = b->m->D;
+    if (layer < 0 || layer >= D.dec_layers) return nl_fail(WLK_ERR_ARG, "decoder layer out of range");
+    for (int r = 0; r < n_rows; ++r)
+        if (!b->slots[slots[r]].encoded) return nl_fail(WLK_ERR_STATE, "NLLB batch: slot not encoded");
+    return nl_guarded([&]() {
+        const size_t d = D.d_model;
+        StepRow table[kNlBatchMaxRows] = {};
+        for (int r = 0; r < n_rows; ++r) table[r] = nlb_row(b, slots[r], 0);
+        WLK_HIP(hipSetDevice(b->m->device));
+        WLK_HIP(hipStreamSynchronize(b->stream));
+        WLK_HIP(hipMemcpyAsync(b->probe_rows_dev, table, (size_t)n_rows * sizeof(StepRow), hipMemcpyHostToDevice, b->stream));
+        WLK_HIP(hipMemcpyAsync(b->dq, q_host, (size_t)n_rows * d * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        WLK_HIP(hipStreamSynchronize(b->stream));           // `table` and q_host are pageable
+        launch_nllb_cross_attention_ragged(b->ctx(), b->dq, b->probe_rows_dev, (long)layer * 2 * d, (long)D.dec_layers * 2 * d, b->datt,
+                                           n_rows, (int)d, D.heads);
+        WLK_HIP(hipMemcpyAsync(out_host, b->datt, (size_t)n_rows * d * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+        WLK_HIP(hipStreamSynchronize(b->stream));
+        return WLK_OK;
+    });
+}
+
+int wlk_nllb_batch_sync(wlk_nllb_batch* b) {
+    if (!b) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    return nl_guarded([&]() {
+        WLK_HIP(hipSetDevice(b->m->device));
+        WLK_HIP(hipStreamSynchronize(b->stream));
+        return WLK_OK;
+    });
+}
+
+}  // extern "C"

@@ -9,6 +9,9 @@ target language code.  This module is that network behind the C ABI (``wlk_nllb_
 * :func:`pack_hf_state_dict` - a ``transformers`` checkpoint's tensors (``model.shared.weight``,
   ``model.encoder.layers.N.self_attn.q_proj.weight`` ...) into the packed arena;
 * :class:`HipNllbModel` / :class:`HipNllbSession` - encoder pass, decoder steps with KV cache, beam reorder, top-k;
+* :class:`HipNllbBatch` / :func:`generate_batch` - up to 8 DIFFERENT sentences per launch chain (csrc/nllb_batch.hip):
+  ``generate`` on a padded batch in ``transformers``, without the padding - greedy decoding of any number of sentences
+  through the slots of one batch, every token position one stacked step;
 * :func:`generate` / :func:`beam_search` - ``GenerationMixin.generate`` for the cases the translation backends use: greedy
   or beam search from ``[decoder_start_token_id]`` with the target language forced as the first generated token and
   ``</s>`` ending a hypothesis.
@@ -22,7 +25,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Mapping, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterable, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -188,6 +191,9 @@ class HipNllbModel:
     def new_session(self, rows: int = 1) -> "HipNllbSession":
         return HipNllbSession(self, rows)
 
+    def new_batch(self, n_slots: int = 8) -> "HipNllbBatch":
+        return HipNllbBatch(self, n_slots)
+
     def close(self) -> None:
         if self._h:
             self.lib.wlk_nllb_destroy(self._h)
@@ -266,6 +272,87 @@ class HipNllbSession:
             pass
 
 
+class HipNllbBatch:
+    """Device state of up to ``n_slots`` (1..8) sentences in flight, stepped together (``wlk_nllb_batch_*``): every slot has
+    its own encoder output, cross K/V, self-attention cache and lengths; one step feeds one token to any subset of the
+    slots and streams the decoder's weights once for all of them.  One caller at a time."""
+
+    def __init__(self, model: HipNllbModel, n_slots: int = 8):
+        if not model.finalized:
+            raise _lib.WlkError("NLLB model must be finalized before creating batches")
+        self.model, self.lib, self.n_slots = model, model.lib, int(n_slots)
+        self._h = C.c_void_p()
+        _lib.check(self.lib.wlk_nllb_batch_create(model._h, self.n_slots, C.byref(self._h)))
+
+    def encode(self, slots: Sequence[int], sources: Sequence[Sequence[int]]) -> None:
+        """One stacked ragged encoder pass: ``sources[i]`` (unpadded ids) into slot ``slots[i]``; other slots are untouched."""
+        if len(slots) != len(sources):
+            raise ValueError("encode: one source per slot")
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        arrs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sources]
+        off = np.zeros(len(arrs) + 1, np.int32)
+        off[1:] = np.cumsum([a.size for a in arrs])
+        ids = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros(0, np.int64))
+        _lib.check(self.lib.wlk_nllb_batch_encode(self._h, sl.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p),
+                                                  off.ctypes.data_as(C.c_void_p), sl.size))
+
+    def step(self, slots: Sequence[int], tokens: Sequence[int], k: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+        """One token per named slot (at most one row per slot, any subset, any order) -> the k best log-probabilities and
+        ids of every row, ``[len(slots), k]``.  A slot's first step after its encode feeds the decoder start token."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        t = np.ascontiguousarray(tokens, dtype=np.int64).reshape(-1)
+        if sl.size != t.size:
+            raise ValueError("step: one token per slot")
+        lp = np.empty((sl.size, k), np.float32)
+        ids = np.empty((sl.size, k), np.int32)
+        _lib.check(self.lib.wlk_nllb_batch_step(self._h, sl.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), sl.size, k,
+                                                lp.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p)))
+        return lp, ids
+
+    def release(self, slot: int) -> None:
+        _lib.check(self.lib.wlk_nllb_batch_release(self._h, int(slot)))
+
+    def _export(self, slot: int, what: str, n: int) -> np.ndarray:
+        buf = np.empty(n, np.float32)
+        got = C.c_uint64()
+        _lib.check(self.lib.wlk_nllb_batch_export(self._h, int(slot), what.encode(), buf.ctypes.data_as(C.c_void_p), buf.size,
+                                                  C.byref(got)))
+        return buf[: got.value]
+
+    def encoder_output(self, slot: int) -> np.ndarray:
+        return self._export(slot, "enc", self.model.cdims.max_src * self.model.cfg.d_model).reshape(-1, self.model.cfg.d_model)
+
+    def logits(self, slot: int) -> np.ndarray:
+        """The slot's row of the latest step's logits, ``[vocab]``."""
+        return self._export(slot, "logits", self.model.cfg.vocab_size)
+
+    def cross_attention(self, slots: Sequence[int], layer: int, q: np.ndarray) -> np.ndarray:
+        """Diagnostics: the ragged cross-attention kernel alone, queries ``q [len(slots), d_model]`` (pre-scaled) against the
+        named slots' cross K/V of decoder layer ``layer``."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        qa = np.ascontiguousarray(q, dtype=np.float32)
+        if qa.shape != (sl.size, self.model.cfg.d_model):
+            raise ValueError("cross_attention: q must be [len(slots), d_model]")
+        out = np.empty_like(qa)
+        _lib.check(self.lib.wlk_nllb_batch_cross_attention(self._h, sl.ctypes.data_as(C.c_void_p), sl.size, int(layer),
+                                                           qa.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def sync(self) -> None:
+        _lib.check(self.lib.wlk_nllb_batch_sync(self._h))
+
+    def close(self) -> None:
+        if self._h:
+            self.lib.wlk_nllb_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def generate(session, src_ids: Sequence[int], forced_bos_token_id: Optional[int] = None, *, max_new_tokens: int = 199,
              forced_eos_token_id: Optional[int] = None) -> List[int]:
     """``model.generate(input_ids, forced_bos_token_id=<target language>, num_beams=1, do_sample=False,
@@ -298,6 +385,90 @@ def generate(session, src_ids: Sequence[int], forced_bos_token_id: Optional[int]
         if nxt == eos:
             break
     return out
+
+
+def _per_sentence(value, n: int, what: str) -> list:
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != n:
+            raise ValueError(f"generate_batch: {what} must be a scalar or one value per sentence")
+        return [None if v is None else int(v) for v in value]
+    return [None if value is None else int(value)] * n
+
+
+def generate_batch(batch, sources: Sequence[Sequence[int]],
+                   forced_bos_token_ids: Union[None, int, Sequence[Optional[int]]] = None, *,
+                   max_new_tokens: Union[int, Sequence[int]] = 199, forced_eos_token_id: Optional[int] = None,
+                   more: Optional[Callable[[], Optional[Iterable[tuple]]]] = None,
+                   done: Optional[Callable[[object, List[int]], None]] = None) -> List[List[int]]:
+    """Greedy :func:`generate` for any number of sentences through the slots of one batch (``HipNllbBatch``, or anything with
+    its ``n_slots`` / ``encode`` / ``step`` / ``release``): ``model.generate`` on a padded batch in ``transformers``, sentence
+    by sentence the same ids as :func:`generate` alone.  ``forced_bos_token_ids`` and ``max_new_tokens`` are scalars or one
+    value per sentence.
+
+    Sentences are admitted to free slots in order (those admitted together share one stacked encoder pass); every token
+    position is ONE ``step`` over the rows still running; a sentence that ends - ``</s>`` or its own length limit -
+    releases its slot, and the next waiting sentence is encoded into it and joins at the following step.  The forced-BOS
+    and forced-EOS rules are :func:`generate`'s, applied per sentence at that sentence's own length.
+
+    ``more`` is polled once per step (and once more before the pass would end): it may return further
+    ``(source, forced_bos, max_new_tokens, ticket)`` work, which queues behind what is already waiting; the ids of such a
+    sentence go to ``done(ticket, ids)`` as soon as it ends.  This is how a serving layer joins a running pass.  Returns
+    the ids of ``sources`` in input order, each including the start token."""
+    cfg = batch.model.cfg
+    eos, start = cfg.eos_token_id, cfg.decoder_start_token_id
+    n = len(sources)
+    bos, limits = _per_sentence(forced_bos_token_ids, n, "forced_bos_token_ids"), _per_sentence(max_new_tokens, n, "max_new_tokens")
+    results: List[Optional[List[int]]] = [None] * n
+    waiting = [dict(src=sources[i], bos=bos[i], max_new=limits[i], index=i, ticket=None) for i in range(n)]
+    free = list(range(batch.n_slots))
+    running: Dict[int, dict] = {}                      # slot -> sentence, in admission order
+
+    def finish(item, slot=None):
+        if slot is not None:
+            batch.release(slot)
+            free.append(slot)
+            free.sort()
+        if item["index"] is not None:
+            results[item["index"]] = item["out"]
+        elif done is not None:
+            done(item["ticket"], item["out"])
+
+    while True:
+        if more is not None:
+            for src, fb, mn, ticket in (more() or ()):
+                waiting.append(dict(src=src, bos=None if fb is None else int(fb), max_new=int(mn), index=None, ticket=ticket))
+        admitted = []
+        while waiting and (free or waiting[0]["max_new"] <= 0):
+            item = waiting.pop(0)
+            item["out"] = [start]
+            if item["max_new"] <= 0:                   # generate's loop does not run: the start token alone
+                finish(item)
+                continue
+            admitted.append((free.pop(0), item))
+        if admitted:
+            batch.encode([s for s, _ in admitted], [it["src"] for _, it in admitted])
+            running.update(admitted)
+        if not running:
+            if waiting:
+                continue
+            break
+        slots = list(running)
+        best = batch.step(slots, [running[s]["out"][-1] for s in slots], 1)[1]
+        for r, slot in enumerate(slots):
+            item = running[slot]
+            out = item["out"]
+            cur_len, max_length = len(out), 1 + item["max_new"]
+            if item["bos"] is not None and cur_len == 1:
+                nxt = item["bos"]
+            elif forced_eos_token_id is not None and cur_len == max_length - 1:
+                nxt = int(forced_eos_token_id)
+            else:
+                nxt = int(best[r, 0])
+            out.append(nxt)
+            if nxt == eos or len(out) == max_length:
+                del running[slot]
+                finish(item, slot)
+    return results
 
 
 def beam_search(session, src_ids: Sequence[int], forced_bos_token_id: Optional[int] = None, *, num_beams: int,

@@ -33,10 +33,16 @@ surface this module uses (``src_lang`` attribute, ``__call__(text).input_ids``, 
 ``decode(ids, skip_special_tokens=True)``) - ``transformers.NllbTokenizer`` over the checkpoint's
 ``sentencepiece.bpe.model`` in deployment, a seeded stand-in in the tests (no SentencePiece model exists offline).
 No CPU fallback: the model is a :class:`whisperlivekit_amd.nllb.HipNllbModel`.
+
+Opt-in stacking (``HipNllbTranslationModel(stack=n)`` / ``WLK_NLLB_STACK=n``, greedy decoding only): the model owns ONE
+``HipNllbBatch`` of n slots and every session hands the segments of a ``process()`` - the closed sentences and the open
+one - to it as one request list; sentences of different sessions that are in flight at the same time share every decoder
+weight pass (``nllb.generate_batch``).  The validated text and the buffers are the ones of the default path.
 """
 from __future__ import annotations
 
 import logging
+import os
 import threading
 from dataclasses import dataclass, field
 from typing import Any, List, Optional, Sequence, Tuple
@@ -85,17 +91,109 @@ def _common_prefix(a: Sequence[str], b: Sequence[str]) -> int:
     return n
 
 
+def resolve_stack(stack: Optional[int]) -> int:
+    """``HipNllbTranslationModel(stack=...)``: an explicit value wins; ``None`` reads ``WLK_NLLB_STACK`` (default 0 = off)."""
+    if stack is None:
+        stack = int(os.environ.get("WLK_NLLB_STACK", "0").strip() or 0)
+    stack = int(stack)
+    if stack < 0 or stack > 8:
+        raise ValueError("stack must be 0 (off) or 1..8 slots")
+    return stack
+
+
+class NllbStacker:
+    """Thread-safe front of one ``HipNllbBatch``: any session thread calls :meth:`translate_many`; the first caller becomes
+    the runner and drives ``nllb.generate_batch``, callers that arrive while a pass is running queue their requests - the
+    runner's ``more`` callback admits them at its next step - and wait on a condition for their tickets.  The runner keeps
+    running until the batch is empty and nobody is queued.  A pass that fails hands its error to every request in flight
+    or queued, so no waiter blocks for ever; the slots are released and the next caller starts a fresh pass."""
+
+    def __init__(self, batch: Any):
+        self.batch = batch
+        self._cv = threading.Condition()
+        self._queue: List[tuple] = []              # (source, forced_bos, max_new_tokens, ticket) not yet handed to the pass
+        self._open: set = set()                    # tickets queued or in flight
+        self._outcome: dict = {}                   # ticket -> (ids, error)
+        self._running = False
+        self._next_ticket = 0
+        self.passes = 0                            # generate_batch passes run (bench / tests)
+        self.sentences = 0
+
+    def translate_many(self, requests: Sequence[Tuple[Sequence[int], Optional[int], int]]) -> List[List[int]]:
+        """``requests``: ``(source ids, forced_bos_token_id, max_new_tokens)`` per sentence -> their ids, in order."""
+        if not requests:
+            return []
+        with self._cv:
+            tickets = list(range(self._next_ticket, self._next_ticket + len(requests)))
+            self._next_ticket += len(requests)
+            for t, (src, bos, max_new) in zip(tickets, requests):
+                self._queue.append((list(src), bos, int(max_new), t))
+                self._open.add(t)
+        while True:
+            with self._cv:
+                while self._running and any(t not in self._outcome for t in tickets):
+                    self._cv.wait()
+                if all(t in self._outcome for t in tickets):
+                    got = [self._outcome.pop(t) for t in tickets]
+                    for _ids, err in got:
+                        if err is not None:
+                            raise err
+                    return [ids for ids, _err in got]
+                self._running = True               # nobody is driving the batch and this caller still waits: it drives
+            self._run()
+
+    def _run(self) -> None:
+        def more():
+            with self._cv:
+                items, self._queue = self._queue, []
+            return items
+
+        def done(ticket, ids):
+            with self._cv:
+                self._outcome[ticket] = (ids, None)
+                self._open.discard(ticket)
+                self.sentences += 1
+                self._cv.notify_all()
+
+        error: Optional[BaseException] = None
+        try:
+            nllb.generate_batch(self.batch, [], more=more, done=done)
+        except BaseException as e:                 # the pass is gone: everyone in it or queued behind it gets the error
+            error = e
+            for slot in range(self.batch.n_slots):  # the next pass starts from free slots
+                try:
+                    self.batch.release(slot)
+                except Exception:                   # the callers receive the pass's own error
+                    pass
+        finally:
+            with self._cv:
+                self.passes += 1
+                if error is not None:
+                    for t in self._open:
+                        self._outcome[t] = (None, error)
+                    self._open.clear()
+                    self._queue = []
+                self._running = False
+                self._cv.notify_all()
+        if error is not None and not isinstance(error, Exception):
+            raise error
+
+
 class HipNllbTranslationModel:
     """The server-wide handle ``nllw.load_model`` returns in the reference (``TranscriptionEngine.translation_model``,
     core.py:320-329): one network per GPU shared by every session, plus the tokenizer and the decoding options.  Device
     sessions are 1-row and cheap; each ``HipOnlineTranslation`` owns one, so sessions never share decoder caches."""
 
     def __init__(self, model: nllb.HipNllbModel, tokenizer: Any, num_beams: int = 1, max_new_tokens: int = 199,
-                 max_source_tokens: int = 200):
+                 max_source_tokens: int = 200, stack: Optional[int] = None):
         self.model, self.tokenizer = model, tokenizer
         self.num_beams, self.max_new_tokens, self.max_source_tokens = int(num_beams), int(max_new_tokens), int(max_source_tokens)
         # a tokenizer with a mutable src_lang (transformers' NllbTokenizer) is shared by all sessions
         self.tokenizer_lock = threading.Lock()
+        # opt-in: one batch of `stack` slots shared by every session (greedy decoding only; beams keep their own sessions)
+        self.stack = resolve_stack(stack) if self.num_beams == 1 else 0
+        self.batch = model.new_batch(self.stack) if self.stack else None
+        self.stacker = NllbStacker(self.batch) if self.batch is not None else None
 
     def language_id(self, code: str) -> int:
         tid = self.tokenizer.convert_tokens_to_ids(code)
@@ -117,6 +215,12 @@ class HipNllbTranslationModel:
 
     def new_session(self, source_language: str, target_language: str) -> "HipOnlineTranslation":
         return HipOnlineTranslation(self, [source_language], [target_language])
+
+    def close(self) -> None:
+        """Releases the shared batch (the network itself belongs to the caller)."""
+        batch, self.batch, self.stacker = self.batch, None, None
+        if batch is not None:
+            batch.close()
 
 
 @dataclass
@@ -152,7 +256,10 @@ class HipOnlineTranslation:
         self.source_language, self.target_language = source_languages[0], target_languages[0]
         self.target_id = translation_model.language_id(self.target_language)       # ValueError for an unknown code
         translation_model.language_id(self.source_language)
-        self.session = translation_model.model.new_session(rows=max(1, translation_model.num_beams))
+        # stacked serving: the sentences live in the slots of the model's batch, the session needs no device state of its own
+        self.session = (translation_model.model.new_session(rows=max(1, translation_model.num_beams))
+                        if translation_model.stacker is None else None)
+        self._ready: List[List[str]] = []          # stacked serving: this call's hypotheses, in the order process() asks for them
         self._segment = _Segment()
         self._closed: List[_Segment] = []          # sentences that ended (punctuation) and await their final translation
         self._validated_words: List[str] = []      # target words of the open segment already handed out
@@ -177,6 +284,8 @@ class HipOnlineTranslation:
                 self._segment = _Segment()
 
     def process(self) -> Tuple[Optional[Translation], TimedText]:
+        if self.shared.stacker is not None:           # every segment this call translates, as ONE request list
+            self._ready = self._translate_many(self._closed + ([self._segment] if self._segment.tokens and self._dirty else []))
         pieces: List[str] = []
         end: Optional[float] = None
         start = self._piece_start(self._closed[0].start if self._closed else self._segment.start)
@@ -236,7 +345,8 @@ class HipOnlineTranslation:
         self._silence += float(duration or 0.0)
 
     def close(self) -> None:
-        self.session.close()
+        if self.session is not None:
+            self.session.close()
 
     # ---- internals --------------------------------------------------------------------------------------------------
     def _piece_start(self, fallback: Optional[float]) -> float:
@@ -249,7 +359,16 @@ class HipOnlineTranslation:
             return TimedText()
         return TimedText(start=self._piece_start(self._segment.start), end=self._segment.end, text=" ".join(self._buffer_words))
 
+    def _translate_many(self, segs: Sequence[_Segment]) -> List[List[str]]:
+        m = self.shared
+        outs = m.stacker.translate_many([(m.encode(seg.text(), self.source_language), self.target_id, m.max_new_tokens)
+                                         for seg in segs])
+        self.translations += len(outs)
+        return [m.decode(out).split() for out in outs]
+
     def _translate(self, seg: _Segment) -> List[str]:
+        if self._ready:                               # stacked serving: translated at the top of process()
+            return self._ready.pop(0)
         m = self.shared
         src = m.encode(seg.text(), self.source_language)
         if m.num_beams > 1:
