@@ -226,6 +226,44 @@ int wlk_job_result(wlk_decode_job* j, wlk_loop_result* result, int64_t* new_toke
                    int32_t* step_frames, float* step_sum_logprobs, int cap);
 int wlk_job_destroy(wlk_decode_job* j);
 
+/* ---- the same loop for the beam decoder, beams 2..7 ----------------------------------------------------------------
+ * wlk_decode_beam_until_stop: arguments as wlk_decode_until_stop; `tokens` is the prompt of ONE row (the prefill feeds
+ * beam copies of it, as AlignAttBase does).  Per step: decoder forward over the beam rows, the adjustments (computed from
+ * row 0, applied to every row), top-(beam+1) per row + the AlignAtt read-out in one read-back, BeamSearchDecoder.update
+ * (whisper/decoding.py:317-376, patience 1) and the stop rules on row 0.  The result describes row 0 (step_sum_logprobs:
+ * sum_logprobs[0] after each update).  No teacher forcing (n_force must be 0).
+ * Single-token steps do not copy the self-attention cache when the hypotheses are re-ranked: a device table
+ * anc[beam][n_text_ctx] names, per hypothesis and position, the physical cache row that holds it, and the step's
+ * self-attention reads through it.  Once such a step has run in an infer the physical rows no longer are the
+ * hypotheses, so wlk_decode(first = 0) and wlk_kv_reorder on that session return WLK_ERR_STATE until the next
+ * wlk_decode(first = 1).  Debug / profiling sessions and shapes the <= 8-row weight-streaming kernels do not take
+ * run every step as wlk_decode + wlk_select + wlk_kv_reorder inside this call instead. */
+int wlk_decode_beam_until_stop(wlk_session* s, const int64_t* tokens, int n_tok, const wlk_loop_params* p,
+                               const int32_t* suppress_ids, int n_suppress, const int32_t* blank_ids, int n_blank,
+                               wlk_loop_result* result, int64_t* new_tokens, int32_t* step_tokens, int32_t* step_frames,
+                               float* step_sum_logprobs, int cap);
+/* single-token steps of this session that ran over the ancestry table so far */
+int wlk_session_beam_stats(wlk_session* s, uint64_t* ancestry_steps);
+/* Diagnostic (tests): one single-token decoder forward over the ancestry table - what wlk_decode(first = 0) computes
+ * after wlk_kv_reorder(source_rows), without moving the cache.  WLK_ERR_STATE when the session does not qualify. */
+int wlk_diag_beam_step(wlk_session* s, const int64_t* tokens, const int32_t* source_rows, int n_rows);
+/* Host half of the beam loop without a GPU, as wlk_job_*: consume takes the [beam][beam + 1] log-probs / ids after the
+ * adjustments and the [beam] attended frames; state hands back the hypotheses ([beam][row_len], rank order), their
+ * sum_logprobs, the source row of each in the last update and whether `finished` is full. */
+typedef struct wlk_beam_job wlk_beam_job;
+int wlk_beam_job_create(const wlk_loop_params* p, int beam, const int64_t* tokens, int n_tok, const int32_t* suppress_ids,
+                        int n_suppress, const int32_t* blank_ids, int n_blank, wlk_beam_job** out);
+int wlk_beam_job_begin_step(wlk_beam_job* j, int32_t* n_feed);
+int wlk_beam_job_no_speech(wlk_beam_job* j, float prob, int32_t* stops);
+int wlk_beam_job_adjustments(wlk_beam_job* j, const int32_t** ids, const float** deltas, int32_t* n);
+int wlk_beam_job_consume(wlk_beam_job* j, const float* top_logprobs, const int32_t* top_ids, const int32_t* frames,
+                         int32_t* goes_on);
+int wlk_beam_job_state(wlk_beam_job* j, int64_t* rows, int cap, int32_t* row_len, float* sum_logprobs, int32_t* source_rows,
+                       int32_t* completed);
+int wlk_beam_job_result(wlk_beam_job* j, wlk_loop_result* result, int64_t* new_tokens, int32_t* step_tokens,
+                        int32_t* step_frames, float* step_sum_logprobs, int cap);
+int wlk_beam_job_destroy(wlk_beam_job* j);
+
 /* Parity/debug exports to host memory.  what: "mel" [n_mels,3000], "enc" [1500,d],
  * "logits_last" / "logits_sot" [n_rows,V], "attn_last" [n_rows, content_mel_len] (after
  * wlk_select), "cross_qk:<layer>" [rows, H, 1500] of the latest wlk_decode (debug sessions only),

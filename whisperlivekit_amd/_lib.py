@@ -155,6 +155,18 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_job_consume": (cint, [p, p, p, cint, C.POINTER(i32)]),
         "wlk_job_result": (cint, [p, C.POINTER(LoopResult), p, p, p, p, cint]),
         "wlk_job_destroy": (cint, [p]),
+        "wlk_decode_beam_until_stop": (cint, [p, p, cint, C.POINTER(LoopParams), p, cint, p, cint, C.POINTER(LoopResult),
+                                              p, p, p, p, cint]),
+        "wlk_session_beam_stats": (cint, [p, C.POINTER(u64)]),
+        "wlk_diag_beam_step": (cint, [p, p, p, cint]),
+        "wlk_beam_job_create": (cint, [C.POINTER(LoopParams), cint, p, cint, p, cint, p, cint, C.POINTER(p)]),
+        "wlk_beam_job_begin_step": (cint, [p, C.POINTER(i32)]),
+        "wlk_beam_job_no_speech": (cint, [p, C.c_float, C.POINTER(i32)]),
+        "wlk_beam_job_adjustments": (cint, [p, C.POINTER(i32p), C.POINTER(f32p), C.POINTER(i32)]),
+        "wlk_beam_job_consume": (cint, [p, p, p, p, C.POINTER(i32)]),
+        "wlk_beam_job_state": (cint, [p, p, cint, C.POINTER(i32), p, p, C.POINTER(i32)]),
+        "wlk_beam_job_result": (cint, [p, C.POINTER(LoopResult), p, p, p, p, cint]),
+        "wlk_beam_job_destroy": (cint, [p]),
         "wlk_export": (cint, [p, C.c_char_p, p, u64, C.POINTER(u64)]),
         "wlk_session_step_stats": (cint, [p, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "wlk_prof_begin": (cint, [p]),
@@ -260,6 +272,9 @@ EXPORTED_SYMBOLS = (
     "wlk_engine_stats", "wlk_engine_encode_stats", "wlk_engine_prefill_stats", "wlk_diag_prefill_stack", "wlk_job_create",
     "wlk_job_begin_step", "wlk_job_no_speech", "wlk_job_adjustments", "wlk_job_consume", "wlk_job_result",
     "wlk_job_destroy", "wlk_export", "wlk_session_step_stats", "wlk_prof_begin",
+    "wlk_decode_beam_until_stop", "wlk_session_beam_stats", "wlk_diag_beam_step", "wlk_beam_job_create",
+    "wlk_beam_job_begin_step", "wlk_beam_job_no_speech", "wlk_beam_job_adjustments", "wlk_beam_job_consume",
+    "wlk_beam_job_state", "wlk_beam_job_result", "wlk_beam_job_destroy",
     "wlk_prof_end", "wlk_melspec_create", "wlk_melspec_run", "wlk_melspec_destroy",
     "wlk_sf_arena_floats", "wlk_sf_tensor_lookup", "wlk_sf_tensor_name", "wlk_sf_create", "wlk_sf_upload",
     "wlk_sf_finalize", "wlk_sf_step", "wlk_sf_step_pcm", "wlk_sf_stats", "wlk_sf_export", "wlk_sf_destroy",

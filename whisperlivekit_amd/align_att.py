@@ -398,6 +398,14 @@ class HipAlignAttHooks:
         return (self.cfg.beam_size == 1 and self.state.decoder_type == "beam"
                 and hasattr(self.session, "decode_until_stop"))
 
+    def beam_loop_available(self) -> bool:
+        """Opt-in (``use_beam_loop`` on the object or WLK_BEAM_LOOP=1): the beam decoder's loop, beams 2-7, inside the
+        library (wlk_decode_beam_until_stop).  Off by default; never with a teacher (forcing is defined for beam 1)."""
+        if not (getattr(self, "use_beam_loop", False) or os.environ.get("WLK_BEAM_LOOP", "0") == "1"):
+            return False
+        return (2 <= self.cfg.beam_size <= 7 and self.state.decoder_type == "beam" and not self.teacher
+                and hasattr(self.session, "decode_beam_until_stop"))
+
     def _decode_until_stop(self, tokens, content_mel_len, is_last, budget):
         """align_att_base.py:206-286 as ONE library call: returns the loop's outcome (engine.LoopOutcome)."""
         from . import _lib
@@ -415,7 +423,10 @@ class HipAlignAttHooks:
         if self.teacher:
             p.force([(si, t, f) for (ci, si), (t, f) in sorted(self.teacher.items()) if ci == self._infer_index])
         blank = list(tok.encode(" ")) + [tok.eot]
-        out = self.session.decode_until_stop(np.asarray(tokens)[0], p, st.suppress_ids, blank)
+        if self.cfg.beam_size > 1:
+            out = self.session.decode_beam_until_stop(np.asarray(tokens)[0], p, st.suppress_ids, blank)
+        else:
+            out = self.session.decode_until_stop(np.asarray(tokens)[0], p, st.suppress_ids, blank)
         self._fresh_infer = False
         self.counters["decode"] += out.decode_calls
         if out.decode_calls:

@@ -488,6 +488,7 @@ int wlk_session_create(wlk_model* m, int beam, int max_audio_samples, wlk_sessio
         s->attn_last = dev_alloc_zero<float>((size_t)beam * T, st);
         s->adj_row = dev_alloc<int>(3 * wlk_session::kAdjCap);   // [rows n | ids n | deltas n] packed per call
         s->src_rows = dev_alloc<int>(8);
+        if (beam >= 2 && beam <= 7) s->anc = dev_alloc_zero<unsigned char>((size_t)beam * ctx, st);
         s->top_vals = dev_alloc<float>((size_t)beam * 18);       // [log-probs B*8 | ids B*8 | frames B | no-speech B]: ONE D2H
         s->top_ids = reinterpret_cast<int*>(s->top_vals) + (size_t)beam * 8;
         s->frames = s->top_ids + (size_t)beam * 8;
@@ -535,6 +536,9 @@ int wlk_session_destroy(wlk_session* s) {
         if (p) (void)hipFree(p);
     for (auto& e : s->step_exec)
         if (e) (void)hipGraphExecDestroy(e);
+    for (auto& e : s->bstep_exec)
+        if (e) (void)hipGraphExecDestroy(e);
+    if (s->anc) (void)hipFree(s->anc);
     if (s->topk_scratch) (void)hipFree(s->topk_scratch);
     if (s->pcm16_dev) (void)hipFree(s->pcm16_dev);
     if (s->eh3) (void)hipFree(s->eh3);
@@ -1043,8 +1047,11 @@ static void mall_prefetch_prepare(wlk_session* s) {
     WLK_HIP(hipStreamSynchronize(s->pf_stream));
 }
 
+constexpr size_t kAncStageOffset = 65536 - 64;   // [source rows 0..6 | fresh] of an ancestry step, at the end of dec_stage
+
 static void enqueue_decode(wlk_session* s, const LaunchCtx& c, int n_rows, int n_tok, bool first, int sot_index,
-                           bool step_block = false, const AlignArgs* side_align = nullptr, int side_blocks = 0, int side_zf = 0) {
+                           bool step_block = false, const AlignArgs* side_align = nullptr, int side_blocks = 0, int side_zf = 0,
+                           bool ancestry = false) {
     wlk_model* m = s->m;
     const wlk_dims& D = m->D;
     const int ctx_len = D.n_text_ctx;
@@ -1058,6 +1065,14 @@ static void enqueue_decode(wlk_session* s, const LaunchCtx& c, int n_rows, int n
     // decode steps (<= 8 rows): LayerNorm and the KV-cache append are fused into the weight-streaming
     // GEMV launches; prefill keeps them as separate kernels in front of the MFMA GEMMs
     const bool fused = gemv_applicable(R, d) && n_tok == 1;
+    if (ancestry) {
+        // beam step over the ancestry table (wlk_beam_step): [source rows | fresh] ride behind the staging block; the table
+        // is brought up to date in front of the layers, which append position `offset` to every physical row
+        if (!fused || step_block || !s->anc) throw std::logic_error("decode: the ancestry step needs the fused beam step");
+        WLK_HIP(hipMemcpyAsync(s->src_rows, static_cast<char*>(s->dec_stage) + kAncStageOffset, 8 * sizeof(int),
+                               hipMemcpyHostToDevice, s->stream));
+        launch_anc_update(c, s->anc, s->src_rows, s->d_offset, n_rows, ctx_len);
+    }
 
     if (step_block)
         launch_embed_step(c, s->step_host_dev, s->step_dev, s->tokens_dev, s->ring_row, s->beam_of_row, s->d_offset,
@@ -1094,8 +1109,11 @@ static void enqueue_decode(wlk_session* s, const LaunchCtx& c, int n_rows, int n
                 launch_kv_append(c, s->dqkv, kc, vc, n_rows, n_tok, s->d_offset, d, ctx_len);
             }
         }
-        launch_decoder_self_attention(c, s->dqkv, kc, vc, s->datt, n_rows, n_tok, s->d_offset, d, H, ctx_len,
-                                      marks ? ProgressMark{&s->step_dev->seq, s->pf_progress, i} : ProgressMark{});
+        if (ancestry)
+            launch_decoder_self_attention_anc(c, s->dqkv, kc, vc, s->anc, s->datt, n_rows, s->d_offset, d, H, ctx_len);
+        else
+            launch_decoder_self_attention(c, s->dqkv, kc, vc, s->datt, n_rows, n_tok, s->d_offset, d, H, ctx_len,
+                                          marks ? ProgressMark{&s->step_dev->seq, s->pf_progress, i} : ProgressMark{});
         GemmArgs o;
         o.A = s->datt; o.lda = d; o.W = L.outw; o.bias = L.outb; o.C = s->dx; o.ldc = d; o.M = R; o.N = d; o.K = d;
         o.flags = kGemmResidual; o.R = s->dx; o.ldr = d;
@@ -1408,6 +1426,8 @@ int wlk_decode(wlk_session* s, const int64_t* tokens, int n_rows, int n_tok, int
     if (n_tok < 1) return fail(WLK_ERR_ARG, "n_tok must be >= 1");
     if (!first && n_tok != 1) return fail(WLK_ERR_ARG, "only one token per row may be fed after the first call");
     if (!first && s->n_steps == 0) return fail(WLK_ERR_STATE, "first decode of an infer must set first=1");
+    if (!first && s->anc_live)
+        return fail(WLK_ERR_STATE, "wlk_decode(first=0) after an ancestry beam step: the cache rows are not the hypotheses");
     if (first && (sot_index < 0 || sot_index >= n_tok)) return fail(WLK_ERR_ARG, "sot_index out of range");
     return guarded([&]() {
         wlk_model* m = s->m;
@@ -1417,6 +1437,7 @@ int wlk_decode(wlk_session* s, const int64_t* tokens, int n_rows, int n_tok, int
         if (first) {
             s->self_len = 0;
             s->n_steps = 0;
+            s->anc_live = false;
         }
         const int offset = s->self_len;
         const int ctx_len = D.n_text_ctx;
@@ -1758,6 +1779,8 @@ extern "C++" int wlk_step_select(wlk_session* s, int64_t token, const int32_t* a
 
 int wlk_kv_reorder(wlk_session* s, const int32_t* source_rows, int n_rows) {
     if (!s || !source_rows || n_rows != s->beam) return fail(WLK_ERR_ARG, "bad reorder request");
+    if (s->anc_live)
+        return fail(WLK_ERR_STATE, "wlk_kv_reorder after an ancestry beam step: the cache rows are not the hypotheses");
     bool identity = true;
     for (int i = 0; i < n_rows; ++i) {
         if (source_rows[i] < 0 || source_rows[i] >= n_rows) return fail(WLK_ERR_ARG, "source row out of range");
@@ -1784,6 +1807,82 @@ int wlk_kv_reorder(wlk_session* s, const int32_t* source_rows, int n_rows) {
         s->kv_cur ^= 1;
         return WLK_OK;
     });
+}
+
+// One single-token decoder forward of a beam session over the ancestry table (internal.h).  wlk_decode's single-token
+// path with two differences: the table update in front of the layers and the self-attention that reads through it.
+extern "C++" int wlk_beam_step(wlk_session* s, const int64_t* tokens, const int32_t* source_rows) {
+    if (!s || !tokens || !source_rows) return fail(WLK_ERR_ARG, "NULL argument");
+    wlk_model* m = s->m;
+    const wlk_dims& D = m->D;
+    const int B = s->beam;
+    if (!s->anc || B < 2 || B > 7 || s->debug || s->prof_on || !s->use_graph || s->n_steps < 1 || !s->encoded ||
+        !gemv_applicable(B, D.n_text_state) || D.n_text_ctx > 512 || D.n_text_state != D.n_text_head * kHeadDim ||
+        (size_t)(s->max_rows * 3 + 4) * sizeof(int) > kAncStageOffset)   // the staging block must leave [src | fresh] its place
+        return 1;
+    if (s->self_len + 1 > D.n_text_ctx) return fail(WLK_ERR_CAPACITY, "text context exceeded");
+    for (int b = 0; b < B; ++b) {
+        if (tokens[b] < 0 || tokens[b] >= D.n_vocab) return fail(WLK_ERR_ARG, "token id out of range");
+        if (source_rows[b] < 0 || source_rows[b] >= B) return fail(WLK_ERR_ARG, "source row out of range");
+    }
+    return guarded([&]() {
+        WLK_HIP(hipSetDevice(m->device));
+        const LaunchCtx c = s->ctx();
+        if (s->dec_stage_used) WLK_HIP(hipEventSynchronize(s->dec_stage_ev));
+        if (drain_staging()) WLK_HIP(hipStreamSynchronize(s->stream));
+        int* stage = static_cast<int*>(s->dec_stage);
+        const int MR = s->max_rows;
+        const int slot_row = D.n_text_ctx + ((s->n_steps - 1) % kAlignWindow);
+        for (int b = 0; b < B; ++b) {
+            stage[b] = (int)tokens[b];
+            stage[MR + b] = slot_row;
+            stage[2 * MR + b] = b;
+        }
+        stage[3 * MR] = s->self_len;
+        int* ctl = reinterpret_cast<int*>(static_cast<char*>(s->dec_stage) + kAncStageOffset);
+        for (int b = 0; b < 7; ++b) ctl[b] = b < B ? source_rows[b] : 0;
+        ctl[7] = s->anc_live ? 0 : 1;
+        // one capture per KV buffer, as step_exec: the chain's nodes carry kcache / vcache[kv_cur], and a wlk_kv_reorder of
+        // an infer that ran without ancestry steps (debug / profiling fallback, the per-token hooks) flips kv_cur
+        hipGraphExec_t& exec = s->bstep_exec[s->kv_cur];
+        if (!exec) {
+            hipGraph_t graph = nullptr;
+            WLK_HIP(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
+            try {
+                enqueue_decode(s, c, B, 1, false, 0, false, nullptr, 0, 0, true);
+            } catch (...) {
+                (void)hipStreamEndCapture(s->stream, &graph);
+                if (graph) (void)hipGraphDestroy(graph);
+                throw;
+            }
+            WLK_HIP(hipStreamEndCapture(s->stream, &graph));
+            WLK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+            (void)hipGraphDestroy(graph);
+        }
+        WLK_HIP(hipGraphLaunch(exec, s->stream));
+        WLK_HIP(hipEventRecord(s->dec_stage_ev, s->stream));
+        s->dec_stage_used = true;
+        s->have_sot = false;
+        s->anc_live = true;
+        s->anc_steps += 1;
+        s->self_len += 1;
+        s->n_steps += 1;
+        s->last_rows = B;
+        s->last_ntok = 1;
+        return WLK_OK;
+    });
+}
+
+int wlk_diag_beam_step(wlk_session* s, const int64_t* tokens, const int32_t* source_rows, int n_rows) {
+    if (!s || n_rows != s->beam) return fail(WLK_ERR_ARG, "n_rows must equal the session's beam size");
+    const int rc = wlk_beam_step(s, tokens, source_rows);
+    return rc == 1 ? fail(WLK_ERR_STATE, "the session does not qualify for the ancestry step") : rc;
+}
+
+int wlk_session_beam_stats(wlk_session* s, uint64_t* ancestry_steps) {
+    if (!s || !ancestry_steps) return fail(WLK_ERR_ARG, "NULL argument");
+    *ancestry_steps = s->anc_steps;
+    return WLK_OK;
 }
 
 int wlk_sync(wlk_session* s) {

@@ -442,6 +442,11 @@ void launch_kv_append(const LaunchCtx& ctx, const float* qkv, float* kc, float* 
                       const int* offset_dev, int d, int ctx_len);
 // stacked prefills: row r appends its k / v to rows[r].kcache / vcache + layer_off at position rows[r].offset
 void launch_kv_append_rows(const LaunchCtx& ctx, const float* qkv, const StepRow* rows, long layer_off, int n_rows, int d);
+// beam steps over the ancestry table (decoder.hip)
+void launch_decoder_self_attention_anc(const LaunchCtx& ctx, const float* qkv, const float* kc, const float* vc,
+                                       const unsigned char* anc, float* out, int n_rows, const int* offset, int d,
+                                       int n_head, int ctx_len);
+void launch_anc_update(const LaunchCtx& ctx, unsigned char* anc, const int* ctl, const int* offset, int n_rows, int ctx_len);
 void launch_decoder_self_attention(const LaunchCtx& ctx, const float* qkv, const float* kc, const float* vc,
                                    float* out, int n_rows, int n_tok, const int* offset_dev, int d, int n_head,
                                    int ctx_len, const ProgressMark& mark = ProgressMark{});

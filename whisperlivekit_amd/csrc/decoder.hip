@@ -174,19 +174,25 @@ void launch_kv_append_rows(const LaunchCtx& ctx, const float* qkv, const StepRow
 // one 256-byte key/value row, a wave covers 4 rows per instruction, 8 instructions are in flight
 // before the first dot product is folded.
 // ---------------------------------------------------------------------------------------------
+template <bool kAnc>
 __global__ __launch_bounds__(256) void decoder_self_attention_kernel(const float* __restrict__ qkv,
                                                                      const float* __restrict__ kc_in,
                                                                      const float* __restrict__ vc_in,
                                                                      const StepRow* __restrict__ step_rows,
                                                                      const int* __restrict__ offset_p, int d,
                                                                      int ctx_len, int n_tok, float* __restrict__ out,
-                                                                     long layer_off, ProgressMark mark) {
+                                                                     long layer_off, ProgressMark mark,
+                                                                     const unsigned char* __restrict__ anc) {
     // Latency diet (round 4): the query slice comes straight from global memory (16 lanes x float4, no LDS stage and no
     // barrier in front of the keys), and the first 128 keys AND values - a whole decode step's cache in the common case -
     // are requested before anything is waited for; later chunks (long prompts) loop as before.  The key rows of the first
     // chunk do not even wait for the cache length (a device scalar): rows past it are allocated cache memory whose scores
     // are never stored.  The 16-lane dot folds and the wave reductions are VALU butterflies in the original order
     // (wave_ops.h); the leading arguments arrive preloaded in SGPRs.  Same arithmetic, same results.
+    // kAnc (beam steps, one fed token per row): key / value j of query row b lives in the physical cache row
+    // anc[b][j].  The 8 ancestry bytes of the first chunk are requested first of all - one dependent load in front of
+    // the keys, no LDS stage, no barrier; the value loads reuse them.  A row index read from the table is clamped to the
+    // launch's row count, so a table in any state cannot lead a load out of the cache.
     __shared__ float sc[448 + 64];
     __shared__ float red[8];
     __shared__ __attribute__((aligned(16))) float part[16 * 64];
@@ -218,17 +224,34 @@ __global__ __launch_bounds__(256) void decoder_self_attention_kernel(const float
     const gcf_ptr kb = kc + (long)b * ctx_len * d + head * 64 + sub * 4;
     const gcf_ptr vb = vc + (long)b * ctx_len * d + head * 64 + sub * 4;
     float4 kk0[8], vv0[8];
+    const long row_stride = (long)ctx_len * d;
+    const int last_row = (int)gridDim.x - 1;
+    const unsigned char* anc_row = kAnc ? anc + (long)row * ctx_len : nullptr;
+    const gcf_ptr kh = kc + head * 64 + sub * 4, vh = vc + head * 64 + sub * 4;   // kAnc: physical row 0 of this head
+    int a0[8];
+    if (kAnc) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int j = wave * 4 + 16 * u + kq;
+            a0[u] = anc_row[j < ctx_len ? j : 0];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) a0[u] = min(a0[u], last_row);
+    }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int j = wave * 4 + 16 * u + kq;
-        kk0[u] = ldg4(kb + (long)(j < ctx_len ? j : 0) * d);
+        if (kAnc) kk0[u] = ldg4(kh + a0[u] * row_stride + (long)(j < ctx_len ? j : 0) * d);
+        else kk0[u] = ldg4(kb + (long)(j < ctx_len ? j : 0) * d);
     }
     __builtin_amdgcn_sched_barrier(0);   // the key loads go out before the wait for the cache length
     const int n_keys = offset + p + 1;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int j = wave * 4 + 16 * u + kq;
-        vv0[u] = ldg4(vb + (long)(j < n_keys ? j : 0) * d);
+        // (kAnc: a lane past the cache length reads position 0 of its own row - prefill data, finite, weight 0)
+        if (kAnc) vv0[u] = j < n_keys ? ldg4(vh + a0[u] * row_stride + (long)j * d) : ldg4(vb);
+        else vv0[u] = ldg4(vb + (long)(j < n_keys ? j : 0) * d);
     }
 
     float mx = -INFINITY;
@@ -239,6 +262,7 @@ __global__ __launch_bounds__(256) void decoder_self_attention_kernel(const float
             const int j = base + 16 * u + kq;
             const bool ok = j < n_keys;
             if (base == wave * 4) kk[u] = kk0[u];
+            else if (kAnc) kk[u] = ok ? ldg4(kh + min((int)anc_row[j], last_row) * row_stride + (long)j * d) : ldg4(kb);
             else kk[u] = ldg4(kb + (long)(ok ? j : 0) * d);
         }
 #pragma unroll
@@ -282,6 +306,7 @@ __global__ __launch_bounds__(256) void decoder_self_attention_kernel(const float
             const int j = base + 16 * u + kq;
             const bool ok = j < n_keys;
             if (base == wave * 4) vv[u] = vv0[u];
+            else if (kAnc) vv[u] = ok ? ldg4(vh + min((int)anc_row[j], last_row) * row_stride + (long)j * d) : ldg4(vb);
             else vv[u] = ldg4(vb + (long)(ok ? j : 0) * d);
             ww[u] = ok ? sc[j] : 0.f;
         }
@@ -310,8 +335,9 @@ void launch_decoder_self_attention(const LaunchCtx& ctx, const float* qkv, const
                                    int ctx_len, const ProgressMark& mark) {
     if (ctx_len > 448 + 64) throw std::invalid_argument("self-attention: context too long");
     KernelScope ks(ctx, "dec_self_attention");
-    hipLaunchKernelGGL(decoder_self_attention_kernel, dim3(n_rows * n_tok, n_head), dim3(256), 0, ctx.stream, qkv,
-                       kc, vc, (const StepRow*)nullptr, offset, d, ctx_len, n_tok, out, 0L, mark);
+    hipLaunchKernelGGL(decoder_self_attention_kernel<false>, dim3(n_rows * n_tok, n_head), dim3(256), 0, ctx.stream, qkv,
+                       kc, vc, (const StepRow*)nullptr, offset, d, ctx_len, n_tok, out, 0L, mark,
+                       (const unsigned char*)nullptr);
     WLK_HIP(hipGetLastError());
 }
 
@@ -319,9 +345,57 @@ void launch_decoder_self_attention_rows(const LaunchCtx& ctx, const float* qkv, 
                                         float* out, int n_rows, int d, int n_head, int ctx_len) {
     if (ctx_len > 448 + 64) throw std::invalid_argument("self-attention: context too long");
     KernelScope ks(ctx, "dec_self_attention");
-    hipLaunchKernelGGL(decoder_self_attention_kernel, dim3(n_rows, n_head), dim3(256), 0, ctx.stream, qkv,
+    hipLaunchKernelGGL(decoder_self_attention_kernel<false>, dim3(n_rows, n_head), dim3(256), 0, ctx.stream, qkv,
                        (const float*)nullptr, (const float*)nullptr, rows, (const int*)nullptr, d, ctx_len, 1, out,
-                       layer_off, ProgressMark{});
+                       layer_off, ProgressMark{}, (const unsigned char*)nullptr);
+    WLK_HIP(hipGetLastError());
+}
+
+// Beam step: row b's keys / values are gathered through its ancestry row (one fed token per row, rows = hypotheses).
+void launch_decoder_self_attention_anc(const LaunchCtx& ctx, const float* qkv, const float* kc, const float* vc,
+                                       const unsigned char* anc, float* out, int n_rows, const int* offset, int d,
+                                       int n_head, int ctx_len) {
+    if (ctx_len > 448 + 64) throw std::invalid_argument("self-attention: context too long");
+    if (n_rows < 1 || n_rows > 8 || !anc) throw std::invalid_argument("ancestry self-attention: 1..8 rows and a table");
+    KernelScope ks(ctx, "dec_self_attention");
+    hipLaunchKernelGGL(decoder_self_attention_kernel<true>, dim3(n_rows, n_head), dim3(256), 0, ctx.stream, qkv, kc, vc,
+                       (const StepRow*)nullptr, offset, d, ctx_len, 1, out, 0L, ProgressMark{}, anc);
+    WLK_HIP(hipGetLastError());
+}
+
+// Ancestry table of a beam session, anc[b][t] = physical cache row that holds position t of hypothesis b (uint8,
+// [n_rows][ctx_len]).  In front of a step that appends position `offset`: hypothesis b continues hypothesis src[b] of
+// the previous step, so it inherits that row's history, and its own new position is in its own physical row.  Thread t
+// owns column t of every row - it reads the column before it writes it, so the update is in place and needs neither a
+// second table nor a barrier.  ctl = [src 0..6 | fresh]: fresh != 0 means no ancestry step has run since the prefill,
+// i.e. every physical row still holds its own history (the table's previous content is ignored).
+__global__ __launch_bounds__(512) void anc_update_kernel(unsigned char* __restrict__ anc, const int* __restrict__ ctl,
+                                                         const int* __restrict__ offset_p, int n_rows, int ctx_len) {
+    const int t = threadIdx.x;
+    if (t >= ctx_len) return;
+    const int offset = *offset_p;
+    const bool fresh = ctl[7] != 0;
+    int col[7];
+#pragma unroll
+    for (int b = 0; b < 7; ++b) col[b] = b < n_rows ? (fresh ? b : (int)anc[(long)b * ctx_len + t]) : 0;
+#pragma unroll
+    for (int b = 0; b < 7; ++b) {
+        if (b >= n_rows) break;
+        const int sb = ctl[b];
+        int v = b;
+        if (t < offset) {
+#pragma unroll
+            for (int k = 0; k < 7; ++k)
+                if (sb == k) v = col[k];     // (a select chain, not an indexed register array)
+        }
+        anc[(long)b * ctx_len + t] = (unsigned char)min(v, n_rows - 1);
+    }
+}
+
+void launch_anc_update(const LaunchCtx& ctx, unsigned char* anc, const int* ctl, const int* offset, int n_rows, int ctx_len) {
+    if (n_rows < 1 || n_rows > 7 || ctx_len > 512) throw std::invalid_argument("ancestry update: 1..7 rows, context <= 512");
+    KernelScope ks(ctx, "dec_anc_update");
+    hipLaunchKernelGGL(anc_update_kernel, dim3(1), dim3(512), 0, ctx.stream, anc, ctl, offset, n_rows, ctx_len);
     WLK_HIP(hipGetLastError());
 }
 

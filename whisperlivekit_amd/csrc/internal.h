@@ -267,6 +267,14 @@ struct wlk_session {
     unsigned step_seq = 0;
     uint64_t step_ns = 0, step_launch_ns = 0, step_count = 0;   // wlk_session_step_stats (WLK_STEP_TIMING=1: also printed when the session is destroyed)
 
+    // beam sessions (2..7 rows): ancestry table of the self-attention cache, [beam][n_text_ctx] physical row indices
+    // (wlk_beam_step; decoder.hip), the captured single-token step that reads through it, and whether such a step has
+    // run since the last prefill (the physical rows then no longer are the hypotheses: see wlk_decode / wlk_kv_reorder)
+    unsigned char* anc = nullptr;
+    hipGraphExec_t bstep_exec[2] = {nullptr, nullptr};  // per KV buffer, as step_exec
+    bool anc_live = false;
+    uint64_t anc_steps = 0;                              // wlk_session_beam_stats
+
     wlk::LaunchCtx ctx() { return wlk::LaunchCtx{stream, prof_on ? &prof : nullptr}; }
     // word-timestamp alignment (word_align.hip): the prefill leaves the alignment heads' raw scores in the window, and
     // its workspace (grown on demand)
@@ -326,6 +334,10 @@ inline void wlk_wait_step_flags(hipStream_t stream, const wlk::StepResult* res, 
 // graph replay without copy nodes.  Returns 1 (and does nothing) when the session / step does not qualify.
 int wlk_step_select(wlk_session* s, int64_t token, const int32_t* adj_ids, const float* adj_deltas, int n_adj,
                     int content_mel_len, float* top_logprobs2, int32_t* top_ids2, int32_t* frame);
+// One single-token decoder forward of a beam session (2..7 rows) over the ancestry table: what wlk_kv_reorder(source_rows)
+// followed by wlk_decode(first = 0) computes, as one graph replay that moves no K/V bytes.  Returns 1 (and does nothing)
+// when the session does not qualify; the caller then makes those two calls.
+int wlk_beam_step(wlk_session* s, const int64_t* tokens, const int32_t* source_rows);
 // wlk_no_speech_prob + wlk_select of the first step of an infer behind one synchronisation (the read-out runs whatever the
 // probability turns out to be; a caller that stops on no-speech simply ignores it)
 int wlk_select_first(wlk_session* s, int no_speech_token, const int32_t* adj_row, const int32_t* adj_ids,

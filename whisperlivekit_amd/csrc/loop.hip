@@ -8,6 +8,7 @@
 // (plain integer logic, no GPU), driven either by wlk_decode_until_stop() over one session's kernels
 // or by the cross-session batch engine (engine.hip) over rows = sessions.  The wlk_job_* entry
 // points expose the same logic without a GPU so the CPU tests can drive it with oracle numerics.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -54,6 +55,12 @@ bool DecodeJob::no_speech(float prob) {
 }
 
 void DecodeJob::adjustments(std::vector<int32_t>& ids, std::vector<float>& deltas) const {
+    loop_adjustments(P, seq, fresh, blank_ids, suppress_ids, ids, deltas);
+}
+
+void loop_adjustments(const wlk_loop_params& P, const std::vector<int64_t>& seq, bool fresh,
+                      const std::vector<int32_t>& blank_ids, const std::vector<int32_t>& suppress_ids,
+                      std::vector<int32_t>& ids, std::vector<float>& deltas) {
     std::map<int32_t, float> adj;                      // one entry per token id (the device applies them in parallel)
     const float ninf = -INFINITY;
     if (fresh)
@@ -158,6 +165,142 @@ void DecodeJob::fill(wlk_loop_result* r) const {
     r->decode_calls = produced - (stop == WLK_STOP_BUDGET ? 1 : 0);
 }
 
+// ---- beams 2-7 --------------------------------------------------------------------------------------------------------
+BeamJob::BeamJob(const wlk_loop_params& p, int beam, const int64_t* tokens, int n_tok, const int32_t* suppress, int n_sup,
+                 const int32_t* blank, int n_blank)
+    : P(p), B(beam), rows((size_t)beam, std::vector<int64_t>(tokens, tokens + n_tok)), n_before(n_tok),
+      suppress_ids(suppress, suppress + n_sup), blank_ids(blank, blank + n_blank), sums((size_t)beam, 0.f),
+      src((size_t)beam), last_attend(p.last_attend_frame) {
+    for (int b = 0; b < beam; ++b) src[(size_t)b] = b;
+}
+
+bool BeamJob::begin_step() {
+    if (stop != WLK_STOP_NONE) return false;
+    if ((int)rows[0].size() >= P.max_text_len) {
+        stop = WLK_STOP_CONTEXT_FULL;
+        n_keep = (int)rows[0].size() - n_before;
+        return false;
+    }
+    produced += 1;
+    if (produced > P.budget) {
+        n_keep = 0;
+        stop = WLK_STOP_BUDGET;
+        return false;
+    }
+    return true;
+}
+
+bool BeamJob::no_speech(float prob) {
+    no_speech_prob = prob;
+    if (prob > P.no_speech_threshold) {
+        stop = WLK_STOP_NO_SPEECH;
+        return true;
+    }
+    return false;
+}
+
+void BeamJob::adjustments(std::vector<int32_t>& ids, std::vector<float>& deltas) const {
+    loop_adjustments(P, rows[0], fresh, blank_ids, suppress_ids, ids, deltas);
+}
+
+int BeamJob::consume(const float* top_lp, const int32_t* top_ids, const int32_t* frames) {
+    fresh = false;
+    const int K = B + 1;
+    // candidates in the reference's dict order: a sequence seen again keeps the place of its first insertion and takes
+    // the later row's score and source (rows are equal only on the first step, where all are copies of the prompt)
+    struct Cand { int cls; int32_t id; float score; int row; };
+    std::vector<int> cls((size_t)B);
+    for (int j = 0; j < B; ++j) {
+        cls[(size_t)j] = j;
+        for (int i = 0; i < j; ++i)
+            if (rows[(size_t)i] == rows[(size_t)j]) { cls[(size_t)j] = i; break; }
+    }
+    std::vector<Cand> cand;
+    cand.reserve((size_t)B * K);
+    for (int j = 0; j < B; ++j)
+        for (int c = 0; c < K; ++c) {
+            const int32_t id = top_ids[j * K + c];
+            const float score = sums[(size_t)j] + top_lp[j * K + c];      // fp32 + fp32
+            bool seen = false;
+            for (Cand& e : cand)
+                if (e.cls == cls[(size_t)j] && e.id == id) { e.score = score; e.row = j; seen = true; break; }
+            if (!seen) cand.push_back(Cand{cls[(size_t)j], id, score, j});
+        }
+    std::stable_sort(cand.begin(), cand.end(), [](const Cand& a, const Cand& b) { return a.score > b.score; });
+    std::vector<std::vector<int64_t>> nxt;
+    std::vector<float> nsum;
+    std::vector<int32_t> nsrc;
+    std::vector<const Cand*> fin;       // this step's finished candidates, already in descending score order
+    for (const Cand& e : cand) {
+        if (e.id == P.eot) { fin.push_back(&e); continue; }
+        std::vector<int64_t> seq = rows[(size_t)e.row];
+        seq.push_back(e.id);
+        nxt.push_back(std::move(seq));
+        nsum.push_back(e.score);
+        nsrc.push_back(e.row);
+        if ((int)nxt.size() == B) break;
+    }
+    if ((int)nxt.size() < B) return -1;
+    const int max_candidates = B;       // round(beam_size * patience), patience 1.0
+    for (const Cand* e : fin) {
+        if ((int)fin_seqs.size() >= max_candidates) break;
+        std::vector<int64_t> seq = rows[(size_t)e->row];
+        seq.push_back(e->id);
+        bool seen = false;
+        for (size_t i = 0; i < fin_seqs.size(); ++i)
+            if (fin_seqs[i] == seq) { fin_scores[i] = e->score; seen = true; break; }
+        if (!seen) {
+            fin_seqs.push_back(std::move(seq));
+            fin_scores.push_back(e->score);
+        }
+    }
+    completed = (int)fin_seqs.size() >= max_candidates;
+    rows = std::move(nxt);
+    sums = std::move(nsum);
+    src = std::move(nsrc);
+
+    const int frame = frames[0];        // physical row 0, read before the reorder
+    const std::vector<int64_t>& seq = rows[0];
+    const int n = (int)seq.size();
+    step_tokens.push_back((int32_t)seq[(size_t)n - 1]);
+    step_frames.push_back(frame);
+    step_sums.push_back(sums[0]);
+    n_keep = n - n_before;
+    if (completed) {
+        n_keep -= 1;
+        stop = WLK_STOP_COMPLETED;
+        return 0;
+    }
+    if (!P.is_last && last_attend - frame > P.rewind_threshold) {
+        if (n > 1 && seq[(size_t)n - 2] >= P.dec_pad) {
+            last_attend = frame;
+        } else {
+            last_attend = -P.rewind_threshold;
+            n_keep = 0;
+            stop = WLK_STOP_REWIND;
+            return 0;
+        }
+    } else {
+        last_attend = frame;
+    }
+    if (P.content_mel_len - frame <= (P.is_last ? 4 : P.frame_threshold)) {
+        n_keep -= 1;
+        stop = WLK_STOP_FRAME;
+        return 0;
+    }
+    return 1;
+}
+
+void BeamJob::fill(wlk_loop_result* r) const {
+    r->n_steps = (int32_t)step_tokens.size();
+    r->n_new_tokens = n_keep;
+    r->stop_reason = stop;
+    r->last_attend_frame = last_attend;
+    r->no_speech_prob = no_speech_prob;
+    r->sum_logprob = sums[0];
+    r->decode_calls = produced - (stop == WLK_STOP_BUDGET ? 1 : 0);
+}
+
 }  // namespace wlk
 
 using namespace wlk;
@@ -197,6 +340,29 @@ static int copy_result(const DecodeJob& j, wlk_loop_result* result, int64_t* new
         if (step_tokens) step_tokens[i] = j.step_tokens[i];
         if (step_frames) step_frames[i] = j.step_frames[i];
         if (step_sum_logprobs) step_sum_logprobs[i] = j.step_sums[i];
+    }
+    return WLK_OK;
+}
+
+struct wlk_beam_job {
+    BeamJob job;
+    std::vector<int32_t> ids;
+    std::vector<float> deltas;
+    wlk_beam_job(const wlk_loop_params& p, int beam, const int64_t* t, int n, const int32_t* s, int ns, const int32_t* b, int nb)
+        : job(p, beam, t, n, s, ns, b, nb) {}
+};
+
+static int copy_beam_result(const BeamJob& j, wlk_loop_result* result, int64_t* new_tokens, int32_t* step_tokens,
+                            int32_t* step_frames, float* step_sum_logprobs, int cap) {
+    if (!result) return loop_fail(WLK_ERR_ARG, "decode loop: result is NULL");
+    j.fill(result);
+    if (result->n_steps > cap || result->n_new_tokens > cap) return loop_fail(WLK_ERR_CAPACITY, "decode loop: output capacity too small");
+    for (int i = 0; i < result->n_new_tokens; ++i)
+        if (new_tokens) new_tokens[i] = j.rows[0][(size_t)(j.n_before + i)];
+    for (int i = 0; i < result->n_steps; ++i) {
+        if (step_tokens) step_tokens[i] = j.step_tokens[(size_t)i];
+        if (step_frames) step_frames[i] = j.step_frames[(size_t)i];
+        if (step_sum_logprobs) step_sum_logprobs[i] = j.step_sums[(size_t)i];
     }
     return WLK_OK;
 }
@@ -252,6 +418,132 @@ int wlk_job_result(wlk_decode_job* j, wlk_loop_result* result, int64_t* new_toke
 int wlk_job_destroy(wlk_decode_job* j) {
     delete j;
     return WLK_OK;
+}
+
+int wlk_beam_job_create(const wlk_loop_params* p, int beam, const int64_t* tokens, int n_tok, const int32_t* suppress_ids,
+                        int n_suppress, const int32_t* blank_ids, int n_blank, wlk_beam_job** out) {
+    if (int rc = check_loop_args(p, tokens, n_tok, suppress_ids, n_suppress, blank_ids, n_blank)) return rc;
+    if (beam < 2 || beam > 7) return loop_fail(WLK_ERR_ARG, "beam decode loop: beam must be in 2..7");
+    if (p->n_force != 0) return loop_fail(WLK_ERR_ARG, "beam decode loop: teacher forcing is defined for beam 1 only");
+    if (!out) return loop_fail(WLK_ERR_ARG, "decode loop: out is NULL");
+    *out = new wlk_beam_job(*p, beam, tokens, n_tok, suppress_ids, n_suppress, blank_ids, n_blank);
+    return WLK_OK;
+}
+
+int wlk_beam_job_begin_step(wlk_beam_job* j, int32_t* n_feed) {
+    if (!j || !n_feed) return loop_fail(WLK_ERR_ARG, "decode loop: NULL argument");
+    const bool first = j->job.fresh;
+    if (!j->job.begin_step()) {
+        *n_feed = 0;
+        return WLK_OK;
+    }
+    *n_feed = first ? (int32_t)j->job.rows[0].size() : 1;
+    return WLK_OK;
+}
+
+int wlk_beam_job_no_speech(wlk_beam_job* j, float prob, int32_t* stops) {
+    if (!j || !stops) return loop_fail(WLK_ERR_ARG, "decode loop: NULL argument");
+    *stops = j->job.no_speech(prob) ? 1 : 0;
+    return WLK_OK;
+}
+
+int wlk_beam_job_adjustments(wlk_beam_job* j, const int32_t** ids, const float** deltas, int32_t* n) {
+    if (!j || !ids || !deltas || !n) return loop_fail(WLK_ERR_ARG, "decode loop: NULL argument");
+    j->job.adjustments(j->ids, j->deltas);
+    *ids = j->ids.data();
+    *deltas = j->deltas.data();
+    *n = (int32_t)j->ids.size();
+    return WLK_OK;
+}
+
+int wlk_beam_job_consume(wlk_beam_job* j, const float* top_logprobs, const int32_t* top_ids, const int32_t* frames,
+                         int32_t* goes_on) {
+    if (!j || !top_logprobs || !top_ids || !frames || !goes_on) return loop_fail(WLK_ERR_ARG, "decode loop: NULL argument");
+    if (j->job.stop != WLK_STOP_NONE) return loop_fail(WLK_ERR_STATE, "beam decode loop: the loop is over");
+    const int rc = j->job.consume(top_logprobs, top_ids, frames);
+    if (rc < 0) return loop_fail(WLK_ERR_ARG, "beam decode loop: fewer live candidates than beams");
+    *goes_on = rc;
+    return WLK_OK;
+}
+
+int wlk_beam_job_state(wlk_beam_job* j, int64_t* rows, int cap, int32_t* row_len, float* sum_logprobs, int32_t* source_rows,
+                       int32_t* completed) {
+    if (!j || !row_len) return loop_fail(WLK_ERR_ARG, "decode loop: NULL argument");
+    const BeamJob& job = j->job;
+    const int n = (int)job.rows[0].size();
+    *row_len = n;
+    if (rows) {
+        if (cap < job.B * n) return loop_fail(WLK_ERR_CAPACITY, "beam decode loop: row buffer too small");
+        for (int b = 0; b < job.B; ++b)
+            for (int i = 0; i < n; ++i) rows[(size_t)b * n + i] = job.rows[(size_t)b][(size_t)i];
+    }
+    for (int b = 0; b < job.B; ++b) {
+        if (sum_logprobs) sum_logprobs[b] = job.sums[(size_t)b];
+        if (source_rows) source_rows[b] = job.src[(size_t)b];
+    }
+    if (completed) *completed = job.completed ? 1 : 0;
+    return WLK_OK;
+}
+
+int wlk_beam_job_result(wlk_beam_job* j, wlk_loop_result* result, int64_t* new_tokens, int32_t* step_tokens,
+                        int32_t* step_frames, float* step_sum_logprobs, int cap) {
+    if (!j) return loop_fail(WLK_ERR_ARG, "decode loop: job is NULL");
+    return copy_beam_result(j->job, result, new_tokens, step_tokens, step_frames, step_sum_logprobs, cap);
+}
+
+int wlk_beam_job_destroy(wlk_beam_job* j) {
+    delete j;
+    return WLK_OK;
+}
+
+int wlk_decode_beam_until_stop(wlk_session* s, const int64_t* tokens, int n_tok, const wlk_loop_params* p,
+                               const int32_t* suppress_ids, int n_suppress, const int32_t* blank_ids, int n_blank,
+                               wlk_loop_result* result, int64_t* new_tokens, int32_t* step_tokens, int32_t* step_frames,
+                               float* step_sum_logprobs, int cap) {
+    if (!s) return loop_fail(WLK_ERR_ARG, "decode loop: session is NULL");
+    if (int rc = check_loop_args(p, tokens, n_tok, suppress_ids, n_suppress, blank_ids, n_blank)) return rc;
+    const int B = s->beam, K = B + 1;
+    if (B < 2 || B > 7) return loop_fail(WLK_ERR_ARG, "beam decode loop: the session's beam must be in 2..7");
+    if (p->n_force != 0) return loop_fail(WLK_ERR_ARG, "beam decode loop: teacher forcing is defined for beam 1 only");
+    BeamJob job(*p, B, tokens, n_tok, suppress_ids, n_suppress, blank_ids, n_blank);
+    std::vector<int32_t> ids, adj_rows, top((size_t)B * K), frames((size_t)B);
+    std::vector<float> deltas, lp((size_t)B * K), prob((size_t)B);
+    std::vector<int64_t> feed;
+    while (job.begin_step()) {
+        const bool first = job.fresh;
+        if (first) {
+            feed.clear();
+            for (int b = 0; b < B; ++b) feed.insert(feed.end(), tokens, tokens + n_tok);   // B copies of the prompt
+            if (int rc = wlk_decode(s, feed.data(), B, n_tok, 1, p->sot_index)) return rc;
+        } else {
+            feed.resize((size_t)B);
+            for (int b = 0; b < B; ++b) feed[(size_t)b] = job.rows[(size_t)b].back();
+            // the step over the beam ancestry table (no K/V bytes move); 1 = this session does not qualify: the
+            // per-token calls, reorder first (the update that chose job.src came before this decode)
+            const int rc = wlk_beam_step(s, feed.data(), job.src.data());
+            if (rc == 1) {
+                if (int rc2 = wlk_kv_reorder(s, job.src.data(), B)) return rc2;
+                if (int rc2 = wlk_decode(s, feed.data(), B, 1, 0, p->sot_index)) return rc2;
+            } else if (rc != WLK_OK) {
+                return rc;
+            }
+        }
+        job.adjustments(ids, deltas);
+        adj_rows.assign(ids.size(), -1);
+        if (first && p->no_speech_token >= 0) {
+            if (int rc = wlk_select_first(s, p->no_speech_token, adj_rows.data(), ids.data(), deltas.data(), (int)ids.size(), K,
+                                          p->content_mel_len, prob.data(), lp.data(), top.data(), frames.data()))
+                return rc;
+            if (job.no_speech(prob[0])) break;
+        } else if (int rc = wlk_select(s, adj_rows.data(), ids.data(), deltas.data(), (int)ids.size(), K, p->content_mel_len,
+                                       lp.data(), top.data(), frames.data())) {
+            return rc;
+        }
+        const int go = job.consume(lp.data(), top.data(), frames.data());
+        if (go < 0) return loop_fail(WLK_ERR_STATE, "beam decode loop: fewer live candidates than beams");
+        if (go == 0) break;
+    }
+    return copy_beam_result(job, result, new_tokens, step_tokens, step_frames, step_sum_logprobs, cap);
 }
 
 int wlk_decode_until_stop(wlk_session* s, const int64_t* tokens, int n_tok, const wlk_loop_params* p,

@@ -375,6 +375,34 @@ class HipSession:
                                                   blank.size, C.byref(res), vp(new), vp(st), vp(sf), vp(ss), cap))
         return LoopOutcome(res, new, st, sf, ss)
 
+    def decode_beam_until_stop(self, tokens: Sequence[int], params: "_lib.LoopParams", suppress_ids: Sequence[int],
+                               blank_ids: Sequence[int]) -> "LoopOutcome":
+        """The same loop for the beam decoder, beams 2-7 (wlk_decode_beam_until_stop); ``tokens`` is one row's prompt."""
+        t = np.ascontiguousarray(tokens, dtype=np.int64).reshape(-1)
+        sup = np.ascontiguousarray(suppress_ids, dtype=np.int32)
+        blank = np.ascontiguousarray(blank_ids, dtype=np.int32)
+        cap = int(params.max_text_len) + 8
+        res = _lib.LoopResult()
+        new = np.empty(cap, np.int64)
+        st, sf = np.empty(cap, np.int32), np.empty(cap, np.int32)
+        ss = np.empty(cap, np.float32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        _lib.check(self.lib.wlk_decode_beam_until_stop(self._h, vp(t), t.size, C.byref(params), vp(sup), sup.size, vp(blank),
+                                                       blank.size, C.byref(res), vp(new), vp(st), vp(sf), vp(ss), cap))
+        return LoopOutcome(res, new, st, sf, ss)
+
+    def beam_step(self, tokens: Sequence[int], source_rows: Sequence[int]) -> None:
+        """Diagnostic: one single-token forward over the beam ancestry table (wlk_diag_beam_step)."""
+        t = np.ascontiguousarray(tokens, dtype=np.int64).reshape(-1)
+        src = np.ascontiguousarray(source_rows, dtype=np.int32).reshape(-1)
+        _lib.check(self.lib.wlk_diag_beam_step(self._h, t.ctypes.data_as(C.c_void_p), src.ctypes.data_as(C.c_void_p), t.size))
+
+    def beam_stats(self) -> Dict[str, int]:
+        """Single-token steps of this session that ran over the ancestry table (wlk_session_beam_stats)."""
+        n = C.c_uint64()
+        _lib.check(self.lib.wlk_session_beam_stats(self._h, C.byref(n)))
+        return dict(ancestry_steps=int(n.value))
+
     def attach_engine(self) -> None:
         _lib.check(self.lib.wlk_engine_attach(self._h))
 

@@ -287,8 +287,10 @@ class AlignAttPolicy:
         n_before = tokens.shape[1]
         budget = max(50, int(self.segments_len() * 15 * 1.5))     # align_att_base.py:200-201
         device_loop = getattr(self, "device_loop_available", None)
-        if device_loop is not None and device_loop():
-            # the per-token loop below runs inside the library (wlk_decode_until_stop)
+        beam_loop = getattr(self, "beam_loop_available", None)
+        if (device_loop is not None and device_loop()) or (beam_loop is not None and beam_loop()):
+            # the per-token loop below runs inside the library (wlk_decode_until_stop; beams 2-7, opt-in:
+            # wlk_decode_beam_until_stop)
             out = self._decode_until_stop(tokens, content_mel_len, is_last, budget)
             stamps = [f * 0.02 + st.cumulative_time_offset for f in out.step_frames]
             st.last_attend_frame = out.last_attend_frame
