@@ -544,6 +544,42 @@ int wlk_engine_prefill_stats(wlk_model* m, uint64_t* batches, uint64_t* sessions
 int wlk_diag_encoder_attention_time(int t, int d, int n_head, int k_splits, int reps, float* us_per_launch);
 /* qkv [t, 3d] with q and k pre-scaled -> softmax(q k^T) v per 64-wide head, out [t, d] */
 int wlk_diag_encoder_attention(const float* qkv, int t, int d, int n_head, float* out);
+/* Token selection and AlignAtt read-out (csrc/select.hip, csrc/align_body.h) on host data, through ONE chosen route.  The
+ * launchers are the ones a decode step uses, unchanged; logits, adjustments and the alignment window are the caller's.
+ *   route 0  launch_logsoftmax_topk + launch_alignatt (LDS arg-max where the window fits) [+ launch_token_prob]
+ *   route 1  as 0 with the read-out's second stage forced to align_argmax_kernel (no LDS)
+ *   route 2  launch_select_fused(early_z = false), the no-speech block riding in its second launch when asked for
+ *   route 3  align_zscore_kernel, then launch_select_fused(early_z = true) over those z rows
+ *   route 4  launch_logsoftmax_topk + launch_alignatt_rows: row r is a beam-0 session of its own with its own counters
+ * Row r of the logits is beam r of the window (n_beam = n_rows).  prefill_rows / n_single / newest_row / content_len are
+ * arrays of n_rows entries; routes 0-3 have one set for all rows and return WLK_ERR_ARG when the entries differ.  A route
+ * that cannot run the shape (fused form refusing, early form with a no-speech request, counters that leave the ring)
+ * returns WLK_ERR_ARG with a message in wlk_diag_last_error(); it never runs another route instead.  ns_token < 0: no
+ * no-speech probability (ns_logits / ns_probs may be NULL).  All pointers are host memory; the call is synchronous. */
+typedef struct wlk_diag_select_args {
+    int32_t route, n_rows, n_vocab, k;
+    const float* logits;            /* [n_rows][n_vocab] */
+    const int32_t* adj_row;         /* [n_adj] row of the adjustment, < 0 = every row */
+    const int32_t* adj_ids;         /* [n_adj] unique per row */
+    const float* adj_deltas;        /* [n_adj] added to the logit (-inf suppresses) */
+    int32_t n_adj;
+    int32_t n_align, ring_rows, T, single_base;
+    const float* ring;              /* [n_align][n_rows][ring_rows][T] */
+    const int32_t* prefill_rows;    /* [n_rows] window = ring rows [0, prefill_rows) + single_base + [0, n_single) */
+    const int32_t* n_single;        /* [n_rows] */
+    const int32_t* newest_row;      /* [n_rows] ring row of the newest query row */
+    const int32_t* content_len;     /* [n_rows] the arg-max runs over frames [0, content_len) */
+    int32_t ns_token;
+    const float* ns_logits;         /* [n_rows][n_vocab] */
+    float* top_logprobs;            /* out [n_rows][k] */
+    int32_t* top_ids;               /* out [n_rows][k] */
+    int32_t* frames;                /* out [n_rows] */
+    float* attn_last;               /* out [n_rows][T] head mean of the median-filtered z rows */
+    float* z;                       /* out [n_rows][n_align][T] */
+    float* ns_probs;                /* out [n_rows] */
+    float* logits_out;              /* out [n_rows][n_vocab] the logits as the call left them in memory (adjusted) */
+} wlk_diag_select_args;
+int wlk_diag_select(const wlk_diag_select_args* args);
 /* the VALU wave butterflies of csrc/wave_ops.h (DPP / v_permlane{16,32}_swap) against the __shfl_xor loops they replace,
  * on one wave of 64 floats: ten rows of 64 results each (sum, max, 16-lane sum, xor 1 .. 32 exchanges, arg-max index) */
 int wlk_diag_wave_ops(const float* in64, float* out640, float* ref640);

@@ -74,6 +74,16 @@ class LoopParams(C.Structure):
             self.force_step[i], self.force_token[i], self.force_frame[i] = int(step), int(token), int(frame)
 
 
+class DiagSelectArgs(C.Structure):
+    """wlk_diag_select_args (include/wlk_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("route", "n_rows", "n_vocab", "k")] + [
+        ("logits", C.c_void_p), ("adj_row", C.c_void_p), ("adj_ids", C.c_void_p), ("adj_deltas", C.c_void_p),
+        ("n_adj", C.c_int32)] + [(n, C.c_int32) for n in ("n_align", "ring_rows", "T", "single_base")] + [
+        (n, C.c_void_p) for n in ("ring", "prefill_rows", "n_single", "newest_row", "content_len")] + [
+        ("ns_token", C.c_int32)] + [(n, C.c_void_p) for n in (
+            "ns_logits", "top_logprobs", "top_ids", "frames", "attn_last", "z", "ns_probs", "logits_out")]
+
+
 class LoopResult(C.Structure):
     """wlk_loop_result (include/wlk_hip.h)"""
     _fields_ = [("n_steps", C.c_int32), ("n_new_tokens", C.c_int32), ("stop_reason", C.c_int32),
@@ -248,6 +258,7 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_encoder_attention_x3": (cint, [p, cint, cint, cint, p]),
         "wlk_diag_encoder_attention_x3_time": (cint, [cint, cint, cint, cint, C.POINTER(C.c_float)]),
         "wlk_diag_qkv_x3_attention": (cint, [p, p, p, cint, cint, cint, C.c_float, p, p]),
+        "wlk_diag_select": (cint, [C.POINTER(DiagSelectArgs)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -293,6 +304,7 @@ EXPORTED_SYMBOLS = (
     "wlk_diag_encoder_attention", "wlk_diag_encoder_attention_time", "wlk_diag_wave_ops", "wlk_diag_env_refresh",
     "wlk_diag_linear_x3", "wlk_diag_linear_x3_time", "wlk_diag_layernorm_x3",
     "wlk_diag_encoder_attention_x3", "wlk_diag_encoder_attention_x3_time", "wlk_diag_qkv_x3_attention",
+    "wlk_diag_select",
 )
 
 

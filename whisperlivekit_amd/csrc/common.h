@@ -594,6 +594,10 @@ struct AlignArgs {
     float* part = nullptr;           // early z-score form: [n_beam][64] (value, frame) pairs, one per 256-frame block
 };
 void launch_alignatt(const LaunchCtx& ctx, const AlignArgs& a);
+// the two launches of launch_alignatt on their own (diag.hip: wlk_diag_select): the z-score alone, and the second stage
+// in its form without LDS whatever the window size
+void launch_align_zscore(const LaunchCtx& ctx, const AlignArgs& a);
+void launch_align_argmax_plain(const LaunchCtx& ctx, const AlignArgs& a);
 // top-k (with adjustments) and AlignAtt read-out of the same rows in two launches instead of four; returns false when
 // the configuration needs the separate kernels (no alignment heads, window too large for LDS, WLK_SELECT_FUSED=0)
 bool launch_select_fused(const LaunchCtx& ctx, float* logits, int n_vocab, int n_rows, int k, float* top_vals, int* top_ids,

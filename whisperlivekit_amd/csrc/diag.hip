@@ -489,4 +489,144 @@ int wlk_diag_encoder_attention_x3_time(int t, int d, int n_head, int reps, float
     });
 }
 
+/* Token selection and AlignAtt read-out (select.hip) on host data through one chosen route: the launchers a decode step
+ * uses, unchanged, on caller-chosen logits, adjustments and alignment window (see include/wlk_hip.h) */
+int wlk_diag_select(const wlk_diag_select_args* q) {
+    std::string bad;
+    auto arg_check = [&]() -> bool {
+        auto fail = [&](const std::string& m) { bad = "wlk_diag_select: " + m; return false; };
+        if (!q) return fail("null arguments");
+        if (q->route < 0 || q->route > 4) return fail("route must be 0..4");
+        if (q->n_rows < 1 || q->n_rows > 64 || q->n_vocab < 1 || q->k < 1 || q->k > 8) return fail("n_rows in [1, 64], n_vocab >= 1, k in [1, 8]");
+        if (!q->logits || !q->top_logprobs || !q->top_ids || !q->frames || !q->attn_last || !q->z || !q->logits_out)
+            return fail("null logits / output pointer");
+        if (q->n_adj < 0 || (q->n_adj > 0 && (!q->adj_row || !q->adj_ids || !q->adj_deltas))) return fail("bad adjustment triple");
+        for (int i = 0; i < q->n_adj; ++i)
+            if (q->adj_ids[i] < 0 || q->adj_ids[i] >= q->n_vocab || q->adj_row[i] >= q->n_rows) return fail("adjustment outside the logits");
+        if (q->n_align < 1 || q->n_align > 64 || q->T < 1 || q->ring_rows < 1 || !q->ring) return fail("n_align in [1, 64], T >= 1, ring_rows >= 1");
+        if (!q->prefill_rows || !q->n_single || !q->newest_row || !q->content_len) return fail("null window counters");
+        if (q->single_base < 0) return fail("single_base < 0");
+        for (int r = 0; r < q->n_rows; ++r) {
+            const int pre = q->prefill_rows[r], ns = q->n_single[r], nw = q->newest_row[r], cl = q->content_len[r];
+            if (pre < 0 || ns < 0 || pre + ns < 1 || pre > q->ring_rows || (ns > 0 && q->single_base + ns > q->ring_rows) || nw < 0 ||
+                nw >= q->ring_rows || cl < 0 || cl > q->T)
+                return fail("window counters of row " + std::to_string(r) + " leave the ring");
+            if (q->route != 4 && (pre != q->prefill_rows[0] || ns != q->n_single[0] || nw != q->newest_row[0] || cl != q->content_len[0]))
+                return fail("routes 0-3 take one set of window counters and one content_len for all rows");
+        }
+        if (q->ns_token >= 0 && (q->ns_token >= q->n_vocab || !q->ns_logits || !q->ns_probs)) return fail("bad no-speech request");
+        if (q->ns_token >= 0 && q->route == 3) return fail("the early form (route 3) carries no no-speech block");
+        if (q->route == 3 && (q->T + 255) / 256 > 64) return fail("the early form (route 3) needs T <= 16384");
+        return true;
+    };
+    if (!arg_check()) {
+        g_diag_error = bad;
+        return WLK_ERR_ARG;
+    }
+    bool refused = false;
+    const int rc = run([&]() {
+        const int R = q->n_rows, V = q->n_vocab, k = q->k, T = q->T, A = q->n_align;
+        const bool ns = q->ns_token >= 0;
+        struct Stream {
+            hipStream_t s = nullptr;
+            Stream() { WLK_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+            ~Stream() { (void)hipStreamDestroy(s); }
+        } st;
+        // z carries a guard band on both sides: below T = 4 the read-out kernels form (and discard) median taps whose
+        // reflected index lies up to three floats outside the row
+        constexpr size_t kGuard = 64;
+        const size_t ring_floats = (size_t)A * R * q->ring_rows * T;
+        DevBuf L((size_t)R * V, q->logits), NL(ns ? (size_t)R * V : 1, ns ? q->ns_logits : nullptr), NP(R), TV((size_t)R * k),
+            RG(ring_floats, q->ring), Z((size_t)R * A * T + 2 * kGuard), AL((size_t)R * T), PT((size_t)R * 64 * 2),
+            SC(topk_scratch_bytes(R) / sizeof(float) + 1);
+        struct IntBuf {
+            int* p = nullptr;
+            IntBuf(size_t n, const int32_t* host = nullptr) {
+                WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(int)));
+                if (host) WLK_HIP(hipMemcpy(p, host, n * sizeof(int), hipMemcpyHostToDevice));
+            }
+            ~IntBuf() { (void)hipFree(p); }
+        } TI((size_t)R * k), FR(R), AR(q->n_adj, q->adj_row), AI(q->n_adj, q->adj_ids);
+        DevBuf AD(q->n_adj, q->adj_deltas);
+        WLK_HIP(hipMemset(Z.p, 0, ((size_t)R * A * T + 2 * kGuard) * sizeof(float)));
+        WLK_HIP(hipMemset(FR.p, 0xff, R * sizeof(int)));
+        WLK_HIP(hipDeviceSynchronize());   // the uploads and fills above ran on the legacy stream; st does not wait for it
+        LaunchCtx ctx;
+        ctx.stream = st.s;
+        AlignArgs a;
+        a.ring = RG.p; a.n_align = A; a.n_beam = R; a.ring_rows = q->ring_rows; a.T = T;
+        a.prefill_rows = q->prefill_rows[0]; a.n_single = q->n_single[0]; a.newest_row = q->newest_row[0];
+        a.single_base = q->single_base; a.content_len = q->content_len[0];
+        a.z = Z.p + kGuard; a.attn_last = AL.p; a.frames = FR.p;
+        const int *adj_row = q->n_adj ? AR.p : nullptr, *adj_ids = q->n_adj ? AI.p : nullptr;
+        const float* adj_deltas = q->n_adj ? AD.p : nullptr;
+        StepRow* rows_dev = nullptr;
+        struct RowsFree {
+            StepRow*& p;
+            ~RowsFree() { (void)hipFree(p); }
+        } rows_free{rows_dev};
+        switch (q->route) {
+        case 0:
+        case 1:
+            launch_logsoftmax_topk(ctx, L.p, V, R, k, TV.p, TI.p, SC.p, adj_row, adj_ids, adj_deltas, q->n_adj);
+            if (q->route == 0) {
+                launch_alignatt(ctx, a);
+            } else {
+                launch_align_zscore(ctx, a);
+                launch_align_argmax_plain(ctx, a);
+            }
+            if (ns) launch_token_prob(ctx, NL.p, V, R, q->ns_token, NP.p);
+            break;
+        case 2:
+            refused = !launch_select_fused(ctx, L.p, V, R, k, TV.p, TI.p, SC.p, adj_row, adj_ids, adj_deltas, q->n_adj, a, StepHostOut{},
+                                           ns ? NL.p : nullptr, ns ? q->ns_token : 0, ns ? NP.p : nullptr, false);
+            break;
+        case 3:
+            a.part = PT.p;
+            if (!select_fused_applicable(R, k, a)) {
+                refused = true;
+                break;
+            }
+            launch_align_zscore(ctx, a);
+            refused = !launch_select_fused(ctx, L.p, V, R, k, TV.p, TI.p, SC.p, adj_row, adj_ids, adj_deltas, q->n_adj, a, StepHostOut{},
+                                           nullptr, 0, nullptr, true);
+            break;
+        default: {
+            // row r = a beam-0 session whose window is beam r of the caller's ring: with the ring-row stride of the whole
+            // beam group, rows[r].ring + (head * stride) * T lands on ring[head][r][0]
+            std::vector<StepRow> rows(R);
+            for (int r = 0; r < R; ++r) {
+                StepRow sr{};
+                sr.ring = RG.p + (size_t)r * q->ring_rows * T;
+                sr.prefill_rows = q->prefill_rows[r]; sr.n_single = q->n_single[r]; sr.newest_row = q->newest_row[r];
+                sr.content_len = q->content_len[r];
+                rows[r] = sr;
+            }
+            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&rows_dev), sizeof(StepRow) * R));
+            WLK_HIP(hipMemcpy(rows_dev, rows.data(), sizeof(StepRow) * R, hipMemcpyHostToDevice));
+            a.ring = nullptr;
+            a.ring_rows = R * q->ring_rows;
+            launch_logsoftmax_topk(ctx, L.p, V, R, k, TV.p, TI.p, SC.p, adj_row, adj_ids, adj_deltas, q->n_adj);
+            launch_alignatt_rows(ctx, a, rows_dev);
+            if (ns) launch_token_prob(ctx, NL.p, V, R, q->ns_token, NP.p);
+            break;
+        }
+        }
+        WLK_HIP(hipStreamSynchronize(st.s));
+        if (refused) return;
+        WLK_HIP(hipMemcpy(q->top_logprobs, TV.p, (size_t)R * k * sizeof(float), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(q->top_ids, TI.p, (size_t)R * k * sizeof(int), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(q->frames, FR.p, (size_t)R * sizeof(int), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(q->attn_last, AL.p, (size_t)R * T * sizeof(float), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(q->z, Z.p + kGuard, (size_t)R * A * T * sizeof(float), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(q->logits_out, L.p, (size_t)R * V * sizeof(float), hipMemcpyDeviceToHost));
+        if (ns) WLK_HIP(hipMemcpy(q->ns_probs, NP.p, (size_t)R * sizeof(float), hipMemcpyDeviceToHost));
+    });
+    if (rc == WLK_OK && refused) {
+        g_diag_error = "wlk_diag_select: the fused form does not take this shape (window beyond LDS, or WLK_SELECT_FUSED=0)";
+        return WLK_ERR_ARG;
+    }
+    return rc;
+}
+
 }  // extern "C"

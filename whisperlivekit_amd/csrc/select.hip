@@ -787,34 +787,41 @@ void launch_alignatt_rows(const LaunchCtx& ctx, const AlignArgs& a0, const StepR
     launch_alignatt(ctx, a);
 }
 
+void launch_align_zscore(const LaunchCtx& ctx, const AlignArgs& a) {
+    const int n = a.rows ? kAlignWindow : a.prefill_rows + a.n_single;
+    KernelScope ks(ctx, "align_zscore", 0.0, 4.0 * 2.0 * n * (double)a.n_align * a.T * a.n_beam);
+    hipLaunchKernelGGL(align_zscore_kernel, dim3((a.T + 63) / 64, a.n_align, a.n_beam), dim3(256), 0, ctx.stream, a);
+    WLK_HIP(hipGetLastError());
+}
+
+void launch_align_argmax_plain(const LaunchCtx& ctx, const AlignArgs& a) {
+    KernelScope ks(ctx, "align_argmax");
+    hipLaunchKernelGGL(align_argmax_kernel, dim3(a.n_beam), dim3(256), 0, ctx.stream, a);
+    WLK_HIP(hipGetLastError());
+}
+
 void launch_alignatt(const LaunchCtx& ctx, const AlignArgs& a) {
     if (a.n_align <= 0) {
         WLK_HIP(hipMemsetAsync(a.frames, 0, sizeof(int) * a.n_beam, ctx.stream));
         WLK_HIP(hipMemsetAsync(a.attn_last, 0, sizeof(float) * a.n_beam * a.T, ctx.stream));
         return;
     }
-    {
-        const int n = a.rows ? kAlignWindow : a.prefill_rows + a.n_single;
-        KernelScope ks(ctx, "align_zscore", 0.0, 4.0 * 2.0 * n * (double)a.n_align * a.T * a.n_beam);
-        hipLaunchKernelGGL(align_zscore_kernel, dim3((a.T + 63) / 64, a.n_align, a.n_beam), dim3(256), 0,
-                           ctx.stream, a);
-        WLK_HIP(hipGetLastError());
-    }
+    launch_align_zscore(ctx, a);
     const size_t lds = (size_t)a.n_align * a.T * sizeof(float);
-    KernelScope ks(ctx, "align_argmax");
-    if (lds + 8192 + 1024 <= 150 * 1024) {
-        static std::atomic<bool> attr_set[64];   // launches come from several host threads
-        int dev = 0;
-        WLK_HIP(hipGetDevice(&dev));
-        if (dev < 64 && !attr_set[dev].load(std::memory_order_acquire)) {
-            WLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(align_argmax_lds_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            attr_set[dev].store(true, std::memory_order_release);
-        }
-        hipLaunchKernelGGL(align_argmax_lds_kernel, dim3(a.n_beam), dim3(1024), lds, ctx.stream, a);
-    } else {
-        hipLaunchKernelGGL(align_argmax_kernel, dim3(a.n_beam), dim3(256), 0, ctx.stream, a);
+    if (lds + 8192 + 1024 > 150 * 1024) {
+        launch_align_argmax_plain(ctx, a);
+        return;
     }
+    KernelScope ks(ctx, "align_argmax");
+    static std::atomic<bool> attr_set[64];   // launches come from several host threads
+    int dev = 0;
+    WLK_HIP(hipGetDevice(&dev));
+    if (dev < 64 && !attr_set[dev].load(std::memory_order_acquire)) {
+        WLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(align_argmax_lds_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        attr_set[dev].store(true, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(align_argmax_lds_kernel, dim3(a.n_beam), dim3(1024), lds, ctx.stream, a);
     WLK_HIP(hipGetLastError());
 }
 
