@@ -550,14 +550,8 @@ int wlk_session_destroy(wlk_session* s) {
     if (s->pinned) (void)hipHostFree(s->pinned);
     if (s->dec_stage) (void)hipHostFree(s->dec_stage);
     if (s->audio_stage) (void)hipHostFree(s->audio_stage);
-    if (s->pf_stream) {
-        (void)hipStreamSynchronize(s->pf_stream);
-        (void)hipStreamDestroy(s->pf_stream);
-    }
     if (s->rules_mask) (void)hipFree(s->rules_mask);
     if (s->pick_out) (void)hipFree(s->pick_out);
-    if (s->pf_table) (void)hipFree(s->pf_table);
-    if (s->pf_progress) (void)hipFree(s->pf_progress);
     if (s->audio_stage_ev) (void)hipEventDestroy(s->audio_stage_ev);
     if (s->dec_stage_ev) (void)hipEventDestroy(s->dec_stage_ev);
     if (s->step_host) (void)hipHostFree(s->step_host);
@@ -1008,47 +1002,12 @@ int wlk_session::flash_splits() {
 }
 
 // ---- decode ---------------------------------------------------------------------------------
+constexpr size_t kAncStageOffset = 65536 - 64;   // [source rows 0..6 | fresh] of an ancestry step, at the end of dec_stage
+
 // Enqueue one decoder forward on the session stream.  Everything that changes from call to call
 // (tokens, alignment-window row map, cache offset) is read from the pinned staging block through
 // memcpy nodes / device scalars, so the single-token form of this sequence can be captured once
 // into a hipGraph and replayed.
-// The Infinity-Cache prefetcher beside a graph-replayed single-token step (decoder.hip: mall_prefetch_step_kernel).  OPT-IN
-// (WLK_MALL_PREFETCH=1): measured a loss on large-v3 - step 1.49 -> 1.70 ms, 14.9 -> 14.2 audio-s/s, 510 / 510 decisions either
-// way (profiles/r06k_mall_ab_large-v3.txt) - the second reader competes with the chain's own HBM reads instead of getting
-// ahead of them.  WLK_MALL_LEAD = layers the prefetcher may run ahead of the chain's last mark (default 0).
-static bool mall_prefetch_wanted(const wlk_model*) {
-    static const bool on = [] {
-        const char* e = getenv("WLK_MALL_PREFETCH");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
-static int mall_prefetch_lead() {
-    static const int lead = [] {
-        const char* e = getenv("WLK_MALL_LEAD");
-        return e ? atoi(e) : 0;
-    }();
-    return lead;
-}
-static void mall_prefetch_prepare(wlk_session* s) {
-    if (!mall_prefetch_wanted(s->m) || s->pf_stream) return;
-    const wlk_model* m = s->m;
-    const int L = m->D.n_text_layer, d = m->D.n_text_state;
-    std::vector<TouchRanges> host((size_t)L);
-    const unsigned dd = (unsigned)((size_t)d * d / 4);
-    for (int i = 0; i < L; ++i) {
-        const LayerW& W = m->dec_layers[i];
-        host[(size_t)i] = TouchRanges{{W.qkvw, W.outw, W.xqw, W.xoutw, W.fc1w, W.fc2w}, {3 * dd, dd, dd, dd, 4 * dd, 4 * dd}};
-    }
-    WLK_HIP(hipStreamCreateWithFlags(&s->pf_stream, hipStreamNonBlocking));
-    s->pf_table = dev_alloc<TouchRanges>((size_t)L);
-    s->pf_progress = dev_alloc_zero<unsigned long long>(1, s->pf_stream);
-    WLK_HIP(hipMemcpyAsync(s->pf_table, host.data(), host.size() * sizeof(TouchRanges), hipMemcpyHostToDevice, s->pf_stream));
-    WLK_HIP(hipStreamSynchronize(s->pf_stream));
-}
-
-constexpr size_t kAncStageOffset = 65536 - 64;   // [source rows 0..6 | fresh] of an ancestry step, at the end of dec_stage
-
 static void enqueue_decode(wlk_session* s, const LaunchCtx& c, int n_rows, int n_tok, bool first, int sot_index,
                            bool step_block = false, const AlignArgs* side_align = nullptr, int side_blocks = 0, int side_zf = 0,
                            bool ancestry = false) {
@@ -1082,7 +1041,6 @@ static void enqueue_decode(wlk_session* s, const LaunchCtx& c, int n_rows, int n
     const float scale = std::pow((float)kHeadDim, -0.25f);
     const size_t cache_layer = (size_t)s->beam * ctx_len * d;
     bool scores_dumped = false;   // prefill: raw alignment-head scores are waiting in the window rows
-    const bool marks = s->pf_marks && s->pf_progress && step_block && fused;
     for (int i = 0; i < D.n_text_layer; ++i) {
         const LayerW& L = m->dec_layers[i];
         float* kc = s->kcache[s->kv_cur] + i * cache_layer;
@@ -1112,8 +1070,7 @@ static void enqueue_decode(wlk_session* s, const LaunchCtx& c, int n_rows, int n
         if (ancestry)
             launch_decoder_self_attention_anc(c, s->dqkv, kc, vc, s->anc, s->datt, n_rows, s->d_offset, d, H, ctx_len);
         else
-            launch_decoder_self_attention(c, s->dqkv, kc, vc, s->datt, n_rows, n_tok, s->d_offset, d, H, ctx_len,
-                                          marks ? ProgressMark{&s->step_dev->seq, s->pf_progress, i} : ProgressMark{});
+            launch_decoder_self_attention(c, s->dqkv, kc, vc, s->datt, n_rows, n_tok, s->d_offset, d, H, ctx_len);
         GemmArgs o;
         o.A = s->datt; o.lda = d; o.W = L.outw; o.bias = L.outb; o.C = s->dx; o.ldc = d; o.M = R; o.N = d; o.K = d;
         o.flags = kGemmResidual; o.R = s->dx; o.ldr = d;
@@ -1467,20 +1424,7 @@ int wlk_decode(wlk_session* s, const int64_t* tokens, int n_rows, int n_tok, int
                                !s->prof_on && s->use_graph;
         if (graphable) {
             hipGraphExec_t& exec = s->step_exec[s->kv_cur];
-            if (!exec) {
-                hipGraph_t graph = nullptr;
-                WLK_HIP(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-                try {
-                    enqueue_decode(s, c, n_rows, n_tok, false, sot_index);
-                } catch (...) {
-                    (void)hipStreamEndCapture(s->stream, &graph);
-                    if (graph) (void)hipGraphDestroy(graph);
-                    throw;
-                }
-                WLK_HIP(hipStreamEndCapture(s->stream, &graph));
-                WLK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                (void)hipGraphDestroy(graph);
-            }
+            if (!exec) capture_step_graph(s->stream, exec, [&] { enqueue_decode(s, c, n_rows, n_tok, false, sot_index); });
             WLK_HIP(hipGraphLaunch(exec, s->stream));
         } else {
             enqueue_decode(s, c, n_rows, n_tok, first != 0, sot_index);
@@ -1676,20 +1620,10 @@ extern "C++" int wlk_step_select(wlk_session* s, int64_t token, const int32_t* a
     return guarded([&]() {
         WLK_HIP(hipSetDevice(m->device));
         const LaunchCtx c = s->ctx();
-        const int ctx_len = D.n_text_ctx;
         // the step's inputs (wlk_decode's staging block + wlk_select's arguments); the previous replay has delivered
         // its result, so its first kernel is long past reading this block
         StepBlock& b = *s->step_host;
-        const int steps_after = s->n_steps + 1;
-        b.row.kcache = s->kcache[s->kv_cur]; b.row.vcache = s->vcache[s->kv_cur];
-        b.row.cross_kv = s->cross_kv; b.row.ring = s->ring;
-        b.row.token = (int)token;
-        b.row.offset = s->self_len;
-        b.row.ring_row = ctx_len + ((s->n_steps - 1) % kAlignWindow);
-        b.row.prefill_rows = steps_after <= kAlignWindow ? s->prefill_rows : 0;
-        b.row.n_single = std::min(steps_after - 1, kAlignWindow);
-        b.row.newest_row = ctx_len + ((steps_after - 2) % kAlignWindow);
-        b.row.content_len = content_mel_len;
+        b.row = next_step_row(s, (int)token, content_mel_len);
         b.n_adj = n_adj;
         for (int i = 0; i < n_adj; ++i) {
             b.adj_row[i] = -1;
@@ -1703,8 +1637,6 @@ extern "C++" int wlk_step_select(wlk_session* s, int64_t token, const int32_t* a
         const auto t_enter = std::chrono::steady_clock::now();
         hipGraphExec_t& exec = s->fstep_exec[s->kv_cur];
         if (!exec) {
-            hipGraph_t graph = nullptr;
-            mall_prefetch_prepare(s);
             const int zf_blocks = (a.T + 63) / 64;
             if (!s->step_align_dev) {      // the read-out's arguments as the side workgroups see them: everything that changes
                 AlignArgs ad = a;          // from step to step comes through `rows` (the step's device block)
@@ -1713,16 +1645,13 @@ extern "C++" int wlk_step_select(wlk_session* s, int64_t token, const int32_t* a
                 WLK_HIP(hipMemcpyAsync(s->step_align_dev, &ad, sizeof(AlignArgs), hipMemcpyHostToDevice, s->stream));
             }
             WLK_HIP(hipStreamSynchronize(s->stream));
-            WLK_HIP(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-            try {
+            capture_step_graph(s->stream, exec, [&] {
                 a.rows = &s->step_dev->row;
                 a.part = s->z + (size_t)s->beam * std::max(m->n_align, 1) * D.n_audio_ctx;
                 // the vocabulary projection's weights are a (V / 4 / 4 > 2048 workgroups) stream long enough to hide the z-score
                 const bool early_z = select_early_z_enabled() && D.n_vocab >= 16384;
-                s->pf_marks = true;
                 if (early_z) enqueue_decode(s, c, 1, 1, false, 0, true, s->step_align_dev, zf_blocks * a.n_align * a.n_beam, zf_blocks);
                 else enqueue_decode(s, c, 1, 1, false, 0, true);
-                s->pf_marks = false;
                 StepHostOut ho;
                 ho.result = s->result_host_dev;
                 ho.n_adj = &s->step_dev->n_adj;
@@ -1731,22 +1660,9 @@ extern "C++" int wlk_step_select(wlk_session* s, int64_t token, const int32_t* a
                                          s->step_dev->adj_row, s->step_dev->adj_ids, s->step_dev->adj_deltas, 0, a, ho, nullptr, 0,
                                          nullptr, early_z))
                     throw std::runtime_error("fused step: read-out not available");
-            } catch (...) {
-                s->pf_marks = false;
-                (void)hipStreamEndCapture(s->stream, &graph);
-                if (graph) (void)hipGraphDestroy(graph);
-                throw;
-            }
-            WLK_HIP(hipStreamEndCapture(s->stream, &graph));
-            WLK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(graph);
+            });
         }
         WLK_HIP(hipGraphLaunch(exec, s->stream));
-        if (s->pf_progress) {            // beside the replay: next layers' weights into the Infinity Cache, paced by the chain's marks
-            LaunchCtx pc;
-            pc.stream = s->pf_stream;
-            launch_mall_prefetch_step(pc, s->pf_table, D.n_text_layer, seq, s->pf_progress, mall_prefetch_lead(), s->dh);
-        }
 
         // the last kernel stores the two flags after the fields
         volatile StepResult* r = s->result_host;
@@ -1845,20 +1761,7 @@ extern "C++" int wlk_beam_step(wlk_session* s, const int64_t* tokens, const int3
         // one capture per KV buffer, as step_exec: the chain's nodes carry kcache / vcache[kv_cur], and a wlk_kv_reorder of
         // an infer that ran without ancestry steps (debug / profiling fallback, the per-token hooks) flips kv_cur
         hipGraphExec_t& exec = s->bstep_exec[s->kv_cur];
-        if (!exec) {
-            hipGraph_t graph = nullptr;
-            WLK_HIP(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-            try {
-                enqueue_decode(s, c, B, 1, false, 0, false, nullptr, 0, 0, true);
-            } catch (...) {
-                (void)hipStreamEndCapture(s->stream, &graph);
-                if (graph) (void)hipGraphDestroy(graph);
-                throw;
-            }
-            WLK_HIP(hipStreamEndCapture(s->stream, &graph));
-            WLK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(graph);
-        }
+        if (!exec) capture_step_graph(s->stream, exec, [&] { enqueue_decode(s, c, B, 1, false, 0, false, nullptr, 0, 0, true); });
         WLK_HIP(hipGraphLaunch(exec, s->stream));
         WLK_HIP(hipEventRecord(s->dec_stage_ev, s->stream));
         s->dec_stage_used = true;

@@ -59,6 +59,28 @@ struct KernelScope {  // RAII: brackets one launch with events when profiling is
     }
 };
 
+// Records what `enqueue()` launches on `stream` (thread-local capture) and instantiates it into `exec` (must be null on entry).
+// Whatever happens, the stream is out of capture mode and the hipGraph_t is destroyed when this returns or throws;
+// on any failure `exec` is still null.
+template <typename F>
+void capture_step_graph(hipStream_t stream, hipGraphExec_t& exec, F&& enqueue) {
+    if (exec) throw std::logic_error("capture_step_graph: the executable graph is already recorded");
+    hipGraph_t graph = nullptr;
+    WLK_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+    try {
+        enqueue();
+    } catch (...) {
+        (void)hipStreamEndCapture(stream, &graph);
+        if (graph) (void)hipGraphDestroy(graph);
+        throw;
+    }
+    hipError_t e = hipStreamEndCapture(stream, &graph);
+    if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    if (graph) (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) exec = nullptr;
+    hip_check(e, "recording a step graph", __FILE__, __LINE__);
+}
+
 // ---- cross-session batched decode steps (engine.hip) ---------------------------------------------
 // One row of a batched single-token decode step = one beam-1 session.  The table lives in device memory and is
 // rewritten before every step; kernels that touch per-session state (KV-cache append, self-/cross-attention, the
@@ -114,19 +136,6 @@ struct EngineBlock {
 };
 void launch_embed_rows_step(const LaunchCtx& ctx, const EngineBlock* host_block, EngineBlock* dev_block, const float* tok_emb,
                             const float* pos_emb, float* x, int n_rows, int d);
-// The Infinity-Cache prefetcher beside a single-token decode step (decoder.hip: mall_prefetch_step_kernel): per decoder layer the
-// weight ranges it reads, and the mark the step's chain leaves for it
-struct TouchRanges {
-    const float* p[6];
-    unsigned n16[6];                      // 16-byte units per range
-};
-struct ProgressMark {
-    const unsigned* seq = nullptr;        // device copy of the step's sequence number (StepBlock::seq)
-    unsigned long long* word = nullptr;   // (seq << 32 | layer), stored by the layer's self-attention launch; nullptr = no mark
-    int layer = 0;
-};
-void launch_mall_prefetch_step(const LaunchCtx& ctx, const TouchRanges* table, int n_layer, unsigned seq,
-                               const unsigned long long* progress, int lead, float* sink);
 void launch_embed_step(const LaunchCtx& ctx, const StepBlock* host_block, StepBlock* dev_block, int* tokens_dev,
                        int* ring_row, int* beam_of_row, int* d_offset, const float* tok_emb, const float* pos_emb, float* x,
                        int d);
@@ -449,7 +458,7 @@ void launch_decoder_self_attention_anc(const LaunchCtx& ctx, const float* qkv, c
 void launch_anc_update(const LaunchCtx& ctx, unsigned char* anc, const int* ctl, const int* offset, int n_rows, int ctx_len);
 void launch_decoder_self_attention(const LaunchCtx& ctx, const float* qkv, const float* kc, const float* vc,
                                    float* out, int n_rows, int n_tok, const int* offset_dev, int d, int n_head,
-                                   int ctx_len, const ProgressMark& mark = ProgressMark{});
+                                   int ctx_len);
 struct CrossAttnArgs {
     const float* q;        // [rows][d], pre-scaled
     const float* k;        // [T][ldkv] pre-scaled keys of this layer

@@ -239,21 +239,9 @@ bool wlk_engine::step_batched_one_replay(std::vector<EngineJob*>& group, std::ve
         DecodeJob& job = *group[r]->job;
         if (s->self_len + 1 > ctx_len) throw std::runtime_error("text context exceeded");
         if (s->n_steps < 1) throw std::runtime_error("engine step before the prefill");
-        const int after = s->n_steps + 1;
-        StepRow& sr = b.rows[r];
-        sr.kcache = s->kcache[s->kv_cur];
-        sr.vcache = s->vcache[s->kv_cur];
-        sr.cross_kv = s->cross_kv;
-        sr.ring = s->ring;
-        sr.token = (int)job.seq.back();
-        if (sr.token < 0 || sr.token >= D.n_vocab) throw std::invalid_argument("token id out of range");
-        sr.offset = s->self_len;
-        sr.ring_row = ctx_len + ((s->n_steps - 1) % kAlignWindow);
-        sr.prefill_rows = after <= kAlignWindow ? s->prefill_rows : 0;
-        sr.n_single = std::min(after - 1, kAlignWindow);
-        sr.newest_row = ctx_len + ((after - 2) % kAlignWindow);
-        sr.content_len = std::min(job.P.content_mel_len, T);
-        sr.pad = 0;
+        const int token = (int)job.seq.back();
+        if (token < 0 || token >= D.n_vocab) throw std::invalid_argument("token id out of range");
+        b.rows[r] = next_step_row(s, token, std::min(job.P.content_mel_len, T));
     }
     b.n_adj = n_adj;
     const unsigned seq = ++step_seq ? step_seq : ++step_seq;
@@ -262,7 +250,6 @@ bool wlk_engine::step_batched_one_replay(std::vector<EngineJob*>& group, std::ve
     hipGraphExec_t& exec = fstep_exec[R];
     if (!exec) {
         const LaunchCtx c{stream, nullptr};
-        hipGraph_t graph = nullptr;
         // the rows' z-scores beside the vocabulary projection, medians beside the top-k slices, one folding wave per row at the
         // end (select.hip, early_z) - as a single session's graph step does.  Opt-in here (WLK_EARLY_Z_ENGINE=1): with eight
         // streams on the GPU the step's latency chain is not what bounds the throughput and up to 960 side workgroups compete
@@ -272,8 +259,7 @@ bool wlk_engine::step_batched_one_replay(std::vector<EngineJob*>& group, std::ve
         const int zf_blocks = (T + 63) / 64;
         if (early_z) WLK_HIP(hipMemcpyAsync(align_dev + R, &a, sizeof(AlignArgs), hipMemcpyHostToDevice, stream));
         WLK_HIP(hipStreamSynchronize(stream));
-        WLK_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        try {
+        capture_step_graph(stream, exec, [&] {
             if (early_z) enqueue_decoder(R, true, align_dev + R, zf_blocks * a.n_align * R, zf_blocks);
             else enqueue_decoder(R, true);
             StepHostOut ho;
@@ -285,14 +271,7 @@ bool wlk_engine::step_batched_one_replay(std::vector<EngineJob*>& group, std::ve
             if (!launch_select_fused(c, logits, V, R, 2, top_vals, top_ids, topk_scratch, blk_dev->adj_row, blk_dev->adj_ids,
                                      blk_dev->adj_deltas, 0, a, ho, nullptr, 0, nullptr, early_z))
                 throw std::runtime_error("batched step: read-out not available");
-        } catch (...) {
-            (void)hipStreamEndCapture(stream, &graph);
-            if (graph) (void)hipGraphDestroy(graph);
-            throw;
-        }
-        WLK_HIP(hipStreamEndCapture(stream, &graph));
-        WLK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(graph);
+        });
     }
     WLK_HIP(hipGraphLaunch(exec, stream));
     wlk_wait_step_flags(stream, res_host, R, seq);
@@ -327,21 +306,9 @@ void wlk_engine::step_batched(std::vector<EngineJob*>& group, std::vector<Engine
         DecodeJob& job = *group[r]->job;
         if (s->self_len + 1 > ctx_len) throw std::runtime_error("text context exceeded");
         if (s->n_steps < 1) throw std::runtime_error("engine step before the prefill");
-        const int after = s->n_steps + 1;
-        StepRow& sr = rows[r];
-        sr.kcache = s->kcache[s->kv_cur];
-        sr.vcache = s->vcache[s->kv_cur];
-        sr.cross_kv = s->cross_kv;
-        sr.ring = s->ring;
-        sr.token = (int)job.seq.back();
-        if (sr.token < 0 || sr.token >= D.n_vocab) throw std::invalid_argument("token id out of range");
-        sr.offset = s->self_len;
-        sr.ring_row = ctx_len + ((s->n_steps - 1) % kAlignWindow);
-        sr.prefill_rows = after <= kAlignWindow ? s->prefill_rows : 0;
-        sr.n_single = std::min(after - 1, kAlignWindow);
-        sr.newest_row = ctx_len + ((after - 2) % kAlignWindow);
-        sr.content_len = std::min(job.P.content_mel_len, T);
-        sr.pad = 0;
+        const int token = (int)job.seq.back();
+        if (token < 0 || token >= D.n_vocab) throw std::invalid_argument("token id out of range");
+        rows[r] = next_step_row(s, token, std::min(job.P.content_mel_len, T));
         job.adjustments(ids, deltas);
         for (size_t i = 0; i < ids.size(); ++i) {
             all_rows.push_back(r);
@@ -358,20 +325,7 @@ void wlk_engine::step_batched(std::vector<EngineJob*>& group, std::vector<Engine
     if (n_adj > 0) WLK_HIP(hipMemcpyAsync(adj_dev, adj, (size_t)n_adj * 12, hipMemcpyHostToDevice, stream));
     if (use_graph) {
         hipGraphExec_t& exec = step_exec[R];
-        if (!exec) {
-            hipGraph_t graph = nullptr;
-            WLK_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-            try {
-                enqueue_decoder(R);
-            } catch (...) {
-                (void)hipStreamEndCapture(stream, &graph);
-                if (graph) (void)hipGraphDestroy(graph);
-                throw;
-            }
-            WLK_HIP(hipStreamEndCapture(stream, &graph));
-            WLK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(graph);
-        }
+        if (!exec) capture_step_graph(stream, exec, [&] { enqueue_decoder(R); });
         WLK_HIP(hipGraphLaunch(exec, stream));
     } else {
         enqueue_decoder(R);

@@ -1,6 +1,7 @@
 // Internal object layouts shared by the C-ABI files (api.hip, engine.hip): the model, the per-stream session and the
 // small helpers around them.  Not part of the public interface (include/wlk_hip.h keeps both types opaque).
 #pragma once
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <chrono>
@@ -251,12 +252,6 @@ struct wlk_session {
     // whisper's batch-decoder rules on the device (wlk_rules_set / wlk_pick_greedy): bit 0 = always suppressed, bit 1 = blank
     unsigned char* rules_mask = nullptr;
     int* pick_out = nullptr;                            // [token | log-probability]
-    // Infinity-Cache prefetcher beside a graph-replayed single-token step (wlk_step_select; decoder.hip): its stream, the
-    // per-layer range table and the progress word the step's chain marks
-    hipStream_t pf_stream = nullptr;
-    wlk::TouchRanges* pf_table = nullptr;
-    unsigned long long* pf_progress = nullptr;
-    bool pf_marks = false;                              // set around the capture of a step graph: the chain stores its marks
     bool audio_stage_used = false;
     // single-token steps as one graph replay (wlk_step_select): host-coherent blocks the step's first / last kernel
     // read / write directly, their device-side addresses, the device copy of the input block, one graph per KV set
@@ -284,6 +279,28 @@ struct wlk_session {
     wlk_engine* engine = nullptr;   // set by wlk_engine_attach: single-token steps run batched with the other attached sessions
 };
 
+
+// The StepRow of the single-token step that session `s` is about to take (s->n_steps >= 1): caches of the current KV buffer,
+// cross K|V, alignment window, and the window scalars after this step.  The one place they are derived: the solo step
+// (wlk_step_select) and the engine's batched steps must stay decision-identical.
+inline wlk::StepRow next_step_row(const wlk_session* s, int token, int content_len) {
+    const int ctx_len = s->m->D.n_text_ctx;
+    const int after = s->n_steps + 1;
+    wlk::StepRow r;
+    r.kcache = s->kcache[s->kv_cur];
+    r.vcache = s->vcache[s->kv_cur];
+    r.cross_kv = s->cross_kv;
+    r.ring = s->ring;
+    r.token = token;
+    r.offset = s->self_len;
+    r.ring_row = ctx_len + ((s->n_steps - 1) % wlk::kAlignWindow);
+    r.prefill_rows = after <= wlk::kAlignWindow ? s->prefill_rows : 0;
+    r.n_single = std::min(after - 1, wlk::kAlignWindow);
+    r.newest_row = ctx_len + ((after - 2) % wlk::kAlignWindow);
+    r.content_len = content_len;
+    r.pad = 0;
+    return r;
+}
 
 // Wait for the result flags of a graph-replayed step (written by its last kernel into host-coherent memory).  A step is
 // ~250 us of GPU time, so the wait spins first (lowest latency: the flags arrive over PCIe, there is no interrupt to

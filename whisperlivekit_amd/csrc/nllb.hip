@@ -493,19 +493,7 @@ int wlk_nllb_step(wlk_nllb_session* s, const int64_t* tokens, int32_t n_rows, in
         if (!exec || s->step_exec_k[s->kv_cur] != k || s->step_exec_src[s->kv_cur] != s->src_len) {
             if (exec) { WLK_HIP(hipGraphExecDestroy(exec)); exec = nullptr; }
             s->step_k = k;
-            hipGraph_t graph = nullptr;
-            WLK_HIP(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-            try {
-                nl_decode(s, 1, /*graph_step=*/true);
-            } catch (...) {
-                (void)hipStreamEndCapture(s->stream, &graph);
-                if (graph) (void)hipGraphDestroy(graph);
-                throw;
-            }
-            WLK_HIP(hipStreamEndCapture(s->stream, &graph));
-            const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            WLK_HIP(e);
+            capture_step_graph(s->stream, exec, [&] { nl_decode(s, 1, /*graph_step=*/true); });
             s->step_exec_k[s->kv_cur] = k;
             s->step_exec_src[s->kv_cur] = s->src_len;
         }

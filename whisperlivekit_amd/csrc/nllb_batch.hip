@@ -486,19 +486,7 @@ int wlk_nllb_batch_step(wlk_nllb_batch* b, const int32_t* slots, const int64_t* 
         if (!exec || b->exec_k[n_rows] != k) {
             if (exec) { WLK_HIP(hipGraphExecDestroy(exec)); exec = nullptr; }
             b->step_k = k;
-            hipGraph_t graph = nullptr;
-            WLK_HIP(hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal));
-            try {
-                nlb_step_chain(b, n_rows);
-            } catch (...) {
-                (void)hipStreamEndCapture(b->stream, &graph);
-                if (graph) (void)hipGraphDestroy(graph);
-                throw;
-            }
-            WLK_HIP(hipStreamEndCapture(b->stream, &graph));
-            const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            WLK_HIP(e);
+            capture_step_graph(b->stream, exec, [&] { nlb_step_chain(b, n_rows); });
             b->exec_k[n_rows] = k;
         }
         WLK_HIP(hipGraphLaunch(exec, b->stream));
