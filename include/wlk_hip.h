@@ -580,6 +580,74 @@ typedef struct wlk_diag_select_args {
     float* logits_out;              /* out [n_rows][n_vocab] the logits as the call left them in memory (adjusted) */
 } wlk_diag_select_args;
 int wlk_diag_select(const wlk_diag_select_args* args);
+/* The decoder's attention stage (csrc/decoder.hip, the merged out projection of csrc/gemm_f32.hip, the prefill flash
+ * kernel of csrc/attention.hip) on host data, through ONE chosen route.  The launchers are the ones a decode step uses,
+ * unchanged.  Heads are 64 wide and d = 64 n_head.
+ *   self-attention over a cache [cache rows][ctx_len][d] (kcache / vcache), queries in qkv [n_rows n_tok][3 d]:
+ *     S0  launch_decoder_self_attention(n_rows, n_tok, offsets[0])
+ *     S1  launch_decoder_self_attention_rows: row r reads cache row row_cache[r] with offsets[r]; the caches sit
+ *         layer_off floats into their allocation (the floats in front of them are NaN)
+ *     S2  launch_decoder_self_attention_anc with the table anc [anc_rows >= n_rows][ctx_len] and offsets[0]
+ *   cross-attention of q [n_rows][d] over k / v [n_kv][T][d]; on the device they lie as [T + 1][2][2 d] with layer 0 and
+ *   row T filled with NaN, so the row stride is not 2 d and a read past the keys poisons the result:
+ *     C0  launch_decoder_cross_attention (raw scores to `scores` when it is given)
+ *     C1  launch_decoder_cross_attention_split + merge kernel
+ *     C2  as C1 with the query projection folded in: x [n_rows][d], wq [d][d], bq or NULL, gamma, beta, scale
+ *     C3  split with merge = false, then launch_gemv with the merged operand (GemmArgs::mg_*) as a decode step fills it:
+ *         out row 0 = resid + bo + wo . attention
+ *     C4  as C1 through a StepRow table: row r takes key / value set row_kv[r] and its own alignment window
+ *     C5  launch_prefill_cross_attention with k_splits (1, or 0 = the session default) + launch_ring_softmax
+ *   Alignment rows: head_rank [n_head] (rank or -1; NULL = no alignment head) sends head h of query row r to
+ *   ring[rank][beam_of_row[r]][ring_row[r]][0..T).  Routes C1 - C4 also return the raw scores [n_rows][n_head][T].
+ *   integer and copy operations:
+ *     A0  launch_anc_update n_updates times on anc, update u with ctl [u][8] = (src 0..6, fresh) and upd_offsets[u]
+ *     G0  launch_kv_gather: vcache[l][b] = kcache[l][row_cache[b]] for positions [0, gather_len), n_layer layers
+ *     K0  launch_kv_append(n_rows, n_tok, offsets[0]) of qkv's k | v into kcache / vcache
+ *     K1  launch_kv_append_rows with row_cache / offsets [n_rows] / layer_off as in S1
+ * kcache, vcache, anc, ring, scores and out are uploaded as the caller filled them and copied back whole: what a route
+ * does not address keeps the caller's pattern.  A route that cannot run the shape returns WLK_ERR_ARG with a message in
+ * wlk_diag_last_error(), before any launch of the refused kernel; it never runs another route instead.  All pointers are
+ * host memory; the call is synchronous. */
+enum {
+    WLK_DA_S0 = 0, WLK_DA_S1 = 1, WLK_DA_S2 = 2,
+    WLK_DA_C0 = 10, WLK_DA_C1 = 11, WLK_DA_C2 = 12, WLK_DA_C3 = 13, WLK_DA_C4 = 14, WLK_DA_C5 = 15,
+    WLK_DA_A0 = 20, WLK_DA_G0 = 21, WLK_DA_K0 = 22, WLK_DA_K1 = 23
+};
+typedef struct wlk_diag_dec_attention_args {
+    int32_t route, n_rows, n_tok, d, n_head, ctx_len, T;
+    int32_t anc_rows, n_updates, gather_len, n_layer, n_kv, k_splits, n_align, n_beam, ring_rows;
+    float scale;                    /* C2 */
+    int64_t cache_floats;           /* floats of kcache and of vcache */
+    int64_t layer_off;              /* S1, K1 */
+    int64_t scores_floats, out_floats;
+    const float* qkv;
+    float* kcache;                  /* in / out */
+    float* vcache;                  /* in / out */
+    const int32_t* offsets;         /* [1], or [n_rows] for S1 / K1 */
+    const int32_t* row_cache;       /* [n_rows] S1 / K1: cache row of query row r; G0: source rows */
+    uint8_t* anc;                   /* in / out [anc_rows][ctx_len] */
+    const int32_t* ctl;             /* [n_updates][8] */
+    const int32_t* upd_offsets;     /* [n_updates] */
+    const float* q;
+    const float* k;                 /* [n_kv][T][d] */
+    const float* v;
+    const int32_t* row_kv;          /* [n_rows] C4 */
+    const float* x;
+    const float* wq;
+    const float* bq;
+    const float* gamma;
+    const float* beta;
+    const float* wo;                /* C3 [d][d] */
+    const float* bo;
+    const float* resid;             /* C3 [d] */
+    const int32_t* head_rank;
+    const int32_t* ring_row;        /* [n_rows] */
+    const int32_t* beam_of_row;     /* [n_rows] */
+    float* ring;                    /* in / out [n_align][n_beam][ring_rows][T] */
+    float* scores;                  /* in / out [scores_floats] */
+    float* out;                     /* in / out [out_floats] */
+} wlk_diag_dec_attention_args;
+int wlk_diag_dec_attention(const wlk_diag_dec_attention_args* args);
 /* the VALU wave butterflies of csrc/wave_ops.h (DPP / v_permlane{16,32}_swap) against the __shfl_xor loops they replace,
  * on one wave of 64 floats: ten rows of 64 results each (sum, max, 16-lane sum, xor 1 .. 32 exchanges, arg-max index) */
 int wlk_diag_wave_ops(const float* in64, float* out640, float* ref640);

@@ -84,6 +84,22 @@ class DiagSelectArgs(C.Structure):
             "ns_logits", "top_logprobs", "top_ids", "frames", "attn_last", "z", "ns_probs", "logits_out")]
 
 
+class DiagDecAttentionArgs(C.Structure):
+    """wlk_diag_dec_attention_args (include/wlk_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "route", "n_rows", "n_tok", "d", "n_head", "ctx_len", "T", "anc_rows", "n_updates", "gather_len", "n_layer", "n_kv",
+        "k_splits", "n_align", "n_beam", "ring_rows")] + [("scale", C.c_float)] + [
+        (n, C.c_int64) for n in ("cache_floats", "layer_off", "scores_floats", "out_floats")] + [
+        (n, C.c_void_p) for n in (
+            "qkv", "kcache", "vcache", "offsets", "row_cache", "anc", "ctl", "upd_offsets", "q", "k", "v", "row_kv", "x", "wq",
+            "bq", "gamma", "beta", "wo", "bo", "resid", "head_rank", "ring_row", "beam_of_row", "ring", "scores", "out")]
+
+
+DA_S0, DA_S1, DA_S2 = 0, 1, 2
+DA_C0, DA_C1, DA_C2, DA_C3, DA_C4, DA_C5 = 10, 11, 12, 13, 14, 15
+DA_A0, DA_G0, DA_K0, DA_K1 = 20, 21, 22, 23
+
+
 class LoopResult(C.Structure):
     """wlk_loop_result (include/wlk_hip.h)"""
     _fields_ = [("n_steps", C.c_int32), ("n_new_tokens", C.c_int32), ("stop_reason", C.c_int32),
@@ -259,6 +275,7 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_encoder_attention_x3_time": (cint, [cint, cint, cint, cint, C.POINTER(C.c_float)]),
         "wlk_diag_qkv_x3_attention": (cint, [p, p, p, cint, cint, cint, C.c_float, p, p]),
         "wlk_diag_select": (cint, [C.POINTER(DiagSelectArgs)]),
+        "wlk_diag_dec_attention": (cint, [C.POINTER(DiagDecAttentionArgs)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -304,7 +321,7 @@ EXPORTED_SYMBOLS = (
     "wlk_diag_encoder_attention", "wlk_diag_encoder_attention_time", "wlk_diag_wave_ops", "wlk_diag_env_refresh",
     "wlk_diag_linear_x3", "wlk_diag_linear_x3_time", "wlk_diag_layernorm_x3",
     "wlk_diag_encoder_attention_x3", "wlk_diag_encoder_attention_x3_time", "wlk_diag_qkv_x3_attention",
-    "wlk_diag_select",
+    "wlk_diag_select", "wlk_diag_dec_attention",
 )
 
 

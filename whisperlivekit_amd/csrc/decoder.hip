@@ -768,6 +768,10 @@ __global__ __launch_bounds__(256) void cross_merge_kernel(CrossAttnArgs a, const
 void launch_decoder_cross_attention_split(const LaunchCtx& ctx, const CrossAttnArgs& a, float* scores, float* pm,
                                           float* pl, float* po, bool merge) {
     if ((a.T + kCrossSplit - 1) / kCrossSplit > kCrossUnroll * 16) throw std::invalid_argument("cross-attention: T too large");
+    // every slice must start on a key: a slice that starts at or past T would point its fallback row (k_safe) behind the
+    // last key row, and whatever lies there - times weight 0 - goes into its partial sum (T = 9: chunk 2, slice 5 starts at 10)
+    if ((kCrossSplit - 1) * ((a.T + kCrossSplit - 1) / kCrossSplit) >= a.T)
+        throw std::invalid_argument("cross-attention: T too small for the key split (a slice would hold no key)");
     {
         KernelScope ks(ctx, "dec_cross_split", 4.0 * a.rows * (double)a.T * a.d, 4.0 * 2.0 * a.rows * (double)a.T * a.d);
         const dim3 grid(a.rows, a.n_head, kCrossSplit);

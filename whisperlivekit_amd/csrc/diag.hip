@@ -1,7 +1,11 @@
 // Kernel-level diagnostics behind the C ABI: run ONE kernel on host data and hand the result back,
 // so the GPU parity tests can compare each building block with a plain fp32 reference.
 #include <cstdio>
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "../../include/wlk_hip.h"
@@ -627,6 +631,271 @@ int wlk_diag_select(const wlk_diag_select_args* q) {
         return WLK_ERR_ARG;
     }
     return rc;
+}
+
+/* The decoder's attention stage on host data through one chosen route (see include/wlk_hip.h): the launchers of a decode
+ * step, unchanged.  Every shape is checked here or by its launcher before anything is launched for it. */
+int wlk_diag_dec_attention(const wlk_diag_dec_attention_args* q) {
+    struct Refuse : std::invalid_argument {
+        using std::invalid_argument::invalid_argument;
+    };
+    struct Bytes {      // device allocation, optionally filled from the host
+        char* p = nullptr;
+        size_t n = 0;
+        Bytes() = default;
+        Bytes(size_t bytes, const void* host = nullptr) { alloc(bytes, host); }
+        Bytes(const Bytes&) = delete;
+        void alloc(size_t bytes, const void* host = nullptr) {
+            n = bytes;
+            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(bytes, 16)));
+            if (host && bytes) WLK_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+        }
+        void back(void* host) const { if (n) WLK_HIP(hipMemcpy(host, p, n, hipMemcpyDeviceToHost)); }
+        float* f() const { return reinterpret_cast<float*>(p); }
+        int* i() const { return reinterpret_cast<int*>(p); }
+        ~Bytes() { (void)hipFree(p); }
+    };
+    try {
+        auto need = [](bool ok, const char* what) {
+            if (!ok) throw Refuse(std::string("wlk_diag_dec_attention: ") + what);
+        };
+        need(q != nullptr, "null arguments");
+        const int route = q->route, R = q->n_rows, d = q->d, H = q->n_head, ctx_len = q->ctx_len, T = q->T;
+        const bool self_route = route >= WLK_DA_S0 && route <= WLK_DA_S2, cross_route = route >= WLK_DA_C0 && route <= WLK_DA_C5;
+        need(self_route || cross_route || (route >= WLK_DA_A0 && route <= WLK_DA_K1), "unknown route");
+        need(R >= 1 && R <= 4096, "n_rows in [1, 4096]");
+        const float nanf_v = std::nanf("");
+        LaunchCtx ctx;
+        const size_t F = sizeof(float);
+
+        if (route == WLK_DA_A0) {
+            need(ctx_len >= 1 && q->anc && q->anc_rows >= R && q->n_updates >= 0, "A0: a table of at least n_rows rows");
+            need(q->n_updates == 0 || (q->ctl && q->upd_offsets), "A0: null update list");
+            Bytes A((size_t)q->anc_rows * ctx_len, q->anc), CT(8 * sizeof(int)), OF(sizeof(int));
+            for (int u = 0; u < q->n_updates; ++u) {
+                WLK_HIP(hipMemcpy(CT.p, q->ctl + 8 * u, 8 * sizeof(int), hipMemcpyHostToDevice));
+                WLK_HIP(hipMemcpy(OF.p, q->upd_offsets + u, sizeof(int), hipMemcpyHostToDevice));
+                launch_anc_update(ctx, reinterpret_cast<unsigned char*>(A.p), CT.i(), OF.i(), R, ctx_len);
+                WLK_HIP(hipDeviceSynchronize());
+            }
+            A.back(q->anc);
+            return WLK_OK;
+        }
+
+        need(d >= 64 && d % 64 == 0 && d <= 4096, "d a multiple of 64 up to 4096");
+        if (!cross_route) {
+            // ---- self-attention, append, gather: everything over kcache / vcache ------------------------------------
+            need(ctx_len >= 1 && ctx_len <= 4096 && q->kcache && q->vcache && q->cache_floats > 0, "a cache and ctx_len in [1, 4096]");
+            const size_t row_floats = (size_t)ctx_len * d;
+            const long cache_rows = (long)((size_t)q->cache_floats / row_floats);
+            const bool rows_form = route == WLK_DA_S1 || route == WLK_DA_K1;
+            const long layer_off = rows_form ? q->layer_off : 0;
+            need(layer_off >= 0 && layer_off % 4 == 0 && layer_off <= (1 << 24), "layer_off a multiple of 4 in [0, 2^24]");
+            const int n_tok = route == WLK_DA_G0 ? 1 : q->n_tok;
+            need(n_tok >= 1 && (long)R * n_tok <= 4096, "n_tok >= 1, at most 4096 query rows");
+            if (route != WLK_DA_G0) need(q->qkv && q->offsets, "null qkv / offsets");
+            if (route == WLK_DA_G0) {
+                need(q->n_layer >= 1 && q->row_cache && q->gather_len >= 0 && q->gather_len <= ctx_len &&
+                         (long)q->n_layer * R <= cache_rows, "G0: n_layer x n_rows cache rows, gather_len <= ctx_len");
+                for (int b = 0; b < R; ++b) need(q->row_cache[b] >= 0 && q->row_cache[b] < R, "G0: source row outside the cache");
+            } else if (rows_form) {
+                need(n_tok == 1 && q->row_cache, "rows form: one token per row and a cache row per query row");
+                for (int r = 0; r < R; ++r)
+                    need(q->row_cache[r] >= 0 && q->row_cache[r] < cache_rows && q->offsets[r] >= 0 && q->offsets[r] < ctx_len,
+                         "rows form: cache row or offset outside the cache");
+            } else {
+                need(q->offsets[0] >= 0 && q->offsets[0] + n_tok <= ctx_len && R <= cache_rows, "offset + n_tok <= ctx_len, one cache row per n_rows");
+                if (route == WLK_DA_S2) need(n_tok == 1 && q->anc && q->anc_rows >= R, "S2: one token per row and a table of at least n_rows rows");
+            }
+            const bool attends = self_route;
+            if (attends) {
+                need(H >= 1 && H * 64 <= d, "64 n_head <= d");
+                need(q->out && q->out_floats >= (int64_t)R * n_tok * d, "out holds fewer than the query rows");
+            }
+            const size_t QR = (size_t)R * n_tok;
+            Bytes QKV(route == WLK_DA_G0 ? 0 : QR * 3 * d * F, q->qkv), KC, VC, OUT(attends ? (size_t)q->out_floats * F : 0, q->out),
+                OFF((rows_form ? R : 1) * sizeof(int), route == WLK_DA_G0 ? nullptr : q->offsets), ROWS, ANC, SRC;
+            // the caches sit layer_off floats into their allocations; what lies in front of them is NaN
+            std::vector<float> front((size_t)layer_off, nanf_v);
+            for (Bytes* c : {&KC, &VC}) {
+                c->alloc(((size_t)layer_off + (size_t)q->cache_floats) * F);
+                if (layer_off) WLK_HIP(hipMemcpy(c->p, front.data(), (size_t)layer_off * F, hipMemcpyHostToDevice));
+                WLK_HIP(hipMemcpy(c->f() + layer_off, c == &KC ? q->kcache : q->vcache, (size_t)q->cache_floats * F, hipMemcpyHostToDevice));
+            }
+            if (rows_form) {
+                std::vector<StepRow> rows(R);
+                for (int r = 0; r < R; ++r) {
+                    StepRow sr{};
+                    sr.kcache = KC.f() + (size_t)q->row_cache[r] * row_floats;
+                    sr.vcache = VC.f() + (size_t)q->row_cache[r] * row_floats;
+                    sr.offset = q->offsets[r];
+                    rows[r] = sr;
+                }
+                ROWS.alloc(sizeof(StepRow) * R, rows.data());
+            }
+            if (route == WLK_DA_S2) ANC.alloc((size_t)q->anc_rows * ctx_len, q->anc);
+            if (route == WLK_DA_G0) SRC.alloc(R * sizeof(int), q->row_cache);
+            WLK_HIP(hipDeviceSynchronize());
+            switch (route) {
+            case WLK_DA_S0: launch_decoder_self_attention(ctx, QKV.f(), KC.f(), VC.f(), OUT.f(), R, n_tok, OFF.i(), d, H, ctx_len); break;
+            case WLK_DA_S1:
+                launch_decoder_self_attention_rows(ctx, QKV.f(), reinterpret_cast<const StepRow*>(ROWS.p), layer_off, OUT.f(), R, d, H, ctx_len);
+                break;
+            case WLK_DA_S2:
+                launch_decoder_self_attention_anc(ctx, QKV.f(), KC.f(), VC.f(), reinterpret_cast<const unsigned char*>(ANC.p), OUT.f(), R,
+                                                  OFF.i(), d, H, ctx_len);
+                break;
+            case WLK_DA_G0: launch_kv_gather(ctx, KC.f(), VC.f(), SRC.i(), R, q->gather_len, d, ctx_len, q->n_layer); break;
+            case WLK_DA_K0: launch_kv_append(ctx, QKV.f(), KC.f(), VC.f(), R, n_tok, OFF.i(), d, ctx_len); break;
+            default: launch_kv_append_rows(ctx, QKV.f(), reinterpret_cast<const StepRow*>(ROWS.p), layer_off, R, d); break;
+            }
+            WLK_HIP(hipDeviceSynchronize());
+            if (attends) {
+                OUT.back(q->out);
+            } else {
+                if (route != WLK_DA_G0) WLK_HIP(hipMemcpy(q->kcache, KC.f() + layer_off, (size_t)q->cache_floats * F, hipMemcpyDeviceToHost));
+                WLK_HIP(hipMemcpy(q->vcache, VC.f() + layer_off, (size_t)q->cache_floats * F, hipMemcpyDeviceToHost));
+            }
+            return WLK_OK;
+        }
+
+        // ---- cross-attention ----------------------------------------------------------------------------------------
+        need(H >= 1 && H * 64 == d, "cross-attention: d = 64 n_head");
+        need(T >= 1 && T <= 8192 && q->k && q->v && q->out, "cross-attention: T in [1, 8192], keys, values, out");
+        const bool split_route = route >= WLK_DA_C1 && route <= WLK_DA_C4;
+        const int n_kv = route == WLK_DA_C4 ? q->n_kv : 1;
+        need(n_kv >= 1 && n_kv <= 8 && (route != WLK_DA_C4 || q->row_kv), "C4: 1..8 key / value sets and row_kv");
+        if (split_route) need(R <= 8, "the step forms take at most 8 rows");
+        need(route == WLK_DA_C2 ? (q->x && q->wq && q->gamma && q->beta) : q->q != nullptr, "null query operands");
+        need(q->out_floats >= (int64_t)R * d, "out holds fewer than n_rows rows");
+        const bool align = q->head_rank != nullptr;
+        std::vector<int> side_heads, ranks;
+        if (align) {
+            need(q->n_align >= 1 && q->n_beam >= 1 && q->ring_rows >= 1 && q->ring && q->ring_row && q->beam_of_row, "alignment window missing");
+            for (int h = 0; h < H; ++h) {
+                need(q->head_rank[h] >= -1 && q->head_rank[h] < q->n_align, "head rank outside the window");
+                if (q->head_rank[h] >= 0) { side_heads.push_back(h); ranks.push_back(q->head_rank[h]); }
+            }
+            for (int r = 0; r < R; ++r)
+                need(q->ring_row[r] >= 0 && q->ring_row[r] < q->ring_rows && q->beam_of_row[r] >= 0 && q->beam_of_row[r] < q->n_beam,
+                     "ring row or beam outside the window");
+        }
+        if (route == WLK_DA_C4)
+            for (int r = 0; r < R; ++r) need(q->row_kv[r] >= 0 && q->row_kv[r] < n_kv, "C4: key / value set outside k");
+        if (route == WLK_DA_C3) {
+            need(q->wo && q->bo && q->resid, "C3: null out projection");
+            need(gemv1_folds_merge(d), "C3: the out projection does not fold the merge at this width");
+        }
+        need(route != WLK_DA_C5 || q->k_splits == 0 || q->k_splits == 1, "C5: k_splits is 1 or 0 (the session default)");
+        const size_t score_floats = (size_t)R * H * T;
+        if (q->scores) need((size_t)q->scores_floats >= score_floats, "scores holds fewer than n_rows x n_head x T floats");
+
+        // keys | values of set s as [T + 1][2][2 d]: layer 0 and row T are NaN
+        const long ldkv = 4L * d;
+        const size_t set_floats = (size_t)(T + 1) * ldkv;
+        std::vector<float> kv(set_floats * n_kv, nanf_v);
+        for (int s = 0; s < n_kv; ++s)
+            for (int t = 0; t < T; ++t) {
+                float* row = kv.data() + s * set_floats + (size_t)t * ldkv + 2 * d;
+                memcpy(row, q->k + ((size_t)s * T + t) * d, d * F);
+                memcpy(row + d, q->v + ((size_t)s * T + t) * d, d * F);
+            }
+        const size_t ring_floats = align ? (size_t)q->n_align * q->n_beam * q->ring_rows * T : 0;
+        Bytes KV(kv.size() * F, kv.data()), Q(q->q ? (size_t)R * d * F : 0, q->q), OUT((size_t)q->out_floats * F, q->out),
+            RING(ring_floats * F, q->ring), SC(std::max(score_floats, (size_t)(q->scores ? q->scores_floats : 0)) * F, q->scores),
+            HR(align ? H * sizeof(int) : 0, q->head_rank), RR(align ? R * sizeof(int) : 0, q->ring_row),
+            BR(align ? R * sizeof(int) : 0, q->beam_of_row), SH(side_heads.size() * sizeof(int), side_heads.data()),
+            RK(ranks.size() * sizeof(int), ranks.data());
+        Bytes PM((size_t)R * H * kCrossSplitWays * F), PL((size_t)R * H * kCrossSplitWays * F), PO((size_t)R * H * kCrossSplitWays * 64 * F);
+        Bytes X, WQ, BQ, GA, BE, WO, BO, ROWS, PART;
+        CrossAttnArgs ca{};
+        ca.q = Q.f(); ca.k = KV.f() + 2 * d; ca.v = ca.k + d; ca.ldkv = ldkv; ca.out = OUT.f();
+        ca.rows = R; ca.d = d; ca.n_head = H; ca.T = T;
+        ca.head_rank = align ? HR.i() : nullptr; ca.ring = align ? RING.f() : nullptr; ca.ring_row = RR.i(); ca.beam_of_row = BR.i();
+        ca.ring_rows = q->ring_rows; ca.n_beam = q->n_beam; ca.qk_debug = nullptr; ca.xq_scale = 1.f;
+        if (route == WLK_DA_C2) {
+            X.alloc((size_t)R * d * F, q->x); WQ.alloc((size_t)d * d * F, q->wq); GA.alloc(d * F, q->gamma); BE.alloc(d * F, q->beta);
+            if (q->bq) BQ.alloc(d * F, q->bq);
+            ca.q = nullptr;
+            ca.xq_x = X.f(); ca.xq_w = WQ.f(); ca.xq_b = q->bq ? BQ.f() : nullptr; ca.xq_gamma = GA.f(); ca.xq_beta = BE.f();
+            ca.xq_scale = q->scale;
+        }
+        if (route == WLK_DA_C4) {
+            // row r = a beam-1 session: its keys / values are set row_kv[r], its window is beam beam_of_row[r] of the caller's
+            // ring (the ring-row stride of the whole beam group makes rank * stride land on ring[rank][beam][0])
+            std::vector<StepRow> rows(R);
+            for (int r = 0; r < R; ++r) {
+                StepRow sr{};
+                sr.cross_kv = KV.f() + (size_t)q->row_kv[r] * set_floats;
+                if (align) {
+                    sr.ring = RING.f() + (size_t)q->beam_of_row[r] * q->ring_rows * T;
+                    sr.ring_row = q->ring_row[r];
+                }
+                rows[r] = sr;
+            }
+            ROWS.alloc(sizeof(StepRow) * R, rows.data());
+            ca.step_rows = reinterpret_cast<const StepRow*>(ROWS.p);
+            ca.kv_off = 2 * d;
+            ca.k = nullptr; ca.v = nullptr; ca.ring = nullptr; ca.ring_row = nullptr; ca.beam_of_row = nullptr;
+            ca.ring_rows = q->n_beam * q->ring_rows; ca.n_beam = 1;
+        }
+        WLK_HIP(hipDeviceSynchronize());
+        switch (route) {
+        case WLK_DA_C0:
+            ca.qk_debug = q->scores ? SC.f() : nullptr;
+            launch_decoder_cross_attention(ctx, ca);
+            break;
+        case WLK_DA_C1:
+        case WLK_DA_C2:
+        case WLK_DA_C4: launch_decoder_cross_attention_split(ctx, ca, SC.f(), PM.f(), PL.f(), PO.f(), true); break;
+        case WLK_DA_C3: {
+            WO.alloc((size_t)d * d * F, q->wo); BO.alloc(d * F, q->bo);
+            WLK_HIP(hipMemcpy(OUT.p, q->resid, d * F, hipMemcpyHostToDevice));      // the residual stream is updated in place
+            launch_decoder_cross_attention_split(ctx, ca, SC.f(), PM.f(), PL.f(), PO.f(), false);
+            GemmArgs xo;
+            xo.mg_pm = PM.f(); xo.mg_pl = PL.f(); xo.mg_po = PO.f(); xo.mg_scores = SC.f();
+            xo.mg_head_rank = ca.head_rank; xo.mg_ring = ca.ring; xo.mg_ring_row = ca.ring_row;
+            xo.mg_side_heads = align ? SH.i() : nullptr;
+            xo.mg_beam_of_row = ca.beam_of_row; xo.mg_heads = H; xo.mg_T = T;
+            xo.mg_ring_rows = q->ring_rows; xo.mg_n_beam = q->n_beam;
+            xo.mg_side_blocks = align ? (int)side_heads.size() : 0;
+            xo.A = Q.f(); xo.lda = d; xo.W = WO.f(); xo.bias = BO.f(); xo.C = OUT.f(); xo.ldc = d; xo.M = R; xo.N = d;
+            xo.K = d; xo.flags = kGemmResidual; xo.R = OUT.f(); xo.ldr = d;
+            launch_gemv(ctx, xo, "diag_dec_xout");
+            break;
+        }
+        default: {
+            FlashArgs fa;
+            fa.q = Q.f(); fa.ldq = d; fa.k = ca.k; fa.v = ca.v; fa.ldkv = ldkv; fa.out = OUT.f(); fa.ldo = d;
+            fa.Tq = R; fa.Tk = T; fa.n_head = H;
+            fa.head_rank = ca.head_rank; fa.ring = ca.ring; fa.ring_row = align ? RR.i() : nullptr;
+            fa.beam_of_row = align ? BR.i() : nullptr; fa.ring_rows = q->ring_rows; fa.n_beam = q->n_beam;
+            if (q->k_splits == 0) {
+                fa.k_splits = wlk_session::flash_splits();
+                PART.alloc(flash_split_scratch_floats(R, H, fa.k_splits) * F);
+                fa.part_o = PART.f();
+                fa.part_m = fa.part_o + (size_t)R * H * fa.k_splits * 64;
+                fa.part_l = fa.part_m + (size_t)R * H * fa.k_splits;
+            }
+            launch_prefill_cross_attention(ctx, fa);
+            // (a session softmaxes every rank behind its last layer; this is one layer, so: the ranks of its heads)
+            if (align) launch_ring_softmax(ctx, RING.f(), RR.i(), BR.i(), RK.i(), (int)ranks.size(), R, q->ring_rows, q->n_beam, T);
+            break;
+        }
+        }
+        WLK_HIP(hipDeviceSynchronize());
+        OUT.back(q->out);
+        if (align) RING.back(q->ring);
+        if (q->scores) WLK_HIP(hipMemcpy(q->scores, SC.p, (size_t)q->scores_floats * F, hipMemcpyDeviceToHost));
+        return WLK_OK;
+    } catch (const std::invalid_argument& e) {
+        (void)hipDeviceSynchronize();
+        g_diag_error = e.what();
+        return WLK_ERR_ARG;
+    } catch (const std::exception& e) {
+        g_diag_error = e.what();
+        return WLK_ERR_HIP;
+    }
 }
 
 }  // extern "C"
