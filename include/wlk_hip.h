@@ -408,7 +408,7 @@ int wlk_vad_stream_destroy(wlk_vad_stream* s);
 
 /* ---- diagnostics: one kernel on host data (used by the GPU parity tests only) ---------------- */
 const char* wlk_diag_last_error(void);
-/* environment switches the library caches on first use (WLK_PREFILL_LN_FUSE) are read again at their next use: for tests
+/* environment switches the library caches on first use (WLK_X3_PERSIST) are read again at their next use: for tests
  * that flip one inside a process */
 int wlk_diag_env_refresh(void);
 /* c[m,n] = epilogue(a[m,k](row stride lda, a_floats floats in total) . w[n,k]^T + bias); flags:
@@ -529,7 +529,7 @@ int wlk_find_alignment(wlk_session* s, const int64_t* tokens, int32_t n_tokens, 
  * device-resident pseudo-random operands (same `force_gemv` meaning as wlk_diag_linear) */
 int wlk_diag_linear_time(int m, int n, int k, int flags, int force_gemv, int reps, float* us_per_launch);
 /* c[m,n] = LayerNorm(a[m,k]; gamma, beta, eps 1e-5) . w[n,k]^T + bias, m <= 8: the fused pre-LN projections
- * of the decode-step (weight-streaming) path */
+ * of the decode-step (weight-streaming) path.  m > 8 is an error: no MFMA kernel takes the LayerNorm */
 int wlk_diag_linear_ln(const float* a, const float* w, const float* bias, const float* gamma, const float* beta,
                        int m, int n, int k, int force_gemv, float* c);
 int wlk_diag_layernorm(const float* x, const float* gamma, const float* beta, int rows, int d, float* y);

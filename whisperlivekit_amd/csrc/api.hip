@@ -724,9 +724,6 @@ static void transformer_mlp(const LaunchCtx& c, const LayerW& L, float* x, float
     if (gemv_applicable(rows, d)) {
         g.A = x; g.ln_gamma = L.ln2w; g.ln_beta = L.ln2b;
         launch_gemv(c, g, "dec_ln2_fc1");
-    } else if (gemm_fuses_layernorm(rows, 4 * d, d)) {   // decoder prefill: see gemm_nt_f32_kwave16_kernel
-        g.A = x; g.ln_gamma = L.ln2w; g.ln_beta = L.ln2b;
-        launch_gemm(c, g, "dec_ln2_fc1");
     } else {
         launch_layernorm(c, x, d, L.ln2w, L.ln2b, h, d, rows, d, t_ln);
         g.A = h;
@@ -1052,10 +1049,6 @@ static void enqueue_decode(wlk_session* s, const LaunchCtx& c, int n_rows, int n
             g.A = s->dx; g.ln_gamma = L.ln1w; g.ln_beta = L.ln1b;
             g.kcache = kc; g.vcache = vc; g.kv_pos = s->d_offset; g.kv_d = d; g.kv_ctx = ctx_len;
             launch_gemv(c, g, "dec_ln1_qkv_kv");
-        } else if (gemm_fuses_layernorm(R, 3 * d, d)) {   // prompt rows: the 16 x 16 kernel normalises its A rows itself
-            g.A = s->dx; g.ln_gamma = L.ln1w; g.ln_beta = L.ln1b;
-            g.kcache = kc; g.vcache = vc; g.kv_pos = s->d_offset; g.kv_d = d; g.kv_ctx = ctx_len; g.kv_ntok = n_tok;
-            launch_gemm(c, g, "dec_ln1_qkv");
         } else {
             launch_layernorm(c, s->dx, d, L.ln1w, L.ln1b, s->dh, d, R, d, "dec_ln1");
             g.A = s->dh;
@@ -1088,9 +1081,6 @@ static void enqueue_decode(wlk_session* s, const LaunchCtx& c, int n_rows, int n
         } else if (fused) {
             q.A = s->dx; q.ln_gamma = L.lnxw; q.ln_beta = L.lnxb;
             launch_gemv(c, q, "dec_lnx_xq");
-        } else if (gemm_fuses_layernorm(R, d, d)) {
-            q.A = s->dx; q.ln_gamma = L.lnxw; q.ln_beta = L.lnxb;
-            launch_gemm(c, q, "dec_lnx_xq");
         } else {
             launch_layernorm(c, s->dx, d, L.lnxw, L.lnxb, s->dh, d, R, d, "dec_lnx");
             q.A = s->dh;
@@ -1306,19 +1296,11 @@ extern "C++" void wlk_prefill_group(const std::vector<wlk_prefill_item*>& items,
         g.force_kwave = true;
         launch_gemm(c, g, tag);
     };
-    // LayerNorm + projection: one launch where the 16 x 16 kernel takes it (the same rule as a session's own prefill, so
-    // that a stacked row gets its solo arithmetic - which it would either way: the fused statistics are the kernel's)
+    // LayerNorm + projection, as in a session's own prefill
     auto ln_linear = [&](const float* gamma, const float* beta, const float* W, const float* bias, float* C, long ldc, int N,
                          int flags, float sc, int sc_cols, const char* t_ln, const char* tag) {
-        if (gemm_fuses_layernorm(R, N, d)) {
-            GemmArgs g;
-            g.A = ws.dx; g.lda = d; g.W = W; g.bias = bias; g.C = C; g.ldc = ldc; g.M = R; g.N = N; g.K = d;
-            g.flags = flags; g.scale = sc; g.scale_cols = sc_cols; g.ln_gamma = gamma; g.ln_beta = beta;
-            launch_gemm(c, g, tag);
-        } else {
-            launch_layernorm(c, ws.dx, d, gamma, beta, ws.dh, d, R, d, t_ln);
-            linear(ws.dh, d, W, bias, C, ldc, N, d, flags, nullptr, sc, sc_cols, tag);
-        }
+        launch_layernorm(c, ws.dx, d, gamma, beta, ws.dh, d, R, d, t_ln);
+        linear(ws.dh, d, W, bias, C, ldc, N, d, flags, nullptr, sc, sc_cols, tag);
     };
     for (int i = 0; i < L; ++i) {
         const LayerW& W = m->dec_layers[i];

@@ -191,13 +191,9 @@ struct GemmArgs {
     int batch = 0;
     long long* dbg_clock = nullptr;  // probe only: 4 s_memtime stamps per workgroup (start, loop start, loop end, end)
     // ---- the rest -----------------------------------------------------------------------------------------------------
-    // GEMV path only (decode steps): fused pre-LayerNorm of the A rows (eps 1e-5) ...
+    // GEMV path only (decode steps; launch_gemm and launch_gemm_kp refuse it): fused pre-LayerNorm of the A rows (eps 1e-5) ...
     const float* ln_gamma = nullptr;
     const float* ln_beta = nullptr;
-    // 16 x 16 k-wave kernel with the LayerNorm inside (round 6): the column-tile-0 workgroups also store the normalised rows
-    // here ([M][ld_ln_out]) - for networks that use LN(x) twice (the Sortformer's post-LN Transformer: projection input AND residual)
-    float* ln_out = nullptr;
-    long ld_ln_out = 0;
     // ... and fused KV-cache append: output columns [kv_d, 2kv_d) / [2kv_d, 3kv_d) of row m are ALSO
     // written to kcache/vcache[(m*kv_ctx + *kv_pos) * kv_d + col] (one fed token per row)
     float* kcache = nullptr;
@@ -228,7 +224,7 @@ struct GemmArgs {
     const AlignArgs* side_align = nullptr;
     int side_blocks = 0, side_zf = 0;
     bool force_kwave = false;            // diagnostics: take the k-wave kernel (under-filled grids) whatever the shape
-    int force_kernel = 0;                // diagnostics / A-B: 0 = by shape, 2 = k-wave, 3 = the 64x64 kernel, 4 = the k-split kernel
+    int force_kernel = 0;                // diagnostics / A-B: 0 = by shape, 2 = k-wave, 3 = the 64x64 kernel, 4 = the one-tile-per-CU k-pipe kernel
     bool gemm_plain_loop = false;        // A/B switch: LDS fragment reads right before use instead of a group ahead
 };
 // First statement of every kernel that takes GemmArgs by value: the hot block above is requested together and held in
@@ -246,9 +242,8 @@ void launch_gemm(const LaunchCtx& ctx, const GemmArgs& g, const char* tag);
 // the "kp" family: one per-element arithmetic (the k-pipe kernel's) for every tile, so stacked rows keep their solo results
 void launch_gemm_kp(const LaunchCtx& ctx, const GemmArgs& g, const char* tag);
 bool gemm_kp_takes_kpipe(int M, int N, int K);
-bool gemm_kp_fuses_layernorm(int M, int N, int K);   // launch_gemm_kp takes ln_gamma / ln_beta for this problem (rows < 512, K = 512)
 bool gemm_takes_kwave(int M, int N, int K);
-bool gemm_takes_ksplit(int M, int N, int K);  // ... for the one-tile-per-CU k-split kernel (encoder-sized problems)   // launch_gemm's shape rule for the k-wave kernel (under-filled grids)
+bool gemm_takes_ksplit(int M, int N, int K);  // ... for the one-tile-per-CU k-pipe kernel (encoder-sized problems)   // launch_gemm's shape rule for the k-wave kernel (under-filled grids)
 // weight-streaming path for M <= 8 rows (decode steps); same contract as launch_gemm
 void launch_gemv(const LaunchCtx& ctx, const GemmArgs& g, const char* tag);
 inline int gemv_row_bucket(int M) { return M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : 8; }
@@ -258,7 +253,6 @@ inline bool gemv_applicable(int M, int K) {
 // can launch_gemv take the cross-attention output in split form (single-row kernel, K = d)?
 bool gemv1_folds_merge(int K);
 void refresh_env_switches();                      // cached environment switches are read again at their next use (tests)
-bool gemm_fuses_layernorm(int M, int N, int K);   // launch_gemm takes ln_gamma / ln_beta for this problem (prefill rows)
 inline void launch_linear(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
     if (gemv_applicable(g.M, g.K)) launch_gemv(ctx, g, tag);
     else launch_gemm(ctx, g, tag);

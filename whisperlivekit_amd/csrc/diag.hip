@@ -188,7 +188,7 @@ int wlk_diag_linear_ln(const float* a, const float* w, const float* bias, const 
         LaunchCtx ctx;
         (void)force_gemv;
         if (m <= 8) launch_gemv(ctx, g, "diag_gemv_ln");     // decode steps: the weight-streaming kernels
-        else launch_gemm(ctx, g, "diag_gemm_ln");            // prompt rows: the 16 x 16 kernel (throws where it does not apply)
+        else launch_gemm(ctx, g, "diag_gemm_ln");            // more rows: throws (no MFMA kernel takes the LayerNorm)
         WLK_HIP(hipDeviceSynchronize());
         WLK_HIP(hipMemcpy(c, Cc.p, (size_t)m * n * sizeof(float), hipMemcpyDeviceToHost));
     });

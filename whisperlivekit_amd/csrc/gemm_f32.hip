@@ -19,7 +19,6 @@
 // four k values with ONE 16-byte LDS read instead of four strided 4-byte reads.
 #include <algorithm>
 #include <atomic>
-#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -390,20 +389,12 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kwave_kernel(GemmArgs g) {
 // Every wave feeds the k values of its quarter in the order the 32 x 32 x 2 sequence accumulates them (k-group s: 8s,
 // 8s+4, 8s+1, 8s+5 | 8s+2, 8s+6, 8s+3, 8s+7), and the four partials are folded in wave order as above.
 // -------------------------------------------------------------------------------------------------
-// NPL > 0: the LayerNorm in front of the projection (ln1 -> qkv, lnx -> xq, ln2 -> fc1) is part of the kernel.  K = 64 NPL is
-// the model width; each wave derives mean and rstd of four of the tile's sixteen rows exactly as layernorm_kernel does
-// (lane-strided elements summed in index order, butterfly fold, two passes) while the first two slabs are in flight, and
-// the A values are normalised - (x - mean) * rstd * gamma + beta, the same expression - on their way into LDS.  Bit for
-// bit the LayerNorm launch + this kernel (tests/test_gpu_parity.py::test_prefill_gemm_fuses_the_layernorm); 18 launches
-// less per prefill.
 // KP (round 6): the k-pipe kernel's partition of K, as in gemm_nt_f32_kwave_kernel<true> - wave w takes the eight k values
 // 8 w .. 8 w + 7 of each of the slab's four 32-deep sub-tiles (in the same in-group order), so the 16 x 16 tiles join the "kp"
 // family: bit for bit the 32 x 32 k-wave tiles' and every k-pipe tile's result.
-template <int NPL, bool KP = false>
+template <bool KP = false>
 __global__ __launch_bounds__(256) void gemm_nt_f32_kwave16_kernel(GemmArgs g) {
     WLK_PIN_GEMM_ARGS(g);
-    constexpr bool LN = NPL > 0;
-    __shared__ float ln_stat[LN ? 32 : 1];
     constexpr int KW = 4, SLAB = BK * KW, SUB = 16 * LDS_LD;
     __shared__ __attribute__((aligned(16))) float As[2][KW * SUB];
     __shared__ __attribute__((aligned(16))) float Ws[2][KW * SUB];
@@ -430,7 +421,6 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kwave16_kernel(GemmArgs g) {
     }
     struct Slab {
         float4 a[2], w[2];
-        float4 ga, be;      // LN: gamma / beta of this thread's four k columns of the slab
     };
     auto fetch = [&](Slab& st, int ks) {
         const int k0 = ks * SLAB;
@@ -445,29 +435,10 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kwave16_kernel(GemmArgs g) {
             const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, (int)(in ? w_byte[i] + (unsigned)k0 * 4u : kOob), 0, 0);
             st.w[i] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
         }
-        if constexpr (LN) {
-            const int kk = min(k0 + kcol, g.K - 4);
-            st.ga = *reinterpret_cast<const float4*>(g.ln_gamma + kk);
-            st.be = *reinterpret_cast<const float4*>(g.ln_beta + kk);
-        }
     };
-    [[maybe_unused]] float ln_mean[2] = {0.f, 0.f}, ln_rstd[2] = {1.f, 1.f};
-    // LN: the workgroups of column tile 0 also keep the normalised rows (GemmArgs::ln_out) - `ks` is the slab being stashed
-    [[maybe_unused]] const bool keep_ln = LN && g.ln_out != nullptr && tile_n == 0;
-    auto stash = [&](const Slab& st, int buf, [[maybe_unused]] int ks = 0) {
+    auto stash = [&](const Slab& st, int buf) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            float4 a4 = st.a[i];
-            if constexpr (LN) {
-                a4.x = (a4.x - ln_mean[i]) * ln_rstd[i] * st.ga.x + st.be.x;
-                a4.y = (a4.y - ln_mean[i]) * ln_rstd[i] * st.ga.y + st.be.y;
-                a4.z = (a4.z - ln_mean[i]) * ln_rstd[i] * st.ga.z + st.be.z;
-                a4.w = (a4.w - ln_mean[i]) * ln_rstd[i] * st.ga.w + st.be.w;
-                const int row = m0 + (tid >> 5) + 8 * i, kk = ks * SLAB + kcol;
-                if (keep_ln && row < g.M && kk < g.K) *reinterpret_cast<float4*>(g.ln_out + (long)row * g.ld_ln_out + kk) = a4;
-            }
-            *reinterpret_cast<float4*>(&As[buf][lds_at[i]]) = a4;
-        }
+        for (int i = 0; i < 2; ++i) *reinterpret_cast<float4*>(&As[buf][lds_at[i]]) = st.a[i];
 #pragma unroll
         for (int i = 0; i < 2; ++i) *reinterpret_cast<float4*>(&Ws[buf][lds_at[i]]) = st.w[i];
     };
@@ -501,62 +472,22 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kwave16_kernel(GemmArgs g) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) res[r] = (has_res ? g.R + (long)min(row_base + r, g.M - 1) * g.ldr + colc : g.W)[0];
     int kv_off = (g.kcache ? g.kv_pos : reinterpret_cast<const int*>(g.W))[0];
-    // LN: rows m0 + 4 wave + q - layernorm_kernel's statistics, all four rows' elements requested together (and before the
-    // pins below: a pin waits for what it names)
-    [[maybe_unused]] float v[4][LN ? NPL : 1];
-    if constexpr (LN) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float* xr = g.A + (long)min(m0 + 4 * wave + q, g.M - 1) * g.lda;
-#pragma unroll
-            for (int i = 0; i < NPL; ++i) v[q][i] = xr[lane + 64 * i];
-        }
-    }
     pin_loaded(b);
 #pragma unroll
     for (int r = 0; r < 4; ++r) pin_loaded(res[r]);
     asm volatile("" : "+v"(kv_off));
-    if constexpr (LN) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            float sum = 0.f;
-#pragma unroll
-            for (int i = 0; i < NPL; ++i) sum += v[q][i];
-            sum = wave_sum(sum);
-            const float mean = sum / (float)g.K;
-            float sq = 0.f;
-#pragma unroll
-            for (int i = 0; i < NPL; ++i) {
-                const float t = v[q][i] - mean;
-                sq += t * t;
-            }
-            sq = wave_sum(sq);
-            const float rstd = 1.0f / sqrtf(sq / (float)g.K + 1e-5f);
-            if (lane == 0) {
-                ln_stat[2 * (4 * wave + q)] = mean;
-                ln_stat[2 * (4 * wave + q) + 1] = rstd;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int row = (tid >> 5) + 8 * i;
-            ln_mean[i] = ln_stat[2 * row];
-            ln_rstd[i] = ln_stat[2 * row + 1];
-        }
-    }
-    stash(s0, 0, 0);
+    stash(s0, 0);
     __syncthreads();
     for (int ks = 0; ks < ns2; ks += 2) {
         fetch(s0, ks + 2);
         __builtin_amdgcn_sched_barrier(0);
         mma(0);
-        stash(s1, 1, ks + 1);
+        stash(s1, 1);
         __syncthreads();
         fetch(s1, ks + 3);
         __builtin_amdgcn_sched_barrier(0);
         mma(1);
-        stash(s0, 0, ks + 2);
+        stash(s0, 0);
         __syncthreads();
     }
     // fold the four k-partials in wave order
@@ -615,13 +546,7 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kwave16_kernel(GemmArgs g) {
 // 96 x 128), and the four partial tiles are added in wave order through LDS at the end (fixed order: run-to-run
 // identical; the order does not depend on the batch, so a session stacked with others gets its solo arithmetic).
 // Per MFMA this needs (TM + TN) / (TM TN) LDS fragment reads instead of 2, and per flop the fewest bytes from L2.
-//
-// Slabs arrive by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write pass), one 1 KiB piece per wave
-// instruction = 8 rows x one 128-byte line, issued for slab t+1 before the math on slab t and waited for at the one
-// barrier per slab.  The DMA writes lane-linearly, so the bank swizzle lives in the SOURCE address: lane l of a piece
-// fetches 16-byte chunk (l & 7) ^ ((row >> 1) & 7) of its row's line, and the fragment reads apply the same XOR - each
-// 16-lane service group of a ds_read_b128 then touches 16 distinct bank quads (rows of equal parity in a group have
-// distinct (row >> 1) & 7).  The k-permutation of the kernels above applies unchanged: one 16-byte read = 4 MFMA steps.
+// The kernel itself (gemm_nt_f32_kpipe_kernel) follows the pieces of its fold and epilogue.
 // -------------------------------------------------------------------------------------------------
 // compile-time loop: f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>) - indices into register arrays
 // stay constants whatever the optimiser thinks of the body's size (a runtime-indexed accumulator array goes to scratch)
@@ -642,7 +567,7 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
-// Fold of the four k-partials + epilogue, shared by the k-split and the k-pipe kernel.
+// Fold of the four k-partials + epilogue of the k-pipe kernel.
 //
 // Every wave finishes a quarter of EVERY tile - accumulator registers 4w .. 4w+3 = rows 8w .. 8w+3 (+4 for lanes 32-63):
 // balanced for any tile count, and no accumulator is ever selected by a runtime index.  What shaped the rest (all
@@ -760,161 +685,17 @@ __device__ __forceinline__ void ksplit_fold_store(const GemmArgs& g, f32x16 (&ac
     });
 }
 
-// KS = slab depth (32 or 64 floats of K per trip; each of the four waves contracts KS / 4 of them)
-template <int TM, int TN, int KS>
-struct KSplitCfg {
-    static constexpr int BM = 32 * TM, BN = 32 * TN;
-    static constexpr int HALVES = KS / 32;                                        // 128-byte lines per slab row
-    static constexpr int A_PIECES = BM / 8 * HALVES, W_PIECES = BN / 8 * HALVES;  // 1 KiB pieces per slab
-    static constexpr int PIECES_PER_WAVE = (A_PIECES + W_PIECES) / 4;
-    static constexpr int SLAB_FLOATS = (BM + BN) * KS;
-    static constexpr int RED_FLOATS = TM * TN * 1024 + 512 + 2 * 4096;            // the fold: residuals + constants + >= 2 tiles per pass
-    static constexpr int LDS_FLOATS = (2 * SLAB_FLOATS > RED_FLOATS ? 2 * SLAB_FLOATS : RED_FLOATS);
-    static constexpr size_t LDS_BYTES = (size_t)LDS_FLOATS * sizeof(float);
-};
-
-// ABL (timing ablations of the probe only, results are wrong): 1 = no DMA inside the loop, 2 = no MFMA, 3 = no fragment reads
-template <int TM, int TN, int KS, int ABL = 0>
-__global__ __launch_bounds__(256) void gemm_nt_f32_ksplit_kernel(GemmArgs g) {
-    WLK_PIN_GEMM_ARGS(g);
-    using Cfg = KSplitCfg<TM, TN, KS>;
-    constexpr int BM = Cfg::BM, BN = Cfg::BN, NP = Cfg::PIECES_PER_WAVE, HALVES = Cfg::HALVES, STEPS = KS / 32;
-    extern __shared__ __attribute__((aligned(1024))) float lds[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const bool batched = g.batch > 0;
-    const float* const gA = batched ? table_at(g.z.in, blockIdx.y) : g.A;
-    float* const gC = batched ? table_at(g.z.out, blockIdx.y) : g.C;
-    const float* const gR = batched ? table_at(g.z.res, blockIdx.y) : g.R;
-    // XCD-aware tile mapping (see gemm_nt_f32_kernel): 4 row bands x 2 column bands, one per XCD
-    const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-    int tile_m, tile_n;
-    if (tiles_m >= 8) {
-        const int band_m = (tiles_m + 3) / 4, band_n = (tiles_n + 1) / 2;
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        tile_m = (xcd >> 1) * band_m + slot / band_n;
-        tile_n = (xcd & 1) * band_n + slot % band_n;
-        if (slot >= band_m * band_n || tile_m >= tiles_m || tile_n >= tiles_n) return;   // padding workgroups
-    } else {
-        tile_m = blockIdx.x / tiles_n;
-        tile_n = blockIdx.x - tile_m * tiles_n;
-        if (tile_m >= tiles_m) return;
-    }
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
-
-    // DMA sources of this wave's pieces (piece j = wave + 4 i: A pieces first, then W; piece = (row group of 8, line)).
-    // Rows past the end of the operand are clamped: they only feed output rows / columns that are never stored.
-    const float* src[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const int j = wave + 4 * i;
-        const bool is_a = j < Cfg::A_PIECES;
-        const int jj = is_a ? j : j - Cfg::A_PIECES;
-        const int row_local = (jj / HALVES) * 8 + (lane >> 3);
-        const int chunk = (lane & 7) ^ ((row_local >> 1) & 7);
-        const int col = (jj % HALVES) * 32 + chunk * 4;
-        if (is_a) src[i] = gA + (long)min(m0 + row_local, g.M - 1) * g.lda + col;
-        else src[i] = g.W + (long)min(n0 + row_local, g.N - 1) * g.K + col;
-    }
-    // one DMA piece of this wave: slab kt -> buffer buf
-    auto issue_piece = [&](auto I, int kt, int buf) {
-        constexpr int i = decltype(I)::value;
-        const int j = wave + 4 * i;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[i] + (long)kt * KS),
-                                         (__attribute__((address_space(3))) void*)(lds + buf * Cfg::SLAB_FLOATS + j * 256), 16, 0, 0);
-    };
-
-    // fragment addresses (floats): row r of an operand sits in piece (r >> 3, line), 8 x 16-byte chunks per line; wave w
-    // owns chunks [w KS / 16, (w + 1) KS / 16) of a slab row; read step s takes chunk 2 s (lanes 0-31) / 2 s + 1 (32-63)
-    const int cg0 = (KS / 16) * wave + (lane >> 5);     // chunk of step 0 within the slab row; step 1 is + 2 (same line)
-    const int line = cg0 >> 3, c0 = cg0 & 7;
-    int a_off[TM], w_off[TN];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) {
-        const int r = 32 * t + (lane & 31);
-        a_off[t] = (((r >> 3) * HALVES + line) * 64 + (r & 7) * 8 + (c0 ^ ((r >> 1) & 7))) * 4;
-    }
-#pragma unroll
-    for (int t = 0; t < TN; ++t) {
-        const int r = 32 * t + (lane & 31);
-        w_off[t] = Cfg::A_PIECES * 256 + (((r >> 3) * HALVES + line) * 64 + (r & 7) * 8 + (c0 ^ ((r >> 1) & 7))) * 4;
-    }
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    // One slab per trip, one basic block: fragment reads of slab kt (all STEPS (TM + TN) of them) FIRST - a ds_read placed
-    // behind an outstanding LDS-DMA would make hipcc drain the DMA queue (it cannot tell the two buffers apart) - then
-    // the MFMAs with the DMA pieces of slab kt + 1 (other buffer) dealt between the first of them, then the one barrier
-    // (hipcc waits for the DMA in front of it; the sched_barrier keeps the matrix work from sinking below it, which
-    // would expose the whole DMA latency).  The last trip re-fetches its own slab into the idle buffer instead of
-    // branching; the barrier drains it before the fold reuses LDS.  The other buffer's last reads sit before the
-    // previous trip's barrier.
-    const int nslab = g.K / KS;
-    EpilogueOperands<TM, TN> eo;          // residual / bias values: in flight during the main loop (see ksplit_fold_store)
-    ksplit_fetch_epilogue<TM, TN>(g, eo, wave, lane, m0, n0, gR);
-    static_for<NP>([&](auto I) { issue_piece(I, 0, 0); });
-    __syncthreads();
-    constexpr int NMF = 4 * STEPS * TM * TN;            // MFMAs per trip
-    constexpr int GAP = NMF / NP >= 2 ? 2 : 1;          // one DMA piece every GAP MFMAs (a piece's ~60 issue cycles fit inside one
-                                                        // MFMA's 64); front-loaded, so the rest of the trip covers the DMA latency
-    for (int kt = 0; kt < nslab; ++kt) {
-        const int cur = kt & 1;
-        const int nxt = min(kt + 1, nslab - 1);
-        const float* base = lds + cur * Cfg::SLAB_FLOATS;
-        float4 fa[STEPS][TM], fb[STEPS][TN];
-#pragma unroll
-        for (int s = 0; s < STEPS; ++s) {      // step 1 = chunk + 2: one XOR on the float offset (bit 3)
-#pragma unroll
-            for (int t = 0; t < TM; ++t) {
-                if constexpr (ABL == 3) fa[s][t] = make_float4(1.f, 2.f, 3.f, (float)kt);
-                else fa[s][t] = *reinterpret_cast<const float4*>(base + (a_off[t] ^ (s * 8)));
-            }
-#pragma unroll
-            for (int t = 0; t < TN; ++t) {
-                if constexpr (ABL == 3) fb[s][t] = make_float4(1.f, 2.f, 3.f, (float)kt);
-                else fb[s][t] = *reinterpret_cast<const float4*>(base + (w_off[t] ^ (s * 8)));
-            }
-        }
-        static_for<NMF>([&](auto X) {
-            constexpr int x = decltype(X)::value;
-            constexpr int s = x / (4 * TM * TN), c = (x / (TM * TN)) & 3, q = x % (TM * TN), i = q / TN, j = q % TN;
-            const float a = c == 0 ? fa[s][i].x : c == 1 ? fa[s][i].y : c == 2 ? fa[s][i].z : fa[s][i].w;
-            const float b = c == 0 ? fb[s][j].x : c == 1 ? fb[s][j].y : c == 2 ? fb[s][j].z : fb[s][j].w;
-            if constexpr (ABL == 2) {
-                asm volatile("" ::"v"(a), "v"(b));
-            } else {
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[i][j], 0, 0, 0);
-            }
-            if constexpr (ABL != 1 && x % GAP == GAP - 1 && x / GAP < NP) {
-                issue_piece(std::integral_constant<int, x / GAP>{}, nxt, cur ^ 1);
-            }
-        });
-        if constexpr (ABL == 0) {
-            // issue order of the trip: all fragment reads, then GAP MFMAs / one DMA piece, NP times, then the remaining
-            // MFMAs (left to itself hipcc bunches the pieces behind one MFMA: ~60 cycles of issue each, the pipe idles)
-            __builtin_amdgcn_sched_group_barrier(0x100, STEPS * (TM + TN), 0);
-            static_for<NP>([&](auto) {
-                __builtin_amdgcn_sched_group_barrier(0x008, GAP, 0);
-                __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-            });
-            if constexpr (NMF - NP * GAP > 0) __builtin_amdgcn_sched_group_barrier(0x008, NMF - NP * GAP, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-    }
-
-    ksplit_fold_store<TM, TN, Cfg::LDS_FLOATS>(g, acc, eo, lds, wave, lane, m0, n0, gC);
-}
-
 // -------------------------------------------------------------------------------------------------
-// The same kernel with the slab pipeline under manual control ("k-pipe"): 32-deep slabs in a ring of NB LDS buffers,
-// the DMA of slab t + NB - 1 issued during trip t, COUNTED waits (s_waitcnt vmcnt((NB - 2) NP): only slab t + 1 has to
+// The one-tile-per-CU kernel ("k-pipe").
+//
+// Slabs arrive by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write pass), one 1 KiB piece per wave
+// instruction = 8 rows x one 128-byte line, issued ahead of the math and waited for at the one barrier per slab
+// (below).  The DMA writes lane-linearly, so the bank swizzle lives in the SOURCE address: lane l of a piece fetches 16-byte chunk (l & 7) ^ ((row >> 1) & 7) of its row's line, and the fragment reads apply the same XOR - each
+// 16-lane service group of a ds_read_b128 then touches 16 distinct bank quads (rows of equal parity in a group have
+// distinct (row >> 1) & 7).  The k-permutation of the kernels above applies unchanged: one 16-byte read = 4 MFMA steps.
+//
+// The slab pipeline is under manual control: 32-deep slabs in a ring of NB = 4 LDS buffers, one slab per trip (= per
+// barrier), the DMA of slab t + NB - 1 issued during trip t, COUNTED waits (s_waitcnt vmcnt((NB - 2) NP): only slab t + 1 has to
 // have landed, the younger slabs stay in flight across the barrier), fragment reads of slab t + 1 issued in the
 // middle of trip t so that their latency hides behind the second half of the trip's MFMAs.  hipcc cannot express
 // this: it drains the whole DMA queue in front of every __syncthreads() and in front of any LDS read that follows an
@@ -931,13 +712,9 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_ksplit_kernel(GemmArgs g) {
 // drains everything before the fold reuses LDS.
 // -------------------------------------------------------------------------------------------------
 typedef float f32x4v __attribute__((ext_vector_type(4)));
-// NB = ring slots (32-deep slabs), STEPS = slabs per trip (= per barrier).  Thin tiles take STEPS = 2: a trip of 96 x 32 is
-// only 12 MFMAs (768 cycles) per slab, and the ~180 cycles per trip in which the wave cannot feed the matrix pipe (the
-// barrier, the fragment-read issue, DMA issue slots longer than an MFMA's shadow, loop control) were 19 % of its loop.
-template <int TM, int TN, int NB, int STEPS>
+template <int TM, int TN>
 struct KPipeCfg {
-    static_assert(NB % STEPS == 0 && NB / STEPS >= 2, "the ring holds whole trips, at least two");
-    static constexpr int BM = 32 * TM, BN = 32 * TN, KS = 32;
+    static constexpr int BM = 32 * TM, BN = 32 * TN, KS = 32, NB = 4;              // NB = ring slots (32-deep slabs)
     static constexpr int A_PIECES = BM / 8, W_PIECES = BN / 8;                   // 1 KiB pieces per slab (8 rows x 128 B)
     static constexpr int PIECES_PER_WAVE = (A_PIECES + W_PIECES) / 4;
     static constexpr int SLAB_FLOATS = (BM + BN) * KS;
@@ -951,10 +728,7 @@ __device__ __forceinline__ void wait_vmcnt() {
     static_assert(N >= 0 && N < 64, "vmcnt range");
     if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #define WLK_VM(n) else if constexpr (N == n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory");
-    WLK_VM(1) WLK_VM(2) WLK_VM(3) WLK_VM(4) WLK_VM(5) WLK_VM(6) WLK_VM(7) WLK_VM(8) WLK_VM(9) WLK_VM(10) WLK_VM(11) WLK_VM(12)
-    WLK_VM(13) WLK_VM(14) WLK_VM(15) WLK_VM(16) WLK_VM(17) WLK_VM(18) WLK_VM(19) WLK_VM(20) WLK_VM(21) WLK_VM(22) WLK_VM(23)
-    WLK_VM(24) WLK_VM(25) WLK_VM(26) WLK_VM(27) WLK_VM(28) WLK_VM(30) WLK_VM(32) WLK_VM(33) WLK_VM(35) WLK_VM(36) WLK_VM(40)
-    WLK_VM(42) WLK_VM(44) WLK_VM(48)
+    WLK_VM(6) WLK_VM(8) WLK_VM(10) WLK_VM(12) WLK_VM(14)      // 2 (TM + TN) of the instantiated tiles
 #undef WLK_VM
     else static_assert(N < 0, "add the vmcnt literal");
 }
@@ -963,26 +737,23 @@ __device__ __forceinline__ void wait_vmcnt() {
 // scheduled above the wait)
 template <int N>
 __device__ __forceinline__ void wait_lgkm_tied(f32x4v* f) {
-    static_assert(N >= 2 && N <= 8, "operand list");
-    if constexpr (N == 2) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]));
-    else if constexpr (N == 3) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]));
+    static_assert(N >= 3 && N <= 7, "operand list");
+    if constexpr (N == 3) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]));
     else if constexpr (N == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
     else if constexpr (N == 5) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]));
     else if constexpr (N == 6) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]));
-    else if constexpr (N == 7)
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]));
     else
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7]));
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]));
 }
 
-template <int TM, int TN, int NB, int STEPS>
+template <int TM, int TN>
 __global__ __launch_bounds__(256) void gemm_nt_f32_kpipe_kernel(GemmArgs g) {
     WLK_PIN_GEMM_ARGS(g);
-    using Cfg = KPipeCfg<TM, TN, NB, STEPS>;
-    constexpr int BM = Cfg::BM, BN = Cfg::BN, NP = Cfg::PIECES_PER_WAVE, KS = 32;
-    constexpr int DT = NB / STEPS - 1;                  // trips of DMA in flight beyond the one being multiplied
-    constexpr int NF = TM + TN, NFT = STEPS * NF;       // fragment registers (float4) per slab / per trip
-    static_assert(NFT <= 8, "fragment operand list");
+    using Cfg = KPipeCfg<TM, TN>;
+    constexpr int BM = Cfg::BM, BN = Cfg::BN, NP = Cfg::PIECES_PER_WAVE, KS = Cfg::KS, NB = Cfg::NB;
+    constexpr int DT = NB - 1;                          // slabs of DMA in flight beyond the one being multiplied
+    constexpr int NF = TM + TN;                         // fragment registers (float4) per slab
+    static_assert(NF <= 7, "fragment operand list");
     extern __shared__ __attribute__((aligned(1024))) float lds[];
     const long long t_start = g.dbg_clock ? (long long)__builtin_readcyclecounter() : 0;
     const int lane = threadIdx.x & 63;
@@ -1039,14 +810,11 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kpipe_kernel(GemmArgs g) {
         const int r = 32 * t + (lane & 31);
         f_addr[TM + t] = lds_base + (unsigned)(Cfg::A_PIECES * 1024 + ((r >> 3) * 64 + (r & 7) * 8 + (c0 ^ ((r >> 1) & 7))) * 16);
     }
-    // fragments of trip `trip` (slabs trip STEPS + s in slot (trip STEPS + s) % NB) -> f[s NF + t]
-    auto read_frags = [&](f32x4v (&f)[NFT], int trip) {
+    // fragments of slab `slab` (in slot slab % NB) -> f[t]
+    auto read_frags = [&](f32x4v (&f)[NF], int slab) {
+        const unsigned off = (unsigned)(slab % NB) * (unsigned)(Cfg::SLAB_FLOATS * 4);
 #pragma unroll
-        for (int s = 0; s < STEPS; ++s) {
-            const unsigned off = (unsigned)((trip * STEPS + s) % NB) * (unsigned)(Cfg::SLAB_FLOATS * 4);
-#pragma unroll
-            for (int t = 0; t < NF; ++t) asm volatile("ds_read_b128 %0, %1" : "=v"(f[s * NF + t]) : "v"(f_addr[t] + off));
-        }
+        for (int t = 0; t < NF; ++t) asm volatile("ds_read_b128 %0, %1" : "=v"(f[t]) : "v"(f_addr[t] + off));
     };
 
     f32x16 acc[TM][TN];
@@ -1057,54 +825,52 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kpipe_kernel(GemmArgs g) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    constexpr int NMF = 4 * STEPS * TM * TN;             // MFMAs per trip
+    constexpr int NMF = 4 * TM * TN;                     // MFMAs per trip
     constexpr int HEAD = NMF / 2;                        // ... in front of the barrier
-    constexpr int NPT = STEPS * NP;                      // DMA pieces per wave per trip
-    constexpr int GAP = HEAD / NPT >= 1 ? HEAD / NPT : 1;   // one DMA piece every GAP MFMAs of the head
-    static_assert(NPT <= HEAD, "more DMA pieces than head MFMAs");
+    constexpr int GAP = HEAD / NP >= 1 ? HEAD / NP : 1;  // one DMA piece (of the NP per wave and trip) every GAP MFMAs of the head
+    static_assert(NP <= HEAD, "more DMA pieces than head MFMAs");
 
     // residual / bias values first: they are older than every DMA piece, so the counted waits below cover them, and they
     // land during the first trips (see ksplit_fold_store)
     EpilogueOperands<TM, TN> eo;
     ksplit_fetch_epilogue<TM, TN>(g, eo, wave, lane, m0, n0, gR);
-    // prologue: trips 0 .. DT-1 in flight, trip 0 landed and read
-    static_for<DT * STEPS>([&](auto S) {
+    // prologue: slabs 0 .. DT-1 in flight, slab 0 landed and read
+    static_for<DT>([&](auto S) {
         constexpr int sl = decltype(S)::value;
         static_for<NP>([&](auto I) { issue_piece(I, sl, sl % NB); });
     });
-    wait_vmcnt<(DT - 1) * NPT>();
+    wait_vmcnt<(DT - 1) * NP>();
     __builtin_amdgcn_s_barrier();
-    f32x4v f0[NFT], f1[NFT];
+    f32x4v f0[NF], f1[NF];
     read_frags(f0, 0);
-    wait_lgkm_tied<NFT>(f0);
+    wait_lgkm_tied<NF>(f0);
 
-    // one trip: MFMAs of trip `tt` from f; DMA of trip tt + DT; reads of trip tt + 1 into fn
-    auto trip = [&](f32x4v (&f)[NFT], f32x4v (&fn)[NFT], int tt) {
+    // one trip: MFMAs of slab `tt` from f; DMA of slab tt + DT; reads of slab tt + 1 into fn
+    auto trip = [&](f32x4v (&f)[NF], f32x4v (&fn)[NF], int tt) {
         auto mfma_at = [&](auto X) {
             constexpr int x = decltype(X)::value;
-            constexpr int s = x / (4 * TM * TN), c = (x / (TM * TN)) & 3, q = x % (TM * TN), i = q / TN, j = q % TN;
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(f[s * NF + i][c], f[s * NF + TM + j][c], acc[i][j], 0, 0, 0);
+            constexpr int c = x / (TM * TN), q = x % (TM * TN), i = q / TN, j = q % TN;
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(f[i][c], f[TM + j][c], acc[i][j], 0, 0, 0);
         };
         static_for<HEAD>([&](auto X) {
             constexpr int x = decltype(X)::value;
             mfma_at(X);
-            if constexpr (x % GAP == GAP - 1 && x / GAP < NPT) {
-                constexpr int pc = x / GAP, st = pc / NP;
-                const int slab = (tt + DT) * STEPS + st;
-                issue_piece(std::integral_constant<int, pc % NP>{}, slab, slab % NB);
+            if constexpr (x % GAP == GAP - 1 && x / GAP < NP) {
+                const int slab = tt + DT;
+                issue_piece(std::integral_constant<int, x / GAP>{}, slab, slab % NB);
             }
         });
         __builtin_amdgcn_sched_barrier(0);
-        wait_vmcnt<(DT - 1) * NPT>();
+        wait_vmcnt<(DT - 1) * NP>();
         __builtin_amdgcn_s_barrier();
         read_frags(fn, tt + 1);
         __builtin_amdgcn_sched_barrier(0);
         static_for<NMF - HEAD>([&](auto X) { mfma_at(std::integral_constant<int, HEAD + decltype(X)::value>{}); });
         __builtin_amdgcn_sched_barrier(0);
-        wait_lgkm_tied<NFT>(fn);
+        wait_lgkm_tied<NF>(fn);
     };
     const long long t_loop = g.dbg_clock ? (long long)__builtin_readcyclecounter() : 0;
-    const int ntrip = nslab / STEPS;                     // launch_gemm only sends K % 64 == 0 here
+    const int ntrip = nslab;                             // one slab per trip
     int tt = 0;
     for (; tt + 1 < ntrip; tt += 2) {
         trip(f0, f1, tt);
@@ -1126,39 +892,34 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kpipe_kernel(GemmArgs g) {
 // trip / barrier (ring of 6) and DMA issued by four dedicated LOADER waves instead of the compute waves.  Neither moves
 // the 96 x 32 loop off 944 cycles per slab (768 of MFMA): that tile needs 32 KB per slab per CU = 8.8 TB/s chip-wide out
 // of L2 at the rate it runs, i.e. the thin tile sits on the L2 -> LDS bandwidth, not on issue slots or barriers.)
-template <int TM, int TN, int NB, int STEPS>
+template <int TM, int TN>
 static void launch_kpipe(const LaunchCtx& ctx, const GemmArgs& g) {
-    using Cfg = KPipeCfg<TM, TN, NB, STEPS>;
+    using Cfg = KPipeCfg<TM, TN>;
     static_assert(Cfg::LDS_BYTES <= 160 * 1024, "ring does not fit the 160 KiB LDS");
     static std::atomic<uint64_t> configured{0};
     int dev = 0;
     WLK_HIP(hipGetDevice(&dev));
     if (!(configured.load(std::memory_order_acquire) >> (dev & 63) & 1)) {
-        WLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_f32_kpipe_kernel<TM, TN, NB, STEPS>),
+        WLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_f32_kpipe_kernel<TM, TN>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES));
         configured.fetch_or(1ull << (dev & 63), std::memory_order_release);
     }
     const int tiles_m = (g.M + Cfg::BM - 1) / Cfg::BM, tiles_n = (g.N + Cfg::BN - 1) / Cfg::BN;
     const int blocks = tiles_m >= 8 ? 8 * ((tiles_m + 3) / 4) * ((tiles_n + 1) / 2) : tiles_m * tiles_n;
-    hipLaunchKernelGGL((gemm_nt_f32_kpipe_kernel<TM, TN, NB, STEPS>), dim3(blocks, std::max(g.batch, 1)), dim3(256), Cfg::LDS_BYTES,
+    hipLaunchKernelGGL((gemm_nt_f32_kpipe_kernel<TM, TN>), dim3(blocks, std::max(g.batch, 1)), dim3(256), Cfg::LDS_BYTES,
                        ctx.stream, g);
 }
 
-// ks code of a k-pipe configuration: 100 + ring slots (103 / 104: a ring of 3 / 4 slabs, one slab per trip)
-static bool dispatch_kpipe(const LaunchCtx& ctx, const GemmArgs& g, int tm, int tn, int ks) {
-#define WLK_KP(a, b, nb, st) if (tm == a && tn == b) { launch_kpipe<a, b, nb, st>(ctx, g); return true; }
-    if (ks == 104) {
-        WLK_KP(3, 4, 4, 1) WLK_KP(3, 3, 4, 1) WLK_KP(3, 2, 4, 1) WLK_KP(3, 1, 4, 1) WLK_KP(2, 4, 4, 1) WLK_KP(2, 2, 4, 1) WLK_KP(2, 1, 4, 1) WLK_KP(4, 2, 4, 1)
-    } else if (ks == 103) {
-        WLK_KP(3, 4, 3, 1) WLK_KP(3, 3, 3, 1) WLK_KP(3, 2, 3, 1) WLK_KP(3, 1, 3, 1) WLK_KP(2, 4, 3, 1) WLK_KP(2, 2, 3, 1) WLK_KP(2, 1, 3, 1) WLK_KP(4, 2, 3, 1)
-    }
+static bool dispatch_kpipe(const LaunchCtx& ctx, const GemmArgs& g, int tm, int tn) {
+#define WLK_KP(a, b) if (tm == a && tn == b) { launch_kpipe<a, b>(ctx, g); return true; }
+    WLK_KP(3, 4) WLK_KP(3, 3) WLK_KP(3, 2) WLK_KP(3, 1) WLK_KP(2, 4) WLK_KP(2, 2) WLK_KP(2, 1) WLK_KP(4, 2)
 #undef WLK_KP
     return false;
 }
 
-// Tile of the k-split kernel for an (M, N, K) problem, or {0, 0} when it does not apply: the shape that needs the fewest
+// Tile of the k-pipe kernel for an (M, N, K) problem, or {0, 0} when it does not apply: the shape that needs the fewest
 // rounds of 256 workgroups x tile area (ties: the larger tile).  Depends on the problem only, never on the batch.
-struct KSplitTile { int tm, tn, ks; };
+struct KSplitTile { int tm, tn; };
 // Which problems take the one-tile-per-CU kernels, and with which tile.  Measured on MI355X (scripts/gemm_time_probe.py,
 // profiles/r03_gemm_probe_*.txt), M = 1500: they win where the output is narrow - N = 512: 12.3 / 34.6 / 28.0 us (out
 // projection, fc2, conv2) against 14.8 / 45.3 / 36.5 for the 64x64 kernel; N = 768 (small): 27 / 86 / 68 against
@@ -1169,16 +930,12 @@ struct KSplitTile { int tm, tn, ks; };
 // (M, N, K) only - never on the batch - so a session stacked with others keeps its solo arithmetic.
 // `forced` (diagnostics, force_kernel 4): any applicable problem, so that every tile instantiation stays tested.
 static KSplitTile ksplit_tile(int M, int N, int K, bool forced = false) {
-    static const int mode = [] {
-        const char* e = getenv("WLK_GEMM");
-        return e && e[0] == 'c' ? 0 : 1;      // WLK_GEMM=classic: the 64x64 kernel everywhere (A/B switch)
-    }();
-    if (K % 64 != 0 || K < 256 || M < 512) return {0, 0, 0};
+    if (K % 64 != 0 || K < 256 || M < 512) return {0, 0};
     // K >= 512: with fewer than 16 slabs the fixed cost of a launch dominates either kernel, and the one measured case
     // (large-v3 conv1, K = 384, M = 3000) favours the 64x64 kernel (36 vs 44 us)
-    if (!forced && (!mode || N > 1536 || K < 512)) return {0, 0, 0};
-    static const KSplitTile cand[] = {{3, 4, 104}, {3, 3, 104}, {3, 2, 104}, {3, 1, 104}, {2, 4, 104}, {2, 2, 104}, {2, 1, 104}, {4, 2, 104}};
-    KSplitTile best{0, 0, 0};
+    if (!forced && (N > 1536 || K < 512)) return {0, 0};
+    static const KSplitTile cand[] = {{3, 4}, {3, 3}, {3, 2}, {3, 1}, {2, 4}, {2, 2}, {2, 1}, {4, 2}};
+    KSplitTile best{0, 0};
     double best_cost = 0.0;
     for (const KSplitTile& c : cand) {
         const long tiles = (long)((M + 32 * c.tm - 1) / (32 * c.tm)) * ((N + 32 * c.tn - 1) / (32 * c.tn));
@@ -1187,32 +944,6 @@ static KSplitTile ksplit_tile(int M, int N, int K, bool forced = false) {
         if (best.tm == 0 || cost < best_cost) { best = c; best_cost = cost; }
     }
     return best;
-}
-
-template <int TM, int TN, int KS, int ABL = 0>
-static void launch_ksplit(const LaunchCtx& ctx, const GemmArgs& g) {
-    using Cfg = KSplitCfg<TM, TN, KS>;
-    static_assert(Cfg::LDS_BYTES <= 160 * 1024, "tile does not fit the 160 KiB LDS");
-    static std::atomic<uint64_t> configured{0};     // per device: more than 64 KiB of dynamic LDS has to be asked for
-    int dev = 0;
-    WLK_HIP(hipGetDevice(&dev));
-    if (!(configured.load(std::memory_order_acquire) >> (dev & 63) & 1)) {
-        WLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_f32_ksplit_kernel<TM, TN, KS, ABL>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES));
-        configured.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
-    const int tiles_m = (g.M + Cfg::BM - 1) / Cfg::BM, tiles_n = (g.N + Cfg::BN - 1) / Cfg::BN;
-    const int blocks = tiles_m >= 8 ? 8 * ((tiles_m + 3) / 4) * ((tiles_n + 1) / 2) : tiles_m * tiles_n;
-    hipLaunchKernelGGL((gemm_nt_f32_ksplit_kernel<TM, TN, KS, ABL>), dim3(blocks, std::max(g.batch, 1)), dim3(256), Cfg::LDS_BYTES,
-                       ctx.stream, g);
-}
-
-template <int KS, int ABL>
-static bool dispatch_ksplit(const LaunchCtx& ctx, const GemmArgs& g, int tm, int tn) {
-#define WLK_KS(a, b) if (tm == a && tn == b) { launch_ksplit<a, b, KS, ABL>(ctx, g); return true; }
-    WLK_KS(3, 4) WLK_KS(3, 3) WLK_KS(3, 2) WLK_KS(3, 1) WLK_KS(2, 4) WLK_KS(2, 2) WLK_KS(2, 1) WLK_KS(4, 2)
-#undef WLK_KS
-    return false;
 }
 
 // 32x32 output tiles at or below which the k-wave kernel is used (WLK_KWAVE_MAX_TILES overrides; 0 disables)
@@ -1231,68 +962,25 @@ bool gemm_takes_kwave(int M, int N, int K) {
 
 bool gemm_takes_ksplit(int M, int N, int K) { return ksplit_tile(M, N, K).tm != 0; }
 
-// prompt-sized row counts (decoder prefill): 16 x 16 tiles - four times the workgroups, a quarter of the chain each
-static bool kwave16_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("WLK_KWAVE16");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// Can launch_gemm take the LayerNorm in front of this projection (GemmArgs::ln_gamma / ln_beta, A = the un-normalised rows)?
-// Only the 16 x 16 prefill kernel does, for K = a Whisper width.
-static bool gemm_can_fuse_layernorm(int M, int N, int K) {
-    return kwave16_enabled() && M > 8 && M <= 128 && gemm_takes_kwave(M, N, K) && ksplit_tile(M, N, K).tm == 0 &&
-           (K == 384 || K == 512 || K == 768 || K == 1024 || K == 1280);
-}
-// ... and do the decoder's prefill chains ask for it?  Measured neutral (profiles/r04p_ab_prefill_ln_fuse.txt: 18 launches
-// less per prefill, but 128-512 workgroups each re-derive the statistics of their sixteen rows - 200.7-201.7 fused against
-// 200.5-203.5 audio-s/s, 8 streams 358-363 either way), so the separate launch stays the default; WLK_PREFILL_LN_FUSE=1
-// turns the fused form on (bit-identical: tests/test_gpu_parity.py::test_prefill_gemm_fuses_the_layernorm).
-static std::atomic<int> g_prefill_ln_fuse{-1};          // -1: not read yet; the switch is read ONCE (this sits on the decode path)
 void x3_refresh_env_switches();                          // gemm_x3.hip: WLK_X3_PERSIST
-void refresh_env_switches() {
-    g_prefill_ln_fuse.store(-1, std::memory_order_relaxed);
-    x3_refresh_env_switches();
-}   // wlk_diag_env_refresh: the parity test flips the switch inside one process
-bool gemm_fuses_layernorm(int M, int N, int K) {
-    int on = g_prefill_ln_fuse.load(std::memory_order_relaxed);
-    if (on < 0) {
-        const char* e = getenv("WLK_PREFILL_LN_FUSE");
-        on = e && e[0] == '1';
-        g_prefill_ln_fuse.store(on, std::memory_order_relaxed);
-    }
-    return on && gemm_can_fuse_layernorm(M, N, K);
-}
+void refresh_env_switches() { x3_refresh_env_switches(); }   // wlk_diag_env_refresh: a test flips a switch inside one process
 
 void launch_gemm(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
     if (g.M <= 0 || g.N <= 0) return;
     if (g.K % 4 != 0 || g.lda % 4 != 0) throw std::invalid_argument("gemm: K and lda must be multiples of 4");
     if ((((long)g.M - 1) * g.lda + g.K) * 4 >= (1L << 31) || (long)g.N * g.K * 4 >= (1L << 31))
         throw std::invalid_argument("gemm: operand larger than 2 GiB");
+    if (g.ln_gamma) throw std::invalid_argument("gemm: only the GEMV kernels (rows <= 8) take the LayerNorm; launch it separately");
     const double nb = std::max(g.batch, 1);
     KernelScope ks(ctx, tag, nb * 2.0 * g.M * g.N * g.K,
                    4.0 * (nb * (double)g.M * g.K + (double)g.N * g.K + nb * (double)g.M * g.N));
     if (g.batch > kMaxBatch) throw std::invalid_argument("gemm: batch too large");
     const bool want_kwave = g.force_kwave || g.force_kernel == 2;
     // encoder-sized problems: one tile per compute unit, K split over the waves (force_kernel 3 = the 64x64 kernel)
-    const KSplitTile kt = (want_kwave || g.kcache || g.force_kernel == 3) ? KSplitTile{0, 0, 0} : ksplit_tile(g.M, g.N, g.K, g.force_kernel == 4);
-    if (g.force_kernel == 4 && !kt.tm) throw std::invalid_argument("gemm: the k-split kernel does not take this shape");
-    if (g.ln_gamma && !(gemm_can_fuse_layernorm(g.M, g.N, g.K) && !kt.tm && g.force_kernel == 0 && g.batch == 0))
-        throw std::invalid_argument("gemm: only the 16 x 16 prefill kernel takes the LayerNorm (gemm_fuses_layernorm)");
+    const KSplitTile kt = (want_kwave || g.kcache || g.force_kernel == 3) ? KSplitTile{0, 0} : ksplit_tile(g.M, g.N, g.K, g.force_kernel == 4);
+    if (g.force_kernel == 4 && !kt.tm) throw std::invalid_argument("gemm: the k-pipe kernel does not take this shape");
     if (kt.tm) {
-        // probe override (scripts/gemm_tile_probe.py): WLK_KSPLIT_FORCE="tm,tn,ks" (ks 64: compiler-scheduled k-split; 103 / 104: k-pipe)
-        static const KSplitTile forced = [] {
-            KSplitTile f{0, 0, 0};
-            if (const char* e = getenv("WLK_KSPLIT_FORCE")) sscanf(e, "%d,%d,%d", &f.tm, &f.tn, &f.ks);
-            return f;
-        }();
-        const KSplitTile use = forced.tm ? forced : kt;
-        bool ok;
-        if (use.ks >= 100) ok = dispatch_kpipe(ctx, g, use.tm, use.tn, use.ks);
-        else ok = dispatch_ksplit<64, 0>(ctx, g, use.tm, use.tn);
-        if (!ok) throw std::logic_error("gemm: k-split tile without an instantiation");
+        if (!dispatch_kpipe(ctx, g, kt.tm, kt.tn)) throw std::logic_error("gemm: k-pipe tile without an instantiation");
         WLK_HIP(hipGetLastError());
         return;
     }
@@ -1304,18 +992,9 @@ void launch_gemm(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
     if (g.kcache && !(gemm_takes_kwave(g.M, g.N, g.K) || want_kwave))
         throw std::invalid_argument("gemm: fused KV-cache append is only available on the k-wave path");
     if ((gemm_takes_kwave(g.M, g.N, g.K) && g.force_kernel != 3) || (want_kwave && g.K >= 256)) {
-        if (kwave16_enabled() && g.M <= 128 && g.force_kernel != 2) {
+        if (g.M <= 128 && g.force_kernel != 2) {   // prompt-sized row counts (decoder prefill): 16 x 16 tiles
             const long tiles16 = (long)((g.N + 15) / 16) * ((g.M + 15) / 16);
-            const dim3 grid((unsigned)tiles16);
-            switch (g.ln_gamma ? g.K / 64 : 0) {
-                case 0: hipLaunchKernelGGL(gemm_nt_f32_kwave16_kernel<0>, grid, dim3(256), 0, ctx.stream, g); break;
-                case 6: hipLaunchKernelGGL(gemm_nt_f32_kwave16_kernel<6>, grid, dim3(256), 0, ctx.stream, g); break;
-                case 8: hipLaunchKernelGGL(gemm_nt_f32_kwave16_kernel<8>, grid, dim3(256), 0, ctx.stream, g); break;
-                case 12: hipLaunchKernelGGL(gemm_nt_f32_kwave16_kernel<12>, grid, dim3(256), 0, ctx.stream, g); break;
-                case 16: hipLaunchKernelGGL(gemm_nt_f32_kwave16_kernel<16>, grid, dim3(256), 0, ctx.stream, g); break;
-                case 20: hipLaunchKernelGGL(gemm_nt_f32_kwave16_kernel<20>, grid, dim3(256), 0, ctx.stream, g); break;
-                default: throw std::invalid_argument("gemm: fused LayerNorm needs K = 384 / 512 / 768 / 1024 / 1280");
-            }
+            hipLaunchKernelGGL(gemm_nt_f32_kwave16_kernel<>, dim3((unsigned)tiles16), dim3(256), 0, ctx.stream, g);
         } else {
             hipLaunchKernelGGL(gemm_nt_f32_kwave_kernel<false>, dim3((unsigned)tiles32), dim3(256), 0, ctx.stream, g);
         }
@@ -1370,62 +1049,28 @@ static KSplitTile kp_tile(int M, int N, int K) {
         {192, 512, {{2, 1}, {2, 1}, {2, 1}, {3, 1}}},     // encoder projection
     };
     for (const Row& r : rows)
-        if (r.n == N && r.k == K) return KSplitTile{r.t[band][0], r.t[band][1], 104};
-    if (N == 256 && K == 256) return M < 4000 ? KSplitTile{2, 1, 104} : M < 9000 ? KSplitTile{2, 2, 104} : KSplitTile{2, 1, 104};   // stem pointwise
+        if (r.n == N && r.k == K) return KSplitTile{r.t[band][0], r.t[band][1]};
+    if (N == 256 && K == 256) return M < 4000 ? KSplitTile{2, 1} : M < 9000 ? KSplitTile{2, 2} : KSplitTile{2, 1};   // stem pointwise
     return ksplit_tile(M, N, K, true);
 }
 // below 512 rows: 16 x 16 tiles (four times the workgroups, a quarter of the dependent MFMA chain per wave) or 32 x 32 tiles?
-// force_kernel 6 / 7 (diagnostics): 16 x 16 / 32 x 32 whatever the shape.  WLK_KP16=0 / 1 overrides the rule.
+// force_kernel 6 / 7 (diagnostics): 16 x 16 / 32 x 32 whatever the shape.
 static bool kp_takes_16(int M, int N, int K, int force) {
     if (force == 6) return true;
     if (force == 7 || force == 8) return false;
-    static const int env = [] { const char* e = getenv("WLK_KP16"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-    if (env >= 0) return env == 1;
     const long tiles16 = (long)((N + 15) / 16) * ((M + 15) / 16);
     return kp16_rule(M, N, K, tiles16);
-}
-// Can launch_gemm_kp take the LayerNorm in front (GemmArgs::ln_gamma / ln_beta, A = the un-normalised rows)?  Opt-in
-// (WLK_SF_LN_FUSE=1): measured a LOSS on the single-session Sortformer step (68 launches less per chunk, bit-identical, but 4.13 ms
-// per chunk against 3.89: hundreds of workgroups re-deriving the statistics of their rows cost more than the 4.5 us launches they
-// replace - the third time this trade was measured, after the encoder's large tiles in round 1 and the prefill in round 4).
-bool gemm_kp_fuses_layernorm(int M, int N, int K) {
-    static const bool on = [] { const char* e = getenv("WLK_SF_LN_FUSE"); return e && e[0] == '1'; }();
-    // K = 192 (the Transformer half, round 6; opt-in WLK_SF_TF_LN_FUSE=1): sixteen rows of 192 are only 12 KB per workgroup and the
-    // column-tile-0 workgroups keep the normalised rows for the block's residual (GemmArgs::ln_out) - 35 launches less per chunk,
-    // bit-identical, and STILL a loss: 3.61 against 3.57 ms per chunk (profiles/r06t_tf_ln_fuse.txt).  A LayerNorm launch's 4.4 us
-    // are its own chain (row load -> two dependent reductions -> store), which moves into every consumer workgroup's critical
-    // path when folded; the kernel boundary it saves is the smaller part.  Needs the k-wave tiles for K = 192 (WLK_KP_SHORT_K).
-    static const bool on192 = [] {
-        const char* e = getenv("WLK_SF_TF_LN_FUSE");
-        const char* k = getenv("WLK_KP_SHORT_K");
-        return e && e[0] == '1' && !(k && k[0] == '0');
-    }();
-    (void)N;
-    return M > 0 && M < 512 && ((on && K == 512) || (on192 && K == 192));
 }
 bool gemm_kp_takes_kpipe(int M, int N, int K) { return K % 128 == 0 && K >= 256 && M >= 512 && ksplit_tile(M, N, K, true).tm != 0; }
 void launch_gemm_kp(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
     if (g.M <= 0 || g.N <= 0) return;
     if (g.K % 4 != 0 || g.lda % 4 != 0) throw std::invalid_argument("gemm: K and lda must be multiples of 4");
     if (g.batch > 0 || g.kcache) throw std::invalid_argument("gemm (kp family): plain projections only");
-    if (g.ln_gamma) {
-        // the LayerNorm in front of the projection inside the 16 x 16 kernel (gemm_nt_f32_kwave16_kernel<NPL, true>: every workgroup
-        // derives layernorm_kernel's statistics of its sixteen rows while the first slabs are in flight) - bit for bit the separate
-        // launch, one kernel boundary less.  Rows < 512, K = 512 only (gemm_kp_fuses_layernorm); the stacked steps keep the launch.
-        if (!gemm_kp_fuses_layernorm(g.M, g.N, g.K)) throw std::invalid_argument("gemm (kp family): this shape does not take the LayerNorm");
-        KernelScope ks(ctx, tag, 2.0 * g.M * g.N * g.K, 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));
-        const long tiles16 = (long)((g.N + 15) / 16) * ((g.M + 15) / 16);
-        if (g.K == 192) hipLaunchKernelGGL((gemm_nt_f32_kwave16_kernel<3, true>), dim3((unsigned)tiles16), dim3(256), 0, ctx.stream, g);
-        else hipLaunchKernelGGL((gemm_nt_f32_kwave16_kernel<8, true>), dim3((unsigned)tiles16), dim3(256), 0, ctx.stream, g);
-        WLK_HIP(hipGetLastError());
-        return;
-    }
+    if (g.ln_gamma) throw std::invalid_argument("gemm (kp family): the LayerNorm is a launch of its own");
     // K = 192 (the Sortformer's Transformer width; any multiple of 32 from 128 to 255): the k-wave tiles too, at EVERY row count -
     // the last 128-deep slab is half zeros, a row's arithmetic (wave w: k = 32 t + 8 w .. + 7, partials folded in wave order) does
-    // not depend on M.  Until round 6 these shapes took the 64 x 64 family, where ONE wave walks K (7.9 us per launch for 64 MFLOP);
-    // WLK_KP_SHORT_K=0 keeps that.
-    static const bool short_k = [] { const char* e = getenv("WLK_KP_SHORT_K"); return !(e && e[0] == '0'); }();
-    const bool short_k_kwave = short_k && g.K % 32 == 0 && g.K >= 128 && g.K < 256;
+    // not depend on M.  Until round 6 these shapes took the 64 x 64 family, where ONE wave walks K (7.9 us per launch for 64 MFLOP).
+    const bool short_k_kwave = g.K % 32 == 0 && g.K >= 128 && g.K < 256;
     if (!short_k_kwave && (g.K % 128 != 0 || g.K < 256)) {
         GemmArgs p = g;
         p.force_kernel = 3;
@@ -1437,11 +1082,11 @@ void launch_gemm_kp(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
     KernelScope ks(ctx, tag, 2.0 * g.M * g.N * g.K, 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));
     if (!short_k_kwave && gemm_kp_takes_kpipe(g.M, g.N, g.K)) {
         KSplitTile kt = kp_tile(g.M, g.N, g.K);
-        if (g.force_kernel >= 500) kt = KSplitTile{(g.force_kernel - 500) / 10, (g.force_kernel - 500) % 10, 104};   // tile probe
-        if (!dispatch_kpipe(ctx, g, kt.tm, kt.tn, kt.ks)) throw std::logic_error("gemm: k-pipe tile without an instantiation");
+        if (g.force_kernel >= 500) kt = KSplitTile{(g.force_kernel - 500) / 10, (g.force_kernel - 500) % 10};   // tile probe
+        if (!dispatch_kpipe(ctx, g, kt.tm, kt.tn)) throw std::logic_error("gemm: k-pipe tile without an instantiation");
     } else if ((!short_k_kwave || g.M < 512) && kp_takes_16(g.M, g.N, g.K, g.force_kernel)) {
         const long tiles16 = (long)((g.N + 15) / 16) * ((g.M + 15) / 16);
-        hipLaunchKernelGGL((gemm_nt_f32_kwave16_kernel<0, true>), dim3((unsigned)tiles16), dim3(256), 0, ctx.stream, g);
+        hipLaunchKernelGGL((gemm_nt_f32_kwave16_kernel<true>), dim3((unsigned)tiles16), dim3(256), 0, ctx.stream, g);
     } else {
         const long tiles32 = (long)((g.N + 31) / 32) * ((g.M + 31) / 32);
         // more than two tiles per compute unit: the one-buffer form (36.9 KB of LDS, three to four workgroups per CU) keeps them all

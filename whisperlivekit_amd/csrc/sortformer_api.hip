@@ -307,20 +307,11 @@ static void sf_linear(const LaunchCtx& c, const float* A, long lda, const float*
     launch_gemm_kp(c, g, tag);
 }
 
-// LayerNorm + projection: ONE launch while the rows are few (a single session's step: the 16 x 16 kernel normalises its A rows
-// itself, bit for bit layernorm_kernel's values), LayerNorm launch + projection from 512 rows on (stacked steps: the k-pipe tiles
-// take their operands by LDS-DMA and cannot normalise them on the way).  Same results either way.
+// LayerNorm launch + projection (folding the LayerNorm into the projection kernel was measured slower: DESIGN.md)
 static void sf_ln_linear(const LaunchCtx& c, const float* x, const float* lnw, const float* lnb, float* xn, const float* W,
                          const float* b, float* C, long ldc, int M, int N, int K, int flags, const char* tag) {
-    if (gemm_kp_fuses_layernorm(M, N, K)) {
-        GemmArgs g;
-        g.A = x; g.lda = K; g.W = W; g.bias = b; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.flags = flags;
-        g.ln_gamma = lnw; g.ln_beta = lnb;
-        launch_gemm_kp(c, g, tag);
-    } else {
-        launch_layernorm(c, x, K, lnw, lnb, xn, K, M, K, "sf_ln");
-        sf_linear(c, xn, K, W, b, C, ldc, M, N, K, flags, nullptr, 0, tag);
-    }
+    launch_layernorm(c, x, K, lnw, lnb, xn, K, M, K, "sf_ln");
+    sf_linear(c, xn, K, W, b, C, ldc, M, N, K, flags, nullptr, 0, tag);
 }
 
 static void sf_set_segments(SfAttnArgs& a, const SfSegments& rows) {
@@ -365,22 +356,11 @@ static void sf_network(wlk_sortformer* m, wlk_sortformer::Lane* w_, const Launch
     const int dt = D.tf_d_model, dht = dt / D.tf_heads, inner = D.tf_inner;
     sf_linear(c, w_->x, d, m->P("proj.w"), m->P("proj.b"), w_->tx, dt, T, dt, d, 0, nullptr, 0, "sf_proj");
     const float qk_scale = 1.0f / sqrtf(sqrtf((float)dht));
-    // Round 6, opt-in (WLK_SF_TF_LN_FUSE=1, gemm_kp_fuses_layernorm): a single session's step folds the two LayerNorms of a
-    // (post-LN) Transformer block into the projection that reads them, whose column-tile-0 workgroups keep the normalised rows
-    // for the block's residual (GemmArgs::ln_out).  Bit for bit the LayerNorm launch + projection, 35 launches less per chunk -
-    // and measured 1 % slower, so the default stays LayerNorm launch + projection.
+    // the (post-LN) Transformer block's LayerNorm, kept in xn for the block's residual, + the projection that reads it
     auto tf_ln_linear = [&](const float* y, const float* lnw, const float* lnb, float* xn, const float* W, const float* b, float* C,
                             int N, int flags, const char* tag, float scale, int scale_cols) {
-        if (gemm_kp_fuses_layernorm(T, N, dt)) {
-            GemmArgs g;
-            g.A = y; g.lda = dt; g.W = W; g.bias = b; g.C = C; g.ldc = N; g.M = T; g.N = N; g.K = dt; g.flags = flags;
-            g.scale = scale; g.scale_cols = scale_cols;
-            g.ln_gamma = lnw; g.ln_beta = lnb; g.ln_out = xn; g.ld_ln_out = dt;
-            launch_gemm_kp(c, g, tag);
-        } else {
-            launch_layernorm(c, y, dt, lnw, lnb, xn, dt, T, dt, "sf_ln");
-            sf_linear(c, xn, dt, W, b, C, N, T, N, dt, flags, nullptr, 0, tag, scale, scale_cols);
-        }
+        launch_layernorm(c, y, dt, lnw, lnb, xn, dt, T, dt, "sf_ln");
+        sf_linear(c, xn, dt, W, b, C, N, T, N, dt, flags, nullptr, 0, tag, scale, scale_cols);
     };
     for (int l = 0; l < D.tf_layers; ++l) {
         const SfTfLayer& w = m->tf[l];
