@@ -121,6 +121,14 @@ typedef struct wlk_pick_params {
 } wlk_pick_params;
 int wlk_rules_set(wlk_session* s, const int32_t* suppressed, int n_suppressed, const int32_t* blank, int n_blank);
 int wlk_pick_greedy(wlk_session* s, const wlk_pick_params* p, int32_t* token_host, float* logprob_host);
+/* The same rules for every row of a session with beam == n_rows (1..8), each row with its own parameter block - first_step,
+ * without_timestamps and max_initial are the same in all; ts_mode and ts_bound follow each row's sampled tokens - and the
+ * k (1..8) best log-probabilities of each row - what BeamSearchDecoder.update (whisper/decoding.py:332-338) reads, in one
+ * read-back.  Applied to the logits of the last wlk_decode / wlk_decode_ancestry.  Entries are ordered by (log-probability
+ * descending, id ascending); a row that allows fewer than k tokens fills up with (-inf, -1).  WLK_ERR_STATE before a decode
+ * or before wlk_rules_set, WLK_ERR_ARG on a bad shape. */
+int wlk_pick_topk(wlk_session* s, const wlk_pick_params* p /* [n_rows] */, int n_rows, int k,
+                  float* logprobs_host /* [n_rows, k] */, int32_t* ids_host /* [n_rows, k] */);
 
 /* a6+a7+a8 in one launch group and ONE readback:
  *  - logits[row, ids[i]] += deltas[i] (-inf suppresses: SuppressTokens.apply whisper/decoding.py:427-432,
@@ -242,7 +250,13 @@ int wlk_decode_beam_until_stop(wlk_session* s, const int64_t* tokens, int n_tok,
                                const int32_t* suppress_ids, int n_suppress, const int32_t* blank_ids, int n_blank,
                                wlk_loop_result* result, int64_t* new_tokens, int32_t* step_tokens, int32_t* step_frames,
                                float* step_sum_logprobs, int cap);
-/* single-token steps of this session that ran over the ancestry table so far */
+/* One single-token step of a beam session whose row b continues hypothesis source_rows[b] of the previous step: what
+ * wlk_kv_reorder(source_rows) followed by wlk_decode(first = 0) computes.  Sessions that qualify (see above) take the step
+ * over the ancestry table, nothing moves in the cache, and the rule above holds: wlk_decode(first = 0) and wlk_kv_reorder
+ * are refused until the next wlk_decode(first = 1).  Every other session makes those two calls inside this one.  Which of
+ * the two a session takes does not change during an infer. */
+int wlk_decode_ancestry(wlk_session* s, const int64_t* tokens /* [n_rows] */, const int32_t* source_rows, int n_rows);
+/* single-token steps of this session that ran over the ancestry table so far (either entry point) */
 int wlk_session_beam_stats(wlk_session* s, uint64_t* ancestry_steps);
 /* Diagnostic (tests): one single-token decoder forward over the ancestry table - what wlk_decode(first = 0) computes
  * after wlk_kv_reorder(source_rows), without moving the cache.  WLK_ERR_STATE when the session does not qualify. */

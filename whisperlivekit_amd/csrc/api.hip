@@ -1463,7 +1463,7 @@ int wlk_rules_set(wlk_session* s, const int32_t* suppressed, int n_suppressed, c
         for (int i = 0; i < n_blank; ++i) host[(size_t)blank[i]] |= 2;
         if (!s->rules_mask) {
             s->rules_mask = dev_alloc<unsigned char>((size_t)V);
-            s->pick_out = dev_alloc<int>(2);
+            s->pick_out = dev_alloc<int>(2 + 2 * kMaxPickRows * 8);   // [token | log-probability] of wlk_pick_greedy, [log-probs | ids] of wlk_pick_topk
         }
         WLK_HIP(hipStreamSynchronize(s->stream));           // a pick of the previous rule set may still be reading the mask
         copy_sync(s->rules_mask, host.data(), host.size(), hipMemcpyHostToDevice);
@@ -1489,6 +1489,38 @@ int wlk_pick_greedy(wlk_session* s, const wlk_pick_params* p, int32_t* token_hos
         WLK_HIP(hipStreamSynchronize(s->stream));
         std::memcpy(token_host, s->pinned, 4);
         std::memcpy(logprob_host, static_cast<char*>(s->pinned) + 4, 4);
+        return WLK_OK;
+    });
+}
+
+// The rules for every row of a beam session and the k best log-probabilities of each (select.hip: rules_topk_kernel): one
+// launch, one read-back of n_rows * k pairs.
+int wlk_pick_topk(wlk_session* s, const wlk_pick_params* p, int n_rows, int k, float* logprobs_host, int32_t* ids_host) {
+    if (!s || !p || !logprobs_host || !ids_host) return fail(WLK_ERR_ARG, "NULL argument");
+    if (n_rows < 1 || n_rows > kMaxPickRows || n_rows != s->beam) return fail(WLK_ERR_ARG, "wlk_pick_topk: n_rows must be the session's beam, 1..8");
+    if (k < 1 || k > 8) return fail(WLK_ERR_ARG, "k must be in [1, 8]");
+    if (s->n_steps == 0) return fail(WLK_ERR_STATE, "wlk_pick_topk before wlk_decode");
+    if (!s->rules_mask) return fail(WLK_ERR_STATE, "wlk_pick_topk before wlk_rules_set");
+    const int V = s->m->D.n_vocab;
+    PickRulesRows rules{};
+    for (int b = 0; b < n_rows; ++b) {
+        const wlk_pick_params& q = p[b];
+        if (q.timestamp_begin < 0 || q.timestamp_begin > V || q.eot < 0 || q.eot >= V || q.ts_mode < 0 || q.ts_mode > 2)
+            return fail(WLK_ERR_ARG, "rule parameters out of range");
+        rules.r[b] = PickRules{q.first_step, q.without_timestamps, q.timestamp_begin, q.eot, q.no_timestamps, q.ts_mode, q.ts_bound,
+                               q.max_initial};
+    }
+    return guarded([&]() {
+        WLK_HIP(hipSetDevice(s->m->device));
+        const LaunchCtx c = s->ctx();
+        const size_t n = (size_t)n_rows * k;
+        float* lp_dev = reinterpret_cast<float*>(s->pick_out + 2);
+        int* ids_dev = s->pick_out + 2 + n;
+        launch_rules_topk(c, s->logits_last, V, n_rows, s->rules_mask, rules, k, lp_dev, ids_dev);
+        WLK_HIP(hipMemcpyAsync(s->pinned, lp_dev, 2 * n * 4, hipMemcpyDeviceToHost, s->stream));
+        WLK_HIP(hipStreamSynchronize(s->stream));
+        std::memcpy(logprobs_host, s->pinned, n * 4);
+        std::memcpy(ids_host, static_cast<char*>(s->pinned) + n * 4, n * 4);
         return WLK_OK;
     });
 }
@@ -1762,6 +1794,20 @@ int wlk_diag_beam_step(wlk_session* s, const int64_t* tokens, const int32_t* sou
     if (!s || n_rows != s->beam) return fail(WLK_ERR_ARG, "n_rows must equal the session's beam size");
     const int rc = wlk_beam_step(s, tokens, source_rows);
     return rc == 1 ? fail(WLK_ERR_STATE, "the session does not qualify for the ancestry step") : rc;
+}
+
+// The public form of that step: over the ancestry table where the session qualifies, else as the two calls it stands for.
+// What decides (beam, shapes, debug / profiling, graphs) does not change during an infer, so an infer is one or the other.
+int wlk_decode_ancestry(wlk_session* s, const int64_t* tokens, const int32_t* source_rows, int n_rows) {
+    if (!s || !tokens || !source_rows) return fail(WLK_ERR_ARG, "NULL argument");
+    if (n_rows != s->beam) return fail(WLK_ERR_ARG, "n_rows must equal the session's beam size");
+    if (!s->encoded) return fail(WLK_ERR_STATE, "wlk_decode_ancestry before wlk_encode");
+    if (s->n_steps == 0) return fail(WLK_ERR_STATE, "wlk_decode_ancestry before the prefill (wlk_decode with first=1)");
+    const int rc = wlk_beam_step(s, tokens, source_rows);
+    if (rc != 1) return rc;
+    if (s->anc_live) return fail(WLK_ERR_STATE, "wlk_decode_ancestry: the session stopped qualifying for the ancestry step inside an infer");
+    if (int rc2 = wlk_kv_reorder(s, source_rows, n_rows)) return rc2;
+    return wlk_decode(s, tokens, n_rows, 1, 0, 0);
 }
 
 int wlk_session_beam_stats(wlk_session* s, uint64_t* ancestry_steps) {

@@ -582,6 +582,13 @@ struct PickRules {
 };
 void launch_rules_pick(const LaunchCtx& ctx, const float* logits, int n_vocab, const unsigned char* mask, const PickRules& p,
                        int* out_token, float* out_logprob);
+// the same rules for up to 8 rows with a history each, and the k <= 8 best log-probabilities / ids of every row ([n_rows][k])
+constexpr int kMaxPickRows = 8;
+struct PickRulesRows {
+    PickRules r[kMaxPickRows];
+};
+void launch_rules_topk(const LaunchCtx& ctx, const float* logits, int n_vocab, int n_rows, const unsigned char* mask,
+                       const PickRulesRows& rules, int k, float* out_lp, int* out_ids);
 struct AlignArgs {
     const float* ring;   // [n_align][n_beam][ring_rows][T]
     int n_align, n_beam, ring_rows, T;

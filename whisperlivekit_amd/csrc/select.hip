@@ -697,6 +697,19 @@ __device__ __forceinline__ PickBest pick_wave_best(PickBest x) {
     }
     return x;
 }
+// allowed(v) of the header comment: one statement of the rules for the one-row pick and the n-row top-k
+__device__ __forceinline__ bool rules_allowed(const unsigned char* __restrict__ mask, const PickRules& p, int v) {
+    const int tb = p.timestamp_begin;
+    const unsigned char m = mask[v];
+    if ((m & 1) || (p.first_step && (m & 2))) return false;
+    if (p.without_timestamps) return true;
+    if (v == p.no_timestamps) return false;
+    if (p.ts_mode == 1 && v >= tb) return false;
+    if (p.ts_mode == 2 && v < p.eot) return false;
+    if (v >= tb && v < p.ts_bound) return false;
+    if (p.first_step && (v < tb || (p.max_initial >= 0 && v >= tb + p.max_initial + 1))) return false;
+    return true;
+}
 }  // namespace
 
 __global__ __launch_bounds__(1024) void rules_pick_kernel(const float* __restrict__ logits, int n_vocab,
@@ -706,17 +719,7 @@ __global__ __launch_bounds__(1024) void rules_pick_kernel(const float* __restric
     __shared__ float s_text[16], s_sum_all[16], s_sum_ts[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tb = p.timestamp_begin;
-    auto allowed = [&](int v) -> bool {
-        const unsigned char m = mask[v];
-        if ((m & 1) || (p.first_step && (m & 2))) return false;
-        if (p.without_timestamps) return true;
-        if (v == p.no_timestamps) return false;
-        if (p.ts_mode == 1 && v >= tb) return false;
-        if (p.ts_mode == 2 && v < p.eot) return false;
-        if (v >= tb && v < p.ts_bound) return false;
-        if (p.first_step && (v < tb || (p.max_initial >= 0 && v >= tb + p.max_initial + 1))) return false;
-        return true;
-    };
+    auto allowed = [&](int v) -> bool { return rules_allowed(mask, p, v); };
     PickBest all{-INFINITY, 0x7fffffff}, ts{-INFINITY, 0x7fffffff};
     float text = -INFINITY;
     for (int v = tid; v < n_vocab; v += 1024) {
@@ -778,6 +781,147 @@ void launch_rules_pick(const LaunchCtx& ctx, const float* logits, int n_vocab, c
                        int* out_token, float* out_logprob) {
     KernelScope ks(ctx, "rules_pick", 0.0, 8.0 * n_vocab);
     hipLaunchKernelGGL(rules_pick_kernel, dim3(1), dim3(1024), 0, ctx.stream, logits, n_vocab, mask, p, out_token, out_logprob);
+    WLK_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same rules for the B rows of a beam session (batch `transcribe` with beam_size 2..7), each row with its own timestamp
+// history, and the k best log-probabilities of every row instead of the arg-max: what BeamSearchDecoder.update
+// (decoding.py:332-338) reads, k = beam + 1.  One 1024-thread workgroup per row.
+//   * The row is read ONCE: thread t keeps entries t, t + 1024, ... in registers (kRulesKeep = 52 of them: every Whisper
+//     vocabulary), an entry the rules forbid as -inf.  Longer rows (kRegs = false) re-read memory in every sweep instead.
+//   * max and sum exp(x - max) over the allowed set and over the allowed timestamps, the "timestamps outweigh text"
+//     decision in the host's form (logsumexp(logprobs[tb:]) > max(logprobs[:tb]), both under the same log_softmax); when the
+//     timestamps win the text entries drop out and the normaliser is the timestamps' sum.
+//   * the k best by (value descending, index ascending) in k rounds of exclusion: every thread holds the best entry it has
+//     left, a round is one wave_argmax butterfly + a 16-entry fold through LDS, and only the thread that owned the winner
+//     looks for its next entry ("after the winner" in that order - which also excludes everything it gave up before).
+//     Chosen over per-thread sorted lists + merge: a list of k per thread is k * 2 more registers and a runtime-indexed
+//     head, for rounds that here cost one 52-entry register scan in one thread.
+//   logprob = (x - max) - logf(sum); a row with fewer than k allowed (finite) entries fills up with (-inf, -1).
+// ---------------------------------------------------------------------------------------------
+constexpr int kRulesKeep = 52;
+namespace {
+// x comes strictly after w in the order (value descending, index ascending)
+__device__ __forceinline__ bool pick_after(float xv, int xi, PickBest w) { return xv < w.v || (xv == w.v && xi > w.i); }
+}  // namespace
+
+template <bool kRegs>
+__device__ __forceinline__ void rules_topk_body(const float* __restrict__ x, int n_vocab, const unsigned char* __restrict__ mask,
+                                                const PickRules& p, int k, float* __restrict__ out_lp,
+                                                int* __restrict__ out_ids) {
+    __shared__ PickBest s_best[16];
+    __shared__ float s_a[16], s_b[16], s_c[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tb = p.timestamp_begin;
+    float xv[kRegs ? kRulesKeep : 1];
+    if constexpr (kRegs) {
+#pragma unroll
+        for (int j = 0; j < kRulesKeep; ++j) {
+            const int v = tid + 1024 * j, vc = v < n_vocab ? v : 0;
+            const float raw = x[vc];
+            xv[j] = (v < n_vocab && rules_allowed(mask, p, vc)) ? raw : -INFINITY;
+        }
+    }
+    // f(index, value under the rules) over this thread's entries, ascending index
+    auto sweep = [&](auto&& f) {
+        if constexpr (kRegs) {
+#pragma unroll
+            for (int j = 0; j < kRulesKeep; ++j) f(tid + 1024 * j, xv[j]);
+        } else {
+            for (int v = tid; v < n_vocab; v += 1024) f(v, rules_allowed(mask, p, v) ? x[v] : -INFINITY);
+        }
+    };
+    float m_ts = -INFINITY, m_text = -INFINITY;
+    sweep([&](int v, float val) {
+        if (v >= tb) m_ts = fmaxf(m_ts, val);
+        else m_text = fmaxf(m_text, val);
+    });
+    m_ts = wave_max(m_ts);
+    m_text = wave_max(m_text);
+    if (lane == 0) {
+        s_a[wave] = m_ts;
+        s_b[wave] = m_text;
+    }
+    __syncthreads();
+    m_ts = s_a[0];
+    m_text = s_b[0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) {
+        m_ts = fmaxf(m_ts, s_a[w]);
+        m_text = fmaxf(m_text, s_b[w]);
+    }
+    const float m_all = fmaxf(m_ts, m_text);
+    float sum_all = 0.f, sum_ts = 0.f;
+    sweep([&](int v, float val) {
+        if (val > -INFINITY) {
+            sum_all += expf(val - m_all);
+            if (v >= tb) sum_ts += expf(val - m_ts);
+        }
+    });
+    sum_all = wave_sum(sum_all);
+    sum_ts = wave_sum(sum_ts);
+    __syncthreads();                       // the maxima have been read
+    if (lane == 0) {
+        s_a[wave] = sum_all;
+        s_c[wave] = sum_ts;
+    }
+    __syncthreads();
+    sum_all = 0.f;
+    sum_ts = 0.f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) {        // every thread folds the 16 partials in the same order
+        sum_all += s_a[w];
+        sum_ts += s_c[w];
+    }
+    const float lse_all = m_all + logf(sum_all);
+    const bool ts_wins = !p.without_timestamps && m_ts > -INFINITY && (m_ts + logf(sum_ts)) - lse_all > m_text - lse_all;
+    const float mx = ts_wins ? m_ts : m_all;
+    const float logsum = logf(ts_wins ? sum_ts : sum_all);
+    const int lo = ts_wins ? tb : 0;       // timestamps as a group outweigh every text token: the text entries drop out
+
+    auto best_after = [&](PickBest w) {
+        PickBest b{-INFINITY, 0x7fffffff};
+        sweep([&](int v, float val) {
+            if (v >= lo && val > -INFINITY && pick_after(val, v, w)) b = pick_better(b, PickBest{val, v});
+        });
+        return b;
+    };
+    PickBest mine = best_after(PickBest{INFINITY, -1});
+    for (int round = 0; round < k; ++round) {
+        PickBest w = mine;
+        wave_argmax(w.v, w.i);
+        __syncthreads();                   // the previous round's fold has been read
+        if (lane == 0) s_best[wave] = w;
+        __syncthreads();
+        w = s_best[0];
+#pragma unroll
+        for (int i = 1; i < 16; ++i) w = pick_better(w, s_best[i]);
+        const bool some = w.i != 0x7fffffff;
+        if (tid == 0) {
+            out_ids[round] = some ? w.i : -1;
+            out_lp[round] = some ? (w.v - mx) - logsum : -INFINITY;
+        }
+        if (some && mine.i == w.i) mine = best_after(w);
+    }
+}
+
+__global__ __launch_bounds__(1024) void rules_topk_kernel(const float* __restrict__ logits, int n_vocab,
+                                                          const unsigned char* __restrict__ mask, PickRulesRows rules, int k,
+                                                          float* __restrict__ out_lp, int* __restrict__ out_ids) {
+    const int row = blockIdx.x;
+    const PickRules p = rules.r[row];
+    const float* x = logits + (long)row * n_vocab;
+    if (n_vocab <= kRulesKeep * 1024) rules_topk_body<true>(x, n_vocab, mask, p, k, out_lp + row * k, out_ids + row * k);
+    else rules_topk_body<false>(x, n_vocab, mask, p, k, out_lp + row * k, out_ids + row * k);
+}
+
+void launch_rules_topk(const LaunchCtx& ctx, const float* logits, int n_vocab, int n_rows, const unsigned char* mask,
+                       const PickRulesRows& rules, int k, float* out_lp, int* out_ids) {
+    if (n_rows < 1 || n_rows > kMaxPickRows || k < 1 || k > kMaxTopK) throw std::invalid_argument("rules top-k: 1..8 rows, k in [1, 8]");
+    KernelScope ks(ctx, "rules_topk", 0.0, 5.0 * n_rows * (double)n_vocab);
+    hipLaunchKernelGGL(rules_topk_kernel, dim3(n_rows), dim3(1024), 0, ctx.stream, logits, n_vocab, mask, rules, k, out_lp,
+                       out_ids);
     WLK_HIP(hipGetLastError());
 }
 

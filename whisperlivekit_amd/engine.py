@@ -332,7 +332,11 @@ class HipSession:
         """The token lists of whisper's SuppressTokens / SuppressBlank for wlk_pick_greedy (decoding.py:417-432)."""
         a = np.ascontiguousarray(suppressed, dtype=np.int32).reshape(-1)
         b = np.ascontiguousarray(blank, dtype=np.int32).reshape(-1)
+        key = (a.tobytes(), b.tobytes())
+        if key == getattr(self, "_rules_key", None):
+            return              # this mask is the one on the device: no drain of the stream, no upload (one per 30 s window)
         _lib.check(self.lib.wlk_rules_set(self._h, a.ctypes.data_as(C.c_void_p), a.size, b.ctypes.data_as(C.c_void_p), b.size))
+        self._rules_key = key
 
     def pick_greedy(self, *, first_step: bool, without_timestamps: bool, timestamp_begin: int, eot: int, no_timestamps: int,
                     ts_mode: int, ts_bound: int, max_initial: int) -> Tuple[int, float]:
@@ -344,6 +348,29 @@ class HipSession:
         _lib.check(self.lib.wlk_pick_greedy(self._h, prm.ctypes.data_as(C.c_void_p), tok.ctypes.data_as(C.c_void_p),
                                             lp.ctypes.data_as(C.c_void_p)))
         return int(tok[0]), float(lp[0])
+
+    PICK_FIELDS = ("first_step", "without_timestamps", "timestamp_begin", "eot", "no_timestamps", "ts_mode", "ts_bound",
+                   "max_initial")
+
+    def pick_topk(self, states: Sequence[dict], k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Logit rules + log-softmax + the k best of every row of the last decode on the device (wlk_pick_topk): ``states``
+        holds one dictionary of pick_greedy's keywords per row.  -> (log-probabilities [rows, k], ids [rows, k])."""
+        prm = np.asarray([[int(st[f]) for f in self.PICK_FIELDS] for st in states], dtype=np.int32).reshape(-1, 8)
+        n, kk = prm.shape[0], max(int(k), 0)
+        lp = np.empty((n, kk), np.float32)
+        ids = np.empty((n, kk), np.int32)
+        _lib.check(self.lib.wlk_pick_topk(self._h, prm.ctypes.data_as(C.c_void_p), n, int(k), lp.ctypes.data_as(C.c_void_p),
+                                          ids.ctypes.data_as(C.c_void_p)))
+        return lp, ids
+
+    def decode_ancestry(self, last_tokens: Sequence[int], sources: Sequence[int]) -> None:
+        """One single-token step whose row b continues hypothesis sources[b] of the previous step (wlk_decode_ancestry):
+        kv_reorder(sources) + decode(last_tokens) without moving the cache where the session qualifies."""
+        t = np.ascontiguousarray(last_tokens, dtype=np.int64).reshape(-1)
+        src = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        if src.size != t.size:
+            raise ValueError("decode_ancestry: one source row per token")
+        _lib.check(self.lib.wlk_decode_ancestry(self._h, t.ctypes.data_as(C.c_void_p), src.ctypes.data_as(C.c_void_p), t.size))
 
     def select(self, adj_rows: Sequence[int], adj_ids: Sequence[int], adj_deltas: Sequence[float], k: int,
                content_mel_len: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

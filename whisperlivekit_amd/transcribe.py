@@ -8,7 +8,9 @@ What runs where: the log-mel of the whole recording (``wlk_log_mel``), the encod
 and the device half of the word alignment (``wlk_find_alignment``) are HIP kernels.  The per-step logit rules are a handful
 of masked fills and one log-softmax over the vocabulary row the step produced; they run on that row on the host
 (single-threaded numpy; the sampling draw takes its random numbers from torch's global generator exactly as the reference's
-``Categorical.sample()`` does, so a seeded run consumes the generator as the reference does).  There is no CPU model path: without the library / a GPU the first call raises.
+``Categorical.sample()`` does, so a seeded run consumes the generator as the reference does); greedy decoding at temperature 0
+applies them on the device (``wlk_pick_greedy``), and so does beam search with 2-7 beams under WLK_TRANSCRIBE_DEVICE_BEAM=1
+(``wlk_pick_topk``, with single-token steps over the KV ancestry table: ``wlk_decode_ancestry``).  There is no CPU model path: without the library / a GPU the first call raises.
 
 Same keyword names, defaults and result dictionary as the reference; ``fp16`` is accepted and ignored (the path computes
 in fp32, as the reference does on its CPU).  Decoding a file name (ffmpeg) is outside the path: ``audio`` is samples.
@@ -305,22 +307,29 @@ class _WindowDecoder:
                 changed = True
         return _log_softmax(logits) if changed else logprobs
 
-    def _pick_state(self, tokens: np.ndarray) -> dict:
-        """What ApplyTimestampRules (decoding.py:441-499) reads from the sampled tokens of the one sequence, as the fields of
-        wlk_pick_params: the device applies the rules to the logits row, the history stays here."""
+    def _pick_states(self, tokens: np.ndarray) -> List[dict]:
+        """What ApplyTimestampRules (decoding.py:441-499) reads from the sampled tokens of every row, as the fields of
+        wlk_pick_params: the device applies the rules to the logits rows, the histories stay here."""
         tb = self.tok.timestamp_begin
-        sampled = tokens[0, self.sample_begin:]
-        last_ts = len(sampled) >= 1 and sampled[-1] >= tb
-        before_last_ts = len(sampled) < 2 or sampled[-2] >= tb
-        stamps = sampled[sampled >= tb]
-        bound = tb
-        if len(stamps) > 0:
-            bound = int(stamps[-1]) if (last_ts and not before_last_ts) else int(stamps[-1]) + 1
-        return dict(first_step=tokens.shape[1] == self.sample_begin, without_timestamps=bool(self.o.without_timestamps),
-                    timestamp_begin=tb, eot=self.tok.eot,
-                    no_timestamps=-1 if self.tok.no_timestamps is None else int(self.tok.no_timestamps),
-                    ts_mode=0 if not last_ts else (1 if before_last_ts else 2), ts_bound=bound,
-                    max_initial=-1 if self.max_initial_ts is None else int(self.max_initial_ts))
+        states = []
+        for row in tokens:
+            sampled = row[self.sample_begin:]
+            last_ts = len(sampled) >= 1 and sampled[-1] >= tb
+            before_last_ts = len(sampled) < 2 or sampled[-2] >= tb
+            stamps = sampled[sampled >= tb]
+            bound = tb
+            if len(stamps) > 0:
+                bound = int(stamps[-1]) if (last_ts and not before_last_ts) else int(stamps[-1]) + 1
+            states.append(dict(first_step=tokens.shape[1] == self.sample_begin,
+                               without_timestamps=bool(self.o.without_timestamps), timestamp_begin=tb, eot=self.tok.eot,
+                               no_timestamps=-1 if self.tok.no_timestamps is None else int(self.tok.no_timestamps),
+                               ts_mode=0 if not last_ts else (1 if before_last_ts else 2), ts_bound=bound,
+                               max_initial=-1 if self.max_initial_ts is None else int(self.max_initial_ts)))
+        return states
+
+    def _pick_state(self, tokens: np.ndarray) -> dict:
+        """The one sequence of the greedy loop: row 0 of `_pick_states`."""
+        return self._pick_states(tokens[:1])[0]
 
     # -- the loop ------------------------------------------------------------------------------------------------------
     def run(self, mel_segment: Optional[np.ndarray], session: Optional[HipSession] = None) -> DecodingResult:
@@ -349,12 +358,27 @@ class _WindowDecoder:
         # step (WLK_TRANSCRIBE_DEVICE_RULES=0: the host path below, which sampling and beam search always take)
         device_rules = (beam is None and rows == 1 and o.temperature == 0 and hasattr(s, "pick_greedy")
                         and os.environ.get("WLK_TRANSCRIBE_DEVICE_RULES", "1") != "0")
-        if device_rules:
+        # beam search (2..7 beams) at temperature 0 with WLK_TRANSCRIBE_DEVICE_BEAM=1: rules, log-softmax and the beam + 1 best
+        # of every row on the device (beam * (beam + 1) pairs back per step), and single-token steps that read the
+        # self-attention cache through the ancestry table instead of gathering it.  Off by default.
+        device_beam = (beam is not None and 2 <= o.beam_size <= 7 and o.temperature == 0 and hasattr(s, "pick_topk")
+                       and os.environ.get("WLK_TRANSCRIBE_DEVICE_BEAM", "0") == "1")
+        if device_rules or device_beam:
             s.set_rules(self.suppressed or [], self.blank_ids or [])
+        sources = None
         for i in range(self.sample_len):
-            s.decode(tokens if i == 0 else tokens[:, -1:], first=(i == 0), sot_index=self.sot_index)
+            if device_beam and i > 0:
+                s.decode_ancestry(tokens[:, -1], sources)
+            else:
+                s.decode(tokens if i == 0 else tokens[:, -1:], first=(i == 0), sot_index=self.sot_index)
             if i == 0 and tok.no_speech is not None:
                 no_speech = float(s.no_speech_prob(tok.no_speech)[0])
+            if device_beam:
+                top_lp, top_id = s.pick_topk(self._pick_states(tokens), o.beam_size + 1)
+                tokens, done, sources = beam.update(tokens, top_lp, top_id, sum_logprobs)
+                if done or tokens.shape[-1] > self.n_ctx:
+                    break
+                continue
             if device_rules:
                 nxt_id, picked = s.pick_greedy(**self._pick_state(tokens))
                 if tokens[0, -1] != tok.eot:
