@@ -554,8 +554,8 @@ int wlk_diag_prefill_stack(wlk_session** sessions, const int64_t* tokens, const 
                            int32_t* taken);
 /* prefill chains run by the engine's prefill lane and the sessions stacked in them */
 int wlk_engine_prefill_stats(wlk_model* m, uint64_t* batches, uint64_t* sessions);
-/* kernel-tuning probe: average microseconds per encoder self-attention launch (pseudo-random qkv, k_splits key ranges) */
-int wlk_diag_encoder_attention_time(int t, int d, int n_head, int k_splits, int reps, float* us_per_launch);
+/* kernel-tuning probe: average microseconds per encoder self-attention launch (pseudo-random qkv) */
+int wlk_diag_encoder_attention_time(int t, int d, int n_head, int reps, float* us_per_launch);
 /* qkv [t, 3d] with q and k pre-scaled -> softmax(q k^T) v per 64-wide head, out [t, d] */
 int wlk_diag_encoder_attention(const float* qkv, int t, int d, int n_head, float* out);
 /* Token selection and AlignAtt read-out (csrc/select.hip, csrc/align_body.h) on host data, through ONE chosen route.  The

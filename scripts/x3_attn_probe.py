@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""X3 encoder attention timing (base.en / large-v3 shapes); WLK_X3_ATTN_ABL selects an ablation.  GPU box only."""
+"""X3 encoder attention timing (base.en / large-v3 shapes).  GPU box only."""
 import ctypes as C
 import os
 import sys

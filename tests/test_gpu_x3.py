@@ -142,30 +142,39 @@ def test_persistent_walk_is_bit_identical_to_one_workgroup_per_tile(M, N, K, fla
 
 @pytest.mark.parametrize("M,N,K,flags", [(1500, 1280, 1280, 0), (1500, 1280, 5120, 4), (1500, 2048, 512, 1), (333, 1152, 384, 0),
                                          (2999, 1536, 384, 5), (64, 1024, 128, 0)])
-def test_tile_height_and_wave_split_do_not_change_an_element(M, N, K, flags, monkeypatch):
-    """Round 6: the two-wave kernel (a slab's k-steps split between the two compute waves of a SIMD) takes 64-row tiles where
+def test_tile_height_does_not_change_an_element_and_the_result_is_as_close_to_float64_as_fp32(M, N, K, flags, monkeypatch):
+    """Round 6: the wide kernel (a slab's k-steps split between the two compute waves of a SIMD) takes 64-row tiles where
     96-row tiles leave CUs idle (WLK_X3_BM forces either).  An element's arithmetic does not depend on the tile height: both
-    heights give bit-identical results; against the one-wave kernel of round 5 (WLK_X3_KSPLIT=0), which groups a tile's K sum
-    differently, the difference stays at rounding level."""
+    heights give bit-identical results.  And the result is held to this file's accuracy criterion: against float64 (same
+    epilogue: bias, scaled columns, erf-GELU) as close as the fp32-MFMA kernel and as torch's CPU fp32 GEMM."""
     lib = _lib.load()
     rng = np.random.default_rng(M + N + K)
     a = rng.standard_normal((M, K)).astype(np.float32)
     w = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
     bias = (0.1 * rng.standard_normal(N)).astype(np.float32)
     out = {}
-    for name, env in (("bm96", {"WLK_X3_BM": "96"}), ("bm64", {"WLK_X3_BM": "64"}), ("one_wave", {"WLK_X3_KSPLIT": "0"})):
-        for k in ("WLK_X3_BM", "WLK_X3_KSPLIT"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+    for name, bm in (("bm96", "96"), ("bm64", "64")):
+        monkeypatch.setenv("WLK_X3_BM", bm)
         assert lib.wlk_diag_env_refresh() == 0
         c = np.full((M, N), np.nan, np.float32)
         assert lib.wlk_diag_linear_x3(vp(a), vp(w), vp(bias), M, N, K, flags, 0.5, N // 2, vp(c)) == 0, lib.wlk_diag_last_error()
         out[name] = c
-    for k in ("WLK_X3_BM", "WLK_X3_KSPLIT"):
-        monkeypatch.delenv(k, raising=False)
+    monkeypatch.delenv("WLK_X3_BM")
     assert lib.wlk_diag_env_refresh() == 0
     assert np.isfinite(out["bm96"]).all()
     assert np.array_equal(out["bm96"].view(np.uint32), out["bm64"].view(np.uint32)), float(np.abs(out["bm96"] - out["bm64"]).max())
-    scale = float(np.abs(out["one_wave"]).max())
-    assert float(np.abs(out["bm96"] - out["one_wave"]).max()) <= 4e-6 * max(1.0, scale)
+    ref = a.astype(np.float64) @ w.astype(np.float64).T + bias
+    if flags & 4:
+        ref[:, :N // 2] *= 0.5
+    if flags & 1:
+        ref = 0.5 * ref * (1.0 + torch.erf(torch.from_numpy(ref) * 0.7071067811865476).numpy())
+    c32 = np.empty((M, N), np.float32)
+    assert lib.wlk_diag_linear(vp(a), K, M * K, vp(w), vp(bias), None, N, M, N, K, flags, 0.5, N // 2, 0, vp(c32)) == 0
+    t = torch.from_numpy(a) @ torch.from_numpy(w).T + torch.from_numpy(bias)
+    if flags & 4:
+        t[:, :N // 2] *= 0.5
+    if flags & 1:
+        t = torch.nn.functional.gelu(t)
+    e3, e32, et = _err(out["bm96"], ref), _err(c32, ref), _err(t.numpy(), ref)
+    print(f"M{M} N{N} K{K} flags{flags}: x3 max/mean {e3[0]:.2e} {e3[1]:.2e} | fp32 mfma {e32[0]:.2e} {e32[1]:.2e} | torch cpu {et[0]:.2e} {et[1]:.2e}")
+    assert e3[1] <= 2.0 * max(e32[1], et[1]) and e3[0] <= 3.0 * max(e32[0], et[0]), (e3, e32, et)

@@ -266,7 +266,7 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_linear_time": (cint, [cint, cint, cint, cint, cint, cint, C.POINTER(C.c_float)]),
         "wlk_diag_linear_ln": (cint, [p, p, p, p, p, cint, cint, cint, cint, p]),
         "wlk_diag_layernorm": (cint, [p, p, p, cint, cint, p]),
-        "wlk_diag_encoder_attention_time": (cint, [cint, cint, cint, cint, cint, C.POINTER(C.c_float)]),
+        "wlk_diag_encoder_attention_time": (cint, [cint, cint, cint, cint, C.POINTER(C.c_float)]),
         "wlk_diag_encoder_attention": (cint, [p, cint, cint, cint, p]),
         "wlk_diag_wave_ops": (cint, [p, p, p]),
         "wlk_diag_env_refresh": (cint, []),

@@ -482,8 +482,6 @@ int wlk_session_create(wlk_model* m, int beam, int max_audio_samples, wlk_sessio
         if (m->n_align > 0) s->ring = dev_alloc<float>((size_t)m->n_align * beam * s->ring_rows * T);
         s->xsplit = dev_alloc<float>(cross_split_scratch_floats(8, D.n_text_head, (int)T));
         s->fsplit = dev_alloc<float>(flash_split_scratch_floats(s->max_rows, D.n_text_head, wlk_session::kFlashSplitsMax));
-        // partial softmax states of the encoder attention's key splits (<= 8 per (query, head))
-        s->esplit = dev_alloc<float>(flash_split_scratch_floats(D.n_audio_ctx, D.n_audio_head, 8));
         s->z = dev_alloc<float>((size_t)beam * std::max(m->n_align, 1) * T + (size_t)beam * 128);   // + the read-out's per-block (value, frame) pairs
         s->attn_last = dev_alloc_zero<float>((size_t)beam * T, st);
         s->adj_row = dev_alloc<int>(3 * wlk_session::kAdjCap);   // [rows n | ids n | deltas n] packed per call
@@ -546,7 +544,6 @@ int wlk_session_destroy(wlk_session* s) {
     if (s->enc_out3) (void)hipFree(s->enc_out3);
     if (s->emlp3) (void)hipFree(s->emlp3);
     if (s->wa_buf) (void)hipFree(s->wa_buf);
-    if (s->esplit) (void)hipFree(s->esplit);
     if (s->pinned) (void)hipHostFree(s->pinned);
     if (s->dec_stage) (void)hipHostFree(s->dec_stage);
     if (s->audio_stage) (void)hipHostFree(s->audio_stage);
@@ -829,8 +826,7 @@ extern "C++" void wlk_encode_group(const std::vector<wlk_session*>& group, const
     const float scale = std::pow((float)kHeadDim, -0.25f);
     const PtrTable z_ex_eh = table([](wlk_session* s) { return (const float*)s->ex; }, [](wlk_session* s) { return s->eh; }, none);
     const PtrTable z_eh_qkv = table([](wlk_session* s) { return (const float*)s->eh; }, [](wlk_session* s) { return s->eqkv; }, none);
-    const PtrTable z_qkv_att = table([](wlk_session* s) { return (const float*)s->eqkv; }, [](wlk_session* s) { return s->eatt; },
-                                     [](wlk_session* s) { return (const float*)s->esplit; });
+    const PtrTable z_qkv_att = table([](wlk_session* s) { return (const float*)s->eqkv; }, [](wlk_session* s) { return s->eatt; }, none);
     const PtrTable z_att_ex = table([](wlk_session* s) { return (const float*)s->eatt; }, [](wlk_session* s) { return s->ex; },
                                     [](wlk_session* s) { return (const float*)s->ex; });
     const PtrTable z_eh_mlp = table([](wlk_session* s) { return (const float*)s->eh; }, [](wlk_session* s) { return s->emlp; }, none);

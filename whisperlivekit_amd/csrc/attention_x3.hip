@@ -89,8 +89,6 @@ struct AttnX3Args {
 // 18 us of MFMA time).  Here ALL EIGHT waves compute: wave (qs, ks) owns 16 queries (v_mfma_f32_16x16x32_bf16: same flop
 // rate, half the accumulator and softmax work per wave) of key stream ks, the two waves of a SIMD belong to different
 // streams and cover each other's softmax and DMA issue (6 pieces per wave and step) with their MFMAs.
-// ABL (timing probe, WLK_X3_ATTN_ABL): 1 = DMA and barriers only, 2 = no DMA, 3 = MFMAs only (no softmax, no DMA)
-template <int ABL>
 __global__ __launch_bounds__(512) void enc_attention_x3_kernel(AttnX3Args a) {
     asm volatile("" ::"s"(a.qk3), "s"(a.ldqk), "s"(a.vt_off), "s"(a.vt_ld), "s"(a.out), "s"(a.ldo), "s"(a.T), "s"(a.d), "s"(a.n_head),
                  "s"(a.batch));
@@ -152,7 +150,6 @@ __global__ __launch_bounds__(512) void enc_attention_x3_kernel(AttnX3Args a) {
         }
     }
     auto issue_step = [&](int step) {
-        if constexpr (ABL >= 2) return;
         const int sc = min(step, n_steps - 1);         // the tail re-fetches the last pair into a free slot
         const int slot = step % AX_NB;
         ax_static_for<AX_NPW>([&](auto I) {
@@ -229,33 +226,28 @@ __global__ __launch_bounds__(512) void enc_attention_x3_kernel(AttnX3Args a) {
     };
     auto phase_pv = [&]() {                                 // online softmax of s, O^T += V^T P^T
         bf16x8 pf[3];
-        if constexpr (ABL != 3) {
-            // this lane's query column: its 8 keys here, the others in lanes ^ 16, ^ 32
-            float mt = fmaxf(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])), fmaxf(fmaxf(s[4], s[5]), fmaxf(s[6], s[7])));
-            mt = fmaxf(mt, wave_xor<16>(mt));
-            mt = fmaxf(mt, wave_xor<32>(mt));
-            const float m_new = fmaxf(m_run, mt);
-            const float alpha = __expf(m_run - m_new);
-            float rs = 0.f;
+        // this lane's query column: its 8 keys here, the others in lanes ^ 16, ^ 32
+        float mt = fmaxf(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])), fmaxf(fmaxf(s[4], s[5]), fmaxf(s[6], s[7])));
+        mt = fmaxf(mt, wave_xor<16>(mt));
+        mt = fmaxf(mt, wave_xor<32>(mt));
+        const float m_new = fmaxf(m_run, mt);
+        const float alpha = __expf(m_run - m_new);
+        float rs = 0.f;
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                s[i] = __expf(s[i] - m_new);
-                rs += s[i];
-            }
-            rs += wave_xor<16>(rs);
-            rs += wave_xor<32>(rs);
-            l_run = l_run * alpha + rs;
-            m_run = m_new;
-            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
-#pragma unroll
-                for (int db = 0; db < 4; ++db) o[db] *= alpha;
-            }
-            // the lane's 8 probabilities are, split into planes, its B fragment
-            ax_split8(s, pf);
-        } else {
-#pragma unroll
-            for (int p = 0; p < 3; ++p) pf[p] = __builtin_bit_cast(bf16x8, vf[p]);
+        for (int i = 0; i < 8; ++i) {
+            s[i] = __expf(s[i] - m_new);
+            rs += s[i];
         }
+        rs += wave_xor<16>(rs);
+        rs += wave_xor<32>(rs);
+        l_run = l_run * alpha + rs;
+        m_run = m_new;
+        if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
+#pragma unroll
+            for (int db = 0; db < 4; ++db) o[db] *= alpha;
+        }
+        // the lane's 8 probabilities are, split into planes, its B fragment
+        ax_split8(s, pf);
         ax_static_for<24>([&](auto X) {
             constexpr int x = decltype(X)::value;
             constexpr int t = x / 4, db = x % 4;      // product t of feature block db: four independent chains
@@ -269,7 +261,7 @@ __global__ __launch_bounds__(512) void enc_attention_x3_kernel(AttnX3Args a) {
         issue_step(st + AX_DT);
         const unsigned off = (unsigned)(st % AX_NB) * (unsigned)AX_SLOT_BYTES;
         const int tile = 2 * st + ks;
-        if (ABL != 1 && tile < n_tiles) {      // wave-uniform
+        if (tile < n_tiles) {      // wave-uniform
             phase_s(tile, off);
             phase_pv();
         }
@@ -380,10 +372,7 @@ void launch_encoder_attention_x3(const LaunchCtx& ctx, const unsigned short* qk3
     int dev = 0;
     WLK_HIP(hipGetDevice(&dev));
     if (!(configured.load(std::memory_order_acquire) >> (dev & 63) & 1)) {
-        WLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc_attention_x3_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)AX_LDS_BYTES));
-        WLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc_attention_x3_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)AX_LDS_BYTES));
-        WLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc_attention_x3_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)AX_LDS_BYTES));
-        WLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc_attention_x3_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)AX_LDS_BYTES));
+        WLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc_attention_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)AX_LDS_BYTES));
         configured.fetch_or(1ull << (dev & 63), std::memory_order_release);
     }
     AttnX3Args a{};
@@ -394,15 +383,8 @@ void launch_encoder_attention_x3(const LaunchCtx& ctx, const unsigned short* qk3
     if (batch > 0) a.z = *z;
     const int q_tiles = (T + AX_QT - 1) / AX_QT;
     KernelScope ks(ctx, "enc_attention_x3", (batch > 0 ? batch : 1) * 4.0 * (double)T * T * 64 * n_head, 0.0);
-    static const int abl = [] {
-        const char* e = getenv("WLK_X3_ATTN_ABL");
-        return e ? atoi(e) : 0;
-    }();
     const dim3 grid(q_tiles * n_head, batch > 0 ? batch : 1);
-    if (abl == 1) hipLaunchKernelGGL(enc_attention_x3_kernel<1>, grid, dim3(512), AX_LDS_BYTES, ctx.stream, a);
-    else if (abl == 2) hipLaunchKernelGGL(enc_attention_x3_kernel<2>, grid, dim3(512), AX_LDS_BYTES, ctx.stream, a);
-    else if (abl == 3) hipLaunchKernelGGL(enc_attention_x3_kernel<3>, grid, dim3(512), AX_LDS_BYTES, ctx.stream, a);
-    else hipLaunchKernelGGL(enc_attention_x3_kernel<0>, grid, dim3(512), AX_LDS_BYTES, ctx.stream, a);
+    hipLaunchKernelGGL(enc_attention_x3_kernel, grid, dim3(512), AX_LDS_BYTES, ctx.stream, a);
     WLK_HIP(hipGetLastError());
 }
 

@@ -402,7 +402,6 @@ struct FlashArgs {
     // keys / values from tile_rows[t].cross_kv + tile_kv_off (values tile_v_off floats further) and dumps alignment
     // scores into tile_rows[t].ring (one beam); ring_row[] stays indexed by the stacked row
     const StepRow* tile_rows = nullptr;
-    long long* dbg_clock = nullptr;   // probe only (enc_attention_pw_kernel): 8 s_memtime figures per workgroup
     // ---- the rest ---------------------------------------------------------------------------------------------------
     long tile_kv_off = 0, tile_v_off = 0;
     // decoder prefill only: raw scores of alignment heads go to the alignment window
@@ -420,14 +419,12 @@ struct FlashArgs {
     do {                                                                                                                   \
         asm volatile("" ::"s"((a).q), "s"((a).ldq), "s"((a).k), "s"((a).v), "s"((a).ldkv), "s"((a).out), "s"((a).ldo),      \
                      "s"((a).Tq), "s"((a).Tk), "s"((a).n_head), "s"((a).batch), "s"((a).z_k_off), "s"((a).z_v_off),         \
-                     "s"((a).k_splits), "s"((a).ring_rows), "s"((a).tile_rows), "s"((a).dbg_clock));                        \
+                     "s"((a).k_splits), "s"((a).ring_rows), "s"((a).tile_rows));                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                                 \
     } while (0)
-extern long long* g_attn_dbg_clock;   // set by the timing probe (diag.hip); nullptr otherwise
 size_t flash_split_scratch_floats(int rows, int n_head, int k_splits);
 // encoder self-attention over qkv[T][3d] (q and k pre-scaled), out[T][d]
-void launch_encoder_attention(const LaunchCtx& ctx, const float* qkv, float* out, int T, int d, int n_head,
-                              int k_splits = 1, float* split_scratch = nullptr);
+void launch_encoder_attention(const LaunchCtx& ctx, const float* qkv, float* out, int T, int d, int n_head);
 // encoder self-attention of `batch` sessions in one launch: qkv = z.in[i] ([T][3d]), out = z.out[i]
 void launch_encoder_attention_batched(const LaunchCtx& ctx, const PtrTable& z, int batch, int T, int d, int n_head);
 void launch_prefill_cross_attention(const LaunchCtx& ctx, const FlashArgs& a);

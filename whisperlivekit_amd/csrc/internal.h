@@ -176,8 +176,6 @@ struct wlk_session {
     bool debug = false;
     bool use_graph = true;
     hipGraphExec_t step_exec[2] = {nullptr, nullptr};   // single-token decode step, per KV buffer
-    int enc_ksplit = 1;                                 // key split of the encoder attention (WLK_ENC_KSPLIT)
-    float* esplit = nullptr;
     short* pcm16_dev = nullptr;                         // staging of wlk_audio_append_pcm16 (lazily allocated)
 
     // audio (two buffers: eviction copies the tail into the other one)
