@@ -419,6 +419,29 @@ int wlk_vad_stream_reset(wlk_vad_stream* s);                       /* model.rese
 int wlk_vad_stream_run(wlk_vad_stream* s, const float* pcm_host, int n_windows, float* probs_host);
 int wlk_vad_stream_state(wlk_vad_stream* s, float* h_host /* [128] */, float* c_host /* [128] */);
 int wlk_vad_stream_destroy(wlk_vad_stream* s);
+/* wlk_vad_stream_run on int16 PCM as it comes off the wire: the samples are widened on the GPU as
+ * (float)v * (1.0f / 32768.0f), the exact value of astype(float32) / 32768, so the result has the bits of
+ * wlk_vad_stream_run on that fp32 audio. */
+int wlk_vad_stream_run_pcm16(wlk_vad_stream* s, const int16_t* pcm_host, int n_windows, float* probs_host);
+/* One call for the chunks of many streams (config 4: 8 sessions with VAC on, one tick): one upload, three launches (stage
+ * the streams' [context | chunk] runs, the per-window front end over all windows, the recurrent cell with one workgroup
+ * per stream), one download, one synchronise.  A wlk_vad_group holds only scratch: (h, c) and the 64-sample context stay
+ * in each wlk_vad_stream, and a stream's probabilities and state have the bits a wlk_vad_stream_run of the same chunk
+ * gives, whatever is stacked beside it - so a stream may go through solo and group calls in any order.
+ * streams[i] consumes n_windows[i] x 512 samples; pcm_host holds the streams' chunks back to back in that order, all
+ * fp32 or all int16 (sample_format); probs_host receives sum(n_windows) probabilities in the same order.
+ * Rejected before anything is enqueued, so that every stream keeps its state and context: a NULL pointer, an unknown
+ * sample_format, n_streams < 1, a window count < 1, the same stream twice, a stream created from another wlk_vad: WLK_ERR_ARG;
+ * n_streams > max_streams, sum(n_windows) > max_windows_total: WLK_ERR_CAPACITY.
+ * Calls are synchronous.  A stream is in at most one call at a time, solo or group (the rule of wlk_vad_stream_run); a
+ * group serves one call at a time. */
+#define WLK_VAD_F32 0
+#define WLK_VAD_S16 1
+typedef struct wlk_vad_group wlk_vad_group;
+int wlk_vad_group_create(wlk_vad* m, int max_streams /* 1..64 */, int max_windows_total /* 1..4096 */, wlk_vad_group** out);
+int wlk_vad_group_run(wlk_vad_group* g, wlk_vad_stream* const* streams, const int32_t* n_windows, int n_streams,
+                      const void* pcm_host, int sample_format, float* probs_host);
+int wlk_vad_group_destroy(wlk_vad_group* g);
 
 /* ---- diagnostics: one kernel on host data (used by the GPU parity tests only) ---------------- */
 const char* wlk_diag_last_error(void);

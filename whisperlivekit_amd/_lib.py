@@ -254,6 +254,10 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_vad_stream_run": (cint, [p, p, cint, p]),
         "wlk_vad_stream_state": (cint, [p, p, p]),
         "wlk_vad_stream_destroy": (cint, [p]),
+        "wlk_vad_stream_run_pcm16": (cint, [p, p, cint, p]),
+        "wlk_vad_group_create": (cint, [p, cint, cint, C.POINTER(p)]),
+        "wlk_vad_group_run": (cint, [p, C.POINTER(p), i32p, cint, p, cint, p]),
+        "wlk_vad_group_destroy": (cint, [p]),
         "wlk_diag_last_error": (C.c_char_p, []),
         "wlk_diag_linear": (cint, [p, C.c_int64, C.c_int64, p, p, p, C.c_int64, cint, cint, cint, cint, C.c_float,
                                    cint, cint, p]),
@@ -312,7 +316,8 @@ EXPORTED_SYMBOLS = (
     "wlk_sf_session_update", "wlk_sf_session_get_state", "wlk_sf_session_set_state",
     "wlk_vad_weights_floats", "wlk_vad_tensor_lookup", "wlk_vad_tensor_name", "wlk_vad_create", "wlk_vad_destroy",
     "wlk_vad_stream_create", "wlk_vad_stream_reset", "wlk_vad_stream_run", "wlk_vad_stream_state",
-    "wlk_vad_stream_destroy",
+    "wlk_vad_stream_destroy", "wlk_vad_stream_run_pcm16", "wlk_vad_group_create", "wlk_vad_group_run",
+    "wlk_vad_group_destroy",
     "wlk_dtw", "wlk_encode_mel", "wlk_log_mel", "wlk_find_alignment",
     "wlk_nllb_arena_floats", "wlk_nllb_tensor_lookup", "wlk_nllb_tensor_name", "wlk_nllb_create", "wlk_nllb_upload",
     "wlk_nllb_finalize", "wlk_nllb_destroy", "wlk_nllb_session_create", "wlk_nllb_session_destroy", "wlk_nllb_encode",

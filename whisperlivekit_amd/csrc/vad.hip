@@ -9,6 +9,10 @@
 //   vad_lstm_kernel      one 512-thread workgroup per stream walks the windows in order: each thread keeps its row
 //                        of W_hh in registers (128 VGPRs), h/c live in LDS; LSTMCell -> ReLU -> Conv1d(128,1) ->
 //                        sigmoid = speech probability of the window.
+// A wlk_vad_group runs the same two bodies for the chunks of many streams in one call: a staging kernel
+// lays every stream's [64 context | n x 512] run out in the group's scratch (int16 wire audio is widened there), the
+// feature kernel takes one window per workgroup from a table, the recurrent kernel one stream per workgroup from a
+// table.  State and context stay in the wlk_vad_stream, so solo and group calls mix freely.
 // Network structure and state handling restated from the archive's code objects; pinned by reference-generated
 // probabilities (tests/golden/vad_cases.npz).  fp32 throughout, like the reference.
 #include <cstring>
@@ -53,8 +57,9 @@ struct VadWeights {
     const float *basisT, *w0, *b0, *w1, *b1, *w2, *b2, *w3, *b3, *wihT, *whhT, *bih, *bhh, *decw, *decb;
 };
 
-__global__ __launch_bounds__(256) void vad_features_kernel(VadWeights W, const float* __restrict__ audio,
-                                                           float* __restrict__ gi) {
+// one window: x1 = its [64 context | 512 samples], gi_row = its 512 gate inputs.  256 threads.
+__device__ __forceinline__ void vad_features_window(const VadWeights& W, const float* __restrict__ x1,
+                                                    float* __restrict__ gi_row) {
     __shared__ float xs[kVadX + kVadPad];
     __shared__ float spec[2 * kVadBins * kVadFrames];
     __shared__ float mag[kVadBins][kVadFrames + 2];      // one zero column either side: Conv1d padding 1
@@ -62,8 +67,7 @@ __global__ __launch_bounds__(256) void vad_features_kernel(VadWeights W, const f
     __shared__ float a1[kVadC1][2 + 2];
     __shared__ float a2[kVadC2];
     __shared__ float feat[kVadC3];
-    const int tid = threadIdx.x, w = blockIdx.x;
-    const float* x1 = audio + (size_t)w * kVadWin;         // this window's [context | samples]
+    const int tid = threadIdx.x;
     for (int i = tid; i < kVadX; i += 256) xs[i] = x1[i];
     if (tid < kVadPad) xs[kVadX + tid] = x1[kVadX - 2 - tid];   // ReflectionPad1d((0, 64))
     __syncthreads();
@@ -130,13 +134,14 @@ __global__ __launch_bounds__(256) void vad_features_kernel(VadWeights W, const f
     for (int g = tid; g < kVadGates; g += 256) {   // LSTMCell input half: W_ih x + b_ih
         float s = 0.f;
         for (int k = 0; k < kVadC3; ++k) s = fmaf(W.wihT[k * kVadGates + g], feat[k], s);
-        gi[(size_t)w * kVadGates + g] = s + W.bih[g];
+        gi_row[g] = s + W.bih[g];
     }
 }
 
-__global__ __launch_bounds__(512) void vad_lstm_kernel(VadWeights W, const float* __restrict__ gi, float* __restrict__ state,
-                                                       float* __restrict__ probs, float* __restrict__ audio,
-                                                       int n_windows) {
+// one stream: walks its n_windows gate-input rows in order, then leaves the chunk's last 64 samples (tail) as the next
+// call's context (ctx).  512 threads.
+__device__ __forceinline__ void vad_lstm_stream(const VadWeights& W, const float* __restrict__ gi, float* __restrict__ state,
+                                                float* __restrict__ probs, float* ctx, const float* tail, int n_windows) {
     __shared__ float hs[kVadHid], cs[kVadHid], gates[kVadGates], red[2];
     const int tid = threadIdx.x, lane = tid & 63;
     float whh[kVadHid];
@@ -169,7 +174,72 @@ __global__ __launch_bounds__(512) void vad_lstm_kernel(VadWeights W, const float
         if (tid == 0) probs[w] = 1.0f / (1.0f + expf(-((red[0] + red[1]) + W.decb[0])));
     }
     if (tid < kVadHid) { state[tid] = hs[tid]; state[kVadHid + tid] = cs[tid]; }
-    if (tid < kVadCtx) audio[tid] = audio[(size_t)n_windows * kVadWin + tid];   // next call's context
+    if (tid < kVadCtx) ctx[tid] = tail[tid];
+}
+
+__global__ __launch_bounds__(256) void vad_features_kernel(VadWeights W, const float* __restrict__ audio,
+                                                           float* __restrict__ gi) {
+    const int w = blockIdx.x;
+    vad_features_window(W, audio + (size_t)w * kVadWin, gi + (size_t)w * kVadGates);
+}
+
+__global__ __launch_bounds__(512) void vad_lstm_kernel(VadWeights W, const float* __restrict__ gi, float* __restrict__ state,
+                                                       float* __restrict__ probs, float* audio, int n_windows) {
+    vad_lstm_stream(W, gi, state, probs, audio, audio + (size_t)n_windows * kVadWin, n_windows);
+}
+
+// int16 PCM off the wire -> fp32: the expression of pcm16_to_float_kernel (mel.hip), an exact power-of-two scale, so it
+// equals astype(float32) / 32768 on the host bit for bit
+__device__ __forceinline__ float vad_widen(short v) { return (float)v * (1.0f / 32768.0f); }
+
+__global__ void vad_widen_kernel(const short* __restrict__ in, float* __restrict__ out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = vad_widen(in[i]);
+}
+
+// ---- group call: tables built on the host, uploaded in front of the audio --------------------------------------------
+struct VadWindowRow {       // one per window of the call, in the order of the concatenated chunks
+    float* x;               // the window's [context | samples] inside its stream's staged run
+    float* gi;              // its 512 gate inputs
+    const float* ctx_src;   // the stream's context (wlk_vad_stream::audio) for a stream's first window, else NULL
+    uint32_t raw_off;       // the window's first sample in the uploaded chunks
+    uint32_t pad_;
+};
+struct VadStreamRow {       // one per stream of the call
+    const float* gi;        // the stream's first gate-input row
+    float* state;           // wlk_vad_stream::state (h | c)
+    float* probs;           // the stream's first probability in the concatenated output
+    float* ctx;             // wlk_vad_stream::audio[0:64]
+    const float* tail;      // the chunk's last 64 samples in the staged run
+    int32_t n_windows;
+    int32_t pad_;
+};
+static_assert(sizeof(VadWindowRow) == 32 && sizeof(VadStreamRow) == 48, "table rows keep the audio behind them 16-byte aligned");
+
+// one workgroup per window: the stream's run becomes [64 context | n x 512] fp32, contiguous, as the solo path keeps it
+__global__ __launch_bounds__(256) void vad_group_stage_kernel(const VadWindowRow* __restrict__ rows,
+                                                              const void* __restrict__ raw, int sample_format) {
+    const VadWindowRow r = rows[blockIdx.x];
+    const int tid = threadIdx.x;
+    float* dst = r.x + kVadCtx;
+    if (sample_format == WLK_VAD_S16) {
+        const short* in = static_cast<const short*>(raw) + r.raw_off;
+        for (int i = tid; i < kVadWin; i += 256) dst[i] = vad_widen(in[i]);
+    } else {
+        const float* in = static_cast<const float*>(raw) + r.raw_off;
+        for (int i = tid; i < kVadWin; i += 256) dst[i] = in[i];
+    }
+    if (r.ctx_src && tid < kVadCtx) r.x[tid] = r.ctx_src[tid];
+}
+
+__global__ __launch_bounds__(256) void vad_group_features_kernel(VadWeights W, const VadWindowRow* __restrict__ rows) {
+    const VadWindowRow r = rows[blockIdx.x];
+    vad_features_window(W, r.x, r.gi);
+}
+
+__global__ __launch_bounds__(512) void vad_group_lstm_kernel(VadWeights W, const VadStreamRow* __restrict__ rows) {
+    const VadStreamRow r = rows[blockIdx.x];
+    vad_lstm_stream(W, r.gi, r.state, r.probs, r.ctx, r.tail, r.n_windows);
 }
 
 }  // namespace wlk
@@ -188,11 +258,31 @@ struct wlk_vad_stream {
     float *audio = nullptr, *gi = nullptr, *state = nullptr, *probs = nullptr;
     float* pinned = nullptr;   // [max_windows * 512 samples | max_windows probs]
 };
+// Scratch of a many-stream call; nothing in it outlives the call (state and context are the streams' own).
+struct wlk_vad_group {
+    wlk_vad* m = nullptr;
+    int max_streams = 0, max_windows_total = 0;
+    hipStream_t stream = nullptr;
+    size_t in_bytes = 0;              // capacity of one upload: [stream rows | window rows | the chunks as they came]
+    unsigned char* d_in = nullptr;
+    float *d_audio = nullptr, *d_gi = nullptr, *d_probs = nullptr;   // staged runs, gate inputs, probabilities
+    unsigned char* pinned = nullptr;  // [in_bytes | max_windows_total probs]
+};
 
 namespace {
 int vad_fail(int code, const std::string& msg) {
     set_last_error(msg);
     return code;
+}
+void vad_group_free(wlk_vad_group* g) {
+    if (!g) return;
+    (void)hipSetDevice(g->m->device);
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    for (void* p : {(void*)g->d_in, (void*)g->d_audio, (void*)g->d_gi, (void*)g->d_probs})
+        if (p) (void)hipFree(p);
+    if (g->pinned) (void)hipHostFree(g->pinned);
+    if (g->stream) (void)hipStreamDestroy(g->stream);
+    delete g;
 }
 template <typename F>
 int vad_guarded(F&& f) {
@@ -316,6 +406,32 @@ int wlk_vad_stream_run(wlk_vad_stream* s, const float* pcm_host, int n_windows, 
     });
 }
 
+int wlk_vad_stream_run_pcm16(wlk_vad_stream* s, const int16_t* pcm_host, int n_windows, float* probs_host) {
+    if (!s || !pcm_host || !probs_host) return vad_fail(WLK_ERR_ARG, "NULL argument");
+    if (n_windows < 1 || n_windows > s->max_windows) return vad_fail(WLK_ERR_CAPACITY, "window count out of range");
+    return vad_guarded([&]() {
+        WLK_HIP(hipSetDevice(s->m->device));
+        const int n = n_windows * kVadWin;
+        std::memcpy(s->pinned, pcm_host, (size_t)n * sizeof(int16_t));
+        // the int16 chunk waits in gi (1 KiB of a window's 2 KiB): the feature kernel fills gi only after the widening
+        // kernel in front of it on the stream has read it
+        short* raw = reinterpret_cast<short*>(s->gi);
+        WLK_HIP(hipMemcpyAsync(raw, s->pinned, (size_t)n * sizeof(int16_t), hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(vad_widen_kernel, dim3((n + 255) / 256), dim3(256), 0, s->stream, raw, s->audio + kVadCtx, n);
+        WLK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(vad_features_kernel, dim3(n_windows), dim3(256), 0, s->stream, s->m->W, s->audio, s->gi);
+        WLK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(vad_lstm_kernel, dim3(1), dim3(512), 0, s->stream, s->m->W, s->gi, s->state, s->probs, s->audio,
+                           n_windows);
+        WLK_HIP(hipGetLastError());
+        float* out = s->pinned + (size_t)s->max_windows * kVadWin;
+        WLK_HIP(hipMemcpyAsync(out, s->probs, (size_t)n_windows * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        WLK_HIP(hipStreamSynchronize(s->stream));
+        std::memcpy(probs_host, out, (size_t)n_windows * sizeof(float));
+        return WLK_OK;
+    });
+}
+
 int wlk_vad_stream_state(wlk_vad_stream* s, float* h_host, float* c_host) {
     if (!s || !h_host || !c_host) return vad_fail(WLK_ERR_ARG, "NULL argument");
     return vad_guarded([&]() {
@@ -336,6 +452,88 @@ int wlk_vad_stream_destroy(wlk_vad_stream* s) {
     if (s->pinned) (void)hipHostFree(s->pinned);
     (void)hipStreamDestroy(s->stream);
     delete s;
+    return WLK_OK;
+}
+
+int wlk_vad_group_create(wlk_vad* m, int max_streams, int max_windows_total, wlk_vad_group** out) {
+    if (!m || !out) return vad_fail(WLK_ERR_ARG, "NULL argument");
+    if (max_streams < 1 || max_streams > 64) return vad_fail(WLK_ERR_ARG, "max_streams out of range");
+    if (max_windows_total < 1 || max_windows_total > 4096) return vad_fail(WLK_ERR_ARG, "max_windows_total out of range");
+    return vad_guarded([&]() {
+        WLK_HIP(hipSetDevice(m->device));
+        std::unique_ptr<wlk_vad_group, void (*)(wlk_vad_group*)> g(new wlk_vad_group, vad_group_free);
+        g->m = m;
+        g->max_streams = max_streams;
+        g->max_windows_total = max_windows_total;
+        const size_t nw = (size_t)max_windows_total;
+        g->in_bytes = max_streams * sizeof(VadStreamRow) + nw * sizeof(VadWindowRow) + nw * kVadWin * sizeof(float);
+        WLK_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+        WLK_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_in), g->in_bytes));
+        WLK_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_audio), ((size_t)max_streams * kVadCtx + nw * kVadWin) * sizeof(float)));
+        WLK_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_gi), nw * kVadGates * sizeof(float)));
+        WLK_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_probs), nw * sizeof(float)));
+        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&g->pinned), g->in_bytes + nw * sizeof(float), hipHostMallocDefault));
+        *out = g.release();
+        return WLK_OK;
+    });
+}
+
+int wlk_vad_group_run(wlk_vad_group* g, wlk_vad_stream* const* streams, const int32_t* n_windows, int n_streams,
+                      const void* pcm_host, int sample_format, float* probs_host) {
+    if (!g || !streams || !n_windows || !pcm_host || !probs_host) return vad_fail(WLK_ERR_ARG, "NULL argument");
+    if (sample_format != WLK_VAD_F32 && sample_format != WLK_VAD_S16) return vad_fail(WLK_ERR_ARG, "unknown sample_format");
+    if (n_streams < 1) return vad_fail(WLK_ERR_ARG, "n_streams < 1");
+    if (n_streams > g->max_streams) return vad_fail(WLK_ERR_CAPACITY, "more streams than the group's max_streams");
+    int total = 0;
+    for (int i = 0; i < n_streams; ++i) {
+        if (!streams[i]) return vad_fail(WLK_ERR_ARG, "NULL stream");
+        if (streams[i]->m != g->m) return vad_fail(WLK_ERR_ARG, "stream belongs to another wlk_vad");
+        for (int j = 0; j < i; ++j)
+            if (streams[j] == streams[i]) return vad_fail(WLK_ERR_ARG, "the same stream twice in one call");
+        if (n_windows[i] < 1) return vad_fail(WLK_ERR_ARG, "window count < 1");
+        if (n_windows[i] > g->max_windows_total - total)
+            return vad_fail(WLK_ERR_CAPACITY, "more windows than the group's max_windows_total");
+        total += n_windows[i];
+    }
+    return vad_guarded([&]() {
+        WLK_HIP(hipSetDevice(g->m->device));
+        const size_t off_wrows = (size_t)n_streams * sizeof(VadStreamRow);
+        const size_t off_raw = off_wrows + (size_t)total * sizeof(VadWindowRow);
+        const size_t raw_bytes = (size_t)total * kVadWin * (sample_format == WLK_VAD_S16 ? sizeof(int16_t) : sizeof(float));
+        auto* srows = reinterpret_cast<VadStreamRow*>(g->pinned);
+        auto* wrows = reinterpret_cast<VadWindowRow*>(g->pinned + off_wrows);
+        int w0 = 0;
+        for (int i = 0; i < n_streams; ++i) {
+            float* run = g->d_audio + (size_t)i * kVadCtx + (size_t)w0 * kVadWin;   // [64 | n_windows[i] x 512]
+            float* gi = g->d_gi + (size_t)w0 * kVadGates;
+            srows[i] = VadStreamRow{gi, streams[i]->state, g->d_probs + w0, streams[i]->audio,
+                                    run + (size_t)n_windows[i] * kVadWin, n_windows[i], 0};
+            for (int w = 0; w < n_windows[i]; ++w)
+                wrows[w0 + w] = VadWindowRow{run + (size_t)w * kVadWin, gi + (size_t)w * kVadGates,
+                                             w == 0 ? streams[i]->audio : nullptr, (uint32_t)(w0 + w) * kVadWin, 0};
+            w0 += n_windows[i];
+        }
+        std::memcpy(g->pinned + off_raw, pcm_host, raw_bytes);
+        WLK_HIP(hipMemcpyAsync(g->d_in, g->pinned, off_raw + raw_bytes, hipMemcpyHostToDevice, g->stream));
+        const auto* d_srows = reinterpret_cast<const VadStreamRow*>(g->d_in);
+        const auto* d_wrows = reinterpret_cast<const VadWindowRow*>(g->d_in + off_wrows);
+        hipLaunchKernelGGL(vad_group_stage_kernel, dim3(total), dim3(256), 0, g->stream, d_wrows,
+                           static_cast<const void*>(g->d_in + off_raw), sample_format);
+        WLK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(vad_group_features_kernel, dim3(total), dim3(256), 0, g->stream, g->m->W, d_wrows);
+        WLK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(vad_group_lstm_kernel, dim3(n_streams), dim3(512), 0, g->stream, g->m->W, d_srows);
+        WLK_HIP(hipGetLastError());
+        float* out = reinterpret_cast<float*>(g->pinned + g->in_bytes);
+        WLK_HIP(hipMemcpyAsync(out, g->d_probs, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+        WLK_HIP(hipStreamSynchronize(g->stream));
+        std::memcpy(probs_host, out, (size_t)total * sizeof(float));
+        return WLK_OK;
+    });
+}
+
+int wlk_vad_group_destroy(wlk_vad_group* g) {
+    vad_group_free(g);
     return WLK_OK;
 }
 

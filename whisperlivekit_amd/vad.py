@@ -8,7 +8,10 @@ every incoming PCM array (audio_processor.py:1189-1190).  Here:
 * ``HipSileroVAD`` has the model's duck type (``model(x, sr)`` -> a scalar with ``.item()``, ``reset_states()``), so
   the reference's own ``FixedVADIterator(HipSileroVAD(...))`` works unmodified - one device call per window;
 * ``HipFixedVADIterator`` is the same iterator with the windows of one call evaluated together (two launches per
-  call instead of ~16 model evaluations per 0.5 s chunk); its events are identical.
+  call instead of ~16 model evaluations per 0.5 s chunk); its events are identical;
+* ``HipSileroVADGroup`` / ``vad_step_many`` evaluate the chunks of many streams in one device call: each
+  stream's probabilities and state have the bits of its own solo call, so streams move between the two forms freely;
+* ``probs_pcm16`` and int16 chunks of a group call take the wire's int16 PCM and widen it on the GPU.
 
 Weights come from the reference's own archive (``load_silero_state_dict``: torch.jit.load on the host, tensors
 only).  No CPU fallback: without libwlk_hip.so / a GPU the constructor raises.
@@ -17,7 +20,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -127,6 +130,21 @@ class HipSileroVAD:
                                                    out[lo:].ctypes.data_as(C.c_void_p)))
         return out
 
+    def probs_pcm16(self, pcm: np.ndarray) -> np.ndarray:
+        """``probs(pcm.astype(float32) / 32768)`` bit for bit, from the int16 samples themselves (half the upload, no
+        widening on the host)."""
+        a = np.ascontiguousarray(pcm).reshape(-1)
+        if a.dtype != np.int16:
+            raise ValueError("HipSileroVAD.probs_pcm16 needs int16 samples")
+        if a.size == 0 or a.size % WINDOW:
+            raise ValueError("HipSileroVAD.probs_pcm16 needs a positive multiple of 512 samples")
+        out = np.empty(a.size // WINDOW, np.float32)
+        for lo in range(0, out.size, self.max_windows):
+            n = min(self.max_windows, out.size - lo)
+            _lib.check(self.lib.wlk_vad_stream_run_pcm16(self._h, a[lo * WINDOW:].ctypes.data_as(C.c_void_p), n,
+                                                         out[lo:].ctypes.data_as(C.c_void_p)))
+        return out
+
     def __call__(self, x, sr: int = SAMPLE_RATE):
         if hasattr(x, "detach"):
             x = x.detach().cpu().numpy()
@@ -145,6 +163,49 @@ class HipSileroVAD:
     def close(self):
         if self._h:
             self.lib.wlk_vad_stream_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HipSileroVADGroup:
+    """Scratch for evaluating the chunks of many ``HipSileroVAD`` streams in one device call.  It keeps no stream state:
+    a stream's (h, c) and context stay in its ``HipSileroVAD``, which may be used alone between group calls."""
+
+    def __init__(self, weights: HipSileroVADWeights, max_streams: int = 16, max_windows: int = 256):
+        self.lib, self.weights = weights.lib, weights
+        self.max_streams, self.max_windows = max_streams, max_windows      # max_windows: of one call, all streams together
+        self._h = C.c_void_p()
+        _lib.check(self.lib.wlk_vad_group_create(weights._h, max_streams, max_windows, C.byref(self._h)))
+
+    def probs(self, models: Sequence[HipSileroVAD], chunks: Sequence[np.ndarray]) -> List[np.ndarray]:
+        """Speech probabilities of ``chunks[i]`` (a positive multiple of 512 samples) continuing ``models[i]``'s stream.
+        The chunks of one call are all int16 (wire PCM, widened on the GPU) or all floating point."""
+        if len(models) != len(chunks):
+            raise _lib.WlkError("HipSileroVADGroup.probs: one chunk per model")
+        arrs = [np.asarray(c).reshape(-1) for c in chunks]
+        pcm16 = [a.dtype == np.int16 for a in arrs]
+        if any(pcm16) and not all(pcm16):
+            raise _lib.WlkError("HipSileroVADGroup.probs: the chunks of one call are all int16 or all floating point")
+        if any(a.size % WINDOW for a in arrs):
+            raise _lib.WlkError("HipSileroVADGroup.probs: every chunk must be a multiple of 512 samples")
+        n_windows = np.array([a.size // WINDOW for a in arrs], np.int32)
+        fmt = 1 if arrs and pcm16[0] else 0
+        flat = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros(0), np.int16 if fmt else np.float32)
+        out = np.empty(int(n_windows.sum()), np.float32)
+        handles = (C.c_void_p * len(models))(*[m._h for m in models])
+        # counts < 1, duplicates, foreign streams and capacity are the library's checks (nothing is enqueued on an error)
+        _lib.check(self.lib.wlk_vad_group_run(self._h, handles, n_windows.ctypes.data_as(C.POINTER(C.c_int32)), len(models),
+                                              flat.ctypes.data_as(C.c_void_p), fmt, out.ctypes.data_as(C.c_void_p)))
+        return np.split(out, np.cumsum(n_windows)[:-1])
+
+    def close(self):
+        if self._h:
+            self.lib.wlk_vad_group_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):  # pragma: no cover
@@ -193,18 +254,42 @@ class HipFixedVADIterator:
             return {"end": int(end) if not return_seconds else round(end / self.sampling_rate, time_resolution)}
         return None
 
-    def __call__(self, x, return_seconds: bool = False) -> List[dict]:
+    def _take(self, x) -> Optional[np.ndarray]:
+        """Append ``x`` to the remainder; the complete windows now buffered (they stay buffered until ``_consume``)."""
         if hasattr(x, "detach"):
             x = x.detach().cpu().numpy()
         self.buffer = np.append(self.buffer, np.asarray(x, np.float32).reshape(-1))
         n = len(self.buffer) // WINDOW
-        if n == 0:
-            return []
-        probs = self.model.probs(self.buffer[: n * WINDOW])
-        self.buffer = self.buffer[n * WINDOW:]
+        return self.buffer[: n * WINDOW] if n else None
+
+    def _consume(self, probs, return_seconds: bool) -> List[dict]:
+        """Drop the windows ``probs`` belongs to from the buffer and step the state machine through them."""
+        self.buffer = self.buffer[len(probs) * WINDOW:]
         events = []
         for p in probs:
             r = self._step(float(p), return_seconds)
             if r is not None:
                 events.append(r)
         return events
+
+    def __call__(self, x, return_seconds: bool = False) -> List[dict]:
+        windows = self._take(x)
+        if windows is None:
+            return []
+        return self._consume(self.model.probs(windows), return_seconds)
+
+
+def vad_step_many(group, iterators: Sequence[HipFixedVADIterator], chunks, return_seconds: bool = False) -> List[List[dict]]:
+    """``[it(chunk) for it, chunk in zip(iterators, chunks)]`` with one device call for all of them: every iterator that
+    has at least one complete window buffered goes through ``group.probs`` together; one that has none returns ``[]``,
+    keeps its remainder and is left out of the call.  ``group`` needs ``probs(models, chunks)``."""
+    if len(iterators) != len(chunks):
+        raise ValueError("vad_step_many: one chunk per iterator")
+    windows = [it._take(x) for it, x in zip(iterators, chunks)]
+    ready = [i for i, w in enumerate(windows) if w is not None]
+    events: List[List[dict]] = [[] for _ in iterators]
+    if ready:
+        probs = group.probs([iterators[i].model for i in ready], [windows[i] for i in ready])
+        for i, p in zip(ready, probs):
+            events[i] = iterators[i]._consume(p, return_seconds)
+    return events
