@@ -496,8 +496,20 @@ int wlk_nllb_decode(wlk_nllb_session* s, const int64_t* tokens, int32_t n_rows, 
 int wlk_nllb_step(wlk_nllb_session* s, const int64_t* tokens, int32_t n_rows, int32_t k, float* logprobs, int32_t* ids);
 /* beam bookkeeping: row i of the self-attention cache becomes the old row source_rows[i] */
 int wlk_nllb_kv_reorder(wlk_nllb_session* s, const int32_t* source_rows, int32_t n_rows);
-/* log_softmax(logits) of the latest decode, the k (<= 8) best per row, descending: [rows][k] */
+/* log_softmax(logits) of the latest decode, the k (<= 16) best per row, descending: [rows][k].  k > 8 takes the wide
+ * kernel (vocabularies of at most 262144 tokens, else WLK_ERR_ARG; a row with fewer than k finite logits fills up with
+ * (-inf, -1)); its ranks 0..7 are bit for bit those of k = 8. */
 int wlk_nllb_topk(wlk_nllb_session* s, int32_t k, float* logprobs, int32_t* ids);
+/* Beam step without moving the cache: row i continues the hypothesis that row source_rows[i] held after the
+ * previous step, is fed tokens[i], and the k (1..16) best continuations of every row come back - the table update, the
+ * decoder step (self-attention through the ancestry table) and the top-k as ONE graph replay.  Synchronous.  Needs
+ * max_tgt <= 512.  The first such step after wlk_nllb_decode with first = 1 starts from rows that hold their own history;
+ * once one has run, wlk_nllb_decode with first = 0, wlk_nllb_step and wlk_nllb_kv_reorder return WLK_ERR_STATE until the
+ * next wlk_nllb_decode with first = 1 or wlk_nllb_encode (wlk_nllb_topk and wlk_nllb_export stay valid). */
+int wlk_nllb_step_beam(wlk_nllb_session* s, const int64_t* tokens /*[n_rows]*/, const int32_t* source_rows /*[n_rows]*/,
+                       int32_t n_rows, int32_t k /*1..16*/, float* logprobs, int32_t* ids);
+/* number of ancestry steps the session has run since it was created */
+int wlk_nllb_session_beam_stats(wlk_nllb_session* s, uint64_t* ancestry_steps);
 /* parity exports: "logits" [rows][vocab] of the latest decode, "enc" [src_len][d_model] */
 int wlk_nllb_export(wlk_nllb_session* s, const char* what, float* host, uint64_t capacity, uint64_t* n_written);
 int wlk_nllb_sync(wlk_nllb_session* s);
@@ -617,6 +629,12 @@ typedef struct wlk_diag_select_args {
     float* logits_out;              /* out [n_rows][n_vocab] the logits as the call left them in memory (adjusted) */
 } wlk_diag_select_args;
 int wlk_diag_select(const wlk_diag_select_args* args);
+/* log_softmax + top-k alone on host logits [n_rows][n_vocab] through one chosen form, on a stream of its own; synchronous.
+ *   form 0  launch_logsoftmax_topk (k in [1, 8], no adjustments)
+ *   form 1  launch_logsoftmax_topk_wide (k in [1, 16], n_vocab <= 262144)
+ * A form that refuses the shape returns WLK_ERR_ARG; the other form never runs in its place.  n_rows in [1, 64]. */
+int wlk_diag_topk(const float* logits, int32_t n_rows, int32_t n_vocab, int32_t k, int32_t form /*0 existing, 1 wide*/,
+                  float* logprobs, int32_t* ids);
 /* The decoder's attention stage (csrc/decoder.hip, the merged out projection of csrc/gemm_f32.hip, the prefill flash
  * kernel of csrc/attention.hip) on host data, through ONE chosen route.  The launchers are the ones a decode step uses,
  * unchanged.  Heads are 64 wide and d = 64 n_head.

@@ -447,6 +447,8 @@ void launch_decoder_self_attention_anc(const LaunchCtx& ctx, const float* qkv, c
                                        const unsigned char* anc, float* out, int n_rows, const int* offset, int d,
                                        int n_head, int ctx_len);
 void launch_anc_update(const LaunchCtx& ctx, unsigned char* anc, const int* ctl, const int* offset, int n_rows, int ctx_len);
+// the same update for 1..8 rows, its operands read from a step's host-coherent block [tokens n_rows | offset | src n_rows | fresh]
+void launch_anc_update_block(const LaunchCtx& ctx, unsigned char* anc, const int* block, int n_rows, int ctx_len);
 void launch_decoder_self_attention(const LaunchCtx& ctx, const float* qkv, const float* kc, const float* vc,
                                    float* out, int n_rows, int n_tok, const int* offset_dev, int d, int n_head,
                                    int ctx_len);
@@ -571,6 +573,14 @@ void launch_logsoftmax_topk(const LaunchCtx& ctx, float* logits, int n_vocab, in
                             float* top_vals, int* top_ids, void* scratch, const int* adj_row, const int* adj_ids,
                             const float* adj_deltas, int n_adj);
 size_t topk_scratch_bytes(int n_rows);
+// the wide form: k in [1, 16], rows of at most 262 144 logits (longer rows: std::invalid_argument), no adjustments;
+// ranks 0..7 are bit for bit those of launch_logsoftmax_topk; a row with fewer than k finite logits fills up with (-inf, -1)
+void launch_logsoftmax_topk_wide(const LaunchCtx& ctx, const float* logits, int n_vocab, int n_rows, int k, float* top_vals,
+                                 int* top_ids, void* scratch);
+size_t topk_wide_scratch_bytes(int n_rows);
+constexpr int kTopkWideMaxK = 16;
+constexpr int kTopkWideMaxVocab = 64 * 4096;      // 64 slices of 256 threads x 16 register entries
+inline bool topk_wide_applicable(int n_vocab, int k) { return n_vocab >= 1 && n_vocab <= kTopkWideMaxVocab && k >= 1 && k <= kTopkWideMaxK; }
 void launch_token_prob(const LaunchCtx& ctx, const float* logits, int n_vocab, int n_rows, int token, float* probs);
 // whisper's batch-decoder logit rules + the greedy pick of one sequence (select.hip: rules_pick_kernel); the fields mirror
 // wlk_pick_params of include/wlk_hip.h

@@ -390,6 +390,41 @@ void launch_anc_update(const LaunchCtx& ctx, unsigned char* anc, const int* ctl,
     WLK_HIP(hipGetLastError());
 }
 
+// The 8-row form (NLLB beam steps): the same in-place rule - thread t owns column t, reads it, then writes it,
+// results clamped to n_rows - 1 - with offset, src and fresh read straight from the step's host-coherent block
+// [tokens n_rows | offset | src n_rows | fresh].
+__global__ __launch_bounds__(512) void anc_update_block_kernel(unsigned char* __restrict__ anc, const int* __restrict__ block,
+                                                               int n_rows, int ctx_len) {
+    const int t = threadIdx.x;
+    if (t >= ctx_len) return;
+    const int offset = block[n_rows];
+    const int* src = block + n_rows + 1;
+    const bool fresh = block[2 * n_rows + 1] != 0;
+    int col[8];
+#pragma unroll
+    for (int b = 0; b < 8; ++b) col[b] = b < n_rows ? (fresh ? b : (int)anc[(long)b * ctx_len + t]) : 0;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        if (b >= n_rows) break;
+        const int sb = src[b];
+        int v = b;
+        if (t < offset) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (sb == k) v = col[k];     // (a select chain, not an indexed register array)
+        }
+        anc[(long)b * ctx_len + t] = (unsigned char)min(v, n_rows - 1);
+    }
+}
+
+void launch_anc_update_block(const LaunchCtx& ctx, unsigned char* anc, const int* block, int n_rows, int ctx_len) {
+    if (n_rows < 1 || n_rows > 8 || ctx_len > 512 || !anc || !block)
+        throw std::invalid_argument("ancestry update: 1..8 rows, context <= 512, a table and a block");
+    KernelScope ks(ctx, "dec_anc_update");
+    hipLaunchKernelGGL(anc_update_block_kernel, dim3(1), dim3(512), 0, ctx.stream, anc, block, n_rows, ctx_len);
+    WLK_HIP(hipGetLastError());
+}
+
 // ---------------------------------------------------------------------------------------------
 // Cross-attention, one 256-thread workgroup per (query row, head).
 //   pass 1: scores s_j = q . K_j for the T = 1500 encoder positions.  A 16-lane group reads one

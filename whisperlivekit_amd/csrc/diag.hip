@@ -607,6 +607,40 @@ int wlk_diag_select(const wlk_diag_select_args* q) {
     return rc;
 }
 
+/* log_softmax + top-k alone through one chosen form (see include/wlk_hip.h): the launchers a step uses, unchanged */
+int wlk_diag_topk(const float* logits, int32_t n_rows, int32_t n_vocab, int32_t k, int32_t form, float* logprobs, int32_t* ids) {
+    if (!logits || !logprobs || !ids || n_rows < 1 || n_rows > 64 || n_vocab < 1 || (form != 0 && form != 1)) {
+        g_diag_error = "wlk_diag_topk: null pointer, n_rows outside [1, 64], n_vocab < 1 or form not 0 / 1";
+        return WLK_ERR_ARG;
+    }
+    if (k < 1 || k > (form == 0 ? 8 : kTopkWideMaxK)) {
+        g_diag_error = "wlk_diag_topk: k must be in [1, 8] (form 0) or [1, 16] (form 1)";
+        return WLK_ERR_ARG;
+    }
+    if (form == 1 && !topk_wide_applicable(n_vocab, k)) {      // (checked here: run() reports what a launcher throws as WLK_ERR_HIP)
+        g_diag_error = "wlk_diag_topk: the wide form takes rows of at most 262144 logits";
+        return WLK_ERR_ARG;
+    }
+    return run([&]() {
+        struct Stream {
+            hipStream_t s = nullptr;
+            Stream() { WLK_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+            ~Stream() { (void)hipStreamDestroy(s); }
+        } st;
+        const size_t sc_bytes = form == 0 ? topk_scratch_bytes(n_rows) : topk_wide_scratch_bytes(n_rows);
+        DevBuf L((size_t)n_rows * n_vocab, logits), TV((size_t)n_rows * k), TI((size_t)n_rows * k), SC(sc_bytes / sizeof(float) + 1);
+        WLK_HIP(hipDeviceSynchronize());   // the uploads ran on the legacy stream; st does not wait for it
+        LaunchCtx ctx;
+        ctx.stream = st.s;
+        int* ti = reinterpret_cast<int*>(TI.p);
+        if (form == 0) launch_logsoftmax_topk(ctx, L.p, n_vocab, n_rows, k, TV.p, ti, SC.p, nullptr, nullptr, nullptr, 0);
+        else launch_logsoftmax_topk_wide(ctx, L.p, n_vocab, n_rows, k, TV.p, ti, SC.p);
+        WLK_HIP(hipStreamSynchronize(st.s));
+        WLK_HIP(hipMemcpy(logprobs, TV.p, (size_t)n_rows * k * sizeof(float), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(ids, ti, (size_t)n_rows * k * sizeof(int), hipMemcpyDeviceToHost));
+    });
+}
+
 /* The decoder's attention stage on host data through one chosen route (see include/wlk_hip.h): the launchers of a decode
  * step, unchanged.  Every shape is checked here or by its launcher before anything is launched for it. */
 int wlk_diag_dec_attention(const wlk_diag_dec_attention_args* q) {

@@ -122,7 +122,7 @@ struct wlk_nllb_session {
     int self_len = 0;
     bool have_logits = false;
     // graph-replayed single-token steps (wlk_nllb_step)
-    int* step_host = nullptr;          // pinned + mapped: [rows] tokens | offset
+    int* step_host = nullptr;          // pinned + mapped: [rows] tokens | offset ( | [rows] source rows | fresh: ancestry steps)
     int* step_host_dev = nullptr;      // the same block as the device sees it
     float* step_vals_host = nullptr;   // pinned + mapped: top-k results written by the top-k kernel itself
     int* step_ids_host = nullptr;
@@ -134,6 +134,14 @@ struct wlk_nllb_session {
     int step_exec_src[2] = {0, 0};     // the source length a captured step was recorded with: the cross-attention launch carries it
                                        // by value, so a sentence of another length needs a new recording (round 5: a session
                                        // that translated a 5-token and then a 7-token source replayed the 5-token graph)
+    // ancestry steps (wlk_nllb_step_beam): the step block continues [... | src rows | fresh]; no cache row moves
+    unsigned char* anc = nullptr;      // [rows][max_tgt]: physical cache row that holds position t of hypothesis b
+    void* topk_wide_scratch = nullptr;
+    bool anc_live = false;             // an ancestry step has run since the last decode(first=1) / encode
+    uint64_t ancestry_steps = 0;
+    hipGraphExec_t beam_exec[2] = {nullptr, nullptr};      // per kv_cur, re-recorded on another k / source length (as step_exec)
+    int beam_exec_k[2] = {0, 0};
+    int beam_exec_src[2] = {0, 0};
     template <typename T>
     T* alloc(size_t n) {
         void* p = nullptr;
@@ -147,6 +155,7 @@ struct wlk_nllb_session {
         if (stream) (void)hipStreamSynchronize(stream);
         for (void* p : owned) (void)hipFree(p);
         for (auto& e : step_exec) if (e) (void)hipGraphExecDestroy(e);
+        for (auto& e : beam_exec) if (e) (void)hipGraphExecDestroy(e);
         if (step_host) (void)hipHostFree(step_host);
         if (step_vals_host) (void)hipHostFree(step_vals_host);
         if (step_ids_host) (void)hipHostFree(step_ids_host);
@@ -185,13 +194,16 @@ static void nl_encode(wlk_nllb_session* s, int S) {
     }
 }
 
-static void nl_decode(wlk_nllb_session* s, int n_tok, bool graph_step = false) {
+// anc_step (n_tok == 1, graph replay): row b continues hypothesis src[b] of the previous step WITHOUT moving the cache - the
+// table update runs in front of the layers and the self-attention reads keys / values through the table
+static void nl_decode(wlk_nllb_session* s, int n_tok, bool graph_step = false, bool anc_step = false) {
     wlk_nllb* m = s->m;
     const wlk_nllb_dims& D = m->D;
     const LaunchCtx c = s->ctx();
     const int d = D.d_model, H = D.heads, f = D.ffn, rows = s->rows, R = rows * n_tok, ctx_len = D.max_tgt, S = s->src_len;
     const float q_scale = 0.125f;
     const bool fused = n_tok == 1 && gemv_applicable(R, d);
+    if (anc_step && (!fused || !graph_step || !s->anc)) throw std::logic_error("NLLB decode: the ancestry step needs the fused graph step");
     if (graph_step)
         hipLaunchKernelGGL(nllb_embed_step_kernel, dim3(R), dim3(256), 0, s->stream, s->step_host_dev, rows, m->emb, m->pos,
                            D.embed_scale, D.pad_id + 1, d, s->offset_dev, s->dx);
@@ -199,6 +211,7 @@ static void nl_decode(wlk_nllb_session* s, int n_tok, bool graph_step = false) {
         hipLaunchKernelGGL(nllb_embed_kernel, dim3(R), dim3(256), 0, s->stream, s->tokens_dev, m->emb, m->pos, D.embed_scale,
                            D.pad_id + 1, s->offset_dev, n_tok, d, s->dx);
     WLK_HIP(hipGetLastError());
+    if (anc_step) launch_anc_update_block(c, s->anc, s->step_host_dev, rows, ctx_len);
     const size_t cache_layer = (size_t)rows * ctx_len * d;
     const long ldkv = (long)D.dec_layers * 2 * d;
     for (int l = 0; l < D.dec_layers; ++l) {
@@ -217,7 +230,8 @@ static void nl_decode(wlk_nllb_session* s, int n_tok, bool graph_step = false) {
             nl_linear(c, s->dh, d, L.qkvw, L.qkvb, s->dqkv, 3 * d, R, 3 * d, d, kGemmScaleCols, nullptr, 0, "nllb_dec_qkv", q_scale, d);
             launch_kv_append(c, s->dqkv, kc, vc, rows, n_tok, s->offset_dev, d, ctx_len);
         }
-        launch_decoder_self_attention(c, s->dqkv, kc, vc, s->datt, rows, n_tok, s->offset_dev, d, H, ctx_len);
+        if (anc_step) launch_decoder_self_attention_anc(c, s->dqkv, kc, vc, s->anc, s->datt, rows, s->offset_dev, d, H, ctx_len);
+        else launch_decoder_self_attention(c, s->dqkv, kc, vc, s->datt, rows, n_tok, s->offset_dev, d, H, ctx_len);
         nl_linear(c, s->datt, d, L.outw, L.outb, s->dx, d, R, d, d, kGemmResidual, s->dx, d, "nllb_dec_out");
 
         if (fused) {
@@ -260,7 +274,9 @@ static void nl_decode(wlk_nllb_session* s, int n_tok, bool graph_step = false) {
         launch_layernorm(c, s->dx + (size_t)(n_tok - 1) * d, (long)n_tok * d, m->dec_lnw, m->dec_lnb, s->hsel, d, rows, d, "nllb_dec_ln");
         nl_linear(c, s->hsel, d, m->emb, nullptr, s->logits, D.vocab, rows, D.vocab, d, 0, nullptr, 0, "nllb_logits");
     }
-    if (graph_step)      // results straight into the host-coherent block: no copy node behind the graph either
+    if (graph_step && s->step_k > 8)     // (ancestry steps only: wlk_nllb_step stops at 8)
+        launch_logsoftmax_topk_wide(c, s->logits, D.vocab, rows, s->step_k, s->step_vals_dev, s->step_ids_dev, s->topk_wide_scratch);
+    else if (graph_step)      // results straight into the host-coherent block: no copy node behind the graph either
         launch_logsoftmax_topk(c, s->logits, D.vocab, rows, s->step_k, s->step_vals_dev, s->step_ids_dev, s->topk_scratch, nullptr,
                                nullptr, nullptr, 0);
 }
@@ -402,7 +418,12 @@ int wlk_nllb_session_create(wlk_nllb* m, int rows, wlk_nllb_session** out) {
         s->top_vals = s->alloc<float>((size_t)rows * 16);
         s->top_ids = s->alloc<int>((size_t)rows * 16);
         s->topk_scratch = s->alloc<char>(topk_scratch_bytes(rows));
-        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->step_host), (size_t)(rows + 1) * sizeof(int), hipHostMallocMapped));
+        s->topk_wide_scratch = s->alloc<char>(topk_wide_scratch_bytes(rows));
+        s->anc = s->alloc<unsigned char>((size_t)rows * Tt);
+        WLK_HIP(hipMemsetAsync(s->anc, 0, (size_t)rows * Tt, s->stream));
+        WLK_HIP(hipStreamSynchronize(s->stream));
+        // [tokens rows | offset] for wlk_nllb_step, continued by [src rows | fresh] for wlk_nllb_step_beam
+        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->step_host), (size_t)(2 * rows + 2) * sizeof(int), hipHostMallocMapped));
         WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->step_host_dev), s->step_host, 0));
         WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->step_vals_host), (size_t)rows * 16 * sizeof(float), hipHostMallocMapped));
         WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->step_vals_dev), s->step_vals_host, 0));
@@ -444,6 +465,7 @@ int wlk_nllb_encode(wlk_nllb_session* s, const int64_t* src_ids, int32_t n) {
         s->encoded = true;
         s->self_len = 0;
         s->have_logits = false;
+        s->anc_live = false;
         return WLK_OK;
     });
 }
@@ -453,6 +475,8 @@ int wlk_nllb_decode(wlk_nllb_session* s, const int64_t* tokens, int32_t n_rows, 
     if (!s->encoded) return nl_fail(WLK_ERR_STATE, "wlk_nllb_decode before wlk_nllb_encode");
     if (n_rows != s->rows) return nl_fail(WLK_ERR_ARG, "n_rows must equal the session's row count");
     if (n_tok < 1) return nl_fail(WLK_ERR_ARG, "n_tok must be >= 1");
+    if (!first && s->anc_live)
+        return nl_fail(WLK_ERR_STATE, "wlk_nllb_decode(first=0) after an ancestry step: the cache rows are no longer the hypotheses");
     return nl_guarded([&]() {
         if (first) s->self_len = 0;
         else if (s->self_len == 0) return nl_fail(WLK_ERR_STATE, "the first decode after an encode must set first=1");
@@ -468,6 +492,7 @@ int wlk_nllb_decode(wlk_nllb_session* s, const int64_t* tokens, int32_t n_rows, 
         nl_decode(s, n_tok);
         s->self_len += n_tok;
         s->have_logits = true;
+        if (first) s->anc_live = false;
         return WLK_OK;
     });
 }
@@ -475,6 +500,7 @@ int wlk_nllb_decode(wlk_nllb_session* s, const int64_t* tokens, int32_t n_rows, 
 int wlk_nllb_step(wlk_nllb_session* s, const int64_t* tokens, int32_t n_rows, int32_t k, float* logprobs, int32_t* ids) {
     if (!s || !tokens || !logprobs || !ids) return nl_fail(WLK_ERR_ARG, "NULL argument");
     if (!s->encoded || s->self_len == 0) return nl_fail(WLK_ERR_STATE, "wlk_nllb_step before the decoder prompt (wlk_nllb_decode first=1)");
+    if (s->anc_live) return nl_fail(WLK_ERR_STATE, "wlk_nllb_step after an ancestry step: the cache rows are no longer the hypotheses");
     if (n_rows != s->rows) return nl_fail(WLK_ERR_ARG, "n_rows must equal the session's row count");
     if (k < 1 || k > 8) return nl_fail(WLK_ERR_ARG, "k must be 1..8 (the top-k kernel's limit)");
     const wlk_nllb_dims& D = s->m->D;
@@ -507,9 +533,61 @@ int wlk_nllb_step(wlk_nllb_session* s, const int64_t* tokens, int32_t n_rows, in
     });
 }
 
+int wlk_nllb_step_beam(wlk_nllb_session* s, const int64_t* tokens, const int32_t* source_rows, int32_t n_rows, int32_t k,
+                       float* logprobs, int32_t* ids) {
+    if (!s || !tokens || !source_rows || !logprobs || !ids) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    if (!s->encoded || s->self_len == 0) return nl_fail(WLK_ERR_STATE, "wlk_nllb_step_beam before the decoder prompt (wlk_nllb_decode first=1)");
+    if (n_rows != s->rows) return nl_fail(WLK_ERR_ARG, "n_rows must equal the session's row count");
+    if (k < 1 || k > kTopkWideMaxK) return nl_fail(WLK_ERR_ARG, "k must be 1..16 (the wide top-k kernel's limit)");
+    const wlk_nllb_dims& D = s->m->D;
+    if (D.max_tgt > 512) return nl_fail(WLK_ERR_ARG, "wlk_nllb_step_beam: max_tgt must be <= 512 (the ancestry attention's limit)");
+    if (!gemv_applicable(n_rows, D.d_model)) return nl_fail(WLK_ERR_ARG, "wlk_nllb_step_beam: too many rows for the single-token path");
+    if (k > 8 && !topk_wide_applicable(D.vocab, k)) return nl_fail(WLK_ERR_ARG, "wlk_nllb_step_beam: k > 8 needs a vocabulary of at most 262144");
+    if (s->self_len + 1 > D.max_tgt) return nl_fail(WLK_ERR_CAPACITY, "target context exceeded");
+    for (int r = 0; r < n_rows; ++r) {
+        if (tokens[r] < 0 || tokens[r] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
+        if (tokens[r] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sequence is not supported");
+        if (source_rows[r] < 0 || source_rows[r] >= n_rows) return nl_fail(WLK_ERR_ARG, "source row out of range");
+    }
+    return nl_guarded([&]() {
+        WLK_HIP(hipSetDevice(s->m->device));
+        WLK_HIP(hipStreamSynchronize(s->stream));           // the previous step's readers of the host block are done
+        for (int r = 0; r < n_rows; ++r) {
+            s->step_host[r] = (int)tokens[r];
+            s->step_host[n_rows + 1 + r] = source_rows[r];
+        }
+        s->step_host[n_rows] = s->self_len;
+        s->step_host[2 * n_rows + 1] = s->anc_live ? 0 : 1;      // fresh: every physical row still holds its own history
+        hipGraphExec_t& exec = s->beam_exec[s->kv_cur];
+        if (!exec || s->beam_exec_k[s->kv_cur] != k || s->beam_exec_src[s->kv_cur] != s->src_len) {
+            if (exec) { WLK_HIP(hipGraphExecDestroy(exec)); exec = nullptr; }
+            s->step_k = k;
+            capture_step_graph(s->stream, exec, [&] { nl_decode(s, 1, /*graph_step=*/true, /*anc_step=*/true); });
+            s->beam_exec_k[s->kv_cur] = k;
+            s->beam_exec_src[s->kv_cur] = s->src_len;
+        }
+        WLK_HIP(hipGraphLaunch(exec, s->stream));
+        WLK_HIP(hipStreamSynchronize(s->stream));
+        std::memcpy(logprobs, s->step_vals_host, (size_t)n_rows * k * sizeof(float));
+        std::memcpy(ids, s->step_ids_host, (size_t)n_rows * k * sizeof(int));
+        s->self_len += 1;
+        s->have_logits = true;
+        s->anc_live = true;
+        s->ancestry_steps += 1;
+        return WLK_OK;
+    });
+}
+
+int wlk_nllb_session_beam_stats(wlk_nllb_session* s, uint64_t* ancestry_steps) {
+    if (!s || !ancestry_steps) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    *ancestry_steps = s->ancestry_steps;
+    return WLK_OK;
+}
+
 int wlk_nllb_kv_reorder(wlk_nllb_session* s, const int32_t* source_rows, int32_t n_rows) {
     if (!s || !source_rows) return nl_fail(WLK_ERR_ARG, "NULL argument");
     if (n_rows != s->rows) return nl_fail(WLK_ERR_ARG, "n_rows must equal the session's row count");
+    if (s->anc_live) return nl_fail(WLK_ERR_STATE, "wlk_nllb_kv_reorder after an ancestry step: the cache rows are no longer the hypotheses");
     bool identity = true;
     for (int i = 0; i < n_rows; ++i) {
         if (source_rows[i] < 0 || source_rows[i] >= n_rows) return nl_fail(WLK_ERR_ARG, "source row out of range");
@@ -534,11 +612,14 @@ int wlk_nllb_kv_reorder(wlk_nllb_session* s, const int32_t* source_rows, int32_t
 int wlk_nllb_topk(wlk_nllb_session* s, int32_t k, float* logprobs, int32_t* ids) {
     if (!s || !logprobs || !ids) return nl_fail(WLK_ERR_ARG, "NULL argument");
     if (!s->have_logits) return nl_fail(WLK_ERR_STATE, "wlk_nllb_topk before a decode");
-    if (k < 1 || k > 8) return nl_fail(WLK_ERR_ARG, "k must be 1..8 (the top-k kernel's limit)");
+    if (k < 1 || k > kTopkWideMaxK) return nl_fail(WLK_ERR_ARG, "k must be 1..16 (the wide top-k kernel's limit)");
     return nl_guarded([&]() {
         WLK_HIP(hipSetDevice(s->m->device));
-        launch_logsoftmax_topk(s->ctx(), s->logits, s->m->D.vocab, s->rows, k, s->top_vals, s->top_ids, s->topk_scratch, nullptr,
-                               nullptr, nullptr, 0);
+        if (k > 8)
+            launch_logsoftmax_topk_wide(s->ctx(), s->logits, s->m->D.vocab, s->rows, k, s->top_vals, s->top_ids, s->topk_wide_scratch);
+        else
+            launch_logsoftmax_topk(s->ctx(), s->logits, s->m->D.vocab, s->rows, k, s->top_vals, s->top_ids, s->topk_scratch, nullptr,
+                                   nullptr, nullptr, 0);
         WLK_HIP(hipMemcpyAsync(logprobs, s->top_vals, (size_t)s->rows * k * sizeof(float), hipMemcpyDeviceToHost, s->stream));
         WLK_HIP(hipMemcpyAsync(ids, s->top_ids, (size_t)s->rows * k * sizeof(int), hipMemcpyDeviceToHost, s->stream));
         WLK_HIP(hipStreamSynchronize(s->stream));

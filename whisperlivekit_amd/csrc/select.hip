@@ -302,6 +302,165 @@ void launch_logsoftmax_topk(const LaunchCtx& ctx, float* logits, int n_vocab, in
 
 size_t topk_scratch_bytes(int n_rows) { return sizeof(SelPartial) * kSelBlocks * (size_t)n_rows; }
 
+// ---------------------------------------------------------------------------------------------
+// The wide form: log_softmax + the k <= 16 best of rows of up to 262 144 logits - what a beam search over
+// NLLB's 256 206-token vocabulary asks for (2 n continuations per row, n <= 8).  Same partition as above (64 slices per
+// row, thread tid of a slice owns lo + tid + 256 j) and the same order of every max / exp-sum, so the (max, sum) of a slice,
+// the row's normaliser and therefore ranks 0..7 are bit for bit those of the forms above; no adjustment list.
+//   * the slice lives in registers, 16 entries per thread, all 16 loads issued before the first use: ONE read of the row
+//     where topk_stage1_stream (which every NLLB-wide row takes above) makes k + 2 passes.  A lane past `hi` loads a
+//     clamped in-row address and holds -inf.
+//   * the k best of the slice by (value descending, index ascending) in k exclusion rounds, rules_topk_body's scheme: every
+//     thread holds the best entry it has left, a round is one wave_argmax + a 4-entry fold through LDS, and only the thread
+//     that owned the winner rescans its 16 registers for what comes after it.  -inf entries are never candidates: a slice
+//     with fewer than k finite entries ends its list with (-inf, none).
+//   * stage 2, one wave per row, lane = slice: the 64 sorted lists sit in LDS as [position][lane] (a lane only ever reads
+//     its own column: no barrier, no bank conflict) and each lane holds the head of its list in registers; a round is one
+//     wave_argmax, and the lane that owned the winner fetches its next entry.  Rows with fewer than k finite entries
+//     fill up with (-inf, -1).
+// ---------------------------------------------------------------------------------------------
+constexpr int kWideTopK = kTopkWideMaxK;
+constexpr int kWideKeep = 16;
+static_assert(kTopkWideMaxVocab == kSelBlocks * 256 * kWideKeep, "the wide form's width limit is its register tile");
+constexpr int kWideNone = 0x7fffffff;
+struct WidePartial {
+    float mx, sum;
+    float v[kWideTopK];
+    int i[kWideTopK];
+};
+
+__global__ __launch_bounds__(256) void topk_wide_stage1_kernel(const float* __restrict__ logits, int n_vocab, int k,
+                                                               WidePartial* __restrict__ parts) {
+    __shared__ float red[16];
+    __shared__ float cand_v[4];
+    __shared__ int cand_i[4];
+    const int tid = threadIdx.x, slice = blockIdx.x, row = blockIdx.y;
+    const int per = (n_vocab + kSelBlocks - 1) / kSelBlocks;
+    const int lo = slice * per;
+    const int hi = min(n_vocab, lo + per);
+    const float* x = logits + (long)row * n_vocab;
+    // (an empty trailing slice has lo >= n_vocab: the fallback element is clamped into the row, as in topk_stage1_body)
+    const int lo_safe = lo < n_vocab ? lo : n_vocab - 1;
+    float xv[kWideKeep];
+#pragma unroll
+    for (int j = 0; j < kWideKeep; ++j) {
+        const int i = lo + tid + 256 * j;
+        xv[j] = x[i < hi ? i : lo_safe];
+    }
+#pragma unroll
+    for (int j = 0; j < kWideKeep; ++j) pin_loaded(xv[j]);
+    __builtin_amdgcn_sched_barrier(0);     // all 16 requests are out before the first wait
+#pragma unroll
+    for (int j = 0; j < kWideKeep; ++j)
+        if (lo + tid + 256 * j >= hi) xv[j] = -INFINITY;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < kWideKeep; ++j)
+        if (lo + tid + 256 * j < hi) mx = fmaxf(mx, xv[j]);
+    mx = block_max(mx, red);
+    float sum = 0.f;
+    if (mx > -INFINITY) {
+#pragma unroll
+        for (int j = 0; j < kWideKeep; ++j)
+            if (lo + tid + 256 * j < hi) sum += expf(xv[j] - mx);
+    }
+    sum = block_sum(sum, red);
+    WidePartial* out = parts + (long)row * kSelBlocks + slice;
+    if (tid == 0) { out->mx = mx; out->sum = sum; }
+    // best entry of this thread strictly after (wv, wi) in the order (value descending, index ascending)
+    auto best_after = [&](float wv, int wi, float& bv, int& bi) {
+        bv = -INFINITY;
+        bi = kWideNone;
+#pragma unroll
+        for (int j = 0; j < kWideKeep; ++j) {
+            const int i = lo + tid + 256 * j;
+            const float v = xv[j];
+            const bool after = v < wv || (v == wv && i > wi);
+            if (v > -INFINITY && after && (v > bv || (v == bv && i < bi))) { bv = v; bi = i; }
+        }
+    };
+    float mv;
+    int mi;
+    best_after(INFINITY, -1, mv, mi);
+    for (int round = 0; round < k; ++round) {
+        float bv = mv;
+        int bi = mi;
+        wave_argmax(bv, bi);
+        __syncthreads();                   // the previous round's fold has been read
+        if ((tid & 63) == 0) { cand_v[tid >> 6] = bv; cand_i[tid >> 6] = bi; }
+        __syncthreads();
+        bv = cand_v[0];
+        bi = cand_i[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (cand_v[w] > bv || (cand_v[w] == bv && cand_i[w] < bi)) { bv = cand_v[w]; bi = cand_i[w]; }
+        if (tid == 0) {
+            out->v[round] = bv;
+            out->i[round] = bi;
+        }
+        if (bi != kWideNone && mi == bi) best_after(bv, bi, mv, mi);
+    }
+}
+
+__global__ __launch_bounds__(64) void topk_wide_stage2_kernel(const WidePartial* __restrict__ parts, int k,
+                                                              float* __restrict__ top_vals, int* __restrict__ top_ids) {
+    __shared__ float list_v[kWideTopK * 64];
+    __shared__ int list_i[kWideTopK * 64];
+    const int lane = threadIdx.x, row = blockIdx.x;
+    const WidePartial* p = parts + (long)row * kSelBlocks + lane;
+    const float pmx = p->mx, psum = p->sum;
+#pragma unroll
+    for (int t = 0; t < kWideTopK; ++t) {
+        list_v[t * 64 + lane] = t < k ? p->v[t] : -INFINITY;
+        list_i[t * 64 + lane] = t < k ? p->i[t] : kWideNone;
+    }
+    const float mx = wave_max(pmx);
+    float sum = pmx > -INFINITY ? psum * expf(pmx - mx) : 0.f;
+    sum = wave_sum(sum);
+    const float lse = logf(sum);
+    int head = 0;                          // next unconsumed entry of this slice's sorted list
+    float cv = list_v[lane];
+    int ci = list_i[lane];
+    for (int round = 0; round < k; ++round) {
+        float wv = cv;
+        int wi = ci;
+        wave_argmax(wv, wi);
+        const bool some = wi != kWideNone;
+        if (some && wi == ci) {
+            ++head;
+            const int h = head < kWideTopK ? head : kWideTopK - 1;
+            cv = head < k ? list_v[h * 64 + lane] : -INFINITY;
+            ci = head < k ? list_i[h * 64 + lane] : kWideNone;
+        }
+        if (lane == 0) {
+            top_ids[row * k + round] = some ? wi : -1;
+            top_vals[row * k + round] = some ? (wv - mx) - lse : -INFINITY;
+        }
+    }
+}
+
+void launch_logsoftmax_topk_wide(const LaunchCtx& ctx, const float* logits, int n_vocab, int n_rows, int k, float* top_vals,
+                                 int* top_ids, void* scratch) {
+    if (k < 1 || k > kWideTopK) throw std::invalid_argument("wide top-k: k must be in [1, 16]");
+    if (n_rows < 1 || n_vocab < 1) throw std::invalid_argument("wide top-k: at least one row and one logit");
+    if (!topk_wide_applicable(n_vocab, k))
+        throw std::invalid_argument("wide top-k: rows of at most 262144 logits (a slice of 4096 held in registers)");
+    WidePartial* parts = static_cast<WidePartial*>(scratch);
+    {
+        KernelScope ks(ctx, "sel_topk_wide_stage1", 0.0, 4.0 * n_rows * (double)n_vocab);
+        hipLaunchKernelGGL(topk_wide_stage1_kernel, dim3(kSelBlocks, n_rows), dim3(256), 0, ctx.stream, logits, n_vocab, k,
+                           parts);
+        WLK_HIP(hipGetLastError());
+    }
+    {
+        KernelScope ks(ctx, "sel_topk_wide_stage2");
+        hipLaunchKernelGGL(topk_wide_stage2_kernel, dim3(n_rows), dim3(64), 0, ctx.stream, parts, k, top_vals, top_ids);
+        WLK_HIP(hipGetLastError());
+    }
+}
+
+size_t topk_wide_scratch_bytes(int n_rows) { return sizeof(WidePartial) * kSelBlocks * (size_t)n_rows; }
+
 // softmax(logits)[token] of one row by one 1024-thread workgroup.  The row is read ONCE (each thread keeps its strided
 // elements in registers between the max pass and the sum pass); the order of every max / sum is that of the plain
 // two-pass loops.

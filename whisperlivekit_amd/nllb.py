@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 from dataclasses import dataclass
 from typing import Callable, Dict, Iterable, List, Mapping, Optional, Sequence, Tuple, Union
 
@@ -239,7 +240,27 @@ class HipNllbSession:
         a = np.ascontiguousarray(source_rows, dtype=np.int32)
         _lib.check(self.lib.wlk_nllb_kv_reorder(self._h, a.ctypes.data_as(C.c_void_p), a.size))
 
+    def step_beam(self, tokens: Sequence[int], sources: Sequence[int], k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Beam step without moving the cache (wlk_nllb_step_beam): row i continues the hypothesis row ``sources[i]`` held
+        after the previous step and is fed ``tokens[i]``; the k (1..16) best continuations of every row, one graph replay.
+        After it ``step`` / ``decode(first=False)`` / ``kv_reorder`` are errors until the next ``decode(first=True)``."""
+        t = np.ascontiguousarray(tokens, dtype=np.int64).reshape(-1)
+        src = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        if src.size != t.size:
+            raise ValueError("step_beam: one source row per token")
+        lp = np.empty((self.rows, k), np.float32)
+        ids = np.empty((self.rows, k), np.int32)
+        _lib.check(self.lib.wlk_nllb_step_beam(self._h, t.ctypes.data_as(C.c_void_p), src.ctypes.data_as(C.c_void_p), t.size, k,
+                                               lp.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p)))
+        return lp, ids
+
+    def beam_stats(self) -> Dict[str, int]:
+        n = C.c_uint64()
+        _lib.check(self.lib.wlk_nllb_session_beam_stats(self._h, C.byref(n)))
+        return {"ancestry_steps": int(n.value)}
+
     def topk(self, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """The k (1..16) best log-probabilities and ids of every row of the latest decode; k > 8 takes the wide kernel."""
         lp = np.empty((self.rows, k), np.float32)
         ids = np.empty((self.rows, k), np.int32)
         _lib.check(self.lib.wlk_nllb_topk(self._h, k, lp.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p)))
@@ -473,7 +494,7 @@ def generate_batch(batch, sources: Sequence[Sequence[int]],
 
 def beam_search(session, src_ids: Sequence[int], forced_bos_token_id: Optional[int] = None, *, num_beams: int,
                 max_new_tokens: int = 199, length_penalty: float = 1.0, early_stopping=False,
-                forced_eos_token_id: Optional[int] = None) -> List[int]:
+                forced_eos_token_id: Optional[int] = None, device_steps: Optional[bool] = None) -> List[int]:
     """``model.generate(input_ids, forced_bos_token_id=..., num_beams=n, do_sample=False, max_new_tokens=...)`` of
     ``transformers`` 5.x for one sentence (``GenerationMixin._beam_search``, generation/utils.py): per step the 2 n best
     (beam, token) continuations by accumulated log-probability; those among the n best that end (``</s>`` or the length
@@ -481,7 +502,12 @@ def beam_search(session, src_ids: Sequence[int], forced_bos_token_id: Optional[i
     stop when no running beam can beat the worst finished one (``early_stopping=False``: judged at the current length;
     ``"never"``: at the maximum length when the penalty favours long outputs; ``True``: as soon as n have finished).
     Returns the best finished sequence including the start token.  The device supplies the 2 n best log-probabilities of
-    every beam row (``topk``) and reorders the caches (``kv_reorder``); the bookkeeping here is float32 like the original."""
+    every beam row (``topk``) and reorders the caches (``kv_reorder``); the bookkeeping here is float32 like the original.
+
+    ``device_steps`` (``None``: the environment's ``WLK_NLLB_BEAM_STEPS=1``; only for sessions that have ``step_beam``): the
+    prompt is ``decode`` + ``topk(2 n)`` and every later step ONE ``step_beam(tokens, sources of the previous re-ranking,
+    2 n)`` - the device's top-16 for any n in 2..8 and the ancestry table instead of ``kv_reorder``; no logits come back and
+    no cache row moves.  Everything behind the 2 n candidates is the same code either way."""
     cfg = session.model.cfg
     n, K = int(num_beams), 2 * int(num_beams)
     if n != session.rows:
@@ -500,9 +526,22 @@ def beam_search(session, src_ids: Sequence[int], forced_bos_token_id: Optional[i
     fin_seq, fin_sc = run_seq.copy(), np.full(n, NEG, f32)
     fin_done, fin_len = np.zeros(n, bool), np.full(n, prompt_len)
     unsatisfied = True
+    if device_steps is None:
+        device_steps = os.environ.get("WLK_NLLB_BEAM_STEPS") == "1"
+    device_steps = bool(device_steps) and hasattr(session, "step_beam")
+    sources = np.arange(n, dtype=np.int32)           # device steps: the rows the running beams continue
     session.encode(src_ids)
     while True:
-        if K <= 8:                                    # the device's top-k takes up to 8 per row
+        if device_steps:
+            if cur_len == prompt_len:
+                session.decode(run_seq[:, :cur_len], first=True)
+                top_lp, top_id = session.topk(K)
+            else:
+                top_lp, top_id = session.step_beam(run_seq[:, cur_len - 1], sources, K)
+            # a row with fewer than K finite logits fills up with (-inf, -1): the padding id keeps such a candidate inside its
+            # own row of `flat` below; it ranks last, and were it ever chosen the next step refuses the token
+            top_id = np.where(top_id < 0, pad, top_id)
+        elif K <= 8:                                  # the device's top-k takes up to 8 per row
             if cur_len == prompt_len:
                 session.decode(run_seq[:, :cur_len], first=True)
                 top_lp, top_id = session.topk(K)
@@ -549,7 +588,10 @@ def beam_search(session, src_ids: Sequence[int], forced_bos_token_id: Optional[i
         fin_len = np.concatenate([fin_len, np.full(K, cur_len + 1)])[best]
         fin_sc = all_sc[best]
         run_seq, run_sc = cand_seq[keep], going[keep]
-        session.kv_reorder(cand_b[keep])
+        if device_steps:
+            sources = cand_b[keep].astype(np.int32)    # handed to the next step_beam; nothing is uploaded after the last step
+        else:
+            session.kv_reorder(cand_b[keep])
         cur_len += 1
         horizon = (max_length - prompt_len) if (early_stopping == "never" and length_penalty > 0.0) else (cur_len - prompt_len)
         best_running = run_sc[0] / f32(horizon ** length_penalty)

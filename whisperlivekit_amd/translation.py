@@ -182,7 +182,9 @@ class NllbStacker:
 class HipNllbTranslationModel:
     """The server-wide handle ``nllw.load_model`` returns in the reference (``TranscriptionEngine.translation_model``,
     core.py:320-329): one network per GPU shared by every session, plus the tokenizer and the decoding options.  Device
-    sessions are 1-row and cheap; each ``HipOnlineTranslation`` owns one, so sessions never share decoder caches."""
+    sessions are 1-row and cheap; each ``HipOnlineTranslation`` owns one, so sessions never share decoder caches.
+    ``num_beams`` > 1 gives every session that many rows and ``nllb.beam_search``; ``WLK_NLLB_BEAM_STEPS=1`` in the
+    environment moves its steps onto the device (``step_beam``; off by default)."""
 
     def __init__(self, model: nllb.HipNllbModel, tokenizer: Any, num_beams: int = 1, max_new_tokens: int = 199,
                  max_source_tokens: int = 200, stack: Optional[int] = None):
