@@ -703,6 +703,55 @@ typedef struct wlk_diag_dec_attention_args {
     float* out;                     /* in / out [out_floats] */
 } wlk_diag_dec_attention_args;
 int wlk_diag_dec_attention(const wlk_diag_dec_attention_args* args);
+/* ONE kernel of csrc/sortformer.hip on host data through its production launcher, unchanged (the Sortformer blocks and the
+ * NLLB encoder share the attention).  Every buffer lives on the device in exactly the floats the caller passes and the
+ * in / out ones (q, k, v, pos, in, in2, out) are copied back whole, so a caller's guard pattern around the addressed part
+ * travels both ways.  Weights have the sizes their kind states.
+ *   ATTENTION    out[i] = softmax_j(scale ((q_i + u) . k_j + (q_i + v) . pos[pos_row0 - i + j])) V per head; rows of q / k / v /
+ *                out are ldq / ldk / ldv / ldo floats apart, head h at columns [h dh, (h + 1) dh).  pos (or NULL) has pos_rows
+ *                rows of ldp floats, bias_u / bias_v (or NULL) [n_head][dh].  n_seg > 0: rows [seg_start[s], + seg_T[s]) are
+ *                independent sequences and T is at least the longest.  form 0 = launch_sf_attention's own rule, 1 = one wave
+ *                per query (no segments), 2 = matrix cores.
+ *   CONV0        in [sum len][F] -> out [sum sub(len)][sub(F)][C], w [C][9], b [C]; sub(n) = (n - 1) / 2 + 1
+ *   DWCONV2D     in [sum len][F][C] -> out [sum sub(len)][sub(F)][C], w [9][C], b [C]
+ *   GLU_DWCONV   in [sum len][2 d] -> out [sum len][d], w [taps][d], b / bn_mean / bn_invstd / bn_w / bn_b [d]
+ *   HEAD         in [T][d] -> out [T][n_spk], w = w1t [d][d] (transposed), b [d], w2 [n_spk][d], b2 [n_spk]
+ *   ASSEMBLE     out[r] = scale * (context row in[r] | chunk row of in2): session s has len[s] rows of which the last len2[s]
+ *                are its chunk rows, taken from in2 [sum len2][d] in session order
+ * n_sess sessions (1 .. 8) of len[s] frames / rows lie one after the other; the segment tables are built from the lengths as a
+ * stacked step builds them.  What the launcher or a buffer cannot hold returns WLK_ERR_ARG with a message in
+ * wlk_diag_last_error() before anything is uploaded or launched.  All pointers are host memory; the call is synchronous. */
+enum {
+    WLK_SFK_ATTENTION = 0, WLK_SFK_CONV0 = 1, WLK_SFK_DWCONV2D = 2, WLK_SFK_GLU_DWCONV = 3, WLK_SFK_HEAD = 4, WLK_SFK_ASSEMBLE = 5
+};
+typedef struct wlk_diag_sf_kernel_args {
+    int32_t kind;
+    int32_t T, n_head, dh, form, pos_row0, pos_rows, n_seg;     /* ATTENTION (T: HEAD too) */
+    int32_t seg_start[8], seg_T[8];
+    int32_t n_sess, len[8], len2[8];
+    int32_t F, C, d, taps, n_spk;
+    float scale;                    /* ATTENTION, ASSEMBLE */
+    int64_t ldq, ldk, ldv, ldo, ldp;
+    int64_t q_floats, k_floats, v_floats, pos_floats, in_floats, in2_floats, out_floats;
+    float* q;                       /* in / out */
+    float* k;                       /* in / out */
+    float* v;                       /* in / out */
+    float* pos;                     /* in / out, or NULL */
+    const float* bias_u;
+    const float* bias_v;
+    float* in;                      /* in / out */
+    float* in2;                     /* in / out (ASSEMBLE) */
+    const float* w;
+    const float* b;
+    const float* w2;
+    const float* b2;
+    const float* bn_mean;
+    const float* bn_invstd;
+    const float* bn_w;
+    const float* bn_b;
+    float* out;                     /* in / out [out_floats] */
+} wlk_diag_sf_kernel_args;
+int wlk_diag_sf_kernel(const wlk_diag_sf_kernel_args* args);
 /* the VALU wave butterflies of csrc/wave_ops.h (DPP / v_permlane{16,32}_swap) against the __shfl_xor loops they replace,
  * on one wave of 64 floats: ten rows of 64 results each (sum, max, 16-lane sum, xor 1 .. 32 exchanges, arg-max index) */
 int wlk_diag_wave_ops(const float* in64, float* out640, float* ref640);

@@ -95,6 +95,18 @@ class DiagDecAttentionArgs(C.Structure):
             "bq", "gamma", "beta", "wo", "bo", "resid", "head_rank", "ring_row", "beam_of_row", "ring", "scores", "out")]
 
 
+class DiagSfKernelArgs(C.Structure):
+    """wlk_diag_sf_kernel_args (include/wlk_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "T", "n_head", "dh", "form", "pos_row0", "pos_rows", "n_seg")] + [
+        ("seg_start", C.c_int32 * 8), ("seg_T", C.c_int32 * 8), ("n_sess", C.c_int32), ("len", C.c_int32 * 8),
+        ("len2", C.c_int32 * 8)] + [(n, C.c_int32) for n in ("F", "C", "d", "taps", "n_spk")] + [("scale", C.c_float)] + [
+        (n, C.c_int64) for n in ("ldq", "ldk", "ldv", "ldo", "ldp", "q_floats", "k_floats", "v_floats", "pos_floats",
+                                 "in_floats", "in2_floats", "out_floats")] + [
+        (n, C.c_void_p) for n in ("q", "k", "v", "pos", "bias_u", "bias_v", "in", "in2", "w", "b", "w2", "b2", "bn_mean",
+                                  "bn_invstd", "bn_w", "bn_b", "out")]
+
+
+SFK_ATTENTION, SFK_CONV0, SFK_DWCONV2D, SFK_GLU_DWCONV, SFK_HEAD, SFK_ASSEMBLE = range(6)
 DA_S0, DA_S1, DA_S2 = 0, 1, 2
 DA_C0, DA_C1, DA_C2, DA_C3, DA_C4, DA_C5 = 10, 11, 12, 13, 14, 15
 DA_A0, DA_G0, DA_K0, DA_K1 = 20, 21, 22, 23
@@ -285,6 +297,7 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_select": (cint, [C.POINTER(DiagSelectArgs)]),
         "wlk_diag_dec_attention": (cint, [C.POINTER(DiagDecAttentionArgs)]),
         "wlk_diag_topk": (cint, [p, i32, i32, i32, i32, p, p]),
+        "wlk_diag_sf_kernel": (cint, [C.POINTER(DiagSfKernelArgs)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -332,7 +345,7 @@ EXPORTED_SYMBOLS = (
     "wlk_diag_encoder_attention", "wlk_diag_encoder_attention_time", "wlk_diag_wave_ops", "wlk_diag_env_refresh",
     "wlk_diag_linear_x3", "wlk_diag_linear_x3_time", "wlk_diag_layernorm_x3",
     "wlk_diag_encoder_attention_x3", "wlk_diag_encoder_attention_x3_time", "wlk_diag_qkv_x3_attention",
-    "wlk_diag_select", "wlk_diag_dec_attention", "wlk_diag_topk",
+    "wlk_diag_select", "wlk_diag_dec_attention", "wlk_diag_topk", "wlk_diag_sf_kernel",
 )
 
 

@@ -528,7 +528,9 @@ struct SfAttnArgs {
     int seg_start[kSfMaxSegments] = {0}, seg_T[kSfMaxSegments] = {0};
 };
 constexpr int kSfMaxFrames = 512;      // attention rows the score buffer in LDS is sized for
-void launch_sf_attention(const LaunchCtx& ctx, const SfAttnArgs& a);
+// form: 0 = the launcher's rule (matrix cores unless WLK_SF_ATTN=valu and no segments), 1 = one wave per query (no segments),
+// 2 = matrix cores - the diagnostics' switch; production passes nothing
+void launch_sf_attention(const LaunchCtx& ctx, const SfAttnArgs& a, int form = 0);
 // Conformer convolution module core: GLU over [T][2d] -> depthwise conv1d (k taps, same padding) -> BatchNorm (eval)
 // -> Swish -> [T][d]; w tap-major [k][d]
 void launch_sf_glu_dwconv(const LaunchCtx& ctx, const float* in, const float* w, const float* b, const float* bn_mean,

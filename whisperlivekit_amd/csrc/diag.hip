@@ -906,4 +906,180 @@ int wlk_diag_dec_attention(const wlk_diag_dec_attention_args* q) {
     }
 }
 
+/* One kernel of csrc/sortformer.hip on host data through its production launcher (see include/wlk_hip.h).  Every argument is
+ * checked here, before anything is uploaded: what reaches a launcher is inside its buffers. */
+int wlk_diag_sf_kernel(const wlk_diag_sf_kernel_args* q) {
+    struct Refuse : std::invalid_argument {
+        using std::invalid_argument::invalid_argument;
+    };
+    struct Buf {        // a device copy of exactly `n` host floats, copied back whole on request
+        float* p = nullptr;
+        float* host = nullptr;
+        size_t n = 0;
+        Buf() = default;
+        Buf(const float* h, size_t floats) { set(h, floats); }
+        Buf(const Buf&) = delete;
+        void set(const float* h, size_t floats) {
+            host = const_cast<float*>(h);
+            n = floats;
+            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 4) * sizeof(float)));
+            if (host && n) WLK_HIP(hipMemcpy(p, host, n * sizeof(float), hipMemcpyHostToDevice));
+        }
+        void back() const { if (host && n) WLK_HIP(hipMemcpy(host, p, n * sizeof(float), hipMemcpyDeviceToHost)); }
+        ~Buf() { (void)hipFree(p); }
+    };
+    try {
+        auto need = [](bool ok, const char* what) {
+            if (!ok) throw Refuse(std::string("wlk_diag_sf_kernel: ") + what);
+        };
+        need(q != nullptr, "null arguments");
+        const int kind = q->kind;
+        need(kind >= WLK_SFK_ATTENTION && kind <= WLK_SFK_ASSEMBLE, "unknown kind");
+        need(q->out && q->out_floats > 0, "null out");
+        LaunchCtx ctx;
+
+        if (kind == WLK_SFK_ATTENTION) {
+            const int T = q->T, H = q->n_head, dh = q->dh, n_seg = q->n_seg;
+            need(q->form >= 0 && q->form <= 2, "form is 0 (the launcher's rule), 1 (one wave per query) or 2 (matrix cores)");
+            need(T >= 1 && T <= kSfMaxFrames, "T in [1, 512]");
+            need(dh >= 4 && dh <= 64 && dh % 4 == 0, "dh a multiple of 4 in [4, 64]");
+            need(H >= 1 && H <= 64, "n_head in [1, 64]");
+            need(n_seg >= 0 && n_seg <= kSfMaxSegments, "n_seg in [0, 8]");
+            need(!(q->form == 1 && n_seg > 0), "the one-wave-per-query form does not take segments");
+            need(q->q && q->k && q->v, "null q / k / v");
+            const long W = (long)H * dh;
+            long last = T;          // one past the last row any segment addresses
+            if (n_seg > 0) {
+                last = 0;
+                for (int s = 0; s < n_seg; ++s) {
+                    need(q->seg_T[s] >= 1 && q->seg_T[s] <= T, "seg_T in [1, T]");
+                    need(q->seg_start[s] >= 0 && q->seg_start[s] <= (1 << 20), "seg_start in [0, 2^20]");
+                    last = std::max(last, (long)q->seg_start[s] + q->seg_T[s]);
+                }
+            }
+            auto inside = [&](int64_t ld, int64_t floats, const char* what) {
+                need(ld >= W && ld % 4 == 0 && ld <= (1 << 20), what);
+                need(floats > 0 && (last - 1) * ld + W <= floats, "a segment lies past a q / k / v / out buffer");
+            };
+            inside(q->ldq, q->q_floats, "ldq a multiple of 4, at least n_head dh");
+            inside(q->ldk, q->k_floats, "ldk a multiple of 4, at least n_head dh");
+            inside(q->ldv, q->v_floats, "ldv a multiple of 4, at least n_head dh");
+            inside(q->ldo, q->out_floats, "ldo a multiple of 4, at least n_head dh");
+            if (q->pos) {
+                need(q->pos_row0 >= T - 1, "pos_row0 below T - 1");
+                need(q->pos_row0 <= (1 << 20) && q->pos_rows >= 2 * q->pos_row0 + 1, "a pos table has at least 2 pos_row0 + 1 rows");
+                need(q->ldp >= W && q->ldp % 4 == 0 && q->ldp <= (1 << 20), "ldp a multiple of 4, at least n_head dh");
+                need((int64_t)(q->pos_rows - 1) * q->ldp + W <= q->pos_floats, "the pos table lies past its buffer");
+            }
+            Buf Q(q->q, q->q_floats), K(q->k, q->k_floats), V(q->v, q->v_floats), O(q->out, q->out_floats), P, U, Vb;
+            if (q->pos) P.set(q->pos, q->pos_floats);
+            if (q->bias_u) U.set(q->bias_u, W);
+            if (q->bias_v) Vb.set(q->bias_v, W);
+            SfAttnArgs a;
+            a.q = Q.p; a.k = K.p; a.v = V.p; a.ldq = q->ldq; a.ldk = q->ldk; a.ldv = q->ldv; a.out = O.p; a.ldo = q->ldo;
+            a.T = T; a.n_head = H; a.dh = dh; a.scale = q->scale;
+            a.pos = q->pos ? P.p : nullptr; a.ldp = q->ldp; a.pos_row0 = q->pos_row0;
+            a.bias_u = q->bias_u ? U.p : nullptr; a.bias_v = q->bias_v ? Vb.p : nullptr;
+            a.n_seg = n_seg;
+            for (int s = 0; s < n_seg; ++s) { a.seg_start[s] = q->seg_start[s]; a.seg_T[s] = q->seg_T[s]; }
+            WLK_HIP(hipDeviceSynchronize());
+            launch_sf_attention(ctx, a, q->form);
+            WLK_HIP(hipDeviceSynchronize());
+            Q.back(); K.back(); V.back(); O.back(); P.back();
+            return WLK_OK;
+        }
+
+        need(q->in && q->in_floats > 0 && (kind == WLK_SFK_ASSEMBLE || (q->w && q->b)), "null in / w / b");
+        if (kind == WLK_SFK_HEAD) {
+            const int T = q->T, d = q->d, ns = q->n_spk;
+            need(T >= 1 && T <= 4096 && d >= 1 && d <= 4096 && ns >= 1 && ns <= 64, "T in [1, 4096], d in [1, 4096], n_spk in [1, 64]");
+            need(q->w2 && q->b2, "null w2 / b2");
+            need((int64_t)T * d <= q->in_floats && (int64_t)T * ns <= q->out_floats, "the rows lie past in / out");
+            Buf X(q->in, q->in_floats), W1(q->w, (size_t)d * d), B1(q->b, d), W2(q->w2, (size_t)ns * d), B2(q->b2, ns), O(q->out, q->out_floats);
+            WLK_HIP(hipDeviceSynchronize());
+            launch_sf_head(ctx, X.p, W1.p, B1.p, W2.p, B2.p, O.p, T, d, ns);
+            WLK_HIP(hipDeviceSynchronize());
+            X.back(); O.back();
+            return WLK_OK;
+        }
+
+        // the stacked kinds: sessions one after the other, tables from the lengths as sf_run_batch builds them
+        const int n = q->n_sess;
+        need(n >= 1 && n <= kSfMaxSegments, "n_sess in [1, 8]");
+        for (int s = 0; s < n; ++s) need(q->len[s] >= (kind == WLK_SFK_ASSEMBLE ? 0 : 1) && q->len[s] <= (1 << 16), "a session length outside [1, 65536]");
+        if (kind == WLK_SFK_CONV0 || kind == WLK_SFK_DWCONV2D) {
+            const int F = q->F, C = q->C;
+            need(F >= 1 && F <= 4096 && C >= 1 && C <= 4096, "F and C in [1, 4096]");
+            SfConvSegs sg;
+            int f0 = 0, t0 = 0;
+            for (int s = 0; s < n; ++s) {
+                sg.in_start[sg.n] = f0; sg.in_len[sg.n] = q->len[s]; sg.out_start[sg.n] = t0;
+                ++sg.n;
+                f0 += q->len[s];
+                t0 += sf_sub_len(q->len[s]);
+            }
+            sg.in_total = f0; sg.out_total = t0;
+            const int64_t per_in = kind == WLK_SFK_CONV0 ? F : (int64_t)F * C;
+            need(f0 * per_in <= q->in_floats && (int64_t)t0 * sf_sub_len(F) * C <= q->out_floats, "the sessions lie past in / out");
+            Buf X(q->in, q->in_floats), Wt(q->w, (size_t)9 * C), B(q->b, C), O(q->out, q->out_floats);
+            WLK_HIP(hipDeviceSynchronize());
+            if (kind == WLK_SFK_CONV0) launch_sf_conv0(ctx, X.p, Wt.p, B.p, O.p, sg, F, C);
+            else launch_sf_dwconv2d(ctx, X.p, Wt.p, B.p, O.p, sg, F, C);
+            WLK_HIP(hipDeviceSynchronize());
+            X.back(); O.back();
+            return WLK_OK;
+        }
+        const int d = q->d;
+        need(d >= 1 && d <= 4096, "d in [1, 4096]");
+        SfSegments rows, chunks;
+        rows.n = chunks.n = n;
+        int r0 = 0, c0 = 0;
+        for (int s = 0; s < n; ++s) {
+            rows.start[s] = r0; rows.len[s] = q->len[s];
+            r0 += q->len[s];
+        }
+        need(r0 >= 1, "no rows");
+        if (kind == WLK_SFK_GLU_DWCONV) {
+            const int taps = q->taps;
+            need(taps >= 1 && taps % 2 == 1 && taps <= 255, "taps odd in [1, 255]");
+            need(q->bn_mean && q->bn_invstd && q->bn_w && q->bn_b, "null batch norm");
+            need((int64_t)r0 * 2 * d <= q->in_floats && (int64_t)r0 * d <= q->out_floats, "the sessions lie past in / out");
+            Buf X(q->in, q->in_floats), Wt(q->w, (size_t)taps * d), B(q->b, d), M(q->bn_mean, d), I(q->bn_invstd, d), G(q->bn_w, d),
+                Bb(q->bn_b, d), O(q->out, q->out_floats);
+            WLK_HIP(hipDeviceSynchronize());
+            launch_sf_glu_dwconv(ctx, X.p, Wt.p, B.p, M.p, I.p, G.p, Bb.p, O.p, rows, d, taps);
+            WLK_HIP(hipDeviceSynchronize());
+            X.back(); O.back();
+            return WLK_OK;
+        }
+        // ASSEMBLE (w / b are not read; in = the context rows at their stacked positions, in2 = the chunk rows)
+        need(d % 4 == 0, "d a multiple of 4");
+        for (int s = 0; s < n; ++s) {
+            need(q->len2[s] >= 0 && q->len2[s] <= q->len[s], "chunk rows in [0, len]");
+            chunks.start[s] = c0; chunks.len[s] = q->len2[s];
+            c0 += q->len2[s];
+        }
+        need(c0 == 0 || (q->in2 && (int64_t)c0 * d <= q->in2_floats), "the chunk rows lie past in2");
+        need((int64_t)r0 * d <= q->in_floats && (int64_t)r0 * d <= q->out_floats, "the sessions lie past in / out");
+        Buf X(q->in, q->in_floats), X2, O(q->out, q->out_floats);
+        if (q->in2 && q->in2_floats > 0) X2.set(q->in2, q->in2_floats);
+        else X2.set(nullptr, 4);
+        WLK_HIP(hipDeviceSynchronize());
+        launch_sf_assemble(ctx, X.p, X2.p, O.p, rows, chunks, d, q->scale);
+        WLK_HIP(hipDeviceSynchronize());
+        X.back(); X2.back(); O.back();
+        return WLK_OK;
+    } catch (const Refuse& e) {
+        g_diag_error = e.what();
+        return WLK_ERR_ARG;
+    } catch (const std::invalid_argument& e) {      // a launcher's own refusal: nothing was launched
+        (void)hipDeviceSynchronize();
+        g_diag_error = e.what();
+        return WLK_ERR_ARG;
+    } catch (const std::exception& e) {
+        g_diag_error = e.what();
+        return WLK_ERR_HIP;
+    }
+}
+
 }  // extern "C"

@@ -456,8 +456,12 @@ static size_t sf_attention_mfma_lds(int T, int dhp, bool pos) {
     return (2 * 16 * (size_t)(dhp + 4) + 16 + 16 * (size_t)(n_kt * 16 + 4) + g_floats) * sizeof(float);
 }
 
-void launch_sf_attention(const LaunchCtx& ctx, const SfAttnArgs& a) {
+void launch_sf_attention(const LaunchCtx& ctx, const SfAttnArgs& a, int form) {
     if (a.T <= 0) return;
+    if (form < 0 || form > 2) throw std::invalid_argument("sortformer attention: unknown form");
+    if (form == 1 && a.n_seg > 0) throw std::invalid_argument("sortformer attention: the one-wave-per-query kernel does not take segments");
+    // row pos_row0 - i + j of the table must exist for every i, j < T (the matrix-core kernel would clamp, the other read before it)
+    if (a.pos && a.pos_row0 < a.T - 1) throw std::invalid_argument("sortformer attention: pos_row0 below T - 1");
     if (a.T > kSfMaxFrames) throw std::invalid_argument("sortformer attention: sequence longer than the LDS score buffer");
     if (a.dh % 4 != 0 || a.dh > 64 || a.dh < 4) throw std::invalid_argument("sortformer attention: unsupported head width");
     if (a.n_seg < 0 || a.n_seg > kSfMaxSegments) throw std::invalid_argument("sortformer attention: too many segments");
@@ -476,7 +480,7 @@ void launch_sf_attention(const LaunchCtx& ctx, const SfAttnArgs& a) {
     KernelScope ks(ctx, a.pos ? "sf_relpos_attention" : "sf_attention", per, 16.0 * tsum * a.n_head * a.dh);
     // WLK_SF_ATTN=valu: the round-1 kernel (one wave per query row) - A/B switch; it does not take stacked sessions
     static const bool valu = [] { const char* e = getenv("WLK_SF_ATTN"); return e && e[0] == 'v'; }();
-    if (valu && a.n_seg == 0) {
+    if (form == 1 || (form == 0 && valu && a.n_seg == 0)) {
         const dim3 grid((a.T + 3) / 4, a.n_head);
         if (a.dh <= 32) hipLaunchKernelGGL((sf_attention_kernel<32>), grid, dim3(256), 0, ctx.stream, a);
         else hipLaunchKernelGGL((sf_attention_kernel<64>), grid, dim3(256), 0, ctx.stream, a);
