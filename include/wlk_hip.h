@@ -510,7 +510,38 @@ int wlk_nllb_step_beam(wlk_nllb_session* s, const int64_t* tokens /*[n_rows]*/, 
                        int32_t n_rows, int32_t k /*1..16*/, float* logprobs, int32_t* ids);
 /* number of ancestry steps the session has run since it was created */
 int wlk_nllb_session_beam_stats(wlk_nllb_session* s, uint64_t* ancestry_steps);
-/* parity exports: "logits" [rows][vocab] of the latest decode, "enc" [src_len][d_model] */
+/* ---- AlignAtt streaming translation (opt-in): which source position a target token was produced from, read
+ * off the decoder's own cross-attention.  A session that never sets heads runs exactly the steps above.
+ * layer_head_pairs = n x (decoder layer, head), n in 1..64; n = 0 switches the read-out off.  WLK_ERR_ARG for a layer or
+ * head out of range, a duplicate pair or n > 64. */
+int wlk_nllb_session_set_align(wlk_nllb_session* s, const int32_t* layer_head_pairs, int32_t n);
+/* wlk_nllb_step + the alignment read-out as ONE graph replay (its own recording, keyed like wlk_nllb_step's on k and the
+ * source length; lo / hi / limit travel in a host-coherent block, so one recording serves every window).  Every selected
+ * head's softmax row over the source (the cross-attention kernel's exp(s - max) / sum) is kept; per row
+ *   p[j]       = (sum of the heads' rows, in the order they were set) * (1 / n)
+ *   align_pos  = the position of the largest p[j], lo <= j < hi, the lowest j on an exact tie; -1 for an empty window
+ *   align_prob = p[align_pos] (0 for an empty window)
+ *   tail_mass  = sum of p[j], j >= limit
+ * Same state rules as wlk_nllb_step; WLK_ERR_STATE before heads are set or after an ancestry step; WLK_ERR_ARG unless
+ * 0 <= lo, hi <= src_len and 0 <= limit <= src_len.  Synchronous. */
+int wlk_nllb_step_align(wlk_nllb_session* s, const int64_t* tokens, int32_t n_rows, int32_t k /*1..8*/, int32_t lo, int32_t hi,
+                        int32_t limit, float* logprobs, int32_t* ids, int32_t* align_pos /*[rows]*/, float* align_prob /*[rows]*/,
+                        float* tail_mass /*[rows]*/);
+/* The AlignAtt decoding loop for a 1-row session, after wlk_nllb_encode of [source language, content..., </s>] (S ids):
+ * prompt = [</s>, target language, committed target ids...] (n_prompt >= 2, else WLK_ERR_ARG); prompt[:-1] is prefilled
+ * (wlk_nllb_decode, first = 1: no alignment rows), prompt[-1] and every later token go through the align step with
+ * lo = 1, hi = S - 1, limit = max(n_accessible - threshold, lo).  Each step yields a candidate y (arg-max) and its
+ * position a.  Not final: the loop ends WITHOUT emitting y when a < 0 or a >= limit (ATTENTION) or y == eos_id (EOS).
+ * Final: only y == eos_id ends it (EOS, not emitted).  Both end after max_new tokens (LENGTH) and when the target context
+ * is full (CONTEXT).  out_ids / out_align [max_new]; *n_out tokens were emitted. */
+enum { WLK_ALIGN_STOP_ATTENTION = 0, WLK_ALIGN_STOP_EOS = 1, WLK_ALIGN_STOP_LENGTH = 2, WLK_ALIGN_STOP_CONTEXT = 3 };
+int wlk_nllb_generate_alignatt(wlk_nllb_session* s, const int64_t* prompt, int32_t n_prompt, int32_t n_accessible,
+                               int32_t threshold, int32_t final, int64_t eos_id, int32_t max_new, int64_t* out_ids,
+                               int32_t* out_align, int32_t* n_out, int32_t* stop_reason);
+/* align steps run and align-step graphs recorded since the session was created */
+int wlk_nllb_session_align_stats(wlk_nllb_session* s, uint64_t* align_steps, uint64_t* graph_captures);
+/* parity exports: "logits" [rows][vocab] of the latest decode, "enc" [src_len][d_model], "align" [rows][src_len] = p of
+ * the latest align step */
 int wlk_nllb_export(wlk_nllb_session* s, const char* what, float* host, uint64_t capacity, uint64_t* n_written);
 int wlk_nllb_sync(wlk_nllb_session* s);
 
@@ -635,6 +666,12 @@ int wlk_diag_select(const wlk_diag_select_args* args);
  * A form that refuses the shape returns WLK_ERR_ARG; the other form never runs in its place.  n_rows in [1, 64]. */
 int wlk_diag_topk(const float* logits, int32_t n_rows, int32_t n_vocab, int32_t k, int32_t form /*0 existing, 1 wide*/,
                   float* logprobs, int32_t* ids);
+/* The NLLB alignment read-out kernel alone (csrc/nllb.hip, through its production launcher) on host data
+ * probs [n_align][rows][S]: p_out [rows][S], pos / prob / mass [rows] as wlk_nllb_step_align defines them.  n_align in
+ * [1, 64], rows in [1, 8], S in [1, 512], 0 <= lo, hi <= S, 0 <= limit <= S; anything else returns WLK_ERR_ARG before any
+ * upload.  Synchronous, on a stream of its own. */
+int wlk_diag_nllb_align(const float* probs, int32_t n_align, int32_t rows, int32_t S, int32_t lo, int32_t hi, int32_t limit,
+                        float* p_out, int32_t* pos, float* prob, float* mass);
 /* The decoder's attention stage (csrc/decoder.hip, the merged out projection of csrc/gemm_f32.hip, the prefill flash
  * kernel of csrc/attention.hip) on host data, through ONE chosen route.  The launchers are the ones a decode step uses,
  * unchanged.  Heads are 64 wide and d = 64 n_head.

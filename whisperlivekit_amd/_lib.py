@@ -119,6 +119,7 @@ class LoopResult(C.Structure):
                 ("decode_calls", C.c_int32)]
 
 
+ALIGN_STOP_REASONS = ("attention", "eos", "length", "context")      # WLK_ALIGN_STOP_* (include/wlk_hip.h)
 STOP_NONE, STOP_CONTEXT_FULL, STOP_BUDGET, STOP_NO_SPEECH, STOP_COMPLETED, STOP_REWIND, STOP_FRAME = range(7)
 
 
@@ -248,6 +249,10 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_nllb_step_beam": (cint, [p, p, p, i32, i32, p, p]),
         "wlk_nllb_session_beam_stats": (cint, [p, C.POINTER(u64)]),
         "wlk_nllb_topk": (cint, [p, i32, p, p]),
+        "wlk_nllb_session_set_align": (cint, [p, p, i32]),
+        "wlk_nllb_step_align": (cint, [p, p, i32, i32, i32, i32, i32, p, p, p, p, p]),
+        "wlk_nllb_generate_alignatt": (cint, [p, p, i32, i32, i32, i32, C.c_int64, i32, p, p, C.POINTER(i32), C.POINTER(i32)]),
+        "wlk_nllb_session_align_stats": (cint, [p, C.POINTER(u64), C.POINTER(u64)]),
         "wlk_nllb_export": (cint, [p, C.c_char_p, p, u64, C.POINTER(u64)]),
         "wlk_nllb_sync": (cint, [p]),
         "wlk_nllb_batch_create": (cint, [p, cint, C.POINTER(p)]),
@@ -297,6 +302,7 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_select": (cint, [C.POINTER(DiagSelectArgs)]),
         "wlk_diag_dec_attention": (cint, [C.POINTER(DiagDecAttentionArgs)]),
         "wlk_diag_topk": (cint, [p, i32, i32, i32, i32, p, p]),
+        "wlk_diag_nllb_align": (cint, [p, i32, i32, i32, i32, i32, i32, p, p, p, p]),
         "wlk_diag_sf_kernel": (cint, [C.POINTER(DiagSfKernelArgs)]),
     }
     for name, (res, args) in sig.items():
@@ -339,13 +345,14 @@ EXPORTED_SYMBOLS = (
     "wlk_nllb_finalize", "wlk_nllb_destroy", "wlk_nllb_session_create", "wlk_nllb_session_destroy", "wlk_nllb_encode",
     "wlk_nllb_decode", "wlk_nllb_step", "wlk_nllb_kv_reorder", "wlk_nllb_topk", "wlk_nllb_export", "wlk_nllb_sync",
     "wlk_nllb_step_beam", "wlk_nllb_session_beam_stats",
+    "wlk_nllb_session_set_align", "wlk_nllb_step_align", "wlk_nllb_generate_alignatt", "wlk_nllb_session_align_stats",
     "wlk_nllb_batch_create", "wlk_nllb_batch_destroy", "wlk_nllb_batch_encode", "wlk_nllb_batch_step", "wlk_nllb_batch_release",
     "wlk_nllb_batch_export", "wlk_nllb_batch_cross_attention", "wlk_nllb_batch_sync",
     "wlk_diag_last_error", "wlk_diag_linear", "wlk_diag_linear_time", "wlk_diag_linear_ln", "wlk_diag_layernorm",
     "wlk_diag_encoder_attention", "wlk_diag_encoder_attention_time", "wlk_diag_wave_ops", "wlk_diag_env_refresh",
     "wlk_diag_linear_x3", "wlk_diag_linear_x3_time", "wlk_diag_layernorm_x3",
     "wlk_diag_encoder_attention_x3", "wlk_diag_encoder_attention_x3_time", "wlk_diag_qkv_x3_attention",
-    "wlk_diag_select", "wlk_diag_dec_attention", "wlk_diag_topk", "wlk_diag_sf_kernel",
+    "wlk_diag_select", "wlk_diag_dec_attention", "wlk_diag_topk", "wlk_diag_sf_kernel", "wlk_diag_nllb_align",
 )
 
 

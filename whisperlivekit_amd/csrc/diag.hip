@@ -11,6 +11,7 @@
 #include "../../include/wlk_hip.h"
 #include "common.h"
 #include "internal.h"
+#include "nllb_internal.h"
 #include "wave_ops.h"
 
 using namespace wlk;
@@ -638,6 +639,39 @@ int wlk_diag_topk(const float* logits, int32_t n_rows, int32_t n_vocab, int32_t 
         WLK_HIP(hipStreamSynchronize(st.s));
         WLK_HIP(hipMemcpy(logprobs, TV.p, (size_t)n_rows * k * sizeof(float), hipMemcpyDeviceToHost));
         WLK_HIP(hipMemcpy(ids, ti, (size_t)n_rows * k * sizeof(int), hipMemcpyDeviceToHost));
+    });
+}
+
+/* the NLLB alignment read-out alone (see include/wlk_hip.h): the launcher an align step uses, unchanged */
+int wlk_diag_nllb_align(const float* probs, int32_t n_align, int32_t rows, int32_t S, int32_t lo, int32_t hi, int32_t limit,
+                        float* p_out, int32_t* pos, float* prob, float* mass) {
+    if (!probs || !p_out || !pos || !prob || !mass || n_align < 1 || n_align > kNlMaxAlign || rows < 1 || rows > 8 || S < 1 ||
+        S > kSfMaxFrames) {
+        g_diag_error = "wlk_diag_nllb_align: null pointer, n_align outside [1, 64], rows outside [1, 8] or S outside [1, 512]";
+        return WLK_ERR_ARG;
+    }
+    if (lo < 0 || hi > S || limit < 0 || limit > S) {
+        g_diag_error = "wlk_diag_nllb_align: needs 0 <= lo, hi <= S and 0 <= limit <= S";
+        return WLK_ERR_ARG;
+    }
+    return run([&]() {
+        struct Stream {
+            hipStream_t s = nullptr;
+            Stream() { WLK_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+            ~Stream() { (void)hipStreamDestroy(s); }
+        } st;
+        const float ctl_host[3] = {__builtin_bit_cast(float, lo), __builtin_bit_cast(float, hi), __builtin_bit_cast(float, limit)};
+        DevBuf P((size_t)n_align * rows * S, probs), CTL(3, ctl_host), PO((size_t)rows * S), POS(rows), PR(rows), MS(rows);
+        WLK_HIP(hipDeviceSynchronize());   // the uploads ran on the legacy stream; st does not wait for it
+        LaunchCtx ctx;
+        ctx.stream = st.s;
+        launch_nllb_align_readout(ctx, P.p, n_align, rows, S, reinterpret_cast<const int*>(CTL.p), PO.p,
+                                  reinterpret_cast<int*>(POS.p), PR.p, MS.p);
+        WLK_HIP(hipStreamSynchronize(st.s));
+        WLK_HIP(hipMemcpy(p_out, PO.p, (size_t)rows * S * sizeof(float), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(pos, POS.p, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(prob, PR.p, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(mass, MS.p, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost));
     });
 }
 

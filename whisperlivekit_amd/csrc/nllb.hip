@@ -14,6 +14,11 @@
 // residual / column-scale epilogues, weight-streaming GEMV for the single-token steps, LayerNorm, the LDS-score
 // attention for the short non-causal encoder, the KV-cache self-attention and the key-parallel cross-attention of the
 // Whisper decoder, log-softmax + top-k): one small kernel is new (token + position embedding).  fp32 throughout.
+//
+// AlignAtt streaming translation (opt-in per session): the single-token step can keep the softmax rows of chosen
+// cross-attention heads (the ring fields of CrossAttnArgs, as the Whisper decoder does) and read off, in one more kernel
+// (nllb_align_readout_kernel), which source position the step leans on; wlk_nllb_generate_alignatt is the decoding loop.
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -24,6 +29,7 @@
 #include "../../include/wlk_hip.h"
 #include "common.h"
 #include "nllb_internal.h"
+#include "wave_ops.h"
 
 namespace wlk {
 
@@ -98,6 +104,64 @@ __global__ __launch_bounds__(256) void nllb_embed_step_kernel(const int* __restr
     for (int c = threadIdx.x; c < d; c += 256) x[(long)r * d + c] = e[c] * scale + p[c];
 }
 
+// AlignAtt read-out of one single-token step.  probs [n_align][rows][S] are the selected heads' softmax rows as
+// decoder_cross_attention_kernel left them (rank-major).  One workgroup per row, S <= 512 = two positions per thread:
+//   p[j]   = (probs[0][row][j] + probs[1][row][j] + ... in rank order) * (1 / n_align)
+//   a      = the position of the largest p[j], j in [lo, hi), the lowest j on an exact tie; -1 when the window is empty
+//   prob   = p[a] (0 when a = -1)
+//   mass   = sum of p[j], j >= limit: per thread (j = tid) + (j = tid + 256), wave butterfly, then (w0 + w1) + (w2 + w3)
+// lo / hi / limit are read from ctl[0..2] (a host-coherent block in a replayed step: the recording serves every window) and
+// clamped to the row.  pos / prob / mass may be host-coherent too: one plain store each.
+__global__ __launch_bounds__(256) void nllb_align_readout_kernel(const float* __restrict__ probs, int n_align, int rows, int S,
+                                                                 float inv_n, const int* __restrict__ ctl,
+                                                                 float* __restrict__ p_out, int* __restrict__ pos,
+                                                                 float* __restrict__ prob, float* __restrict__ mass) {
+    __shared__ float red_v[4], red_m[4];
+    __shared__ int red_i[4];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lo = max(ctl[0], 0), hi = min(ctl[1], S), limit = max(ctl[2], 0);
+    const long head_stride = (long)rows * S;
+    const float* base = probs + (long)row * S;
+    float bv = -INFINITY, tail = 0.f;
+    int bi = INT_MAX;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int j = tid + half * 256;
+        if (j < S) {
+            float acc = 0.f;
+            for (int a = 0; a < n_align; ++a) acc += base[a * head_stride + j];
+            const float p = acc * inv_n;
+            p_out[(long)row * S + j] = p;
+            if (j >= limit) tail += p;
+            if (j >= lo && j < hi && p > bv) { bv = p; bi = j; }      // j ascends: an equal value keeps the lower position
+        }
+    }
+    wave_argmax(bv, bi);
+    tail = wave_sum(tail);
+    if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; red_m[wave] = tail; }
+    __syncthreads();
+    if (tid == 0) {
+        float v = red_v[0];
+        int i = red_i[0];
+        for (int w = 1; w < 4; ++w)
+            if (red_v[w] > v || (red_v[w] == v && red_i[w] < i)) { v = red_v[w]; i = red_i[w]; }
+        const bool found = i != INT_MAX;
+        pos[row] = found ? i : -1;
+        prob[row] = found ? v : 0.f;
+        mass[row] = (red_m[0] + red_m[1]) + (red_m[2] + red_m[3]);
+    }
+}
+
+void launch_nllb_align_readout(const LaunchCtx& ctx, const float* probs, int n_align, int rows, int S, const int* ctl,
+                               float* p_out, int* pos, float* prob, float* mass) {
+    if (n_align < 1 || n_align > kNlMaxAlign || rows < 1 || S < 1 || S > kSfMaxFrames)
+        throw std::invalid_argument("NLLB alignment read-out: 1..64 heads, rows >= 1, 1..512 source positions");
+    KernelScope ks(ctx, "nllb_align_readout");
+    hipLaunchKernelGGL(nllb_align_readout_kernel, dim3(rows), dim3(256), 0, ctx.stream, probs, n_align, rows, S,
+                       1.0f / (float)n_align, ctl, p_out, pos, prob, mass);
+    WLK_HIP(hipGetLastError());
+}
+
 }  // namespace wlk
 
 using namespace wlk;
@@ -142,6 +206,19 @@ struct wlk_nllb_session {
     hipGraphExec_t beam_exec[2] = {nullptr, nullptr};      // per kv_cur, re-recorded on another k / source length (as step_exec)
     int beam_exec_k[2] = {0, 0};
     int beam_exec_src[2] = {0, 0};
+    // AlignAtt steps (wlk_nllb_step_align): selected heads' softmax rows [n_align][rows][src_len] -> read-out
+    int n_align = 0;
+    int* head_rank_dev = nullptr;      // [dec_layers][heads]: rank of the (layer, head) pair or -1
+    int* align_rows_dev = nullptr;     // [rows] zeros (ring row) | [rows] 0, 1, ... (beam of row)
+    float* align_probs = nullptr;      // [kNlMaxAlign][rows][max_src]
+    float* align_p = nullptr;          // [rows][max_src]: head mean of the latest align step
+    int* align_host = nullptr;         // pinned + mapped: lo | hi | limit | [rows] position | [rows] probability | [rows] tail mass
+    int* align_host_dev = nullptr;
+    bool have_align = false;           // align_p holds a step of the current source
+    uint64_t align_steps = 0, align_captures = 0;
+    hipGraphExec_t align_exec[2] = {nullptr, nullptr};     // per kv_cur, re-recorded on another k / source length / head set
+    int align_exec_k[2] = {0, 0};
+    int align_exec_src[2] = {0, 0};
     template <typename T>
     T* alloc(size_t n) {
         void* p = nullptr;
@@ -156,9 +233,11 @@ struct wlk_nllb_session {
         for (void* p : owned) (void)hipFree(p);
         for (auto& e : step_exec) if (e) (void)hipGraphExecDestroy(e);
         for (auto& e : beam_exec) if (e) (void)hipGraphExecDestroy(e);
+        for (auto& e : align_exec) if (e) (void)hipGraphExecDestroy(e);
         if (step_host) (void)hipHostFree(step_host);
         if (step_vals_host) (void)hipHostFree(step_vals_host);
         if (step_ids_host) (void)hipHostFree(step_ids_host);
+        if (align_host) (void)hipHostFree(align_host);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -196,7 +275,9 @@ static void nl_encode(wlk_nllb_session* s, int S) {
 
 // anc_step (n_tok == 1, graph replay): row b continues hypothesis src[b] of the previous step WITHOUT moving the cache - the
 // table update runs in front of the layers and the self-attention reads keys / values through the table
-static void nl_decode(wlk_nllb_session* s, int n_tok, bool graph_step = false, bool anc_step = false) {
+// align_step (n_tok == 1, graph replay): the selected heads leave their softmax rows in align_probs and the read-out follows
+// the top-k
+static void nl_decode(wlk_nllb_session* s, int n_tok, bool graph_step = false, bool anc_step = false, bool align_step = false) {
     wlk_nllb* m = s->m;
     const wlk_nllb_dims& D = m->D;
     const LaunchCtx c = s->ctx();
@@ -204,6 +285,8 @@ static void nl_decode(wlk_nllb_session* s, int n_tok, bool graph_step = false, b
     const float q_scale = 0.125f;
     const bool fused = n_tok == 1 && gemv_applicable(R, d);
     if (anc_step && (!fused || !graph_step || !s->anc)) throw std::logic_error("NLLB decode: the ancestry step needs the fused graph step");
+    if (align_step && (n_tok != 1 || !graph_step || anc_step || s->n_align < 1))
+        throw std::logic_error("NLLB decode: the alignment step is a single-token graph step with heads set");
     if (graph_step)
         hipLaunchKernelGGL(nllb_embed_step_kernel, dim3(R), dim3(256), 0, s->stream, s->step_host_dev, rows, m->emb, m->pos,
                            D.embed_scale, D.pad_id + 1, d, s->offset_dev, s->dx);
@@ -252,6 +335,11 @@ static void nl_decode(wlk_nllb_session* s, int n_tok, bool graph_step = false, b
         ca.rows = R; ca.d = d; ca.n_head = H; ca.T = S;
         ca.head_rank = nullptr; ca.ring = nullptr; ca.ring_row = nullptr; ca.beam_of_row = nullptr;
         ca.ring_rows = 0; ca.n_beam = 1; ca.qk_debug = nullptr;
+        if (align_step) {     // window [n_align][rows][1][S]: row r is "beam" r, ring row 0
+            ca.head_rank = s->head_rank_dev + (size_t)l * H;
+            ca.ring = s->align_probs; ca.ring_row = s->align_rows_dev; ca.beam_of_row = s->align_rows_dev + rows;
+            ca.ring_rows = 1; ca.n_beam = rows;
+        }
         launch_decoder_cross_attention(c, ca);
         nl_linear(c, s->datt, d, L.xoutw, L.xoutb, s->dx, d, R, d, d, kGemmResidual, s->dx, d, "nllb_dec_xout");
         if (fused) {
@@ -279,6 +367,11 @@ static void nl_decode(wlk_nllb_session* s, int n_tok, bool graph_step = false, b
     else if (graph_step)      // results straight into the host-coherent block: no copy node behind the graph either
         launch_logsoftmax_topk(c, s->logits, D.vocab, rows, s->step_k, s->step_vals_dev, s->step_ids_dev, s->topk_scratch, nullptr,
                                nullptr, nullptr, 0);
+    if (align_step) {
+        float* res = reinterpret_cast<float*>(s->align_host_dev + 3);
+        launch_nllb_align_readout(c, s->align_probs, s->n_align, rows, S, s->align_host_dev, s->align_p, s->align_host_dev + 3,
+                                  res + rows, res + 2 * rows);
+    }
 }
 
 }  // namespace wlk
@@ -466,6 +559,7 @@ int wlk_nllb_encode(wlk_nllb_session* s, const int64_t* src_ids, int32_t n) {
         s->self_len = 0;
         s->have_logits = false;
         s->anc_live = false;
+        s->have_align = false;
         return WLK_OK;
     });
 }
@@ -584,6 +678,137 @@ int wlk_nllb_session_beam_stats(wlk_nllb_session* s, uint64_t* ancestry_steps) {
     return WLK_OK;
 }
 
+int wlk_nllb_session_set_align(wlk_nllb_session* s, const int32_t* layer_head_pairs, int32_t n) {
+    if (!s || (n > 0 && !layer_head_pairs)) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    if (n < 0 || n > kNlMaxAlign) return nl_fail(WLK_ERR_ARG, "wlk_nllb_session_set_align: 0..64 (layer, head) pairs");
+    const wlk_nllb_dims& D = s->m->D;
+    std::vector<int> rank((size_t)D.dec_layers * D.heads, -1);
+    for (int i = 0; i < n; ++i) {
+        const int l = layer_head_pairs[2 * i], h = layer_head_pairs[2 * i + 1];
+        if (l < 0 || l >= D.dec_layers || h < 0 || h >= D.heads) return nl_fail(WLK_ERR_ARG, "alignment head: layer or head out of range");
+        if (rank[(size_t)l * D.heads + h] >= 0) return nl_fail(WLK_ERR_ARG, "alignment head: duplicate (layer, head) pair");
+        rank[(size_t)l * D.heads + h] = i;
+    }
+    return nl_guarded([&]() {
+        WLK_HIP(hipSetDevice(s->m->device));
+        WLK_HIP(hipStreamSynchronize(s->stream));
+        for (auto& e : s->align_exec)        // a recording carries the head count by value
+            if (e) { WLK_HIP(hipGraphExecDestroy(e)); e = nullptr; }
+        s->have_align = false;
+        s->n_align = 0;
+        if (n == 0) return WLK_OK;
+        const int rows = s->rows;
+        if (!s->align_host) {
+            s->head_rank_dev = s->alloc<int>(rank.size());
+            s->align_rows_dev = s->alloc<int>(2 * (size_t)rows);
+            s->align_probs = s->alloc<float>((size_t)kNlMaxAlign * rows * D.max_src);
+            s->align_p = s->alloc<float>((size_t)rows * D.max_src);
+            WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->align_host), (size_t)(3 + 3 * rows) * sizeof(int), hipHostMallocMapped));
+            WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->align_host_dev), s->align_host, 0));
+            std::vector<int> rr(2 * (size_t)rows, 0);
+            for (int r = 0; r < rows; ++r) rr[rows + r] = r;
+            copy_sync(s->align_rows_dev, rr.data(), rr.size() * sizeof(int), hipMemcpyHostToDevice);
+        }
+        copy_sync(s->head_rank_dev, rank.data(), rank.size() * sizeof(int), hipMemcpyHostToDevice);
+        s->n_align = n;
+        return WLK_OK;
+    });
+}
+
+// the checks of wlk_nllb_step_align and one replay of the align graph; results stay in the host-coherent blocks
+static int nl_step_align(wlk_nllb_session* s, const int64_t* tokens, int n_rows, int k, int lo, int hi, int limit) {
+    if (!s->encoded || s->self_len == 0) return nl_fail(WLK_ERR_STATE, "wlk_nllb_step_align before the decoder prompt (wlk_nllb_decode first=1)");
+    if (s->n_align < 1) return nl_fail(WLK_ERR_STATE, "wlk_nllb_step_align before wlk_nllb_session_set_align");
+    if (s->anc_live) return nl_fail(WLK_ERR_STATE, "wlk_nllb_step_align after an ancestry step: the cache rows are no longer the hypotheses");
+    if (n_rows != s->rows) return nl_fail(WLK_ERR_ARG, "n_rows must equal the session's row count");
+    if (k < 1 || k > 8) return nl_fail(WLK_ERR_ARG, "k must be 1..8 (the top-k kernel's limit)");
+    if (lo < 0 || hi > s->src_len || limit < 0 || limit > s->src_len)
+        return nl_fail(WLK_ERR_ARG, "wlk_nllb_step_align: needs 0 <= lo, hi <= src_len and 0 <= limit <= src_len");
+    const wlk_nllb_dims& D = s->m->D;
+    if (s->self_len + 1 > D.max_tgt) return nl_fail(WLK_ERR_CAPACITY, "target context exceeded");
+    if (!gemv_applicable(n_rows, D.d_model)) return nl_fail(WLK_ERR_ARG, "wlk_nllb_step_align: too many rows for the single-token path");
+    for (int r = 0; r < n_rows; ++r) {
+        if (tokens[r] < 0 || tokens[r] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
+        if (tokens[r] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sequence is not supported");
+    }
+    return nl_guarded([&]() {
+        WLK_HIP(hipSetDevice(s->m->device));
+        WLK_HIP(hipStreamSynchronize(s->stream));           // the previous step's readers of the host blocks are done
+        for (int r = 0; r < n_rows; ++r) s->step_host[r] = (int)tokens[r];
+        s->step_host[n_rows] = s->self_len;
+        s->align_host[0] = lo; s->align_host[1] = hi; s->align_host[2] = limit;
+        hipGraphExec_t& exec = s->align_exec[s->kv_cur];
+        if (!exec || s->align_exec_k[s->kv_cur] != k || s->align_exec_src[s->kv_cur] != s->src_len) {
+            if (exec) { WLK_HIP(hipGraphExecDestroy(exec)); exec = nullptr; }
+            s->step_k = k;
+            capture_step_graph(s->stream, exec, [&] { nl_decode(s, 1, /*graph_step=*/true, /*anc_step=*/false, /*align_step=*/true); });
+            s->align_exec_k[s->kv_cur] = k;
+            s->align_exec_src[s->kv_cur] = s->src_len;
+            s->align_captures += 1;
+        }
+        WLK_HIP(hipGraphLaunch(exec, s->stream));
+        WLK_HIP(hipStreamSynchronize(s->stream));
+        s->self_len += 1;
+        s->have_logits = true;
+        s->have_align = true;
+        s->align_steps += 1;
+        return WLK_OK;
+    });
+}
+
+int wlk_nllb_step_align(wlk_nllb_session* s, const int64_t* tokens, int32_t n_rows, int32_t k, int32_t lo, int32_t hi, int32_t limit,
+                        float* logprobs, int32_t* ids, int32_t* align_pos, float* align_prob, float* tail_mass) {
+    if (!s || !tokens || !logprobs || !ids || !align_pos || !align_prob || !tail_mass) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    if (int rc = nl_step_align(s, tokens, n_rows, k, lo, hi, limit)) return rc;
+    std::memcpy(logprobs, s->step_vals_host, (size_t)n_rows * k * sizeof(float));
+    std::memcpy(ids, s->step_ids_host, (size_t)n_rows * k * sizeof(int));
+    std::memcpy(align_pos, s->align_host + 3, (size_t)n_rows * sizeof(int));
+    std::memcpy(align_prob, s->align_host + 3 + n_rows, (size_t)n_rows * sizeof(float));
+    std::memcpy(tail_mass, s->align_host + 3 + 2 * n_rows, (size_t)n_rows * sizeof(float));
+    return WLK_OK;
+}
+
+/* The AlignAtt rule (restated in whisperlivekit_amd.nllb.generate_alignatt for device_loop=False). */
+int wlk_nllb_generate_alignatt(wlk_nllb_session* s, const int64_t* prompt, int32_t n_prompt, int32_t n_accessible, int32_t threshold,
+                               int32_t final, int64_t eos_id, int32_t max_new, int64_t* out_ids, int32_t* out_align, int32_t* n_out,
+                               int32_t* stop_reason) {
+    if (!s || !prompt || !n_out || !stop_reason || (max_new > 0 && (!out_ids || !out_align))) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    if (s->rows != 1) return nl_fail(WLK_ERR_ARG, "wlk_nllb_generate_alignatt: needs a 1-row session");
+    if (n_prompt < 2) return nl_fail(WLK_ERR_ARG, "wlk_nllb_generate_alignatt: the prompt needs at least two tokens (</s>, target language)");
+    if (max_new < 0 || threshold < 0) return nl_fail(WLK_ERR_ARG, "wlk_nllb_generate_alignatt: max_new and threshold must be >= 0");
+    if (!s->encoded) return nl_fail(WLK_ERR_STATE, "wlk_nllb_generate_alignatt before wlk_nllb_encode");
+    if (s->n_align < 1) return nl_fail(WLK_ERR_STATE, "wlk_nllb_generate_alignatt before wlk_nllb_session_set_align");
+    const int S = s->src_len;
+    if (n_accessible < 0 || n_accessible > S) return nl_fail(WLK_ERR_ARG, "wlk_nllb_generate_alignatt: n_accessible must be 0..src_len");
+    const int lo = 1, hi = S - 1;                    // the content between the language code and </s>
+    const int limit = std::min(std::max(n_accessible - threshold, lo), S);
+    *n_out = 0;
+    if (int rc = wlk_nllb_decode(s, prompt, 1, n_prompt - 1, 1)) return rc;
+    int64_t last = prompt[n_prompt - 1];
+    int n = 0;
+    for (;;) {
+        if (n >= max_new) { *stop_reason = WLK_ALIGN_STOP_LENGTH; break; }
+        if (s->self_len + 1 > s->m->D.max_tgt) { *stop_reason = WLK_ALIGN_STOP_CONTEXT; break; }
+        if (int rc = nl_step_align(s, &last, 1, 1, lo, hi, limit)) return rc;
+        const int64_t y = s->step_ids_host[0];
+        const int a = s->align_host[3];
+        if (!final && (a < 0 || a >= limit)) { *stop_reason = WLK_ALIGN_STOP_ATTENTION; break; }
+        if (y == eos_id) { *stop_reason = WLK_ALIGN_STOP_EOS; break; }
+        out_ids[n] = y;
+        out_align[n] = a;
+        last = y;
+        *n_out = ++n;
+    }
+    return WLK_OK;
+}
+
+int wlk_nllb_session_align_stats(wlk_nllb_session* s, uint64_t* align_steps, uint64_t* graph_captures) {
+    if (!s || !align_steps || !graph_captures) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    *align_steps = s->align_steps;
+    *graph_captures = s->align_captures;
+    return WLK_OK;
+}
+
 int wlk_nllb_kv_reorder(wlk_nllb_session* s, const int32_t* source_rows, int32_t n_rows) {
     if (!s || !source_rows) return nl_fail(WLK_ERR_ARG, "NULL argument");
     if (n_rows != s->rows) return nl_fail(WLK_ERR_ARG, "n_rows must equal the session's row count");
@@ -640,6 +865,9 @@ int wlk_nllb_export(wlk_nllb_session* s, const char* what, float* host, uint64_t
         } else if (w == "enc") {
             if (!s->encoded) return nl_fail(WLK_ERR_STATE, "not encoded");
             src = s->enc_out; n = (uint64_t)s->src_len * D.d_model;
+        } else if (w == "align") {
+            if (!s->have_align) return nl_fail(WLK_ERR_STATE, "no alignment step yet");
+            src = s->align_p; n = (uint64_t)s->rows * s->src_len;
         } else {
             return nl_fail(WLK_ERR_ARG, "unknown export " + w);
         }

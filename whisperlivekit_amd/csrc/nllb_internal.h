@@ -53,6 +53,13 @@ inline void nl_ffn(const LaunchCtx& c, const NlLayer& L, float* x, float* h, flo
     nl_linear(c, wide, f, L.fc2w, L.fc2b, x, d, R, d, f, kGemmResidual, x, d, "nllb_fc2");
 }
 
+// AlignAtt read-out of an NLLB decoder step (nllb.hip): head mean of the selected heads' softmax rows
+// probs [n_align][rows][S], its arg-max over [ctl[0], ctl[1]) and its mass from ctl[2] on; ctl, pos, prob and mass may be
+// host-coherent memory.  S <= kSfMaxFrames.
+constexpr int kNlMaxAlign = 64;
+void launch_nllb_align_readout(const LaunchCtx& ctx, const float* probs, int n_align, int rows, int S, const int* ctl,
+                               float* p_out, int* pos, float* prob, float* mass);
+
 }  // namespace wlk
 
 struct wlk_nllb {

@@ -12,6 +12,8 @@ target language code.  This module is that network behind the C ABI (``wlk_nllb_
 * :class:`HipNllbBatch` / :func:`generate_batch` - up to 8 DIFFERENT sentences per launch chain (csrc/nllb_batch.hip):
   ``generate`` on a padded batch in ``transformers``, without the padding - greedy decoding of any number of sentences
   through the slots of one batch, every token position one stacked step;
+* :func:`generate_alignatt` - AlignAtt streaming decoding (opt-in): the decoder's cross-attention
+  says which source token a target token leans on, and a token that leans on the unstable end of the source is held back;
 * :func:`generate` / :func:`beam_search` - ``GenerationMixin.generate`` for the cases the translation backends use: greedy
   or beam search from ``[decoder_start_token_id]`` with the target language forced as the first generated token and
   ``</s>`` ending a hypothesis.
@@ -259,6 +261,48 @@ class HipNllbSession:
         _lib.check(self.lib.wlk_nllb_session_beam_stats(self._h, C.byref(n)))
         return {"ancestry_steps": int(n.value)}
 
+    def set_alignment_heads(self, pairs: Sequence[Tuple[int, int]]) -> None:
+        """The ``(decoder layer, head)`` pairs (1..64, no duplicates) whose cross-attention ``step_align`` reads; an empty
+        list switches the read-out off.  The order is the order the heads are summed in."""
+        a = np.ascontiguousarray([tuple(int(v) for v in pr) for pr in pairs], dtype=np.int32).reshape(-1, 2)
+        _lib.check(self.lib.wlk_nllb_session_set_align(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0]))
+
+    def step_align(self, tokens: Sequence[int], k: int, lo: int, hi: int, limit: int):
+        """``step`` + the alignment read-out, one graph replay (wlk_nllb_step_align) -> ``(logprobs [rows, k], ids [rows, k],
+        pos [rows], prob [rows], mass [rows])``: with ``p`` the mean of the selected heads' softmax rows over the source,
+        ``pos`` = the first arg-max of ``p[lo:hi]`` (-1: empty window), ``prob`` = ``p[pos]``, ``mass`` = ``p[limit:].sum()``."""
+        t = np.ascontiguousarray(tokens, dtype=np.int64).reshape(-1)
+        lp = np.empty((self.rows, k), np.float32)
+        ids = np.empty((self.rows, k), np.int32)
+        pos = np.empty(self.rows, np.int32)
+        prob = np.empty(self.rows, np.float32)
+        mass = np.empty(self.rows, np.float32)
+        _lib.check(self.lib.wlk_nllb_step_align(self._h, t.ctypes.data_as(C.c_void_p), t.size, k, int(lo), int(hi), int(limit),
+                                                *(a.ctypes.data_as(C.c_void_p) for a in (lp, ids, pos, prob, mass))))
+        return lp, ids, pos, prob, mass
+
+    def alignment(self) -> np.ndarray:
+        """``p [rows, src_len]`` of the latest ``step_align``."""
+        return self._export("align", self.rows * self.model.cdims.max_src).reshape(self.rows, -1)
+
+    def align_stats(self) -> Dict[str, int]:
+        steps, captures = C.c_uint64(), C.c_uint64()
+        _lib.check(self.lib.wlk_nllb_session_align_stats(self._h, C.byref(steps), C.byref(captures)))
+        return {"align_steps": int(steps.value), "graph_captures": int(captures.value)}
+
+    def generate_alignatt_loop(self, prompt: Sequence[int], n_accessible: int, threshold: int, final: bool, eos_id: int,
+                               max_new: int) -> Tuple[List[int], List[int], str]:
+        """wlk_nllb_generate_alignatt: the loop of :func:`generate_alignatt` inside the library, after ``encode``."""
+        pr = np.ascontiguousarray(prompt, dtype=np.int64).reshape(-1)
+        out = np.empty(max(int(max_new), 1), np.int64)
+        al = np.empty(max(int(max_new), 1), np.int32)
+        n, why = C.c_int32(), C.c_int32()
+        _lib.check(self.lib.wlk_nllb_generate_alignatt(self._h, pr.ctypes.data_as(C.c_void_p), pr.size, int(n_accessible),
+                                                       int(threshold), 1 if final else 0, int(eos_id), int(max_new),
+                                                       out.ctypes.data_as(C.c_void_p), al.ctypes.data_as(C.c_void_p),
+                                                       C.byref(n), C.byref(why)))
+        return out[: n.value].tolist(), al[: n.value].tolist(), _lib.ALIGN_STOP_REASONS[why.value]
+
     def topk(self, k: int) -> Tuple[np.ndarray, np.ndarray]:
         """The k (1..16) best log-probabilities and ids of every row of the latest decode; k > 8 takes the wide kernel."""
         lp = np.empty((self.rows, k), np.float32)
@@ -406,6 +450,77 @@ def generate(session, src_ids: Sequence[int], forced_bos_token_id: Optional[int]
         if nxt == eos:
             break
     return out
+
+
+def default_alignment_heads(cfg: NllbConfig) -> List[Tuple[int, int]]:
+    """Every head of decoder layer ``decoder_layers // 2``.  A PLACEHOLDER: nobody has validated this choice - or the default
+    ``threshold`` of the translation session - on trained weights (no checkpoint exists where this was built); pick heads
+    whose arg-max follows the source monotonically on the deployed checkpoint and pass them explicitly."""
+    layer = cfg.decoder_layers // 2
+    return [(layer, h) for h in range(cfg.attention_heads)]
+
+
+def generate_alignatt(session, src_ids: Sequence[int], forced_bos_token_id: int, *, committed: Sequence[int] = (),
+                      n_accessible: int, threshold: int, final: bool, max_new_tokens: int = 199,
+                      device_loop: bool = True) -> Tuple[List[int], List[int], str]:
+    """AlignAtt decoding of one update of a streaming sentence -> ``(new ids, their source positions, stop reason)``.
+
+    ``src_ids`` = ``[source language, content..., </s>]`` (S ids); the first ``n_accessible`` of them (language code
+    included) belong to committed ASR words, the rest is the unstable tail and ``</s>``.  Decoding continues from
+    ``[</s>, forced_bos_token_id, *committed]``: all but the last of these are prefilled, the last and every later token go
+    through ``step_align`` (alignment heads must be set) with the content window ``lo = 1``, ``hi = S - 1`` and
+    ``limit = max(n_accessible - threshold, lo)``.  Every step yields a candidate ``y`` (the arg-max) and the source
+    position ``a`` it leans on:
+
+    * not ``final``: the loop ends WITHOUT emitting ``y`` when ``a < 0`` or ``a >= limit`` (``"attention"``), or when
+      ``y`` is ``</s>`` (``"eos"``: an open sentence must not end); otherwise ``y`` is emitted;
+    * ``final``: no attention rule; ``</s>`` ends the sentence and is not emitted (``"eos"``);
+    * both end after ``max_new_tokens`` (``"length"``) and on a full target context (``"context"``).
+
+    ``device_loop=True`` runs this inside the library (wlk_nllb_generate_alignatt, one call); ``False`` runs the same rule
+    here over ``step_align`` - the two agree exactly."""
+    cfg = session.model.cfg
+    if session.rows != 1:
+        raise ValueError("generate_alignatt: needs a 1-row session")
+    eos = cfg.eos_token_id
+    prompt = [cfg.decoder_start_token_id, int(forced_bos_token_id)] + [int(t) for t in committed]
+    S = len(src_ids)
+    if not 0 <= n_accessible <= S or threshold < 0 or max_new_tokens < 0:
+        raise ValueError("generate_alignatt: needs 0 <= n_accessible <= len(src_ids), threshold >= 0, max_new_tokens >= 0")
+    session.encode(src_ids)
+    if device_loop:
+        return session.generate_alignatt_loop(prompt, n_accessible, threshold, final, eos, max_new_tokens)
+    return alignatt_loop(session, prompt, S, n_accessible, threshold, final, eos, max_new_tokens)
+
+
+def alignatt_loop(session, prompt: Sequence[int], src_len: int, n_accessible: int, threshold: int, final: bool, eos: int,
+                  max_new: int) -> Tuple[List[int], List[int], str]:
+    """The rule of :func:`generate_alignatt` over ``decode`` + ``step_align`` of an encoded session: wlk_nllb_generate_alignatt
+    (csrc/nllb.hip) restated line by line."""
+    if len(prompt) < 2:
+        raise ValueError("alignatt_loop: the prompt needs at least two tokens (</s>, target language)")
+    lo, hi = 1, src_len - 1
+    limit = min(max(n_accessible - threshold, lo), src_len)
+    max_tgt = getattr(getattr(session.model, "cdims", None), "max_tgt", None)
+    session.decode(np.asarray([list(prompt[:-1])], np.int64), first=True)
+    fed, last = len(prompt) - 1, int(prompt[-1])
+    out: List[int] = []
+    align: List[int] = []
+    while True:
+        if len(out) >= max_new:
+            return out, align, "length"
+        if max_tgt is not None and fed + 1 > max_tgt:
+            return out, align, "context"
+        _lp, ids, pos, _prob, _mass = session.step_align([last], 1, lo, hi, limit)
+        fed += 1
+        y, a = int(ids[0, 0]), int(pos[0])
+        if not final and (a < 0 or a >= limit):
+            return out, align, "attention"
+        if y == eos:
+            return out, align, "eos"
+        out.append(y)
+        align.append(a)
+        last = y
 
 
 def _per_sentence(value, n: int, what: str) -> list:

@@ -34,6 +34,13 @@ surface this module uses (``src_lang`` attribute, ``__call__(text).input_ids``, 
 ``sentencepiece.bpe.model`` in deployment, a seeded stand-in in the tests (no SentencePiece model exists offline).
 No CPU fallback: the model is a :class:`whisperlivekit_amd.nllb.HipNllbModel`.
 
+Opt-in AlignAtt policy (``HipNllbTranslationModel(policy="alignatt")``): :class:`HipAlignAttTranslation`
+meets the same four calls with the policy config 5 names.  The decoder's own cross-attention says which source token a
+target token was produced from; a token that leans on the newest, still unstable source words is held back and everything
+before it is committed at once; the next update decodes on from the committed target ids, so the text on screen only
+grows.  The reference reaches this policy through a WebSocket client of an external sidecar
+(``translation_alignatt.py:99-181``); what is restated here is that client's observable contract, not its wire protocol.
+
 Opt-in stacking (``HipNllbTranslationModel(stack=n)`` / ``WLK_NLLB_STACK=n``, greedy decoding only): the model owns ONE
 ``HipNllbBatch`` of n slots and every session hands the segments of a ``process()`` - the closed sentences and the open
 one - to it as one request list; sentences of different sessions that are in flight at the same time share every decoder
@@ -44,8 +51,9 @@ from __future__ import annotations
 import logging
 import os
 import threading
+import time
 from dataclasses import dataclass, field
-from typing import Any, List, Optional, Sequence, Tuple
+from typing import Any, Callable, List, Optional, Sequence, Tuple
 
 from . import nllb
 
@@ -187,7 +195,23 @@ class HipNllbTranslationModel:
     environment moves its steps onto the device (``step_beam``; off by default)."""
 
     def __init__(self, model: nllb.HipNllbModel, tokenizer: Any, num_beams: int = 1, max_new_tokens: int = 199,
-                 max_source_tokens: int = 200, stack: Optional[int] = None):
+                 max_source_tokens: int = 200, stack: Optional[int] = None, policy: str = "local_agreement", threshold: int = 2,
+                 alignment_heads: Optional[Sequence[Tuple[int, int]]] = None, hypothesis_tail: bool = False):
+        """``policy="alignatt"`` (opt-in, greedy only): sessions are :class:`HipAlignAttTranslation`; a target token whose
+        source position lies within ``threshold`` tokens of the end of the committed source is held back;
+        ``alignment_heads`` = ``(decoder layer, head)`` pairs, ``None`` = ``nllb.default_alignment_heads`` - neither that
+        default nor ``threshold=2`` has been validated on trained weights; ``hypothesis_tail`` asks the ASR for its unstable
+        tail and feeds it to the encoder as context no token may be committed from."""
+        if policy not in ("local_agreement", "alignatt"):
+            raise ValueError("policy must be 'local_agreement' or 'alignatt'")
+        if policy == "alignatt" and int(num_beams) != 1:
+            raise ValueError("policy='alignatt' decodes greedily (num_beams = 1)")
+        if int(threshold) < 0:
+            raise ValueError("threshold must be >= 0")
+        self.policy, self.threshold, self.hypothesis_tail = policy, int(threshold), bool(hypothesis_tail)
+        self.alignment_heads = None if alignment_heads is None else [(int(l), int(h)) for l, h in alignment_heads]
+        if policy == "alignatt":
+            stack = 0                              # the stacked slots have no alignment read-out
         self.model, self.tokenizer = model, tokenizer
         self.num_beams, self.max_new_tokens, self.max_source_tokens = int(num_beams), int(max_new_tokens), int(max_source_tokens)
         # a tokenizer with a mutable src_lang (transformers' NllbTokenizer) is shared by all sessions
@@ -215,8 +239,8 @@ class HipNllbTranslationModel:
     def decode(self, ids: Sequence[int]) -> str:
         return self.tokenizer.decode(list(ids), skip_special_tokens=True)
 
-    def new_session(self, source_language: str, target_language: str) -> "HipOnlineTranslation":
-        return HipOnlineTranslation(self, [source_language], [target_language])
+    def new_session(self, source_language: str, target_language: str):
+        return _session_class(self)(self, [source_language], [target_language])
 
     def close(self) -> None:
         """Releases the shared batch (the network itself belongs to the caller)."""
@@ -381,13 +405,167 @@ class HipOnlineTranslation:
         return m.decode(out).split()
 
 
+@dataclass
+class _Sentence:
+    """One source sentence under the AlignAtt policy: its committed source words and the target ids committed so far."""
+    segment: _Segment = field(default_factory=_Segment)
+    ids: List[int] = field(default_factory=list)      # committed target ids (append-only)
+    text: str = ""                                    # their decoded text as it stands on screen
+    validated: int = 0                                # characters of `text` already handed out as validated
+
+
+class HipAlignAttTranslation:
+    """The AlignAtt session object (``policy="alignatt"``): duck type of audio_processor.py:903-911, with the observable
+    contract of the reference's sidecar client (translation_alignatt.py:99-181; selected at core.py:305-318, 483-493):
+
+    * per open sentence a list of committed target ids; ``process()`` on it runs ONE non-final
+      ``nllb.generate_alignatt`` from those ids, appends what that emitted and returns ``(None, TimedText(text))`` - the
+      text on screen is replaced only by a text that starts with it;
+    * a source word with sentence punctuation ends the sentence: ``process()`` runs one FINAL pass from its committed ids
+      and returns the whole sentence as one ``Translation`` from the last segment's end to the sentence's end - one
+      finished sentence per call, the rest on the next calls;
+    * ``validate_buffer_and_reset()`` returns the text on screen as validated, queues the sentence for its final pass
+      (which then hands out only what lies behind the validated text) and starts a fresh segment;
+    * ``hypothesis_tail``: the newest ``HypothesisTail`` text is appended to the source as words no token may be committed
+      from; a change of the tail alone re-runs the update at most every ``TAIL_INTERVAL`` seconds.
+
+    One call in flight per session; the device session is 1-row."""
+
+    TAIL_INTERVAL = 0.5
+
+    def __init__(self, translation_model: HipNllbTranslationModel, source_languages: Sequence[str],
+                 target_languages: Sequence[str], clock: Callable[[], float] = time.monotonic):
+        if not source_languages or not target_languages:
+            raise ValueError("source and target language lists must not be empty")
+        self.shared = translation_model
+        self.source_language, self.target_language = source_languages[0], target_languages[0]
+        self.target_id = translation_model.language_id(self.target_language)       # ValueError for an unknown code
+        translation_model.language_id(self.source_language)
+        self.wants_hypothesis_tail = bool(translation_model.hypothesis_tail)
+        self.session = translation_model.model.new_session(rows=1)
+        heads = translation_model.alignment_heads
+        self.session.set_alignment_heads(heads if heads is not None else nllb.default_alignment_heads(translation_model.model.cfg))
+        self._device_loop = hasattr(self.session, "generate_alignatt_loop")
+        self._clock = clock
+        self._open = _Sentence()
+        self._finals: List[_Sentence] = []         # ended sentences awaiting their final pass, oldest first
+        self._tail = ""
+        self._dirty = False                        # committed words arrived since the last update
+        self._tail_dirty = False
+        self._last_run: Optional[float] = None
+        self._last_end: Optional[float] = None
+        self._silence = 0.0
+        self.updates = self.finals = 0             # device passes run (bench / tests)
+        self.last_n_accessible: Optional[int] = None
+
+    # ---- duck type --------------------------------------------------------------------------------------------------
+    def insert_tokens(self, items: List[Any]) -> None:
+        for item in items:
+            if type(item).__name__ == "HypothesisTail":
+                text = " ".join((getattr(item, "text", "") or "").split())
+                if self.wants_hypothesis_tail and text != self._tail:
+                    self._tail, self._tail_dirty = text, True
+                continue
+            if not hasattr(item, "text") or not hasattr(item, "end") or not (item.text or "").strip():
+                continue
+            self._open.segment.tokens.append(item)
+            self._dirty = True
+            if _has_punctuation(item):
+                self._finals.append(self._open)
+                self._open = _Sentence()
+                self._tail, self._tail_dirty, self._dirty = "", False, False
+
+    def process(self) -> Tuple[Optional[Translation], TimedText]:
+        while self._finals:                           # one finished sentence per call
+            sent = self._finals.pop(0)
+            src = self.shared.encode(sent.segment.text(), self.source_language)
+            self._decode_on(sent, src, len(src), final=True)
+            self.finals += 1
+            piece = sent.text[sent.validated:].strip()         # (behind what a reset already handed out)
+            if piece:
+                new = Translation(start=self._piece_start(sent.segment.start), end=sent.segment.end, text=piece)
+                self._last_end = new.end
+                return new, self._buffer()
+        sent = self._open
+        if not sent.segment.tokens and not self._tail:
+            return None, self._buffer()
+        now = self._clock()
+        if not self._dirty and not (self._tail_dirty and (self._last_run is None or now - self._last_run >= self.TAIL_INTERVAL)):
+            return None, self._buffer()
+        committed_text = sent.segment.text()
+        src_committed = self.shared.encode(committed_text, self.source_language)
+        src = self.shared.encode((committed_text + " " + self._tail).strip(), self.source_language) if self._tail else src_committed
+        # source positions that belong to committed words: what the two encodings share in front of the committed one's
+        # </s> - a tokenizer that merges the last committed word with the tail can only make this smaller
+        n_accessible = _common_prefix(src_committed[:-1], src)
+        self.last_n_accessible = n_accessible
+        self._dirty = self._tail_dirty = False
+        self._last_run = now
+        if n_accessible - self.shared.threshold > 1:  # else the limit is the window's start and no token can be committed
+            self._decode_on(sent, src, n_accessible, final=False)
+            self.updates += 1
+        return None, self._buffer()
+
+    def validate_buffer_and_reset(self) -> Tuple[Translation, TimedText]:
+        """Silence start / speaker change: what is on screen becomes validated as it stands (shown text is never taken
+        back), its sentence is queued for a final pass, and the next words start a fresh segment."""
+        sent = self._finals[0] if self._finals else self._open
+        start = self._piece_start(sent.segment.start)
+        text = sent.text[sent.validated:].strip()
+        validated = Translation(start=start, end=sent.segment.end if sent.segment.end is not None else start, text=text)
+        sent.validated = len(sent.text)
+        if self._open.segment.tokens:
+            self._finals.append(self._open)
+        self._open = _Sentence()
+        self._tail, self._tail_dirty, self._dirty = "", False, False
+        if validated.text:
+            self._last_end = validated.end
+        return validated, TimedText()
+
+    def insert_silence(self, duration: Optional[float]) -> None:
+        self._silence += float(duration or 0.0)
+
+    def close(self) -> None:
+        self.session.close()
+
+    # ---- internals --------------------------------------------------------------------------------------------------
+    def _decode_on(self, sent: _Sentence, src: Sequence[int], n_accessible: int, final: bool) -> None:
+        m = self.shared
+        room = m.max_new_tokens - len(sent.ids)
+        new_ids, _align, _why = nllb.generate_alignatt(self.session, src, self.target_id, committed=sent.ids,
+                                                       n_accessible=n_accessible, threshold=m.threshold, final=final,
+                                                       max_new_tokens=max(room, 0), device_loop=self._device_loop)
+        sent.ids = sent.ids + [int(t) for t in new_ids]
+        text = m.decode(sent.ids).strip()
+        if text.startswith(sent.text):
+            sent.text = text
+
+    def _piece_start(self, fallback: Optional[float]) -> float:
+        if self._last_end is not None:
+            return self._last_end
+        return fallback if fallback is not None else 0.0
+
+    def _buffer(self) -> TimedText:
+        sent = self._finals[0] if self._finals else self._open
+        text = sent.text[sent.validated:].strip()
+        if not text:
+            return TimedText()
+        return TimedText(start=self._piece_start(sent.segment.start), end=sent.segment.end, text=text)
+
+
+def _session_class(translation_model: Any):
+    return HipAlignAttTranslation if getattr(translation_model, "policy", "local_agreement") == "alignatt" else HipOnlineTranslation
+
+
 def online_translation_factory(translation_model: HipNllbTranslationModel, source_language: str, target_language: str,
-                               fallback_target: Optional[str] = None) -> HipOnlineTranslation:
-    """core.py:483-493 / translation.py:17-47 for this backend: a session object for ``target_language``; an unknown
-    per-session target falls back to the server-wide one (``fallback_target``) like translation.py:40-47."""
+                               fallback_target: Optional[str] = None):
+    """core.py:483-493 / translation.py:17-47 for this backend: a session object for ``target_language`` (the model's policy
+    decides its class); an unknown per-session target falls back to the server-wide one (``fallback_target``) like
+    translation.py:40-47."""
+    cls = _session_class(translation_model)
     try:
-        return HipOnlineTranslation(translation_model, [source_language], [target_language])
+        return cls(translation_model, [source_language], [target_language])
     except ValueError:
         if fallback_target is None or fallback_target == target_language:
             raise
-        return HipOnlineTranslation(translation_model, [source_language], [fallback_target])
+        return cls(translation_model, [source_language], [fallback_target])
