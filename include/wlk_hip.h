@@ -567,13 +567,37 @@ int wlk_nllb_batch_step(wlk_nllb_batch* b, const int32_t* slots, const int64_t* 
                         int32_t* ids);
 /* the slot's sentence is done: the slot must be encoded again before its next step */
 int wlk_nllb_batch_release(wlk_nllb_batch* b, int32_t slot);
-/* parity exports of one slot: "enc" [src_len][d_model], "logits" [vocab] of the slot's row in the latest step */
+/* parity exports of one slot: "enc" [src_len][d_model], "logits" [vocab] of the slot's row in the latest step, "align"
+ * [src_len] = the slot's p of the latest align step (WLK_ERR_STATE if the slot was not in it) */
 int wlk_nllb_batch_export(wlk_nllb_batch* b, int32_t slot, const char* what, float* host, uint64_t capacity, uint64_t* n_written);
 /* diagnostics: the ragged cross-attention kernel alone - queries q_host [n_rows][d_model] (pre-scaled) against decoder
  * layer `layer`'s cross K/V of the encoded slots named, out_host [n_rows][d_model] */
 int wlk_nllb_batch_cross_attention(wlk_nllb_batch* b, const int32_t* slots, int32_t n_rows, int32_t layer, const float* q_host,
                                    float* out_host);
 int wlk_nllb_batch_sync(wlk_nllb_batch* b);
+/* ---- AlignAtt through the stacked batch (opt-in): up to 8 streaming sessions per decoder weight pass.  A batch
+ * that never sets heads allocates nothing for this and records and replays exactly the step graphs above.
+ * The rules of wlk_nllb_session_set_align: n x (decoder layer, head), n = 0 switches the read-out off; WLK_ERR_ARG for a
+ * layer or head out of range, a duplicate pair or n > 64.  Nothing is allocated until the first align step. */
+int wlk_nllb_batch_set_align(wlk_nllb_batch* b, const int32_t* layer_head_pairs, int32_t n);
+/* The prompts of n freshly encoded slots (target length 0) in ONE pass over all sum(P_i) rows: prompt i is
+ * prompt_ids[prompt_offsets[i] .. prompt_offsets[i + 1]) (P_i >= 1; prompt_offsets[0] = 0), token p of it at position p of
+ * slots[i].  No logits are formed - the token whose logits matter goes through a step afterwards.  Afterwards the slot's
+ * target length is P_i.  WLK_ERR_STATE for a slot that is not encoded or already holds target tokens, WLK_ERR_CAPACITY for
+ * P_i > max_tgt - 1, WLK_ERR_ARG for bad ids or a slot named twice; a refused call changes nothing.  Synchronous. */
+int wlk_nllb_batch_prefill(wlk_nllb_batch* b, const int32_t* slots, const int64_t* prompt_ids, const int32_t* prompt_offsets,
+                           int32_t n);
+/* wlk_nllb_batch_step + the alignment read-out of wlk_nllb_step_align per row, as ONE graph replay: row r reads its own
+ * source length and its own window lo[r] | hi[r] | limit[r] (host-coherent block), so one recording per row count - kept
+ * apart from wlk_nllb_batch_step's, dropped when the head set or k changes - serves every mix of source lengths, windows
+ * and slots.  State rules of wlk_nllb_batch_step, plus WLK_ERR_STATE before heads are set or on a slot whose target length
+ * is 0, and WLK_ERR_ARG unless 0 <= lo[r], hi[r] <= src_len_r and 0 <= limit[r] <= src_len_r for every row. */
+int wlk_nllb_batch_step_align(wlk_nllb_batch* b, const int32_t* slots, const int64_t* tokens, int32_t n_rows, int32_t k /*1..8*/,
+                              const int32_t* lo /*[n_rows]*/, const int32_t* hi /*[n_rows]*/, const int32_t* limit /*[n_rows]*/,
+                              float* logprobs, int32_t* ids, int32_t* align_pos /*[n_rows]*/, float* align_prob /*[n_rows]*/,
+                              float* tail_mass /*[n_rows]*/);
+/* align steps run and align-step graphs recorded since the batch was created */
+int wlk_nllb_batch_align_stats(wlk_nllb_batch* b, uint64_t* align_steps, uint64_t* graph_captures);
 
 /* ---- word-timestamp alignment ------------------------------------------------------------------
  * Dynamic time warping of a [n_rows tokens, n_cols frames] fp32 cost matrix on `device`: replaces `dtw_cpu`
@@ -672,6 +696,13 @@ int wlk_diag_topk(const float* logits, int32_t n_rows, int32_t n_vocab, int32_t 
  * upload.  Synchronous, on a stream of its own. */
 int wlk_diag_nllb_align(const float* probs, int32_t n_align, int32_t rows, int32_t S, int32_t lo, int32_t hi, int32_t limit,
                         float* p_out, int32_t* pos, float* prob, float* mass);
+/* The RAGGED read-out of a stacked align step (csrc/nllb_batch.hip, through its production launcher) on host data
+ * probs [n_align][rows][stride]: row r has its own length S[r] (1..stride) and window lo[r] | hi[r] | limit[r]; p_out
+ * [rows][stride] is written at [r][0 .. S[r]) only, pos / prob / mass [rows].  n_align in [1, 64], rows in [1, 8], stride in
+ * [1, 512], 0 <= lo, hi <= S, 0 <= limit <= S per row - anything else is refused (WLK_ERR_ARG) before any upload. */
+int wlk_diag_nllb_align_rows(const float* probs, int32_t n_align, int32_t rows, int32_t stride, const int32_t* S,
+                             const int32_t* lo, const int32_t* hi, const int32_t* limit, float* p_out, int32_t* pos, float* prob,
+                             float* mass);
 /* The decoder's attention stage (csrc/decoder.hip, the merged out projection of csrc/gemm_f32.hip, the prefill flash
  * kernel of csrc/attention.hip) on host data, through ONE chosen route.  The launchers are the ones a decode step uses,
  * unchanged.  Heads are 64 wide and d = 64 n_head.

@@ -263,6 +263,10 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_nllb_batch_export": (cint, [p, i32, C.c_char_p, p, u64, C.POINTER(u64)]),
         "wlk_nllb_batch_cross_attention": (cint, [p, p, i32, i32, p, p]),
         "wlk_nllb_batch_sync": (cint, [p]),
+        "wlk_nllb_batch_set_align": (cint, [p, p, i32]),
+        "wlk_nllb_batch_prefill": (cint, [p, p, p, p, i32]),
+        "wlk_nllb_batch_step_align": (cint, [p, p, p, i32, i32, p, p, p, p, p, p, p, p]),
+        "wlk_nllb_batch_align_stats": (cint, [p, C.POINTER(u64), C.POINTER(u64)]),
         "wlk_vad_weights_floats": (cint, [C.POINTER(u64)]),
         "wlk_vad_tensor_lookup": (cint, [C.c_char_p, C.POINTER(u64), C.POINTER(u64)]),
         "wlk_vad_tensor_name": (cint, [cint, C.POINTER(C.c_char_p)]),
@@ -303,6 +307,7 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_dec_attention": (cint, [C.POINTER(DiagDecAttentionArgs)]),
         "wlk_diag_topk": (cint, [p, i32, i32, i32, i32, p, p]),
         "wlk_diag_nllb_align": (cint, [p, i32, i32, i32, i32, i32, i32, p, p, p, p]),
+        "wlk_diag_nllb_align_rows": (cint, [p, i32, i32, i32, p, p, p, p, p, p, p, p]),
         "wlk_diag_sf_kernel": (cint, [C.POINTER(DiagSfKernelArgs)]),
     }
     for name, (res, args) in sig.items():
@@ -348,11 +353,13 @@ EXPORTED_SYMBOLS = (
     "wlk_nllb_session_set_align", "wlk_nllb_step_align", "wlk_nllb_generate_alignatt", "wlk_nllb_session_align_stats",
     "wlk_nllb_batch_create", "wlk_nllb_batch_destroy", "wlk_nllb_batch_encode", "wlk_nllb_batch_step", "wlk_nllb_batch_release",
     "wlk_nllb_batch_export", "wlk_nllb_batch_cross_attention", "wlk_nllb_batch_sync",
+    "wlk_nllb_batch_set_align", "wlk_nllb_batch_prefill", "wlk_nllb_batch_step_align", "wlk_nllb_batch_align_stats",
     "wlk_diag_last_error", "wlk_diag_linear", "wlk_diag_linear_time", "wlk_diag_linear_ln", "wlk_diag_layernorm",
     "wlk_diag_encoder_attention", "wlk_diag_encoder_attention_time", "wlk_diag_wave_ops", "wlk_diag_env_refresh",
     "wlk_diag_linear_x3", "wlk_diag_linear_x3_time", "wlk_diag_layernorm_x3",
     "wlk_diag_encoder_attention_x3", "wlk_diag_encoder_attention_x3_time", "wlk_diag_qkv_x3_attention",
     "wlk_diag_select", "wlk_diag_dec_attention", "wlk_diag_topk", "wlk_diag_sf_kernel", "wlk_diag_nllb_align",
+    "wlk_diag_nllb_align_rows",
 )
 
 

@@ -675,6 +675,56 @@ int wlk_diag_nllb_align(const float* probs, int32_t n_align, int32_t rows, int32
     });
 }
 
+/* the ragged NLLB alignment read-out alone (see include/wlk_hip.h): the launcher a stacked align step uses, unchanged */
+int wlk_diag_nllb_align_rows(const float* probs, int32_t n_align, int32_t rows, int32_t stride, const int32_t* S, const int32_t* lo,
+                             const int32_t* hi, const int32_t* limit, float* p_out, int32_t* pos, float* prob, float* mass) {
+    if (!probs || !S || !lo || !hi || !limit || !p_out || !pos || !prob || !mass || n_align < 1 || n_align > kNlMaxAlign ||
+        rows < 1 || rows > 8 || stride < 1 || stride > kSfMaxFrames) {
+        g_diag_error = "wlk_diag_nllb_align_rows: null pointer, n_align outside [1, 64], rows outside [1, 8] or stride outside [1, 512]";
+        return WLK_ERR_ARG;
+    }
+    for (int r = 0; r < rows; ++r) {
+        if (S[r] < 1 || S[r] > stride) {
+            g_diag_error = "wlk_diag_nllb_align_rows: every S must be in [1, stride]";
+            return WLK_ERR_ARG;
+        }
+        if (lo[r] < 0 || hi[r] > S[r] || limit[r] < 0 || limit[r] > S[r]) {
+            g_diag_error = "wlk_diag_nllb_align_rows: needs 0 <= lo, hi <= S and 0 <= limit <= S in every row";
+            return WLK_ERR_ARG;
+        }
+    }
+    return run([&]() {
+        struct Stream {
+            hipStream_t s = nullptr;
+            Stream() { WLK_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+            ~Stream() { (void)hipStreamDestroy(s); }
+        } st;
+        StepRow table[8] = {};
+        float ctl_host[3 * 8] = {};
+        for (int r = 0; r < rows; ++r) {
+            table[r].content_len = S[r];
+            ctl_host[3 * r] = __builtin_bit_cast(float, lo[r]);
+            ctl_host[3 * r + 1] = __builtin_bit_cast(float, hi[r]);
+            ctl_host[3 * r + 2] = __builtin_bit_cast(float, limit[r]);
+        }
+        static_assert(sizeof(StepRow) % sizeof(float) == 0, "the row table is uploaded through a float buffer");
+        DevBuf P((size_t)n_align * rows * stride, probs), CTL(3 * 8, ctl_host),
+            TB(8 * (sizeof(StepRow) / sizeof(float)), reinterpret_cast<const float*>(table)), PO((size_t)rows * stride), POS(rows), PR(rows),
+            MS(rows);
+        WLK_HIP(hipDeviceSynchronize());   // the uploads ran on the legacy stream; st does not wait for it
+        LaunchCtx ctx;
+        ctx.stream = st.s;
+        launch_nllb_align_readout_rows(ctx, P.p, n_align, (long)rows * stride, stride, rows, reinterpret_cast<const StepRow*>(TB.p),
+                                       reinterpret_cast<const int*>(CTL.p), PO.p, reinterpret_cast<int*>(POS.p), PR.p, MS.p);
+        WLK_HIP(hipStreamSynchronize(st.s));
+        for (int r = 0; r < rows; ++r)     // only what the kernel wrote: the caller's p_out keeps its fill from S_r on
+            WLK_HIP(hipMemcpy(p_out + (size_t)r * stride, PO.p + (size_t)r * stride, (size_t)S[r] * sizeof(float), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(pos, POS.p, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(prob, PR.p, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(mass, MS.p, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
 /* The decoder's attention stage on host data through one chosen route (see include/wlk_hip.h): the launchers of a decode
  * step, unchanged.  Every shape is checked here or by its launcher before anything is launched for it. */
 int wlk_diag_dec_attention(const wlk_diag_dec_attention_args* q) {

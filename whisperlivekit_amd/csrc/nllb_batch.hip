@@ -28,6 +28,7 @@
 // from the table).  The row table is common.h's StepRow - the type the GEMV's cache append and the self-attention
 // launcher already index - with `content_len` holding the row's source length (its meaning for Whisper rows as well: the
 // number of valid encoder positions).  fp32 throughout.
+#include <climits>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -107,9 +108,17 @@ __global__ __launch_bounds__(256) void nllb_embed_rows_step_kernel(const StepRow
 // Nothing is read at or past key T_r: lanes beyond it re-read key 0 and their scores are never stored.  A workgroup
 // touches only its own row's operands, so a row's output bits do not depend on which other rows share the launch.
 // ---------------------------------------------------------------------------------------------------------------------
+//
+// kAlign (align steps): a (row, head) whose rank in the layer's table head_rank[heads] is >= 0 also stores its
+// normalised sc[0..T_r) - the weights the value pass multiplies by - to align_probs[rank][row][0..T_r) (row stride
+// align_stride, kNlBatchMaxRows rows per rank), each thread the entries it has just normalised.  The attention output has
+// the bits of the kAlign = false instantiation: the stores are the only difference.
+template <bool kAlign>
 __global__ __launch_bounds__(256) void nllb_cross_attention_ragged_kernel(const float* __restrict__ q,
                                                                           const StepRow* __restrict__ rows, long kv_off,
-                                                                          long ldkv, int d, float* __restrict__ out) {
+                                                                          long ldkv, int d, float* __restrict__ out,
+                                                                          const int* __restrict__ head_rank,
+                                                                          float* __restrict__ align_probs, int align_stride) {
     __shared__ float sc[kNlCrossMaxT];
     __shared__ float red[8];
     __shared__ __attribute__((aligned(16))) float part[16 * 64];
@@ -172,7 +181,17 @@ __global__ __launch_bounds__(256) void nllb_cross_attention_ragged_kernel(const 
     if (lane == 0) red[4 + wave] = sum;
     __syncthreads();
     sum = (red[4] + red[5]) + (red[6] + red[7]);
-    for (int j = tid; j < T; j += 256) sc[j] = sc[j] / sum;
+    if (kAlign) {
+        const int rank = head_rank[head];
+        float* keep = align_probs + ((long)(rank < 0 ? 0 : rank) * kNlBatchMaxRows + row) * align_stride;
+        for (int j = tid; j < T; j += 256) {
+            const float w = sc[j] / sum;
+            sc[j] = w;
+            if (rank >= 0) keep[j] = w;
+        }
+    } else {
+        for (int j = tid; j < T; j += 256) sc[j] = sc[j] / sum;
+    }
     __syncthreads();
 
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -208,8 +227,86 @@ __global__ __launch_bounds__(256) void nllb_cross_attention_ragged_kernel(const 
 static void launch_nllb_cross_attention_ragged(const LaunchCtx& ctx, const float* q, const StepRow* rows, long kv_off, long ldkv,
                                                float* out, int n_rows, int d, int n_head) {
     KernelScope ks(ctx, "nllb_cross_attention_ragged");
-    hipLaunchKernelGGL(nllb_cross_attention_ragged_kernel, dim3(n_rows, n_head), dim3(256), 0, ctx.stream, q, rows, kv_off, ldkv,
-                       d, out);
+    hipLaunchKernelGGL(nllb_cross_attention_ragged_kernel<false>, dim3(n_rows, n_head), dim3(256), 0, ctx.stream, q, rows, kv_off,
+                       ldkv, d, out, (const int*)nullptr, (float*)nullptr, 0);
+    WLK_HIP(hipGetLastError());
+}
+
+// the same launch for an align step: n_rows <= kNlBatchMaxRows, head_rank = the layer's [n_head] rank table
+static void launch_nllb_cross_attention_ragged_align(const LaunchCtx& ctx, const float* q, const StepRow* rows, long kv_off,
+                                                     long ldkv, float* out, int n_rows, int d, int n_head, const int* head_rank,
+                                                     float* align_probs, int align_stride) {
+    if (n_rows > kNlBatchMaxRows || !head_rank || !align_probs || align_stride < 1 || align_stride > kNlCrossMaxT)
+        throw std::invalid_argument("NLLB ragged cross-attention: the alignment rows hold 8 rows of at most 512 positions");
+    KernelScope ks(ctx, "nllb_cross_attention_ragged_align");
+    hipLaunchKernelGGL(nllb_cross_attention_ragged_kernel<true>, dim3(n_rows, n_head), dim3(256), 0, ctx.stream, q, rows, kv_off,
+                       ldkv, d, out, head_rank, align_probs, align_stride);
+    WLK_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Ragged AlignAtt read-out: nllb.hip's nllb_align_readout_kernel with every per-row scalar read per row.
+// probs [n_align][.][stride] (head stride by value), one workgroup per row, two positions per thread:
+//   S_r                 = rows[r].content_len (clamped to 1..min(stride, 512): a bad table must not leave the row)
+//   lo_r | hi_r | limit_r = ctl[3 r .. 3 r + 2], a host-coherent block in a replayed step
+//   p[j]  = (probs[0][r][j] + probs[1][r][j] + ... in rank order) * inv_n, j < S_r, written to p_out[r][j] (row stride `stride`)
+//   pos / prob / mass as the session's kernel defines them: a thread takes its lower position first, a tie goes to the
+//   lowest index, the mass is (w0 + w1) + (w2 + w3).  Nothing is read or written at or past S_r of a row.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void nllb_align_readout_rows_kernel(const float* __restrict__ probs, int n_align,
+                                                                      long head_stride, int stride, float inv_n,
+                                                                      const StepRow* __restrict__ rows, const int* __restrict__ ctl,
+                                                                      float* __restrict__ p_out, int* __restrict__ pos,
+                                                                      float* __restrict__ prob, float* __restrict__ mass) {
+    __shared__ float red_v[4], red_m[4];
+    __shared__ int red_i[4];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cap = stride < kNlCrossMaxT ? stride : kNlCrossMaxT;
+    int S = rows[row].content_len;
+    S = S < 1 ? 1 : (S > cap ? cap : S);
+    const int lo = max(__hip_atomic_load(ctl + 3 * row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), 0);
+    const int hi = min(__hip_atomic_load(ctl + 3 * row + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), S);
+    const int limit = max(__hip_atomic_load(ctl + 3 * row + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), 0);
+    const float* base = probs + (long)row * stride;
+    float bv = -INFINITY, tail = 0.f;
+    int bi = INT_MAX;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int j = tid + half * 256;
+        if (j < S) {
+            float acc = 0.f;
+            for (int a = 0; a < n_align; ++a) acc += base[a * head_stride + j];
+            const float p = acc * inv_n;
+            p_out[(long)row * stride + j] = p;
+            if (j >= limit) tail += p;
+            if (j >= lo && j < hi && p > bv) { bv = p; bi = j; }      // j ascends: an equal value keeps the lower position
+        }
+    }
+    wave_argmax(bv, bi);
+    tail = wave_sum(tail);
+    if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; red_m[wave] = tail; }
+    __syncthreads();
+    if (tid == 0) {
+        float v = red_v[0];
+        int i = red_i[0];
+        for (int w = 1; w < 4; ++w)
+            if (red_v[w] > v || (red_v[w] == v && red_i[w] < i)) { v = red_v[w]; i = red_i[w]; }
+        const bool found = i != INT_MAX;
+        pos[row] = found ? i : -1;
+        prob[row] = found ? v : 0.f;
+        mass[row] = (red_m[0] + red_m[1]) + (red_m[2] + red_m[3]);
+    }
+}
+
+void launch_nllb_align_readout_rows(const LaunchCtx& ctx, const float* probs, int n_align, long head_stride, int stride,
+                                    int n_rows, const StepRow* rows, const int* ctl, float* p_out, int* pos, float* prob,
+                                    float* mass) {
+    if (n_align < 1 || n_align > kNlMaxAlign || n_rows < 1 || n_rows > kNlBatchMaxRows || stride < 1 || stride > kNlCrossMaxT ||
+        head_stride < (long)n_rows * stride)
+        throw std::invalid_argument("NLLB ragged alignment read-out: 1..64 heads, 1..8 rows, row stride 1..512");
+    KernelScope ks(ctx, "nllb_align_readout_rows");
+    hipLaunchKernelGGL(nllb_align_readout_rows_kernel, dim3(n_rows), dim3(256), 0, ctx.stream, probs, n_align, head_stride, stride,
+                       1.0f / (float)n_align, rows, ctl, p_out, pos, prob, mass);
     WLK_HIP(hipGetLastError());
 }
 
@@ -218,6 +315,7 @@ struct NlBatchSlot {
     int src_len = 0, self_len = 0;
     bool encoded = false;
     int logits_row = -1;       // row of the latest step's logits that is this slot's, -1: the slot was not in it
+    int align_row = -1;        // row of the latest ALIGN step's p that is this slot's, -1: the slot was not in it
 };
 
 }  // namespace wlk
@@ -247,6 +345,21 @@ struct wlk_nllb_batch {
     int step_k = 1;
     hipGraphExec_t exec[kNlBatchMaxRows + 1] = {nullptr};     // by row count
     int exec_k[kNlBatchMaxRows + 1] = {0};
+    // AlignAtt steps (wlk_nllb_batch_step_align); nothing below is allocated before the first align step
+    int n_align = 0;
+    std::vector<int> head_rank;          // [dec_layers][heads]: rank of the (layer, head) pair or -1, as set
+    bool head_rank_stale = false;        // head_rank_dev does not hold head_rank yet
+    int* head_rank_dev = nullptr;
+    float* align_probs = nullptr;        // [kNlMaxAlign][8][max_src]: the selected heads' softmax rows of the latest align step
+    float* align_p = nullptr;            // [8][max_src]: their mean
+    int* align_host = nullptr;           // pinned + mapped: [8] lo | hi | limit, then [8] position, [8] probability, [8] tail mass
+    int* align_host_dev = nullptr;
+    uint64_t align_steps = 0, align_captures = 0;
+    hipGraphExec_t align_exec[kNlBatchMaxRows + 1] = {nullptr};   // by row count, apart from exec[]: dropped with the head set
+    int align_exec_k[kNlBatchMaxRows + 1] = {0};
+    // stacked prompt prefill (wlk_nllb_batch_prefill): n_slots x max_tgt rows, allocated by the first prefill
+    float *px = nullptr, *ph = nullptr, *pqkv = nullptr, *patt = nullptr, *pq = nullptr, *pwide = nullptr;
+    StepRow *prefill_stage = nullptr, *prefill_rows = nullptr;    // the uploaded table and the copy the embedding leaves
     template <typename T>
     T* alloc(size_t n) {
         void* p = nullptr;
@@ -260,6 +373,8 @@ struct wlk_nllb_batch {
         if (stream) (void)hipStreamSynchronize(stream);
         for (void* p : owned) (void)hipFree(p);
         for (auto& e : exec) if (e) (void)hipGraphExecDestroy(e);
+        for (auto& e : align_exec) if (e) (void)hipGraphExecDestroy(e);
+        if (align_host) (void)hipHostFree(align_host);
         if (rows_host) (void)hipHostFree(rows_host);
         if (vals_host) (void)hipHostFree(vals_host);
         if (ids_host) (void)hipHostFree(ids_host);
@@ -302,8 +417,9 @@ static void nlb_encode(wlk_nllb_batch* b, const NlSegTable& sg, const int* len, 
     }
 }
 
-// embed .. logits .. top-k of R stacked rows; every per-row scalar comes from the row table
-static void nlb_step_chain(wlk_nllb_batch* b, int R) {
+// embed .. logits .. top-k of R stacked rows; every per-row scalar comes from the row table.  align: the selected heads
+// leave their softmax rows in align_probs and the ragged read-out follows the top-k (windows and results in align_host)
+static void nlb_step_chain(wlk_nllb_batch* b, int R, bool align = false) {
     wlk_nllb* m = b->m;
     const wlk_nllb_dims& D = m->D;
     const LaunchCtx c = b->ctx();
@@ -328,7 +444,11 @@ static void nlb_step_chain(wlk_nllb_batch* b, int R) {
         q.A = b->dx; q.lda = d; q.W = L.xqw; q.bias = L.xqb; q.C = b->dq; q.ldc = d; q.M = R; q.N = d; q.K = d;
         q.flags = kGemmScaleCols; q.scale = q_scale; q.scale_cols = d; q.ln_gamma = L.lnxw; q.ln_beta = L.lnxb;
         launch_gemv(c, q, "nllb_lnx_xq");
-        launch_nllb_cross_attention_ragged(c, b->dq, b->rows_dev, (long)l * 2 * d, ldkv, b->datt, R, d, H);
+        if (align)
+            launch_nllb_cross_attention_ragged_align(c, b->dq, b->rows_dev, (long)l * 2 * d, ldkv, b->datt, R, d, H,
+                                                     b->head_rank_dev + (size_t)l * H, b->align_probs, D.max_src);
+        else
+            launch_nllb_cross_attention_ragged(c, b->dq, b->rows_dev, (long)l * 2 * d, ldkv, b->datt, R, d, H);
         nl_linear(c, b->datt, d, L.xoutw, L.xoutb, b->dx, d, R, d, d, kGemmResidual, b->dx, d, "nllb_dec_xout");
         GemmArgs g1;
         g1.A = b->dx; g1.lda = d; g1.W = L.fc1w; g1.bias = L.fc1b; g1.C = b->dwide; g1.ldc = f; g1.M = R; g1.N = f; g1.K = d;
@@ -342,6 +462,40 @@ static void nlb_step_chain(wlk_nllb_batch* b, int R) {
     launch_gemv(c, lg, "nllb_lnf_logits");
     // results straight into the host-coherent block: no copy node behind the graph
     launch_logsoftmax_topk(c, b->logits, D.vocab, R, b->step_k, b->vals_dev, b->ids_dev, b->topk_scratch, nullptr, nullptr, nullptr, 0);
+    if (align) {
+        int* res = b->align_host_dev + 3 * kNlBatchMaxRows;
+        launch_nllb_align_readout_rows(c, b->align_probs, b->n_align, (long)kNlBatchMaxRows * D.max_src, D.max_src, R, b->rows_dev,
+                                       b->align_host_dev, b->align_p, res, reinterpret_cast<float*>(res + kNlBatchMaxRows),
+                                       reinterpret_cast<float*>(res + 2 * kNlBatchMaxRows));
+    }
+}
+
+// Stacked prompt prefill: N rows, row i = (slot, token, position) of prefill_rows - no final LayerNorm, no logits.  Row p of
+// a slot sees cache positions 0..p of that slot: every layer appends ALL rows' keys / values in front of its attention launch.
+static void nlb_prefill_chain(wlk_nllb_batch* b, int N) {
+    wlk_nllb* m = b->m;
+    const wlk_nllb_dims& D = m->D;
+    const LaunchCtx c = b->ctx();
+    const int d = D.d_model, H = D.heads, f = D.ffn, ctx_len = D.max_tgt;
+    const float q_scale = 0.125f;
+    hipLaunchKernelGGL(nllb_embed_rows_step_kernel, dim3(N), dim3(256), 0, b->stream, b->prefill_stage, b->prefill_rows, m->emb,
+                       m->pos, D.embed_scale, D.pad_id + 1, d, b->px);
+    WLK_HIP(hipGetLastError());
+    const long ldkv = (long)D.dec_layers * 2 * d;
+    for (int l = 0; l < D.dec_layers; ++l) {
+        const NlLayer& L = m->dec[l];
+        const long layer_off = (long)l * ctx_len * d;
+        launch_layernorm(c, b->px, d, L.ln1w, L.ln1b, b->ph, d, N, d, "nllb_ln1");
+        nl_linear(c, b->ph, d, L.qkvw, L.qkvb, b->pqkv, 3 * d, N, 3 * d, d, kGemmScaleCols, nullptr, 0, "nllb_dec_qkv", q_scale, d);
+        launch_kv_append_rows(c, b->pqkv, b->prefill_rows, layer_off, N, d);
+        launch_decoder_self_attention_rows(c, b->pqkv, b->prefill_rows, layer_off, b->patt, N, d, H, ctx_len);
+        nl_linear(c, b->patt, d, L.outw, L.outb, b->px, d, N, d, d, kGemmResidual, b->px, d, "nllb_dec_out");
+        launch_layernorm(c, b->px, d, L.lnxw, L.lnxb, b->ph, d, N, d, "nllb_lnx");
+        nl_linear(c, b->ph, d, L.xqw, L.xqb, b->pq, d, N, d, d, kGemmScaleCols, nullptr, 0, "nllb_dec_xq", q_scale, d);
+        launch_nllb_cross_attention_ragged(c, b->pq, b->prefill_rows, (long)l * 2 * d, ldkv, b->patt, N, d, H);
+        nl_linear(c, b->patt, d, L.xoutw, L.xoutb, b->px, d, N, d, d, kGemmResidual, b->px, d, "nllb_dec_xout");
+        nl_ffn(c, L, b->px, b->ph, b->pwide, N, d, f);
+    }
 }
 
 static StepRow nlb_row(const wlk_nllb_batch* b, int slot, int token) {
@@ -458,6 +612,7 @@ int wlk_nllb_batch_encode(wlk_nllb_batch* b, const int32_t* slots, const int64_t
             s.self_len = 0;
             s.encoded = true;
             s.logits_row = -1;
+            s.align_row = -1;
         }
         return WLK_OK;
     });
@@ -503,6 +658,160 @@ int wlk_nllb_batch_step(wlk_nllb_batch* b, const int32_t* slots, const int64_t* 
     });
 }
 
+int wlk_nllb_batch_set_align(wlk_nllb_batch* b, const int32_t* layer_head_pairs, int32_t n) {
+    if (!b || (n > 0 && !layer_head_pairs)) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    if (n < 0 || n > kNlMaxAlign) return nl_fail(WLK_ERR_ARG, "wlk_nllb_batch_set_align: 0..64 (layer, head) pairs");
+    const wlk_nllb_dims& D = b->m->D;
+    std::vector<int> rank((size_t)D.dec_layers * D.heads, -1);
+    for (int i = 0; i < n; ++i) {
+        const int l = layer_head_pairs[2 * i], h = layer_head_pairs[2 * i + 1];
+        if (l < 0 || l >= D.dec_layers || h < 0 || h >= D.heads) return nl_fail(WLK_ERR_ARG, "alignment head: layer or head out of range");
+        if (rank[(size_t)l * D.heads + h] >= 0) return nl_fail(WLK_ERR_ARG, "alignment head: duplicate (layer, head) pair");
+        rank[(size_t)l * D.heads + h] = i;
+    }
+    return nl_guarded([&]() {
+        bool recorded = false;
+        for (auto& e : b->align_exec) recorded = recorded || e;
+        if (recorded) {                      // a recording carries the head count by value
+            WLK_HIP(hipSetDevice(b->m->device));
+            WLK_HIP(hipStreamSynchronize(b->stream));
+            for (auto& e : b->align_exec)
+                if (e) { WLK_HIP(hipGraphExecDestroy(e)); e = nullptr; }
+        }
+        for (auto& s : b->slots) s.align_row = -1;
+        b->head_rank = std::move(rank);      // uploaded by the next align step: nothing is allocated here
+        b->head_rank_stale = true;
+        b->n_align = n;
+        return WLK_OK;
+    });
+}
+
+int wlk_nllb_batch_step_align(wlk_nllb_batch* b, const int32_t* slots, const int64_t* tokens, int32_t n_rows, int32_t k,
+                              const int32_t* lo, const int32_t* hi, const int32_t* limit, float* logprobs, int32_t* ids,
+                              int32_t* align_pos, float* align_prob, float* tail_mass) {
+    if (!b || !slots || !tokens || !lo || !hi || !limit || !logprobs || !ids || !align_pos || !align_prob || !tail_mass)
+        return nl_fail(WLK_ERR_ARG, "NULL argument");
+    if (n_rows < 1 || n_rows > kNlBatchMaxRows || n_rows > b->n_slots)
+        return nl_fail(WLK_ERR_ARG, "NLLB batch step: 1..min(8, n_slots) rows, at most one per slot");
+    if (k < 1 || k > 8) return nl_fail(WLK_ERR_ARG, "k must be 1..8 (the top-k kernel's limit)");
+    if (int rc = nlb_check_slots(b, slots, n_rows)) return rc;
+    if (b->n_align < 1) return nl_fail(WLK_ERR_STATE, "wlk_nllb_batch_step_align before wlk_nllb_batch_set_align");
+    const wlk_nllb_dims& D = b->m->D;
+    // what the two align launchers would refuse is refused here: nothing may throw once the stream is capturing
+    if (b->n_align > kNlMaxAlign || D.max_src < 1 || D.max_src > kNlCrossMaxT)
+        return nl_fail(WLK_ERR_ARG, "wlk_nllb_batch_step_align: the alignment rows hold 64 heads of at most 512 positions");
+    for (int r = 0; r < n_rows; ++r) {
+        const NlBatchSlot& s = b->slots[slots[r]];
+        if (!s.encoded) return nl_fail(WLK_ERR_STATE, "NLLB batch step on a slot that is not encoded");
+        if (s.self_len == 0) return nl_fail(WLK_ERR_STATE, "wlk_nllb_batch_step_align before the slot's decoder prompt (prefill or step first)");
+        if (s.self_len + 1 > D.max_tgt) return nl_fail(WLK_ERR_CAPACITY, "target context exceeded");
+        if (tokens[r] < 0 || tokens[r] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
+        if (tokens[r] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sequence is not supported");
+        if (lo[r] < 0 || hi[r] > s.src_len || limit[r] < 0 || limit[r] > s.src_len)
+            return nl_fail(WLK_ERR_ARG, "wlk_nllb_batch_step_align: needs 0 <= lo, hi <= src_len and 0 <= limit <= src_len in every row");
+    }
+    return nl_guarded([&]() {
+        WLK_HIP(hipSetDevice(b->m->device));
+        WLK_HIP(hipStreamSynchronize(b->stream));           // the previous step's readers of the host blocks are done
+        constexpr int R8 = kNlBatchMaxRows;
+        if (!b->align_host) {
+            b->head_rank_dev = b->alloc<int>((size_t)D.dec_layers * D.heads);
+            b->align_probs = b->alloc<float>((size_t)kNlMaxAlign * R8 * D.max_src);
+            b->align_p = b->alloc<float>((size_t)R8 * D.max_src);
+            WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->align_host), 6 * R8 * sizeof(int), hipHostMallocMapped));
+            WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->align_host_dev), b->align_host, 0));
+            std::memset(b->align_host, 0, 6 * R8 * sizeof(int));
+        }
+        if (b->head_rank_stale) {
+            WLK_HIP(hipMemcpyAsync(b->head_rank_dev, b->head_rank.data(), b->head_rank.size() * sizeof(int), hipMemcpyHostToDevice,
+                                   b->stream));
+            WLK_HIP(hipStreamSynchronize(b->stream));
+            b->head_rank_stale = false;
+        }
+        for (int r = 0; r < n_rows; ++r) {
+            b->rows_host[r] = nlb_row(b, slots[r], (int)tokens[r]);
+            b->align_host[3 * r] = lo[r]; b->align_host[3 * r + 1] = hi[r]; b->align_host[3 * r + 2] = limit[r];
+        }
+        hipGraphExec_t& exec = b->align_exec[n_rows];
+        if (!exec || b->align_exec_k[n_rows] != k) {
+            if (exec) { WLK_HIP(hipGraphExecDestroy(exec)); exec = nullptr; }
+            b->step_k = k;
+            capture_step_graph(b->stream, exec, [&] { nlb_step_chain(b, n_rows, /*align=*/true); });
+            b->align_exec_k[n_rows] = k;
+            b->align_captures += 1;
+        }
+        WLK_HIP(hipGraphLaunch(exec, b->stream));
+        WLK_HIP(hipStreamSynchronize(b->stream));
+        std::memcpy(logprobs, b->vals_host, (size_t)n_rows * k * sizeof(float));
+        std::memcpy(ids, b->ids_host, (size_t)n_rows * k * sizeof(int));
+        std::memcpy(align_pos, b->align_host + 3 * R8, (size_t)n_rows * sizeof(int));
+        std::memcpy(align_prob, b->align_host + 4 * R8, (size_t)n_rows * sizeof(float));
+        std::memcpy(tail_mass, b->align_host + 5 * R8, (size_t)n_rows * sizeof(float));
+        for (auto& s : b->slots) s.logits_row = s.align_row = -1;
+        for (int r = 0; r < n_rows; ++r) {
+            NlBatchSlot& s = b->slots[slots[r]];
+            s.self_len += 1;
+            s.logits_row = s.align_row = r;
+        }
+        b->align_steps += 1;
+        return WLK_OK;
+    });
+}
+
+int wlk_nllb_batch_align_stats(wlk_nllb_batch* b, uint64_t* align_steps, uint64_t* graph_captures) {
+    if (!b || !align_steps || !graph_captures) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    *align_steps = b->align_steps;
+    *graph_captures = b->align_captures;
+    return WLK_OK;
+}
+
+int wlk_nllb_batch_prefill(wlk_nllb_batch* b, const int32_t* slots, const int64_t* prompt_ids, const int32_t* prompt_offsets,
+                           int32_t n) {
+    if (!b || !slots || !prompt_ids || !prompt_offsets) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    if (n < 1 || n > b->n_slots) return nl_fail(WLK_ERR_ARG, "NLLB batch prefill: 1..n_slots prompts per call");
+    if (int rc = nlb_check_slots(b, slots, n)) return rc;
+    const wlk_nllb_dims& D = b->m->D;
+    if (prompt_offsets[0] != 0) return nl_fail(WLK_ERR_ARG, "NLLB batch prefill: prompt_offsets must start at 0");
+    for (int i = 0; i < n; ++i) {
+        const NlBatchSlot& s = b->slots[slots[i]];
+        if (!s.encoded) return nl_fail(WLK_ERR_STATE, "NLLB batch prefill on a slot that is not encoded");
+        if (s.self_len != 0) return nl_fail(WLK_ERR_STATE, "NLLB batch prefill on a slot that already holds target tokens");
+        const long pi = (long)prompt_offsets[i + 1] - prompt_offsets[i];
+        if (pi < 1) return nl_fail(WLK_ERR_ARG, "NLLB batch prefill: every prompt needs at least one token");
+        if (pi > D.max_tgt - 1) return nl_fail(WLK_ERR_CAPACITY, "NLLB batch prefill: a prompt leaves no room for a step");
+    }
+    const int total = prompt_offsets[n];
+    std::vector<StepRow> table((size_t)total);
+    for (int i = 0; i < n; ++i)
+        for (int t = prompt_offsets[i]; t < prompt_offsets[i + 1]; ++t) {
+            if (prompt_ids[t] < 0 || prompt_ids[t] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
+            if (prompt_ids[t] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sequence is not supported");
+            table[t] = nlb_row(b, slots[i], (int)prompt_ids[t]);
+            table[t].offset = t - prompt_offsets[i];
+        }
+    return nl_guarded([&]() {
+        WLK_HIP(hipSetDevice(b->m->device));
+        WLK_HIP(hipStreamSynchronize(b->stream));
+        if (!b->prefill_rows) {
+            const size_t d = D.d_model, N = (size_t)b->n_slots * D.max_tgt;
+            b->px = b->alloc<float>(N * d); b->ph = b->alloc<float>(N * d); b->pqkv = b->alloc<float>(N * 3 * d);
+            b->patt = b->alloc<float>(N * d); b->pq = b->alloc<float>(N * d); b->pwide = b->alloc<float>(N * D.ffn);
+            b->prefill_stage = b->alloc<StepRow>(N);
+            b->prefill_rows = b->alloc<StepRow>(N);
+        }
+        WLK_HIP(hipMemcpyAsync(b->prefill_stage, table.data(), table.size() * sizeof(StepRow), hipMemcpyHostToDevice, b->stream));
+        WLK_HIP(hipStreamSynchronize(b->stream));           // `table` is pageable
+        nlb_prefill_chain(b, total);
+        WLK_HIP(hipStreamSynchronize(b->stream));
+        for (int i = 0; i < n; ++i) {
+            NlBatchSlot& s = b->slots[slots[i]];
+            s.self_len = prompt_offsets[i + 1] - prompt_offsets[i];
+            s.logits_row = -1;
+        }
+        return WLK_OK;
+    });
+}
+
 int wlk_nllb_batch_release(wlk_nllb_batch* b, int32_t slot) {
     if (!b) return nl_fail(WLK_ERR_ARG, "NULL argument");
     if (slot < 0 || slot >= b->n_slots) return nl_fail(WLK_ERR_ARG, "NLLB batch: slot index out of range");
@@ -510,6 +819,7 @@ int wlk_nllb_batch_release(wlk_nllb_batch* b, int32_t slot) {
     s.encoded = false;
     s.src_len = s.self_len = 0;
     s.logits_row = -1;
+    s.align_row = -1;
     return WLK_OK;
 }
 
@@ -528,6 +838,9 @@ int wlk_nllb_batch_export(wlk_nllb_batch* b, int32_t slot, const char* what, flo
             src = b->logits + (size_t)s.logits_row * D.vocab; n = (uint64_t)D.vocab;
         } else if (w == "enc") {
             src = s.enc_out; n = (uint64_t)s.src_len * D.d_model;
+        } else if (w == "align") {
+            if (s.align_row < 0) return nl_fail(WLK_ERR_STATE, "the slot was not in the latest align step: no alignment");
+            src = b->align_p + (size_t)s.align_row * D.max_src; n = (uint64_t)s.src_len;
         } else {
             return nl_fail(WLK_ERR_ARG, "unknown export " + w);
         }

@@ -59,6 +59,12 @@ inline void nl_ffn(const LaunchCtx& c, const NlLayer& L, float* x, float* h, flo
 constexpr int kNlMaxAlign = 64;
 void launch_nllb_align_readout(const LaunchCtx& ctx, const float* probs, int n_align, int rows, int S, const int* ctl,
                                float* p_out, int* pos, float* prob, float* mass);
+// The ragged form of a stacked align step (nllb_batch.hip): row r of n_rows (<= 8) has its own length
+// rows[r].content_len (<= stride <= 512) and its own window ctl[3 r .. 3 r + 2] = lo | hi | limit; probs
+// [n_align][head_stride / stride][stride], p_out [n_rows][stride].  Nothing is read or written at or past a row's length.
+void launch_nllb_align_readout_rows(const LaunchCtx& ctx, const float* probs, int n_align, long head_stride, int stride,
+                                    int n_rows, const StepRow* rows, const int* ctl, float* p_out, int* pos, float* prob,
+                                    float* mass);
 
 }  // namespace wlk
 

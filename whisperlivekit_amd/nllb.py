@@ -374,6 +374,52 @@ class HipNllbBatch:
                                                 lp.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p)))
         return lp, ids
 
+    def set_alignment_heads(self, pairs: Sequence[Tuple[int, int]]) -> None:
+        """The ``(decoder layer, head)`` pairs (1..64, no duplicates) ``step_align`` reads, for every slot; an empty list
+        switches the read-out off.  Nothing is allocated or recorded before the first ``step_align``."""
+        a = np.ascontiguousarray([tuple(int(v) for v in pr) for pr in pairs], dtype=np.int32).reshape(-1, 2)
+        _lib.check(self.lib.wlk_nllb_batch_set_align(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0]))
+
+    def prefill(self, slots: Sequence[int], prompts: Sequence[Sequence[int]]) -> None:
+        """One stacked decoder pass over the prompts of freshly encoded slots (wlk_nllb_batch_prefill): ``prompts[i]`` (at
+        least one id, at most ``max_tgt - 1``) fills positions ``0 .. len - 1`` of slot ``slots[i]``; no logits are formed -
+        the next token of a slot goes through ``step`` / ``step_align``."""
+        if len(slots) != len(prompts):
+            raise ValueError("prefill: one prompt per slot")
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        arrs = [np.asarray(pr, dtype=np.int64).reshape(-1) for pr in prompts]
+        off = np.zeros(len(arrs) + 1, np.int32)
+        off[1:] = np.cumsum([a.size for a in arrs])
+        ids = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros(0, np.int64))
+        _lib.check(self.lib.wlk_nllb_batch_prefill(self._h, sl.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p),
+                                                   off.ctypes.data_as(C.c_void_p), sl.size))
+
+    def step_align(self, slots: Sequence[int], tokens: Sequence[int], k: int, lo: Sequence[int], hi: Sequence[int],
+                   limit: Sequence[int]):
+        """``step`` + the alignment read-out of every row, one graph replay (wlk_nllb_batch_step_align) -> ``(logprobs
+        [rows, k], ids [rows, k], pos [rows], prob [rows], mass [rows])``; row r has its own window ``lo[r], hi[r]`` and
+        ``limit[r]`` over its own source (``HipNllbSession.step_align`` per row).  Every slot named holds a prompt already."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        t = np.ascontiguousarray(tokens, dtype=np.int64).reshape(-1)
+        win = [np.ascontiguousarray(w, dtype=np.int32).reshape(-1) for w in (lo, hi, limit)]
+        if any(a.size != sl.size for a in [t] + win):
+            raise ValueError("step_align: one token and one lo / hi / limit per slot")
+        n = sl.size
+        lp, ids = np.empty((n, k), np.float32), np.empty((n, k), np.int32)
+        pos, prob, mass = np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.float32)
+        _lib.check(self.lib.wlk_nllb_batch_step_align(self._h, sl.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), n, int(k),
+                                                      *(a.ctypes.data_as(C.c_void_p) for a in win + [lp, ids, pos, prob, mass])))
+        return lp, ids, pos, prob, mass
+
+    def alignment(self, slot: int) -> np.ndarray:
+        """``p [src_len]`` of the slot's row in the latest ``step_align``."""
+        return self._export(slot, "align", self.model.cdims.max_src)
+
+    def align_stats(self) -> Dict[str, int]:
+        steps, captures = C.c_uint64(), C.c_uint64()
+        _lib.check(self.lib.wlk_nllb_batch_align_stats(self._h, C.byref(steps), C.byref(captures)))
+        return {"align_steps": int(steps.value), "graph_captures": int(captures.value)}
+
     def release(self, slot: int) -> None:
         _lib.check(self.lib.wlk_nllb_batch_release(self._h, int(slot)))
 
@@ -604,6 +650,111 @@ def generate_batch(batch, sources: Sequence[Sequence[int]],
             if nxt == eos or len(out) == max_length:
                 del running[slot]
                 finish(item, slot)
+    return results
+
+
+def generate_alignatt_batch(batch, requests: Sequence[tuple], *,
+                            more: Optional[Callable[[], Optional[Iterable[tuple]]]] = None,
+                            done: Optional[Callable[[object, Tuple[List[int], List[int], str]], None]] = None
+                            ) -> List[Tuple[List[int], List[int], str]]:
+    """:func:`generate_alignatt` for any number of streaming updates through the slots of one batch (``HipNllbBatch`` with
+    alignment heads set, or anything with its ``n_slots`` / ``encode`` / ``prefill`` / ``step_align`` / ``release``).  Each
+    request is ``(src_ids, forced_bos_token_id, committed, n_accessible, threshold, final, max_new_tokens)`` and is decoded by
+    the rule of :func:`alignatt_loop`, unchanged; -> ``(new ids, their source positions, stop reason)`` per request, in input
+    order, the same as :func:`generate_alignatt` gives for it alone.
+
+    Admission is :func:`generate_batch`'s: waiting requests take free slots in order; those admitted together share ONE
+    stacked ``encode`` and ONE stacked ``prefill`` of their ``prompt[:-1]``; every token position is ONE ``step_align`` over
+    the rows still running, each with its own ``lo = 1``, ``hi = S - 1`` and ``limit``; a request that stops (``"attention"``
+    before ``"eos"``, ``"length"``, ``"context"``) releases its slot and the next waiting request joins at the following step.
+    A request with ``max_new_tokens`` 0 returns ``([], [], "length")`` without taking a slot.
+
+    ``more`` is polled once per step (and once more before the pass would end): it may return further requests with a
+    ticket appended, ``(..., max_new_tokens, ticket)``; the outcome of such a request goes to ``done(ticket, outcome)`` as
+    soon as it stops.  This is how a serving layer joins a running pass."""
+    cfg = batch.model.cfg
+    eos, start = cfg.eos_token_id, cfg.decoder_start_token_id
+    max_tgt = getattr(getattr(batch.model, "cdims", None), "max_tgt", None)
+    results: List[Optional[Tuple[List[int], List[int], str]]] = [None] * len(requests)
+
+    def item_of(req, index, ticket):
+        src, bos, committed, n_acc, thr, final, max_new = req
+        src = [int(t) for t in src]
+        n_acc, thr, max_new = int(n_acc), int(thr), int(max_new)
+        if not 0 <= n_acc <= len(src) or thr < 0 or max_new < 0:
+            raise ValueError("generate_alignatt_batch: needs 0 <= n_accessible <= len(src_ids), threshold >= 0, max_new_tokens >= 0")
+        lo = 1
+        return dict(src=src, prompt=[start, int(bos)] + [int(t) for t in committed], lo=lo, hi=len(src) - 1,
+                    limit=min(max(n_acc - thr, lo), len(src)), final=bool(final), max_new=max_new, index=index, ticket=ticket,
+                    out=[], align=[])
+
+    waiting = [item_of(req, i, None) for i, req in enumerate(requests)]
+    free = list(range(batch.n_slots))
+    running: Dict[int, dict] = {}                      # slot -> request, in admission order
+
+    def finish(item, why, slot=None):
+        if slot is not None:
+            del running[slot]
+            batch.release(slot)
+            free.append(slot)
+            free.sort()
+        outcome = (item["out"], item["align"], why)
+        if item["index"] is not None:
+            results[item["index"]] = outcome
+        elif done is not None:
+            done(item["ticket"], outcome)
+
+    def stopped_before_a_step(item) -> Optional[str]:  # alignatt_loop's checks at the top of its loop
+        if len(item["out"]) >= item["max_new"]:
+            return "length"
+        if max_tgt is not None and item["fed"] + 1 > max_tgt:
+            return "context"
+        return None
+
+    while True:
+        if more is not None:
+            for req in (more() or ()):
+                waiting.append(item_of(req[:-1], None, req[-1]))
+        admitted = []
+        while waiting:
+            item = waiting[0]
+            item["fed"], item["last"] = len(item["prompt"]) - 1, item["prompt"][-1]
+            why = stopped_before_a_step(item)
+            if why is None and not free:
+                break
+            waiting.pop(0)
+            if why is not None:                        # nothing to decode: no slot is taken
+                finish(item, why)
+                continue
+            admitted.append((free.pop(0), item))
+        if admitted:
+            slots = [s for s, _ in admitted]
+            batch.encode(slots, [it["src"] for _, it in admitted])
+            batch.prefill(slots, [it["prompt"][:-1] for _, it in admitted])
+            running.update(admitted)
+        if not running:
+            if waiting:
+                continue
+            break
+        slots = list(running)
+        rows = [running[s] for s in slots]
+        _lp, ids, pos, _prob, _mass = batch.step_align(slots, [it["last"] for it in rows], 1, [it["lo"] for it in rows],
+                                                       [it["hi"] for it in rows], [it["limit"] for it in rows])
+        for r, (slot, item) in enumerate(zip(slots, rows)):
+            item["fed"] += 1
+            y, a = int(ids[r, 0]), int(pos[r])
+            if not item["final"] and (a < 0 or a >= item["limit"]):
+                finish(item, "attention", slot)
+                continue
+            if y == eos:
+                finish(item, "eos", slot)
+                continue
+            item["out"].append(y)
+            item["align"].append(a)
+            item["last"] = y
+            why = stopped_before_a_step(item)
+            if why is not None:
+                finish(item, why, slot)
     return results
 
 

@@ -45,6 +45,11 @@ Opt-in stacking (``HipNllbTranslationModel(stack=n)`` / ``WLK_NLLB_STACK=n``, gr
 ``HipNllbBatch`` of n slots and every session hands the segments of a ``process()`` - the closed sentences and the open
 one - to it as one request list; sentences of different sessions that are in flight at the same time share every decoder
 weight pass (``nllb.generate_batch``).  The validated text and the buffers are the ones of the default path.
+
+Stacked AlignAtt (``policy="alignatt", stack=n``): the batch has the alignment heads set, and every
+update or final pass of every session is ONE request to :class:`NllbAlignAttStacker` - updates of different sessions that
+fall on the same ASR tick share the stacked encode, the stacked prefill of their committed ids and every decoder step
+(``nllb.generate_alignatt_batch``).  The sessions hold no device state; their texts are those of the unstacked policy.
 """
 from __future__ import annotations
 
@@ -129,13 +134,22 @@ class NllbStacker:
 
     def translate_many(self, requests: Sequence[Tuple[Sequence[int], Optional[int], int]]) -> List[List[int]]:
         """``requests``: ``(source ids, forced_bos_token_id, max_new_tokens)`` per sentence -> their ids, in order."""
+        return self._submit([(list(src), bos, int(max_new)) for src, bos, max_new in requests])
+
+    def _drive(self, more, done) -> None:
+        """one pass over the batch: returns when the batch is empty and ``more`` has nothing left"""
+        nllb.generate_batch(self.batch, [], more=more, done=done)
+
+    def _submit(self, requests: Sequence[tuple]) -> list:
+        """queues ``requests`` (the pass's request tuples, without ticket) and waits for their outcomes, driving the pass if
+        nobody else is"""
         if not requests:
             return []
         with self._cv:
             tickets = list(range(self._next_ticket, self._next_ticket + len(requests)))
             self._next_ticket += len(requests)
-            for t, (src, bos, max_new) in zip(tickets, requests):
-                self._queue.append((list(src), bos, int(max_new), t))
+            for t, req in zip(tickets, requests):
+                self._queue.append((*req, t))
                 self._open.add(t)
         while True:
             with self._cv:
@@ -165,7 +179,7 @@ class NllbStacker:
 
         error: Optional[BaseException] = None
         try:
-            nllb.generate_batch(self.batch, [], more=more, done=done)
+            self._drive(more, done)
         except BaseException as e:                 # the pass is gone: everyone in it or queued behind it gets the error
             error = e
             for slot in range(self.batch.n_slots):  # the next pass starts from free slots
@@ -187,6 +201,20 @@ class NllbStacker:
             raise error
 
 
+class NllbAlignAttStacker(NllbStacker):
+    """:class:`NllbStacker` for ``policy="alignatt"``: the same queue, runner and failure contract over
+    ``nllb.generate_alignatt_batch``; ``passes`` counts its passes, ``sentences`` the updates and finals they served."""
+
+    def decode_many(self, requests: Sequence[tuple]) -> List[Tuple[List[int], List[int], str]]:
+        """``requests``: ``(source ids, forced_bos_token_id, committed ids, n_accessible, threshold, final, max_new_tokens)`` per
+        update -> ``(new ids, their source positions, stop reason)`` each, in order."""
+        return self._submit([(list(src), int(bos), [int(t) for t in committed], int(n_acc), int(thr), bool(final), int(max_new))
+                             for src, bos, committed, n_acc, thr, final, max_new in requests])
+
+    def _drive(self, more, done) -> None:
+        nllb.generate_alignatt_batch(self.batch, [], more=more, done=done)
+
+
 class HipNllbTranslationModel:
     """The server-wide handle ``nllw.load_model`` returns in the reference (``TranscriptionEngine.translation_model``,
     core.py:320-329): one network per GPU shared by every session, plus the tokenizer and the decoding options.  Device
@@ -201,7 +229,11 @@ class HipNllbTranslationModel:
         source position lies within ``threshold`` tokens of the end of the committed source is held back;
         ``alignment_heads`` = ``(decoder layer, head)`` pairs, ``None`` = ``nllb.default_alignment_heads`` - neither that
         default nor ``threshold=2`` has been validated on trained weights; ``hypothesis_tail`` asks the ASR for its unstable
-        tail and feeds it to the encoder as context no token may be committed from."""
+        tail and feeds it to the encoder as context no token may be committed from.
+
+        ``policy="alignatt"`` with ``stack=n`` (or ``WLK_NLLB_STACK=n``) stacks: the model owns one batch of n slots with
+        the alignment heads set and a :class:`NllbAlignAttStacker`, and the sessions submit their updates to it instead of
+        owning a device session.  (Before DESIGN.md section 22 this combination silently ran unstacked.)"""
         if policy not in ("local_agreement", "alignatt"):
             raise ValueError("policy must be 'local_agreement' or 'alignatt'")
         if policy == "alignatt" and int(num_beams) != 1:
@@ -210,8 +242,6 @@ class HipNllbTranslationModel:
             raise ValueError("threshold must be >= 0")
         self.policy, self.threshold, self.hypothesis_tail = policy, int(threshold), bool(hypothesis_tail)
         self.alignment_heads = None if alignment_heads is None else [(int(l), int(h)) for l, h in alignment_heads]
-        if policy == "alignatt":
-            stack = 0                              # the stacked slots have no alignment read-out
         self.model, self.tokenizer = model, tokenizer
         self.num_beams, self.max_new_tokens, self.max_source_tokens = int(num_beams), int(max_new_tokens), int(max_source_tokens)
         # a tokenizer with a mutable src_lang (transformers' NllbTokenizer) is shared by all sessions
@@ -219,7 +249,13 @@ class HipNllbTranslationModel:
         # opt-in: one batch of `stack` slots shared by every session (greedy decoding only; beams keep their own sessions)
         self.stack = resolve_stack(stack) if self.num_beams == 1 else 0
         self.batch = model.new_batch(self.stack) if self.stack else None
-        self.stacker = NllbStacker(self.batch) if self.batch is not None else None
+        self.stacker = None
+        if self.batch is not None and policy == "alignatt":
+            heads = self.alignment_heads if self.alignment_heads is not None else nllb.default_alignment_heads(model.cfg)
+            self.batch.set_alignment_heads(heads)
+            self.stacker = NllbAlignAttStacker(self.batch)
+        elif self.batch is not None:
+            self.stacker = NllbStacker(self.batch)
 
     def language_id(self, code: str) -> int:
         tid = self.tokenizer.convert_tokens_to_ids(code)
@@ -429,7 +465,8 @@ class HipAlignAttTranslation:
     * ``hypothesis_tail``: the newest ``HypothesisTail`` text is appended to the source as words no token may be committed
       from; a change of the tail alone re-runs the update at most every ``TAIL_INTERVAL`` seconds.
 
-    One call in flight per session; the device session is 1-row."""
+    One call in flight per session; the device session is 1-row.  Over a stacked model (``stack=n``) there is no device
+    session: every update and final is one request to the model's :class:`NllbAlignAttStacker`."""
 
     TAIL_INTERVAL = 0.5
 
@@ -442,9 +479,11 @@ class HipAlignAttTranslation:
         self.target_id = translation_model.language_id(self.target_language)       # ValueError for an unknown code
         translation_model.language_id(self.source_language)
         self.wants_hypothesis_tail = bool(translation_model.hypothesis_tail)
-        self.session = translation_model.model.new_session(rows=1)
-        heads = translation_model.alignment_heads
-        self.session.set_alignment_heads(heads if heads is not None else nllb.default_alignment_heads(translation_model.model.cfg))
+        self.session = None
+        if translation_model.stacker is None:
+            self.session = translation_model.model.new_session(rows=1)
+            heads = translation_model.alignment_heads
+            self.session.set_alignment_heads(heads if heads is not None else nllb.default_alignment_heads(translation_model.model.cfg))
         self._device_loop = hasattr(self.session, "generate_alignatt_loop")
         self._clock = clock
         self._open = _Sentence()
@@ -526,15 +565,20 @@ class HipAlignAttTranslation:
         self._silence += float(duration or 0.0)
 
     def close(self) -> None:
-        self.session.close()
+        if self.session is not None:
+            self.session.close()
 
     # ---- internals --------------------------------------------------------------------------------------------------
     def _decode_on(self, sent: _Sentence, src: Sequence[int], n_accessible: int, final: bool) -> None:
         m = self.shared
         room = m.max_new_tokens - len(sent.ids)
-        new_ids, _align, _why = nllb.generate_alignatt(self.session, src, self.target_id, committed=sent.ids,
-                                                       n_accessible=n_accessible, threshold=m.threshold, final=final,
-                                                       max_new_tokens=max(room, 0), device_loop=self._device_loop)
+        if m.stacker is not None:                     # stacked serving: one request, decoded beside other sessions' updates
+            (new_ids, _align, _why), = m.stacker.decode_many([(src, self.target_id, sent.ids, n_accessible, m.threshold, final,
+                                                               max(room, 0))])
+        else:
+            new_ids, _align, _why = nllb.generate_alignatt(self.session, src, self.target_id, committed=sent.ids,
+                                                           n_accessible=n_accessible, threshold=m.threshold, final=final,
+                                                           max_new_tokens=max(room, 0), device_loop=self._device_loop)
         sent.ids = sent.ids + [int(t) for t in new_ids]
         text = m.decode(sent.ids).strip()
         if text.startswith(sent.text):
