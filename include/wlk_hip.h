@@ -278,6 +278,35 @@ int wlk_beam_job_result(wlk_beam_job* j, wlk_loop_result* result, int64_t* new_t
                         int32_t* step_frames, float* step_sum_logprobs, int cap);
 int wlk_beam_job_destroy(wlk_beam_job* j);
 
+/* ---- CIF end-of-word head on the device (opt-in) -------------------------------------------------------
+ * Replaces, for callers that ask for it, the host evaluation of simul_whisper/eow_detection.py:62-77 (fire_at_boundary) and
+ * the read-back of the encoder output it needs.  The head (a Linear(n_audio_state, 1): weight [d] and bias) lives in a
+ * device buffer of the model beside the weight arena; weight_host == NULL removes it.  d != n_audio_state: WLK_ERR_ARG.
+ * While a model has a head, every wlk_encode enqueues two small kernels behind the cross-attention K/V projection, on
+ * the stream the encode runs on: alpha[t] = sigmoid(x[t] . w + b) over the T = min(content_mel_len, n_audio_ctx) content
+ * rows, then resize() and the integrate-and-fire test in fp32, leaving the record below in host-coherent memory.  Models
+ * without a head launch and allocate nothing.  Not to be called while an encode of the model is in flight. */
+typedef struct wlk_cif_out {
+    int32_t fire;            /* the decision: 1 = the chunk ends at a word boundary */
+    int32_t n;               /* round(sum(alpha)), ties to even */
+    int32_t cnt;             /* floor(integrate[-1] / 0.999) */
+    int32_t pos;             /* first index with integrate - cnt >= 0, -1 = none */
+    int32_t resize_rounds;   /* rounds of resize()'s loop that ran (0..10) */
+    float total;             /* sum(alpha) */
+    float integ_last;        /* integrate[-1] = cumsum(alpha')[T - 2] */
+    uint32_t seq;            /* sequence number of the encode the record belongs to; written last */
+} wlk_cif_out;
+int wlk_model_set_cif(wlk_model* m, const float* weight_host, int d, float bias);
+/* The record of the session's last encode.  WLK_ERR_STATE when the model has no head, nothing has been encoded with it,
+ * or that encode had fewer than two content frames (the reference raises there).  Waits for the encode's stream only if
+ * the record has not arrived yet. */
+int wlk_cif_result(wlk_session* s, wlk_cif_out* out);
+/* Diagnostic (tests): the two production kernels on host data.  feat_host holds n_stack (1..8) blocks of [T][d]; block i
+ * is evaluated over its first t_each[i] rows (t_each == NULL: T rows each) as session i of one stacked launch, from fp32
+ * rows or, as_x3 != 0, from the X3 image packed on the device.  alphas_out [n_stack][T] (may be NULL), out [n_stack]. */
+int wlk_diag_cif(const float* feat_host, int T, int d, const float* weight, float bias, int as_x3, int n_stack,
+                 const int32_t* t_each, float* alphas_out, wlk_cif_out* out);
+
 /* Parity/debug exports to host memory.  what: "mel" [n_mels,3000], "enc" [1500,d],
  * "logits_last" / "logits_sot" [n_rows,V], "attn_last" [n_rows, content_mel_len] (after
  * wlk_select), "cross_qk:<layer>" [rows, H, 1500] of the latest wlk_decode (debug sessions only),

@@ -112,6 +112,12 @@ DA_C0, DA_C1, DA_C2, DA_C3, DA_C4, DA_C5 = 10, 11, 12, 13, 14, 15
 DA_A0, DA_G0, DA_K0, DA_K1 = 20, 21, 22, 23
 
 
+class CifOut(C.Structure):
+    """wlk_cif_out (include/wlk_hip.h): the device CIF head's record of one encode"""
+    _fields_ = [(n, C.c_int32) for n in ("fire", "n", "cnt", "pos", "resize_rounds")] + [
+        ("total", C.c_float), ("integ_last", C.c_float), ("seq", C.c_uint32)]
+
+
 class LoopResult(C.Structure):
     """wlk_loop_result (include/wlk_hip.h)"""
     _fields_ = [("n_steps", C.c_int32), ("n_new_tokens", C.c_int32), ("stop_reason", C.c_int32),
@@ -309,6 +315,9 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_nllb_align": (cint, [p, i32, i32, i32, i32, i32, i32, p, p, p, p]),
         "wlk_diag_nllb_align_rows": (cint, [p, i32, i32, i32, p, p, p, p, p, p, p, p]),
         "wlk_diag_sf_kernel": (cint, [C.POINTER(DiagSfKernelArgs)]),
+        "wlk_model_set_cif": (cint, [p, p, cint, C.c_float]),
+        "wlk_cif_result": (cint, [p, C.POINTER(CifOut)]),
+        "wlk_diag_cif": (cint, [p, cint, cint, p, C.c_float, cint, cint, p, p, p]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -360,6 +369,7 @@ EXPORTED_SYMBOLS = (
     "wlk_diag_encoder_attention_x3", "wlk_diag_encoder_attention_x3_time", "wlk_diag_qkv_x3_attention",
     "wlk_diag_select", "wlk_diag_dec_attention", "wlk_diag_topk", "wlk_diag_sf_kernel", "wlk_diag_nllb_align",
     "wlk_diag_nllb_align_rows",
+    "wlk_model_set_cif", "wlk_cif_result", "wlk_diag_cif",
 )
 
 

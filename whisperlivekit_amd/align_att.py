@@ -72,6 +72,29 @@ class EncoderFeature:
         return full[:, : self.shape[1], :]
 
 
+class DeviceFire:
+    """fire_at_boundary's answer when the CIF head runs on the device: the kernels were enqueued behind the
+    encoder; the record is read - once - when the policy evaluates ``fire_detected or is_last`` after the decode loop."""
+    __slots__ = ("_session", "_value", "record")
+
+    def __init__(self, session):
+        self._session, self._value, self.record = session, None, None
+
+    def __bool__(self) -> bool:
+        if self._value is None:
+            self.record = self._session.cif_result()
+            self._value = bool(self.record.fire)
+        return self._value
+
+    def __repr__(self):
+        return f"DeviceFire({'pending' if self._value is None else self._value})"
+
+
+def cif_device_enabled(hip_model) -> bool:
+    """The opt-in switch: ``HipSimulStreamingASR(cif_device=True)`` marks the shared model, WLK_CIF_DEVICE=1 the process."""
+    return bool(getattr(hip_model, "cif_device", False)) or os.environ.get("WLK_CIF_DEVICE", "0") == "1"
+
+
 class _Column:
     """``logits[:, tok]`` inside the reference's DRY penalty (align_att_base.py:535):
     supports ``- x`` and ``+ x`` and remembers which column it is."""
@@ -170,6 +193,10 @@ class HipAlignAttHooks:
         else:
             st.always_fire, st.never_fire = False, bool(cfg.never_fire)
             self._load_cif(cfg.cif_ckpt_path)
+            if cif_device_enabled(self.model):
+                # the head goes to the device once per shared model; every encode then leaves the decision there
+                self.model.ensure_cif(cfg.cif_ckpt_path, st.cif_weight, st.cif_bias)
+                self._cif_on_device = True
         st.align_source = {}
         st.num_align_heads = 0
         for layer, head in self.model.alignment_heads:             # simul_whisper.py:151-159
@@ -303,6 +330,11 @@ class HipAlignAttHooks:
             return False
         if st.cif_weight is None:
             return False
+        if getattr(self, "_cif_on_device", False):
+            if feature.shape[1] < 2:
+                # the reference indexes integrate[-1] of an empty tensor here (eow_detection.py:70-71)
+                raise IndexError("index -1 is out of bounds for dimension 0 with size 0")
+            return DeviceFire(self.session)
         return P.cif_fire_at_boundary(feature.numpy()[0], st.cif_weight, st.cif_bias)
 
     def lang_id(self, encoder_features):

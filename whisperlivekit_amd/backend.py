@@ -67,7 +67,8 @@ class HipSimulStreamingASR:
                  state_dict=None, dims: Optional[ModelDims] = None, alignment_heads=None,
                  synthetic_seed: Optional[int] = None, hip_model: Optional[HipWhisperModel] = None,
                  custom_alignment_heads: Optional[Sequence[Tuple[int, int]]] = None,
-                 hw_queues: Optional[int] = None, lora_path: Optional[str] = None, **cfg_kwargs):
+                 hw_queues: Optional[int] = None, lora_path: Optional[str] = None, cif_device: Optional[bool] = None,
+                 **cfg_kwargs):
         if hw_queues is not None:     # explicit deployment knob (process-wide, see _lib.configure_hw_queues); default: off
             from . import _lib
             _lib.configure_hw_queues(hw_queues)
@@ -103,6 +104,10 @@ class HipSimulStreamingASR:
         else:
             raise ValueError("give one of hip_model, model_path, state_dict or synthetic_seed")
         self.shared_model = self.hip_model      # the name the reference processor reads
+        # opt-in (default off; WLK_CIF_DEVICE=1 switches it on process-wide): with a cif_ckpt_path, the CIF end-of-word
+        # decision is computed on the GPU behind the encoder instead of from a read-back of its output
+        if cif_device is not None:
+            self.hip_model.cif_device = bool(cif_device)
 
     def transcribe(self, audio):                # backend.py:566-570: warm-up happens at load time
         pass

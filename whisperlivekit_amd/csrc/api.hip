@@ -403,6 +403,7 @@ int wlk_model_destroy(wlk_model* m) {
     (void)hipFree(m->layer_heads);
     (void)hipFree(m->layer_ranks);
     (void)hipFree(m->all_ranks);
+    if (m->cif_w) (void)hipFree(m->cif_w);
     delete m;
     return WLK_OK;
 }
@@ -509,6 +510,7 @@ int wlk_session_create(wlk_model* m, int beam, int max_audio_samples, wlk_sessio
             s->result_host_dev = reinterpret_cast<StepResult*>(static_cast<char*>(dp) + 2048);
             s->step_dev = reinterpret_cast<StepBlock*>(dev_alloc<int>(sizeof(StepBlock) / 4));
         }
+        if (m->cif_w) wlk_cif_session_prepare(s.get());
         WLK_HIP(hipStreamSynchronize(st));
         *out = s.release();
         return WLK_OK;
@@ -554,6 +556,7 @@ int wlk_session_destroy(wlk_session* s) {
     if (s->step_host) (void)hipHostFree(s->step_host);
     if (s->step_dev) (void)hipFree(s->step_dev);
     if (s->step_align_dev) (void)hipFree(s->step_align_dev);
+    wlk_cif_session_free(s);
     for (auto& e : s->fstep_exec)
         if (e) (void)hipGraphExecDestroy(e);
     for (auto& r : s->prof.recs) {
@@ -950,6 +953,11 @@ extern "C++" void wlk_encode_group(const std::vector<wlk_session*>& group, const
         }
         for (int i = 0; i < B; ++i) group[i]->enc_out_is_x3 = m->xkv_all_w3 != nullptr;
     }
+    // optional CIF end-of-word head (cif.hip): two small kernels behind the chain, the decision stays on the device until
+    // wlk_cif_result asks for it
+    if (m->cif_w) wlk_cif_enqueue(group, c, content_out);
+    else
+        for (int i = 0; i < B; ++i) group[i]->cif_T = -1;
     for (int i = 0; i < B; ++i) {
         wlk_session* s = group[i];
         s->encoded = true;

@@ -154,6 +154,9 @@ struct wlk_model {
     const float *w_tok_emb = nullptr, *w_dec_pos = nullptr, *w_ln_w = nullptr, *w_ln_b = nullptr;
     wlk_engine* engine = nullptr;     // cross-session batched decode steps (engine.hip), created on first attach
     std::mutex engine_mu;
+    // optional CIF end-of-word head (cif.hip; wlk_model_set_cif): a buffer of its own beside the arena, nullptr = none
+    float* cif_w = nullptr;           // [n_audio_state]
+    float cif_b = 0.f;
 
     const float* w(const std::string& name) const {
         auto it = by_name.find(name);
@@ -275,6 +278,13 @@ struct wlk_session {
     float* wa_buf = nullptr;
     size_t wa_cap = 0;
     wlk_engine* engine = nullptr;   // set by wlk_engine_attach: single-token steps run batched with the other attached sessions
+    // CIF head on the device (cif.hip): allocated by the first encode that finds a head on the model (or at creation when
+    // it is already set), for any beam count
+    float* cif_alpha = nullptr;                                  // [n_audio_ctx]
+    wlk_cif_out *cif_host = nullptr, *cif_host_dev = nullptr;    // host-coherent record and its device-side address
+    unsigned cif_seq = 0;                                        // sequence number of the last encode with a head
+    int cif_T = -1;                                              // its content rows; -1 = no such encode yet
+    hipStream_t cif_stream = nullptr;                            // the stream it ran on
 };
 
 
@@ -375,6 +385,11 @@ std::string wlk_prefill_precheck(const wlk_prefill_item& it, const wlk_prefill_w
 void wlk_prefill_group(const std::vector<wlk_prefill_item*>& items, const wlk::LaunchCtx& c, wlk_prefill_ws& ws);
 void wlk_prefill_ws_alloc(const wlk_model* m, wlk_prefill_ws& ws, int max_sessions, int session_rows);
 void wlk_prefill_ws_free(wlk_prefill_ws& ws);
+
+// cif.hip
+void wlk_cif_session_prepare(wlk_session* s);
+void wlk_cif_session_free(wlk_session* s);
+void wlk_cif_enqueue(const std::vector<wlk_session*>& group, const wlk::LaunchCtx& c, const std::vector<int>& content);
 
 // engine.hip
 // the prefill of an attached session through the engine's prefill lane (stacked with the prefills other sessions have

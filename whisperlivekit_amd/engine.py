@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import threading
 from typing import Dict, Iterable, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
@@ -122,6 +123,11 @@ class HipWhisperModel:
         _lib.check(self.lib.wlk_model_create(C.byref(_cdims(dims)), device, ptr, C.byref(self._h)))
         self.alignment_heads: List[Tuple[int, int]] = []
         self.finalized = False
+        # CIF end-of-word head on the device (opt-in; align_att.cif_device_enabled): the switch, and which checkpoint the
+        # first session put there
+        self.cif_device = False
+        self._cif_lock = threading.Lock()
+        self._cif_path: Optional[str] = None
         # the reference's AlignAttBase._base_init reads len(model.decoder.blocks) (align_att_base.py:58)
         import types
         self.decoder = types.SimpleNamespace(blocks=[None] * dims.n_text_layer)
@@ -183,6 +189,29 @@ class HipWhisperModel:
         if batched:
             s.attach_engine()
         return s
+
+    def set_cif(self, weight, bias: float = 0.0) -> None:
+        """Put the CIF end-of-word head (a Linear(n_audio_state, 1): ``weight`` [d], ``bias``) on the device beside the
+        weights: every later encode of this model's sessions leaves the head's decision on the device
+        (:meth:`HipSession.cif_result`).  ``weight=None`` removes it.  Not while an encode of this model is running."""
+        if weight is None:
+            _lib.check(self.lib.wlk_model_set_cif(self._h, None, 0, 0.0))
+            return
+        w = _as_f32(weight).reshape(-1)
+        _lib.check(self.lib.wlk_model_set_cif(self._h, w.ctypes.data_as(C.c_void_p), w.size, float(bias)))
+
+    def ensure_cif(self, path: str, weight, bias: float) -> None:
+        """Called by every session that uses the device CIF head: the first one uploads it (under the model's lock,
+        before that session's first encode); a later session configured with another checkpoint is refused - the head
+        belongs to the shared model."""
+        key = os.path.abspath(str(path))
+        with self._cif_lock:
+            if self._cif_path is None:
+                self.set_cif(weight, bias)
+                self._cif_path = key
+            elif self._cif_path != key:
+                raise ValueError(f"this model's device CIF head was loaded from {self._cif_path}; a session asked for "
+                                 f"{key} (one head per shared model)")
 
     def engine_stats(self) -> Dict[str, int]:
         """Iterations of this GPU's batch engine and the rows (= session steps) advanced in them."""
@@ -247,6 +276,7 @@ class HipSession:
         self._h = C.c_void_p()
         _lib.check(self.lib.wlk_session_create(model._h, beam, max_audio_samples, C.byref(self._h)))
         self.max_audio_samples = max_audio_samples
+        self.export_calls: Dict[str, int] = {}      # wlk_export calls by name (tests pin what stays on the device)
 
     # -- audio (a1) -------------------------------------------------------------------------
     def append(self, pcm: np.ndarray) -> None:
@@ -278,6 +308,13 @@ class HipSession:
         cml = C.c_int32()
         _lib.check(self.lib.wlk_encode(self._h, C.byref(cml)))
         return cml.value
+
+    def cif_result(self) -> "_lib.CifOut":
+        """The device CIF head's record of the last encode (wlk_cif_result): ``fire`` is the end-of-word decision.
+        Waits for the encode only if its record has not arrived yet."""
+        out = _lib.CifOut()
+        _lib.check(self.lib.wlk_cif_result(self._h, C.byref(out)))
+        return out
 
     def encode_mel(self, mel: np.ndarray) -> None:
         """Encode a [n_mels, 3000] log-mel segment as whisper.transcribe() / find_alignment hand it to the model
@@ -454,6 +491,7 @@ class HipSession:
                              self.beam * d.n_text_ctx * d.n_text_head * 1500)
         buf = np.empty(max_floats, np.float32)
         n = C.c_uint64()
+        self.export_calls[what] = self.export_calls.get(what, 0) + 1
         _lib.check(self.lib.wlk_export(self._h, what.encode(), buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(n)))
         return buf[: n.value].copy()
 
