@@ -849,6 +849,45 @@ typedef struct wlk_diag_sf_kernel_args {
     float* out;                     /* in / out [out_floats] */
 } wlk_diag_sf_kernel_args;
 int wlk_diag_sf_kernel(const wlk_diag_sf_kernel_args* args);
+/* ONE linear layer C = epilogue(LayerNorm?(A) W^T + bias) on host data through a production launcher, unchanged, with
+ * every operand a launch can carry.  route: 0 = launch_linear's own choice, 1 = launch_gemv, 2 / 3 / 4 = launch_gemm
+ * with force_kernel (k-wave, 64x64, k-pipe), 5 .. 8 = launch_gemm_kp as wlk_diag_linear encodes them.
+ *   a [a_floats] rows lda apart, w [n][k], bias [n] or NULL, ln_gamma / ln_beta [k] or NULL (fused LayerNorm of the rows),
+ *   c [c_floats] rows ldc apart, arriving as the caller filled it.  Residual (flags & 2): r [r_floats] rows ldr apart, or
+ *   with r_is_c the output buffer itself (its preloaded values; ldr = ldc).
+ *   kv_mode 1: columns [kv_d, 3 kv_d) of row (beam, t) also go to kcache / vcache [beams][kv_ctx][kv_d] at position
+ *   kv_pos + t (rows are [beam][kv_ntok]; the GEMV kernels take kv_ntok = 1 only).  kv_mode 2 (route 1 only): row r
+ *   appends to cache kv_row_cache[r] of n_caches caches lying cache_stride floats apart in kcache / vcache, at
+ *   kv_layer_off + kv_row_offset[r] * kv_d (the StepRow table is built on the device).
+ *   batch > 0: z = 0 .. batch - 1 operand sets at a + a_off[z], c + c_off[z], r + r_off[z] (floats).
+ * Every buffer lives on the device in exactly the floats the caller passes and is copied back whole - inputs too - so a
+ * guard pattern around the addressed part travels both ways.  What a buffer cannot hold, or what a launcher refuses,
+ * returns WLK_ERR_ARG with a message in wlk_diag_last_error() and leaves every buffer untouched; no other route runs
+ * instead.  All pointers are host memory; the call is synchronous. */
+typedef struct wlk_diag_linear_args {
+    int32_t route, m, n, k, flags, scale_cols, scale_period, r_is_c;
+    int32_t kv_mode, kv_pos, kv_d, kv_ctx, kv_ntok, n_caches, batch;
+    int32_t kv_row_cache[8], kv_row_offset[8];
+    float scale;
+    int64_t lda, ldr, ldc, kv_layer_off, cache_stride;
+    int64_t a_floats, w_floats, bias_floats, ln_floats, r_floats, c_floats, cache_floats;
+    int64_t a_off[8], c_off[8], r_off[8];
+    float* a;                       /* in / out */
+    float* w;                       /* in / out */
+    float* bias;                    /* in / out, or NULL */
+    float* ln_gamma;                /* in / out [ln_floats], or NULL */
+    float* ln_beta;                 /* in / out [ln_floats] */
+    float* r;                       /* in / out, or NULL */
+    float* c;                       /* in / out */
+    float* kcache;                  /* in / out [cache_floats] */
+    float* vcache;                  /* in / out [cache_floats] */
+} wlk_diag_linear_args;
+int wlk_diag_linear_ex(const wlk_diag_linear_args* args);
+/* Which kernel launch_gemv takes for m rows of an n x k layer (has_ln: fused LayerNorm; kv_mode as above), as text:
+ * "gemv1<UB,RPW,ln|plain,full|part>" for the single-row kernel, "gemv<MR,RPW>" for the staged one.  The answer of the
+ * function launch_gemv itself switches on; needs no device.  A shape launch_gemv refuses returns WLK_ERR_ARG and the
+ * refusal as text. */
+int wlk_diag_gemv_variant(int m, int n, int k, int has_ln, int kv_mode, char* out_text, int cap);
 /* the VALU wave butterflies of csrc/wave_ops.h (DPP / v_permlane{16,32}_swap) against the __shfl_xor loops they replace,
  * on one wave of 64 floats: ten rows of 64 results each (sum, max, 16-lane sum, xor 1 .. 32 exchanges, arg-max index) */
 int wlk_diag_wave_ops(const float* in64, float* out640, float* ref640);

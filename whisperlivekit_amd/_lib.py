@@ -106,6 +106,18 @@ class DiagSfKernelArgs(C.Structure):
                                   "bn_invstd", "bn_w", "bn_b", "out")]
 
 
+class DiagLinearArgs(C.Structure):
+    """wlk_diag_linear_args (include/wlk_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "route", "m", "n", "k", "flags", "scale_cols", "scale_period", "r_is_c", "kv_mode", "kv_pos", "kv_d", "kv_ctx",
+        "kv_ntok", "n_caches", "batch")] + [("kv_row_cache", C.c_int32 * 8), ("kv_row_offset", C.c_int32 * 8),
+                                            ("scale", C.c_float)] + [
+        (n, C.c_int64) for n in ("lda", "ldr", "ldc", "kv_layer_off", "cache_stride", "a_floats", "w_floats", "bias_floats",
+                                 "ln_floats", "r_floats", "c_floats", "cache_floats")] + [
+        ("a_off", C.c_int64 * 8), ("c_off", C.c_int64 * 8), ("r_off", C.c_int64 * 8)] + [
+        (n, C.c_void_p) for n in ("a", "w", "bias", "ln_gamma", "ln_beta", "r", "c", "kcache", "vcache")]
+
+
 SFK_ATTENTION, SFK_CONV0, SFK_DWCONV2D, SFK_GLU_DWCONV, SFK_HEAD, SFK_ASSEMBLE = range(6)
 DA_S0, DA_S1, DA_S2 = 0, 1, 2
 DA_C0, DA_C1, DA_C2, DA_C3, DA_C4, DA_C5 = 10, 11, 12, 13, 14, 15
@@ -315,6 +327,8 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_nllb_align": (cint, [p, i32, i32, i32, i32, i32, i32, p, p, p, p]),
         "wlk_diag_nllb_align_rows": (cint, [p, i32, i32, i32, p, p, p, p, p, p, p, p]),
         "wlk_diag_sf_kernel": (cint, [C.POINTER(DiagSfKernelArgs)]),
+        "wlk_diag_linear_ex": (cint, [C.POINTER(DiagLinearArgs)]),
+        "wlk_diag_gemv_variant": (cint, [cint, cint, cint, cint, cint, C.c_char_p, cint]),
         "wlk_model_set_cif": (cint, [p, p, cint, C.c_float]),
         "wlk_cif_result": (cint, [p, C.POINTER(CifOut)]),
         "wlk_diag_cif": (cint, [p, cint, cint, p, C.c_float, cint, cint, p, p, p]),
@@ -368,7 +382,7 @@ EXPORTED_SYMBOLS = (
     "wlk_diag_linear_x3", "wlk_diag_linear_x3_time", "wlk_diag_layernorm_x3",
     "wlk_diag_encoder_attention_x3", "wlk_diag_encoder_attention_x3_time", "wlk_diag_qkv_x3_attention",
     "wlk_diag_select", "wlk_diag_dec_attention", "wlk_diag_topk", "wlk_diag_sf_kernel", "wlk_diag_nllb_align",
-    "wlk_diag_nllb_align_rows",
+    "wlk_diag_nllb_align_rows", "wlk_diag_linear_ex", "wlk_diag_gemv_variant",
     "wlk_model_set_cif", "wlk_cif_result", "wlk_diag_cif",
 )
 

@@ -250,6 +250,18 @@ inline int gemv_row_bucket(int M) { return M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 
 inline bool gemv_applicable(int M, int K) {
     return M <= 8 && (long)gemv_row_bucket(M) * K * 4 <= 64 * 1024 && K % 4 == 0;
 }
+// What launch_gemv launches for a set of arguments: the kernel and its template arguments, or why it refuses.  A pure host
+// function of the shape and of which operands are present (gemm_f32.hip); launch_gemv switches on it and
+// wlk_diag_gemv_variant prints it, so a test can ask which instantiation a shape reaches.
+struct GemvPlan {
+    enum Kernel { kRefused, kStaged, kSingleRow, kSingleRowMergeLds };
+    Kernel kernel = kRefused;
+    int width = 0;                  // MR of gemv_f32_kernel, UB of gemv1_f32_kernel / gemv1_mgl_f32_kernel
+    int rpw = 0;                    // output features per wave
+    bool ln = false, mg = false, full = false;      // the single-row kernel's LN, MG and FULL
+    const char* refusal = nullptr;  // kRefused: the text launch_gemv throws
+};
+GemvPlan gemv_plan(const GemmArgs& g);
 // can launch_gemv take the cross-attention output in split form (single-row kernel, K = d)?
 bool gemv1_folds_merge(int K);
 void refresh_env_switches();                      // cached environment switches are read again at their next use (tests)

@@ -1166,4 +1166,182 @@ int wlk_diag_sf_kernel(const wlk_diag_sf_kernel_args* q) {
     }
 }
 
+/* One linear layer on host data through launch_linear / launch_gemv / launch_gemm / launch_gemm_kp, unchanged (see
+ * include/wlk_hip.h).  Everything a kernel of the chosen route may address is checked against the caller's buffer sizes
+ * here, before anything is uploaded; the launchers' own refusals follow before anything is launched. */
+int wlk_diag_linear_ex(const wlk_diag_linear_args* q) {
+    struct Refuse : std::invalid_argument {
+        using std::invalid_argument::invalid_argument;
+    };
+    struct Buf {        // a device copy of exactly `n` host floats (never fewer than 16 allocated), copied back whole
+        float* p = nullptr;
+        float* host = nullptr;
+        size_t n = 0;
+        Buf() = default;
+        Buf(const Buf&) = delete;
+        void set(float* h, size_t floats) {
+            host = h;
+            n = floats;
+            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 16) * sizeof(float)));
+            if (host && n) WLK_HIP(hipMemcpy(p, host, n * sizeof(float), hipMemcpyHostToDevice));
+        }
+        void back() const { if (host && n) WLK_HIP(hipMemcpy(host, p, n * sizeof(float), hipMemcpyDeviceToHost)); }
+        ~Buf() { (void)hipFree(p); }
+    };
+    try {
+        auto need = [](bool ok, const char* what) {
+            if (!ok) throw Refuse(std::string("wlk_diag_linear_ex: ") + what);
+        };
+        need(q != nullptr, "null arguments");
+        const int route = q->route, M = q->m, N = q->n, K = q->k, batch = q->batch;
+        need(route >= 0 && route <= 8, "route in [0, 8]");
+        need(M >= 1 && M <= (1 << 16) && N >= 1 && N <= (1 << 20) && K >= 1 && K <= (1 << 16), "m in [1, 2^16], n in [1, 2^20], k in [1, 2^16]");
+        need((q->flags & ~31) == 0, "unknown flag bits");
+        need(q->a && q->w && q->c, "null a / w / c");
+        need(q->lda >= 1 && q->lda <= (1 << 20) && q->ldc >= N && q->ldc <= (1 << 21), "lda in [1, 2^20], ldc in [n, 2^21]");
+        need(batch >= 0 && batch <= kMaxBatch, "batch in [0, 8]");
+        need(q->scale_cols >= 0 && q->scale_period >= 0, "scale_cols / scale_period below 0");
+        const bool has_res = (q->flags & kGemmResidual) != 0, r_is_c = q->r_is_c != 0;
+        const int nz = std::max(batch, 1);
+        const int64_t a_span = (int64_t)(M - 1) * q->lda + K, c_span = (int64_t)(M - 1) * q->ldc + N;
+        const int64_t ldr = r_is_c ? q->ldc : q->ldr;
+        const int64_t r_span = (int64_t)(M - 1) * ldr + N;
+        need((int64_t)N * K <= q->w_floats, "w holds fewer than n x k floats");
+        need(!q->bias || N <= q->bias_floats, "bias holds fewer than n floats");
+        need((q->ln_gamma != nullptr) == (q->ln_beta != nullptr), "ln_gamma and ln_beta come together");
+        need(!q->ln_gamma || K <= q->ln_floats, "ln_gamma / ln_beta hold fewer than k floats");
+        if (has_res && !r_is_c) need(q->r && ldr >= N && ldr <= (1 << 21), "a residual needs r and ldr in [n, 2^21]");
+        need(!r_is_c || has_res, "r_is_c without the residual flag");
+        for (int z = 0; z < nz; ++z) {
+            const int64_t ao = batch ? q->a_off[z] : 0, co = batch ? q->c_off[z] : 0, ro = batch ? q->r_off[z] : 0;
+            need(ao >= 0 && ao % 4 == 0 && ao + a_span <= q->a_floats, "the rows of a lie past its buffer (offsets are multiples of 4)");
+            need(co >= 0 && co + c_span <= q->c_floats, "the rows of c lie past its buffer");
+            if (has_res && !r_is_c) need(ro >= 0 && ro + r_span <= q->r_floats, "the rows of r lie past its buffer");
+        }
+        const int kv_mode = q->kv_mode;
+        need(kv_mode >= 0 && kv_mode <= 2, "kv_mode is 0, 1 or 2");
+        const bool to_gemv = route == 1 || (route == 0 && gemv_applicable(M, K));
+        if (kv_mode != 0) {
+            need(q->kcache && q->vcache && q->cache_floats > 0, "kv_mode needs kcache / vcache");
+            need(q->kv_d >= 1 && N == 3 * q->kv_d, "kv_mode: n = 3 kv_d");
+            need(q->kv_ctx >= 1 && q->kv_ctx <= (1 << 16), "kv_ctx in [1, 2^16]");
+            need(batch == 0, "kv_mode with batch");
+        }
+        if (kv_mode == 1) {
+            const int ntok = q->kv_ntok;
+            need(ntok >= 1 && M % ntok == 0, "kv_ntok >= 1 divides m");
+            need(!to_gemv || ntok == 1, "the GEMV kernels append one token per row");
+            need(q->kv_pos >= 0 && q->kv_pos + ntok <= q->kv_ctx, "kv_pos + kv_ntok <= kv_ctx");
+            need((int64_t)(M / ntok) * q->kv_ctx * q->kv_d <= q->cache_floats, "the caches hold fewer than beams x kv_ctx x kv_d floats");
+        }
+        if (kv_mode == 2) {
+            need(route == 1, "kv_mode 2 (per-row caches) is a launch_gemv operand: route 1");
+            need(M <= 8, "kv_mode 2: at most 8 rows");
+            need(q->n_caches >= 1 && q->n_caches <= 8 && q->cache_stride >= 1 && q->cache_stride % 4 == 0 &&
+                     (int64_t)q->n_caches * q->cache_stride <= q->cache_floats, "n_caches in [1, 8] caches of cache_stride floats inside the buffer");
+            need(q->kv_layer_off >= 0 && q->kv_layer_off <= q->cache_stride, "kv_layer_off inside a cache");
+            for (int r = 0; r < M; ++r) {
+                need(q->kv_row_cache[r] >= 0 && q->kv_row_cache[r] < q->n_caches, "kv_row_cache outside the caches");
+                need(q->kv_row_offset[r] >= 0 && q->kv_row_offset[r] < q->kv_ctx &&
+                         q->kv_layer_off + ((int64_t)q->kv_row_offset[r] + 1) * q->kv_d <= q->cache_stride, "kv_row_offset outside its cache");
+            }
+        }
+
+        Buf A, W, B, G, Bt, R, Cc, KC, VC, POS, ROWS;
+        A.set(q->a, q->a_floats);
+        W.set(q->w, q->w_floats);
+        if (q->bias) B.set(q->bias, q->bias_floats);
+        if (q->ln_gamma) { G.set(q->ln_gamma, q->ln_floats); Bt.set(q->ln_beta, q->ln_floats); }
+        if (has_res && !r_is_c) R.set(q->r, q->r_floats);
+        Cc.set(q->c, q->c_floats);
+        if (kv_mode != 0) { KC.set(q->kcache, q->cache_floats); VC.set(q->vcache, q->cache_floats); }
+        GemmArgs g;
+        g.A = A.p; g.lda = q->lda; g.W = W.p; g.bias = q->bias ? B.p : nullptr; g.C = Cc.p; g.ldc = q->ldc;
+        g.R = has_res ? (r_is_c ? Cc.p : R.p) : nullptr; g.ldr = ldr;
+        g.M = M; g.N = N; g.K = K; g.flags = q->flags; g.scale = q->scale; g.scale_cols = q->scale_cols;
+        g.scale_period = q->scale_period;
+        g.ln_gamma = q->ln_gamma ? G.p : nullptr; g.ln_beta = q->ln_gamma ? Bt.p : nullptr;
+        g.batch = batch;
+        for (int z = 0; z < batch; ++z) {
+            g.z.in[z] = A.p + q->a_off[z];
+            g.z.out[z] = Cc.p + q->c_off[z];
+            g.z.res[z] = has_res ? (r_is_c ? Cc.p + q->c_off[z] : R.p + q->r_off[z]) : nullptr;
+        }
+        for (int z = batch; z < kMaxBatch; ++z) { g.z.in[z] = nullptr; g.z.out[z] = nullptr; g.z.res[z] = nullptr; }
+        static_assert(sizeof(StepRow) % sizeof(float) == 0 && sizeof(int) == sizeof(float), "tables are uploaded through float buffers");
+        if (kv_mode == 1) {
+            float pos_bits = __builtin_bit_cast(float, (int)q->kv_pos);
+            POS.set(&pos_bits, 1);
+            POS.host = nullptr;
+            g.kcache = KC.p; g.vcache = VC.p; g.kv_pos = reinterpret_cast<const int*>(POS.p);
+            g.kv_d = q->kv_d; g.kv_ctx = q->kv_ctx; g.kv_ntok = q->kv_ntok;
+        } else if (kv_mode == 2) {
+            StepRow table[8] = {};
+            for (int r = 0; r < M; ++r) {
+                table[r].kcache = KC.p + (size_t)q->kv_row_cache[r] * q->cache_stride;
+                table[r].vcache = VC.p + (size_t)q->kv_row_cache[r] * q->cache_stride;
+                table[r].offset = q->kv_row_offset[r];
+            }
+            ROWS.set(reinterpret_cast<float*>(table), 8 * (sizeof(StepRow) / sizeof(float)));
+            ROWS.host = nullptr;
+            g.kv_rows = reinterpret_cast<const StepRow*>(ROWS.p);
+            g.kv_layer_off = q->kv_layer_off; g.kv_d = q->kv_d; g.kv_ctx = q->kv_ctx;
+        }
+        g.force_kwave = route == 2;
+        g.force_kernel = (route >= 2 && route <= 4) || (route >= 6 && route <= 8) ? route : 0;
+        LaunchCtx ctx;
+        WLK_HIP(hipDeviceSynchronize());
+        if (route == 0) launch_linear(ctx, g, "diag_linear");
+        else if (route == 1) launch_gemv(ctx, g, "diag_gemv");
+        else if (route >= 5) launch_gemm_kp(ctx, g, "diag_gemm_kp");
+        else launch_gemm(ctx, g, "diag_gemm");
+        WLK_HIP(hipDeviceSynchronize());
+        A.back(); W.back(); B.back(); G.back(); Bt.back(); R.back(); Cc.back(); KC.back(); VC.back();
+        return WLK_OK;
+    } catch (const Refuse& e) {
+        g_diag_error = e.what();
+        return WLK_ERR_ARG;
+    } catch (const std::invalid_argument& e) {      // a launcher's own refusal: nothing was launched
+        (void)hipDeviceSynchronize();
+        g_diag_error = e.what();
+        return WLK_ERR_ARG;
+    } catch (const std::exception& e) {
+        g_diag_error = e.what();
+        return WLK_ERR_HIP;
+    }
+}
+
+int wlk_diag_gemv_variant(int m, int n, int k, int has_ln, int kv_mode, char* out_text, int cap) {
+    if (!out_text || cap < 1) return WLK_ERR_ARG;
+    // operands that are present are marked by a non-null pointer; gemv_plan dereferences none
+    static const float present = 0.f;
+    static float cache_present = 0.f;
+    GemmArgs g;
+    g.A = &present; g.W = &present; g.lda = k; g.M = m; g.N = n; g.K = k;
+    if (has_ln) { g.ln_gamma = &present; g.ln_beta = &present; }
+    if (kv_mode == 1) { g.kcache = &cache_present; g.vcache = &cache_present; }
+    if (kv_mode == 2) g.kv_rows = reinterpret_cast<const StepRow*>(&present);
+    char text[160];
+    int rc = WLK_OK;
+    if (m < 1 || n < 1 || kv_mode < 0 || kv_mode > 2) {
+        snprintf(text, sizeof text, "wlk_diag_gemv_variant: m >= 1, n >= 1, kv_mode in [0, 2]");
+        rc = WLK_ERR_ARG;
+    } else {
+        const GemvPlan p = gemv_plan(g);
+        if (p.kernel == GemvPlan::kRefused) {
+            snprintf(text, sizeof text, "%s", p.refusal);
+            rc = WLK_ERR_ARG;
+        } else if (p.kernel == GemvPlan::kStaged) {
+            snprintf(text, sizeof text, "gemv<%d,%d>", p.width, p.rpw);
+        } else if (p.kernel == GemvPlan::kSingleRowMergeLds) {
+            snprintf(text, sizeof text, "gemv1_mgl<%d>", p.width);
+        } else {
+            snprintf(text, sizeof text, "gemv1<%d,%d,%s,%s>", p.width, p.rpw, p.mg ? "mg" : p.ln ? "ln" : "plain", p.full ? "full" : "part");
+        }
+    }
+    if (rc != WLK_OK) g_diag_error = text;
+    snprintf(out_text, (size_t)cap, "%s", text);
+    return rc;
+}
+
 }  // extern "C"

@@ -1644,27 +1644,72 @@ bool gemv1_folds_merge(int K) {
     return (e && e[0] == '1') || K <= 512 || gemv1_merge_through_lds(K);
 }
 
-void launch_gemv(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
-    if (g.M <= 0 || g.N <= 0) return;
-    if (!gemv_applicable(g.M, g.K) || g.lda % 4 != 0) throw std::invalid_argument("gemv: unsupported shape");
-    const int mr = gemv_row_bucket(g.M);
+// The ONE place that decides which GEMV kernel a launch takes (launch_gemv switches on the answer, wlk_diag_gemv_variant
+// prints it).  Host arithmetic on the shape and on which operands are present; no pointer is dereferenced.
+GemvPlan gemv_plan(const GemmArgs& g) {
+    GemvPlan p;
+    auto refuse = [&](const char* why) {
+        p = GemvPlan{};
+        p.refusal = why;
+        return p;
+    };
+    if (!gemv_applicable(g.M, g.K) || g.lda % 4 != 0) return refuse("gemv: unsupported shape");
+    // fields the GEMV kernels' epilogues do not read: refused, never silently dropped
+    if (g.scale_period > 0) return refuse("gemv: scale_period is a GEMM operand (the GEMV kernels scale columns below scale_cols only)");
+    if (g.batch > 0) return refuse("gemv: batched operand tables are a GEMM operand");
     // output features per wave per pass: few for narrow layers (more workgroups in flight), more for
     // the 51864-wide vocabulary projection (amortises the shuffle folds)
-    const int rpw = g.N >= 16384 ? 4 : (g.N >= 2048 ? 2 : 1);
-    const int n_groups = (g.N + rpw - 1) / rpw;
-    int blocks = (n_groups + 3) / 4;
-    if (blocks > 2048) blocks = 2048;
-    const size_t lds = (size_t)mr * g.K * sizeof(float);
-    KernelScope ks(ctx, tag, 2.0 * g.M * g.N * g.K, 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));
-    if (g.mg_pm && !(g.M == 1 && g.K <= 2048 && rpw <= 2 && gemv1_enabled() && !g.ln_gamma))
-        throw std::invalid_argument("gemv: the merged cross-attention operand needs the single-row kernel");
+    p.rpw = g.N >= 16384 ? 4 : (g.N >= 2048 ? 2 : 1);
+    p.ln = g.ln_gamma != nullptr;
+    p.mg = g.mg_pm != nullptr;
+    if (p.mg && !(g.M == 1 && g.K <= 2048 && p.rpw <= 2 && gemv1_enabled() && !p.ln))
+        return refuse("gemv: the merged cross-attention operand needs the single-row kernel");
     // the whole K of a row in flight per wave: up to 2048 for every variant, up to 5120 (the MLP's second projection of
     // the large models, 20 float4 per lane) for the plain one-feature-per-wave variant
-    const bool plain1 = rpw == 1 && !g.ln_gamma && !g.mg_pm;
-    if (g.side_blocks > 0 && (!g.side_align || g.side_zf <= 0 || rpw != 4))
-        throw std::invalid_argument("gemv: side workgroups ride only in the vocabulary projection's launch");
-    if (g.M == 1 && (g.K <= 2048 || (plain1 && g.K <= 5120)) && rpw <= 2 && gemv1_enabled() && !g.kv_rows) {
+    const bool plain1 = p.rpw == 1 && !p.ln && !p.mg;
+    if (g.side_blocks > 0 && (!g.side_align || g.side_zf <= 0 || p.rpw != 4))
+        return refuse("gemv: side workgroups ride only in the vocabulary projection's launch");
+    if (g.M == 1 && (g.K <= 2048 || (plain1 && g.K <= 5120)) && p.rpw <= 2 && gemv1_enabled() && !g.kv_rows) {
         const int ub = (g.K / 4 + 63) / 64;
+        if (p.mg && g.mg_side_blocks > 0 && !g.mg_side_heads)
+            return refuse("gemv: the merged operand's side blocks need the layer's alignment head list");
+        if (p.mg && p.rpw == 1 && !g.kcache && gemv1_merge_through_lds(g.K)) {
+            if (!(ub == 3 || ub == 4 || ub == 5 || ub == 6 || ub == 8))
+                return refuse("gemv: no workgroup-merge instantiation for this width");
+            p.kernel = GemvPlan::kSingleRowMergeLds;
+            p.width = ub;
+            p.full = true;
+            return p;
+        }
+        // UB = float4 chunks per lane = registers held and loads in flight: exact for every Whisper width (K = d or 4 d,
+        // d in 384 .. 1280), so that a wave of the large models does not carry dead registers into its occupancy
+        // (K = 1280 as UB 8: 188 VGPRs, 512 of fc1's 640 workgroups resident -> two rounds); the merged operand has
+        // UB 2 / 4 / 8 only
+        p.kernel = GemvPlan::kSingleRow;
+        if (ub <= 2) p.width = 2;
+        else if (ub <= 8) p.width = p.mg ? (ub <= 4 ? 4 : 8) : (ub == 7 ? 8 : ub);
+        else p.width = ub <= 12 ? 12 : ub <= 16 ? 16 : 20;
+        // FULL: K fills every lane of every chunk (all Whisper widths but tiny's 384) - no predicates, one basic block,
+        // every load above the barrier
+        p.full = g.K == 256 * p.width;
+        return p;
+    }
+    p.kernel = GemvPlan::kStaged;
+    p.width = gemv_row_bucket(g.M);
+    p.mg = false;
+    p.full = false;
+    return p;
+}
+
+void launch_gemv(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
+    if (g.M <= 0 || g.N <= 0) return;
+    const GemvPlan p = gemv_plan(g);
+    if (p.kernel == GemvPlan::kRefused) throw std::invalid_argument(p.refusal);
+    const int n_groups = (g.N + p.rpw - 1) / p.rpw;
+    int blocks = (n_groups + 3) / 4;
+    if (blocks > 2048) blocks = 2048;
+    KernelScope ks(ctx, tag, 2.0 * g.M * g.N * g.K, 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));
+    if (p.kernel != GemvPlan::kStaged) {
         blocks += g.mg_pm ? g.mg_side_blocks : 0;
         // absent operands point at the weights: the kernel requests every operand up front, unconditionally
         const float* bias = g.bias ? g.bias : g.W;
@@ -1673,18 +1718,16 @@ void launch_gemv(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
                     g.scale_cols, g.kv_d};
         Gemv1Merge mg{g.mg_pm, g.mg_pl, g.mg_po, g.mg_scores, g.mg_head_rank, g.mg_side_heads, g.mg_ring, g.mg_ring_row,
                       g.mg_beam_of_row, g.mg_T, g.mg_ring_rows, g.mg_n_beam, g.mg_side_blocks};
-        if (g.mg_pm && g.mg_side_blocks > 0 && !g.mg_side_heads)
-            throw std::invalid_argument("gemv: the merged operand's side blocks need the layer's alignment head list");
-        if (g.mg_pm && rpw == 1 && !g.kcache && gemv1_merge_through_lds(g.K)) {
+        if (p.kernel == GemvPlan::kSingleRowMergeLds) {
 #define WLK_GEMV1_MGL(UBv)                                                                                             \
     hipLaunchKernelGGL((gemv1_mgl_f32_kernel<UBv>), dim3(blocks), dim3(256), 0, ctx.stream, g.W, g.K, g.N, bias, res, t, mg)
-            switch (ub) {
+            switch (p.width) {
                 case 3: WLK_GEMV1_MGL(3); break;
                 case 4: WLK_GEMV1_MGL(4); break;
                 case 5: WLK_GEMV1_MGL(5); break;
                 case 6: WLK_GEMV1_MGL(6); break;
                 case 8: WLK_GEMV1_MGL(8); break;
-                default: throw std::invalid_argument("gemv: no workgroup-merge instantiation for this width");
+                default: throw std::logic_error("gemv: workgroup-merge plan without an instantiation");
             }
 #undef WLK_GEMV1_MGL
             WLK_HIP(hipGetLastError());
@@ -1693,43 +1736,38 @@ void launch_gemv(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
 #define WLK_GEMV1_F(UBv, RPWv, LNv, MGv, FULLv)                                                                         \
     hipLaunchKernelGGL((gemv1_f32_kernel<UBv, RPWv, LNv, MGv, FULLv>), dim3(blocks), dim3(256), 0, ctx.stream, g.W, g.A, \
                        g.K, g.N, g.ln_gamma, g.ln_beta, bias, res, t, mg)
-    // FULL: K fills every lane of every chunk (all Whisper widths but tiny's 384) - no predicates, one basic block, every
-    // load above the barrier
-#define WLK_GEMV1_I(UBv, RPWv, LNv, MGv)                             \
-    do {                                                             \
-        if (g.K == 256 * UBv) WLK_GEMV1_F(UBv, RPWv, LNv, MGv, true); \
-        else WLK_GEMV1_F(UBv, RPWv, LNv, MGv, false);                \
+#define WLK_GEMV1_I(UBv, RPWv, LNv, MGv)                       \
+    do {                                                       \
+        if (p.full) WLK_GEMV1_F(UBv, RPWv, LNv, MGv, true);    \
+        else WLK_GEMV1_F(UBv, RPWv, LNv, MGv, false);          \
     } while (0)
-#define WLK_GEMV1_R(UBv, LNv, MGv)                 \
-    do {                                           \
-        if (rpw == 2) WLK_GEMV1_I(UBv, 2, LNv, MGv); \
-        else WLK_GEMV1_I(UBv, 1, LNv, MGv);        \
+#define WLK_GEMV1_R(UBv, LNv, MGv)                   \
+    do {                                             \
+        if (p.rpw == 2) WLK_GEMV1_I(UBv, 2, LNv, MGv); \
+        else WLK_GEMV1_I(UBv, 1, LNv, MGv);          \
     } while (0)
 #define WLK_GEMV1_NOMG(UBv)                                    \
     do {                                                       \
-        if (g.ln_gamma) WLK_GEMV1_R(UBv, true, false);         \
+        if (p.ln) WLK_GEMV1_R(UBv, true, false);               \
         else WLK_GEMV1_R(UBv, false, false);                   \
     } while (0)
 #define WLK_GEMV1(UBv)                                         \
     do {                                                       \
-        if (g.mg_pm) WLK_GEMV1_R(UBv, false, true);            \
+        if (p.mg) WLK_GEMV1_R(UBv, false, true);               \
         else WLK_GEMV1_NOMG(UBv);                              \
     } while (0)
-        // UB = float4 chunks per lane = registers held and loads in flight: exact for every Whisper width (K = d or 4 d,
-        // d in 384 .. 1280), so that a wave of the large models does not carry dead registers into its occupancy
-        // (K = 1280 as UB 8: 188 VGPRs, 512 of fc1's 640 workgroups resident -> two rounds)
-        switch (ub) {
-            case 1: case 2: WLK_GEMV1(2); break;
-            case 3: if (g.mg_pm) WLK_GEMV1(4); else WLK_GEMV1_NOMG(3); break;
+        const bool wide_ok = p.rpw == 1 && !p.ln && !p.mg;     // the only form UB 12 / 16 / 20 exist in
+        switch (p.width) {
+            case 2: WLK_GEMV1(2); break;
             case 4: WLK_GEMV1(4); break;
-            case 5: if (g.mg_pm) WLK_GEMV1(8); else WLK_GEMV1_NOMG(5); break;
-            case 6: if (g.mg_pm) WLK_GEMV1(8); else WLK_GEMV1_NOMG(6); break;
-            case 7: case 8: WLK_GEMV1(8); break;
-            default:
-                if (ub <= 12) WLK_GEMV1_I(12, 1, false, false);
-                else if (ub <= 16) WLK_GEMV1_I(16, 1, false, false);
-                else WLK_GEMV1_I(20, 1, false, false);
-                break;
+            case 8: WLK_GEMV1(8); break;
+            case 3: if (p.mg) throw std::logic_error("gemv: merged plan without an instantiation"); WLK_GEMV1_NOMG(3); break;
+            case 5: if (p.mg) throw std::logic_error("gemv: merged plan without an instantiation"); WLK_GEMV1_NOMG(5); break;
+            case 6: if (p.mg) throw std::logic_error("gemv: merged plan without an instantiation"); WLK_GEMV1_NOMG(6); break;
+            case 12: if (!wide_ok) throw std::logic_error("gemv: wide plan without an instantiation"); WLK_GEMV1_I(12, 1, false, false); break;
+            case 16: if (!wide_ok) throw std::logic_error("gemv: wide plan without an instantiation"); WLK_GEMV1_I(16, 1, false, false); break;
+            case 20: if (!wide_ok) throw std::logic_error("gemv: wide plan without an instantiation"); WLK_GEMV1_I(20, 1, false, false); break;
+            default: throw std::logic_error("gemv: single-row plan without an instantiation");
         }
 #undef WLK_GEMV1
 #undef WLK_GEMV1_NOMG
@@ -1739,16 +1777,17 @@ void launch_gemv(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
         WLK_HIP(hipGetLastError());
         return;
     }
+    const size_t lds = (size_t)p.width * g.K * sizeof(float);
     blocks += g.side_blocks;     // the AlignAtt z-score of a graph step rides in front of the weight stream
 #define WLK_GEMV(MRv, RPWv) \
     hipLaunchKernelGGL((gemv_f32_kernel<MRv, RPWv>), dim3(blocks), dim3(256), lds, ctx.stream, g)
-#define WLK_GEMV_R(MRv)                      \
-    do {                                     \
-        if (rpw == 4) WLK_GEMV(MRv, 4);      \
-        else if (rpw == 2) WLK_GEMV(MRv, 2); \
-        else WLK_GEMV(MRv, 1);               \
+#define WLK_GEMV_R(MRv)                        \
+    do {                                       \
+        if (p.rpw == 4) WLK_GEMV(MRv, 4);      \
+        else if (p.rpw == 2) WLK_GEMV(MRv, 2); \
+        else WLK_GEMV(MRv, 1);                 \
     } while (0)
-    switch (mr) {
+    switch (p.width) {
         case 1: WLK_GEMV_R(1); break;
         case 2: WLK_GEMV_R(2); break;
         case 4: WLK_GEMV_R(4); break;
