@@ -474,8 +474,8 @@ int wlk_vad_group_destroy(wlk_vad_group* g);
 
 /* ---- diagnostics: one kernel on host data (used by the GPU parity tests only) ---------------- */
 const char* wlk_diag_last_error(void);
-/* environment switches the library caches on first use (WLK_X3_PERSIST) are read again at their next use: for tests
- * that flip one inside a process */
+/* environment switches the library caches on first use (WLK_X3_PERSIST, WLK_X3_BM, WLK_X3_COLMAJOR) are read again at
+ * their next use: for tests that flip one inside a process */
 int wlk_diag_env_refresh(void);
 /* c[m,n] = epilogue(a[m,k](row stride lda, a_floats floats in total) . w[n,k]^T + bias); flags:
  * 1 = exact-erf GELU, 2 = add r[m, ldr] after the activation, 4 = scale columns < scale_cols,
@@ -888,6 +888,50 @@ int wlk_diag_linear_ex(const wlk_diag_linear_args* args);
  * function launch_gemv itself switches on; needs no device.  A shape launch_gemv refuses returns WLK_ERR_ARG and the
  * refusal as text. */
 int wlk_diag_gemv_variant(int m, int n, int k, int has_ln, int kv_mode, char* out_text, int cap);
+/* ONE encoder operator on host data through its production launcher, unchanged.  kind:
+ *   WLK_ENC_X3_GEMM    launch_gemm_x3: C = epilogue(A W^T + bias), m x n x k.  a = `in` (fp32 rows ld_in apart, packed on the
+ *                      device with launch_x3_pack) or `in3` (an X3 row image, rows 3 ld_in apart); w [n][k] (launch_x3_pack_w);
+ *                      bias [n] at bias + bias_off, or NULL; flags / scale / scale_cols / scale_period as GemmFlags; residual
+ *                      r rows ldr apart, or with r_is_c the result itself.  form 0: fp32 rows ld_out apart in `out`; form 1:
+ *                      the fc1 row image in out3 (x3_out, rows 3 ld_out3 apart, vt_col0 >= n); form 2: the attention operand
+ *                      image in out3 (columns below vt_col0 as rows 3 ld_out3 apart, the others transposed at vt_off with
+ *                      rows 3 vt_ld apart).  batch >= 1 fills a pointer table as the encoder does; 0 uses plain pointers.
+ *   WLK_ENC_LN         LayerNorm of m rows of n = d features (gamma = w, beta = bias); form 0: launch_layernorm(_batched),
+ *                      fp32 rows ld_out apart; form 1: launch_layernorm_x3(_batched), the X3 row image (rows 3 ld_out3 apart).
+ *   WLK_ENC_ATTENTION  encoder self-attention of m = T frames, n = d = 64 n_head; form 0: launch_encoder_attention(_batched)
+ *                      on fp32 qkv [T][3 d], out [T][d]; form 1: launch_encoder_attention_x3 on `in` (packed with
+ *                      launch_x3_pack_qkv) or on in3 (the operand image form 2 of the GEMM writes), fp32 rows ld_out apart or,
+ *                      with x3_out, the X3 row image in out3 (rows 3 ld_out3 apart).
+ *   WLK_ENC_PACK       launch_x3_pack of m rows of n columns: in (ld_in) -> out3 (ld_out3).
+ * batch > 0: operand set z lies at in + in_off[z] (floats), in3 + in3_off[z], out + out_off[z], out3 + out3_off[z] (16-bit
+ * words), r + r_off[z].  X3 images travel as raw 16-bit words; nothing is zeroed for the caller.  Every buffer lives on the
+ * device in exactly the elements the caller passes and is copied back whole - inputs too.  What a buffer cannot hold, or
+ * what a launcher refuses (by the launcher's own check function, its own text), returns WLK_ERR_ARG with a message in
+ * wlk_diag_last_error() before anything is uploaded or launched; no other route runs instead.  All pointers are host memory; the call is synchronous. */
+#define WLK_ENC_X3_GEMM 0
+#define WLK_ENC_LN 1
+#define WLK_ENC_ATTENTION 2
+#define WLK_ENC_PACK 3
+typedef struct wlk_diag_enc_op_args {
+    int32_t kind, form, m, n, k, n_head, flags, scale_cols, scale_period, r_is_c, x3_out, batch, vt_col0;
+    float scale;
+    int64_t ld_in, ld_out, ld_out3, ldr, vt_off, vt_ld, bias_off;
+    int64_t in_floats, in3_elems, w_floats, bias_floats, r_floats, out_floats, out3_elems;
+    int64_t in_off[8], in3_off[8], r_off[8], out_off[8], out3_off[8];
+    float* in;                      /* in / out, or NULL */
+    uint16_t* in3;                  /* in / out, or NULL */
+    float* w;                       /* in / out */
+    float* bias;                    /* in / out, or NULL */
+    float* r;                       /* in / out, or NULL */
+    float* out;                     /* in / out, or NULL */
+    uint16_t* out3;                 /* in / out, or NULL */
+} wlk_diag_enc_op_args;
+int wlk_diag_enc_op(const wlk_diag_enc_op_args* args);
+/* The launch geometry launch_gemm_x3 takes for `batch` sessions (0 = plain pointers) of an m x n x k problem on a device of
+ * `cus` compute units, as text: "bm=96|64 banded|plain colmajor|rowmajor persist=.. tiles=MxN nslab=.. slots=.. blocks=..
+ * walked=.. max_tiles_per_wg=.. skips_between=0|1" - the answer of the function launch_gemm_x3 itself calls (the WLK_X3_*
+ * switches included), with the walk of the kernel's workgroups counted on the host; needs no device. */
+int wlk_diag_x3_plan(int m, int n, int k, int batch, int cus, char* out_text, int cap);
 /* the VALU wave butterflies of csrc/wave_ops.h (DPP / v_permlane{16,32}_swap) against the __shfl_xor loops they replace,
  * on one wave of 64 floats: ten rows of 64 results each (sum, max, 16-lane sum, xor 1 .. 32 exchanges, arg-max index) */
 int wlk_diag_wave_ops(const float* in64, float* out640, float* ref640);

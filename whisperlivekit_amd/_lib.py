@@ -118,6 +118,18 @@ class DiagLinearArgs(C.Structure):
         (n, C.c_void_p) for n in ("a", "w", "bias", "ln_gamma", "ln_beta", "r", "c", "kcache", "vcache")]
 
 
+class DiagEncOpArgs(C.Structure):
+    """wlk_diag_enc_op_args (include/wlk_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "kind", "form", "m", "n", "k", "n_head", "flags", "scale_cols", "scale_period", "r_is_c", "x3_out", "batch",
+        "vt_col0")] + [("scale", C.c_float)] + [
+        (n, C.c_int64) for n in ("ld_in", "ld_out", "ld_out3", "ldr", "vt_off", "vt_ld", "bias_off", "in_floats", "in3_elems",
+                                 "w_floats", "bias_floats", "r_floats", "out_floats", "out3_elems")] + [
+        (n, C.c_int64 * 8) for n in ("in_off", "in3_off", "r_off", "out_off", "out3_off")] + [
+        (n, C.c_void_p) for n in ("in", "in3", "w", "bias", "r", "out", "out3")]
+
+
+ENC_X3_GEMM, ENC_LN, ENC_ATTENTION, ENC_PACK = range(4)
 SFK_ATTENTION, SFK_CONV0, SFK_DWCONV2D, SFK_GLU_DWCONV, SFK_HEAD, SFK_ASSEMBLE = range(6)
 DA_S0, DA_S1, DA_S2 = 0, 1, 2
 DA_C0, DA_C1, DA_C2, DA_C3, DA_C4, DA_C5 = 10, 11, 12, 13, 14, 15
@@ -329,6 +341,8 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_sf_kernel": (cint, [C.POINTER(DiagSfKernelArgs)]),
         "wlk_diag_linear_ex": (cint, [C.POINTER(DiagLinearArgs)]),
         "wlk_diag_gemv_variant": (cint, [cint, cint, cint, cint, cint, C.c_char_p, cint]),
+        "wlk_diag_enc_op": (cint, [C.POINTER(DiagEncOpArgs)]),
+        "wlk_diag_x3_plan": (cint, [cint, cint, cint, cint, cint, C.c_char_p, cint]),
         "wlk_model_set_cif": (cint, [p, p, cint, C.c_float]),
         "wlk_cif_result": (cint, [p, C.POINTER(CifOut)]),
         "wlk_diag_cif": (cint, [p, cint, cint, p, C.c_float, cint, cint, p, p, p]),
@@ -382,7 +396,8 @@ EXPORTED_SYMBOLS = (
     "wlk_diag_linear_x3", "wlk_diag_linear_x3_time", "wlk_diag_layernorm_x3",
     "wlk_diag_encoder_attention_x3", "wlk_diag_encoder_attention_x3_time", "wlk_diag_qkv_x3_attention",
     "wlk_diag_select", "wlk_diag_dec_attention", "wlk_diag_topk", "wlk_diag_sf_kernel", "wlk_diag_nllb_align",
-    "wlk_diag_nllb_align_rows", "wlk_diag_linear_ex", "wlk_diag_gemv_variant",
+    "wlk_diag_nllb_align_rows", "wlk_diag_linear_ex", "wlk_diag_gemv_variant", "wlk_diag_enc_op",
+    "wlk_diag_x3_plan",
     "wlk_model_set_cif", "wlk_cif_result", "wlk_diag_cif",
 )
 

@@ -364,10 +364,16 @@ bool enc_attention_x3_enabled() {
     return on;
 }
 
-void launch_encoder_attention_x3(const LaunchCtx& ctx, const unsigned short* qk3, long ldqk, long vt_off, long vt_ld, float* out,
-                                 long ldo, int T, int d, int n_head, const PtrTable* z, int batch, bool x3_out) {
+// what launch_encoder_attention_x3 refuses (the launcher calls it first; wlk_diag_enc_op before it uploads anything)
+void enc_attention_x3_check(long ldqk, long vt_ld, long ldo, int T, int d, int n_head, bool x3_out) {
     if (d != n_head * 64 || ldqk % 8 != 0 || vt_ld % 32 != 0 || vt_ld < ((T + 31) / 32) * 32 || T < 64)
         throw std::invalid_argument("x3 attention: unsupported shape");
+    if (x3_out && ldo % 8 != 0) throw std::invalid_argument("x3 attention: X3 result rows need ldo % 8 == 0");
+}
+
+void launch_encoder_attention_x3(const LaunchCtx& ctx, const unsigned short* qk3, long ldqk, long vt_off, long vt_ld, float* out,
+                                 long ldo, int T, int d, int n_head, const PtrTable* z, int batch, bool x3_out) {
+    enc_attention_x3_check(ldqk, vt_ld, ldo, T, d, n_head, x3_out);
     static std::atomic<uint64_t> configured{0};
     int dev = 0;
     WLK_HIP(hipGetDevice(&dev));
@@ -379,7 +385,6 @@ void launch_encoder_attention_x3(const LaunchCtx& ctx, const unsigned short* qk3
     a.qk3 = qk3; a.ldqk = ldqk; a.vt_off = vt_off; a.vt_ld = vt_ld; a.out = out; a.ldo = ldo; a.T = T; a.d = d; a.n_head = n_head;
     a.batch = batch;
     a.x3_out = x3_out ? 1 : 0;
-    if (x3_out && ldo % 8 != 0) throw std::invalid_argument("x3 attention: X3 result rows need ldo % 8 == 0");
     if (batch > 0) a.z = *z;
     const int q_tiles = (T + AX_QT - 1) / AX_QT;
     KernelScope ks(ctx, "enc_attention_x3", (batch > 0 ? batch : 1) * 4.0 * (double)T * T * 64 * n_head, 0.0);

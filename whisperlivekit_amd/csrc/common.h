@@ -304,11 +304,23 @@ struct X3GemmArgs {
 };
 bool gemm_x3_wide_applicable(int M, int N, int K, long lda);
 void launch_gemm_x3(const LaunchCtx& ctx, const X3GemmArgs& g, const char* tag);
+void x3_gemm_check(const X3GemmArgs& g);     // throws std::invalid_argument for what launch_gemm_x3 refuses (pointers: alignment only)
+// the launch geometry launch_gemm_x3 takes for `batch` (>= 1) sessions on `cus` compute units (WLK_X3_BM / _PERSIST /
+// _COLMAJOR included); a host function, so wlk_diag_x3_plan can print it without a device
+struct X3GemmPlan {
+    int bm = 96;                          // tile height: 96 or 64
+    int tiles_m = 0, tiles_n = 0;
+    int banded = 0, colmajor = 0, persist = 1;
+    int slots = 0;                        // walk_slots
+    int blocks = 0;                       // workgroups launched
+};
+X3GemmPlan x3_gemm_plan(int M, int N, int batch, int cus);
 // fp32 weights [n][ld_src] (k used) -> the wide kernel's weight operand (fragment-major, rows padded to 32: gemm_x3.hip)
 size_t x3_w_elems(int n, int k);             // bf16 elements of that operand
 void launch_x3_pack_w(const LaunchCtx& ctx, const float* src, long ld_src, unsigned short* dst, int n, int k);
 // fp32 [rows][ld_src] (cols used) -> X3 [rows][3 * ld_dst]
 void launch_x3_pack(const LaunchCtx& ctx, const float* src, long ld_src, unsigned short* dst, long ld_dst, int rows, int cols);
+void x3_pack_check(long ld_src, long ld_dst, int cols);                       // throws for what launch_x3_pack refuses
 // X3 [rows][3 * ld_src] -> fp32 [rows][ld_dst]: (hi + mid) + lo, the exact fp32 value the planes were split from
 void launch_x3_unpack(const LaunchCtx& ctx, const unsigned short* src, long ld_src, float* dst, long ld_dst, int rows, int cols);
 
@@ -320,9 +332,11 @@ inline size_t x3_attn_image_elems(int T, int d) { return (size_t)x3_attn_vt_off(
 bool enc_attention_x3_enabled();
 void launch_encoder_attention_x3(const LaunchCtx& ctx, const unsigned short* qk3, long ldqk, long vt_off, long vt_ld, float* out,
                                  long ldo, int T, int d, int n_head, const PtrTable* z, int batch, bool x3_out = false);
+void enc_attention_x3_check(long ldqk, long vt_ld, long ldo, int T, int d, int n_head, bool x3_out);   // throws for what the launcher refuses
 void launch_x3_pack_qkv(const LaunchCtx& ctx, const float* qkv, unsigned short* out, int T, int d, long vt_off, long vt_ld);
 
 // ---- layernorm.hip --------------------------------------------------------------------------
+void layernorm_check(int d, long ldx, long ldy3, bool x3, int batch);        // throws for what the launchers below refuse
 void launch_layernorm(const LaunchCtx& ctx, const float* x, long ldx, const float* gamma, const float* beta,
                       float* y, long ldy, int rows, int d, const char* tag);
 // the same for `batch` sessions at once: x = z.in[i], y = z.out[i]

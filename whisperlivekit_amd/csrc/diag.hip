@@ -1344,4 +1344,285 @@ int wlk_diag_gemv_variant(int m, int n, int k, int has_ln, int kv_mode, char* ou
     return rc;
 }
 
+/* One encoder operator on host data through its production launcher, unchanged (see include/wlk_hip.h).  Everything a
+ * kernel of the chosen kind may address is checked against the caller's buffer sizes here; what a launcher refuses is
+ * decided by the launcher's own check function (x3_gemm_check, layernorm_check, enc_attention_x3_check, x3_pack_check),
+ * called here on the same arguments before anything is uploaded, and again by the launcher. */
+int wlk_diag_enc_op(const wlk_diag_enc_op_args* q) {
+    struct Refuse : std::invalid_argument {
+        using std::invalid_argument::invalid_argument;
+    };
+    struct Buf {        // a device copy of exactly `n` host elements of `esz` bytes (never fewer than 64 bytes), copied back whole
+        char* p = nullptr;
+        void* host = nullptr;
+        size_t bytes = 0;
+        Buf() = default;
+        Buf(const Buf&) = delete;
+        void set(void* h, size_t n, size_t esz) {
+            host = h;
+            bytes = n * esz;
+            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(bytes, 64)));
+            if (host && bytes) WLK_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+        }
+        float* f() const { return reinterpret_cast<float*>(p); }
+        unsigned short* u() const { return reinterpret_cast<unsigned short*>(p); }
+        void back() const { if (host && bytes) WLK_HIP(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost)); }
+        ~Buf() { (void)hipFree(p); }
+    };
+    try {
+        auto need = [](bool ok, const char* what) {
+            if (!ok) throw Refuse(std::string("wlk_diag_enc_op: ") + what);
+        };
+        need(q != nullptr, "null arguments");
+        const int kind = q->kind, form = q->form, M = q->m, N = q->n, K = q->k, batch = q->batch;
+        need(kind >= WLK_ENC_X3_GEMM && kind <= WLK_ENC_PACK, "kind in [0, 3]");
+        need(batch >= 0 && batch <= kMaxBatch, "batch in [0, 8]");
+        need(M >= 1 && M <= (1 << 16) && N >= 1 && N <= (1 << 16), "m and n in [1, 2^16]");
+        const int nz = std::max(batch, 1);
+        const int64_t LD_MAX = 1 << 20;
+        auto off = [&](const int64_t (&o)[8], int z) -> int64_t { return batch ? o[z] : 0; };
+        // an operand set of `span` elements at o[z], inside `cap` elements, every offset a multiple of `align`
+        auto fits = [&](const int64_t (&o)[8], int64_t span, int64_t cap, int align, const char* what) {
+            for (int z = 0; z < nz; ++z) need(off(o, z) >= 0 && off(o, z) % align == 0 && off(o, z) + span <= cap, what);
+        };
+        const bool in_is_x3 = q->in3 != nullptr;
+        Buf IN, IN3, W, B, R, OUT, OUT3;
+        auto upload = [&]() {
+            if (q->in) IN.set(q->in, q->in_floats, 4);
+            if (q->in3) IN3.set(q->in3, q->in3_elems, 2);
+            if (q->w) W.set(q->w, q->w_floats, 4);
+            if (q->bias) B.set(q->bias, q->bias_floats, 4);
+            if (q->r) R.set(q->r, q->r_floats, 4);
+            if (q->out) OUT.set(q->out, q->out_floats, 4);
+            if (q->out3) OUT3.set(q->out3, q->out3_elems, 2);
+        };
+        auto download = [&]() { IN.back(); IN3.back(); W.back(); B.back(); R.back(); OUT.back(); OUT3.back(); };
+        std::vector<unsigned short*> scratch;      // packed operands (device only)
+        struct FreeAll {
+            std::vector<unsigned short*>& v;
+            ~FreeAll() { for (auto* p : v) (void)hipFree(p); }
+        } free_all{scratch};
+        auto dev_u16 = [&](size_t n) {
+            unsigned short* p = nullptr;
+            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 32) * sizeof(unsigned short)));
+            scratch.push_back(p);
+            return p;
+        };
+        LaunchCtx ctx;
+        PtrTable z{};
+        if (kind == WLK_ENC_X3_GEMM) {
+            need(form >= 0 && form <= 2, "X3_GEMM: form 0 (fp32 rows), 1 (fc1 row image) or 2 (attention operand image)");
+            need(K >= 1 && K <= (1 << 16), "k in [1, 2^16]");
+            need((q->in != nullptr) != in_is_x3, "X3_GEMM: a is either in (fp32) or in3 (an X3 row image)");
+            need(q->w && (int64_t)N * K <= q->w_floats, "w holds fewer than n x k floats");
+            need(q->ld_in >= K && q->ld_in <= LD_MAX, "lda in [k, 2^20]");
+            need(q->scale_cols >= 0 && q->scale_period >= 0, "scale_cols / scale_period below 0");
+            need(q->bias_off >= 0 && (!q->bias || q->bias_off + N <= q->bias_floats), "bias holds fewer than bias_off + n floats");
+            const bool has_res = (q->flags & kGemmResidual) != 0, r_is_c = q->r_is_c != 0;
+            need(!r_is_c || has_res, "r_is_c without the residual flag");
+            const int64_t ldr = r_is_c ? q->ld_out : q->ldr;
+            {   // the launcher's own refusals, by the launcher's own function, before anything is uploaded.  Pointers stand in
+                // with the alignment the device copies will have: hipMalloc returns 256-byte aligned blocks
+                float* const base = reinterpret_cast<float*>(uintptr_t(1) << 20);
+                X3GemmArgs t;
+                t.lda = q->ld_in; t.bias = q->bias ? base + q->bias_off : nullptr; t.M = M; t.N = N; t.K = K; t.flags = q->flags;
+                t.ldc = q->ld_out; t.ldr = ldr; t.batch = batch; t.C = base; t.R = has_res ? base : nullptr;
+                t.x3_out = form != 0; t.ldc3 = q->ld_out3; t.vt_col0 = q->vt_col0; t.vt_off = q->vt_off; t.vt_ld = q->vt_ld;
+                x3_gemm_check(t);
+            }
+            if (in_is_x3) fits(q->in3_off, (int64_t)(M - 1) * 3 * q->ld_in + 3 * (int64_t)K, q->in3_elems, 8, "the rows of the X3 a lie past in3 (offsets are multiples of 8)");
+            else fits(q->in_off, (int64_t)(M - 1) * q->ld_in + K, q->in_floats, 4, "the rows of a lie past its buffer (offsets are multiples of 4)");
+            if (form == 0) {
+                need(q->out && q->ld_out >= N && q->ld_out <= LD_MAX, "an fp32 result needs out and ldc in [n, 2^20]");
+                fits(q->out_off, (int64_t)(M - 1) * q->ld_out + N, q->out_floats, 4, "the rows of c lie past out (offsets are multiples of 4)");
+                if (has_res && !r_is_c) {
+                    need(q->r && ldr >= N && ldr <= LD_MAX, "a residual needs r and ldr in [n, 2^20]");
+                    fits(q->r_off, (int64_t)(M - 1) * ldr + N, q->r_floats, 4, "the rows of r lie past its buffer (offsets are multiples of 4)");
+                }
+            } else {
+                need(q->out3 != nullptr, "an X3 result needs out3");
+                need(q->vt_col0 >= 0 && q->vt_ld <= LD_MAX, "vt_col0 >= 0, vt_ld <= 2^20");
+                const int row_cols = std::min(N, q->vt_col0), vt_rows = N - row_cols;
+                need(form != 1 || vt_rows == 0, "form 1: vt_col0 >= n (every column goes to the row image)");
+                need(q->ld_out3 >= row_cols && q->ld_out3 <= LD_MAX, "ldc3 is at least the row image's columns");
+                const int64_t rows_span = row_cols ? (int64_t)(M - 1) * 3 * q->ld_out3 + 3 * (int64_t)row_cols : 0;
+                int64_t span = rows_span;
+                if (vt_rows > 0) {
+                    need(q->vt_off >= rows_span && q->vt_off % 8 == 0, "vt_off lies behind the row image (a multiple of 8)");
+                    span = q->vt_off + (int64_t)vt_rows * 3 * q->vt_ld;
+                }
+                fits(q->out3_off, span, q->out3_elems, 8, "the X3 result lies past out3 (offsets are multiples of 8)");
+            }
+            upload();
+            unsigned short* w3 = dev_u16(x3_w_elems(N, K));
+            WLK_HIP(hipDeviceSynchronize());
+            launch_x3_pack_w(ctx, W.f(), K, w3, N, K);
+            X3GemmArgs g;
+            g.lda = q->ld_in; g.W3 = w3; g.bias = q->bias ? B.f() + q->bias_off : nullptr; g.M = M; g.N = N; g.K = K;
+            g.flags = q->flags; g.scale = q->scale; g.scale_cols = q->scale_cols; g.scale_period = q->scale_period;
+            g.ldc = q->ld_out; g.ldr = ldr; g.batch = batch;
+            if (form != 0) {
+                g.x3_out = true; g.ldc3 = q->ld_out3; g.vt_col0 = q->vt_col0; g.vt_off = q->vt_off; g.vt_ld = q->vt_ld;
+            }
+            for (int i = 0; i < nz; ++i) {
+                const unsigned short* a3;
+                if (in_is_x3) {
+                    a3 = IN3.u() + off(q->in3_off, i);
+                } else {
+                    unsigned short* p = dev_u16((size_t)M * 3 * q->ld_in);
+                    launch_x3_pack(ctx, IN.f() + off(q->in_off, i), q->ld_in, p, q->ld_in, M, K);
+                    a3 = p;
+                }
+                float* c = form == 0 ? OUT.f() + off(q->out_off, i) : reinterpret_cast<float*>(OUT3.u() + off(q->out3_off, i));
+                const float* r = has_res ? (r_is_c ? c : R.f() + off(q->r_off, i)) : nullptr;
+                if (batch) {        // exactly run_encode_group's table: in = the X3 image, out = the result (fp32 or X3), res
+                    z.in[i] = reinterpret_cast<const float*>(a3); z.out[i] = c; z.res[i] = r;
+                } else {
+                    g.A3 = a3; g.R = r;
+                    if (form == 0) g.C = c;
+                    else g.C3 = reinterpret_cast<unsigned short*>(c);
+                }
+            }
+            g.z = z;
+            WLK_HIP(hipDeviceSynchronize());
+            launch_gemm_x3(ctx, g, "diag_enc_x3_gemm");
+        } else if (kind == WLK_ENC_LN) {
+            const int d = N;
+            need(form == 0 || form == 1, "LN: form 0 (fp32 rows) or 1 (X3 row image)");
+            need(q->in && q->w && q->bias, "LN: in, gamma (w) and beta (bias)");
+            layernorm_check(d, q->ld_in, q->ld_out3, form == 1, batch);
+            need(d <= q->w_floats && d <= q->bias_floats, "gamma / beta hold fewer than d floats");
+            need(q->ld_in >= d && q->ld_in <= LD_MAX, "ldx in [d, 2^20]");
+            fits(q->in_off, (int64_t)(M - 1) * q->ld_in + d, q->in_floats, form == 1 ? 4 : 1, "the rows of x lie past in");
+            if (form == 0) {
+                need(q->out && q->ld_out >= d && q->ld_out <= LD_MAX, "an fp32 result needs out and ldy in [d, 2^20]");
+                fits(q->out_off, (int64_t)(M - 1) * q->ld_out + d, q->out_floats, 1, "the rows of y lie past out");
+            } else {
+                need(q->out3 && q->ld_out3 >= d && q->ld_out3 <= LD_MAX, "an X3 result needs out3 and ldy3 in [d, 2^20]");
+                fits(q->out3_off, (int64_t)(M - 1) * 3 * q->ld_out3 + 3 * (int64_t)d, q->out3_elems, 8, "the X3 rows of y lie past out3 (offsets are multiples of 8)");
+            }
+            upload();
+            for (int i = 0; i < nz; ++i) {
+                z.in[i] = IN.f() + off(q->in_off, i);
+                z.out[i] = form == 0 ? OUT.f() + off(q->out_off, i) : reinterpret_cast<float*>(OUT3.u() + off(q->out3_off, i));
+            }
+            WLK_HIP(hipDeviceSynchronize());
+            if (form == 0 && batch) launch_layernorm_batched(ctx, z, batch, q->ld_in, W.f(), B.f(), q->ld_out, M, d, "diag_enc_ln");
+            else if (form == 0) launch_layernorm(ctx, z.in[0], q->ld_in, W.f(), B.f(), z.out[0], q->ld_out, M, d, "diag_enc_ln");
+            else if (batch) launch_layernorm_x3_batched(ctx, z, batch, q->ld_in, W.f(), B.f(), q->ld_out3, M, d, "diag_enc_ln_x3");
+            else launch_layernorm_x3(ctx, z.in[0], q->ld_in, W.f(), B.f(), reinterpret_cast<unsigned short*>(z.out[0]), q->ld_out3, M, d, "diag_enc_ln_x3");
+        } else if (kind == WLK_ENC_ATTENTION) {
+            const int T = M, d = N, H = q->n_head;
+            need(form == 0 || form == 1, "ATTENTION: form 0 (fp32 kernel) or 1 (X3 kernel)");
+            need(H >= 1 && d == 64 * H, "attention: d = 64 n_head");
+            const bool x3_out = q->x3_out != 0;
+            if (form == 0) {
+                need(q->in && !in_is_x3 && !x3_out, "the fp32 attention reads fp32 qkv and writes fp32 rows");
+                need(q->out && q->ld_out == d, "the fp32 attention writes rows d apart");
+                fits(q->in_off, (int64_t)T * 3 * d, q->in_floats, 4, "qkv [T][3 d] lies past in (offsets are multiples of 4)");
+                fits(q->out_off, (int64_t)T * d, q->out_floats, 4, "out [T][d] lies past out (offsets are multiples of 4)");
+            } else {
+                enc_attention_x3_check(2L * d, x3_attn_vt_ld(T), x3_out ? q->ld_out3 : q->ld_out, T, d, H, x3_out);
+                need((q->in != nullptr) != in_is_x3, "ATTENTION: qkv is either in (fp32) or in3 (the X3 operand image)");
+                if (in_is_x3) fits(q->in3_off, (int64_t)x3_attn_image_elems(T, d), q->in3_elems, 8, "the operand image lies past in3 (offsets are multiples of 8)");
+                else fits(q->in_off, (int64_t)T * 3 * d, q->in_floats, 1, "qkv [T][3 d] lies past in");
+                if (x3_out) {
+                    need(q->out3 && q->ld_out3 >= d && q->ld_out3 <= LD_MAX, "X3 result rows need out3 and ldo in [d, 2^20]");
+                    fits(q->out3_off, (int64_t)(T - 1) * 3 * q->ld_out3 + 3 * (int64_t)d, q->out3_elems, 8, "the X3 rows of out lie past out3 (offsets are multiples of 8)");
+                } else {
+                    need(q->out && q->ld_out >= d && q->ld_out <= LD_MAX, "an fp32 result needs out and ldo in [d, 2^20]");
+                    fits(q->out_off, (int64_t)(T - 1) * q->ld_out + d, q->out_floats, 1, "the rows of out lie past out");
+                }
+            }
+            upload();
+            WLK_HIP(hipDeviceSynchronize());
+            for (int i = 0; i < nz; ++i) {
+                if (form == 0) {
+                    z.in[i] = IN.f() + off(q->in_off, i);
+                    z.out[i] = OUT.f() + off(q->out_off, i);
+                    continue;
+                }
+                if (in_is_x3) {
+                    z.in[i] = reinterpret_cast<const float*>(IN3.u() + off(q->in3_off, i));
+                } else {
+                    unsigned short* img = dev_u16(x3_attn_image_elems(T, d));
+                    launch_x3_pack_qkv(ctx, IN.f() + off(q->in_off, i), img, T, d, x3_attn_vt_off(T, d), x3_attn_vt_ld(T));
+                    z.in[i] = reinterpret_cast<const float*>(img);
+                }
+                z.out[i] = x3_out ? reinterpret_cast<float*>(OUT3.u() + off(q->out3_off, i)) : OUT.f() + off(q->out_off, i);
+            }
+            WLK_HIP(hipDeviceSynchronize());
+            if (form == 0 && batch) launch_encoder_attention_batched(ctx, z, batch, T, d, H);
+            else if (form == 0) launch_encoder_attention(ctx, z.in[0], z.out[0], T, d, H);
+            else
+                launch_encoder_attention_x3(ctx, batch ? nullptr : reinterpret_cast<const unsigned short*>(z.in[0]), 2L * d, x3_attn_vt_off(T, d),
+                                            x3_attn_vt_ld(T), batch ? nullptr : z.out[0], x3_out ? q->ld_out3 : q->ld_out, T, d, H,
+                                            batch ? &z : nullptr, batch, x3_out);
+        } else {
+            need(batch == 0, "PACK: no batch");
+            need(q->in && q->out3, "PACK: in and out3");
+            x3_pack_check(q->ld_in, q->ld_out3, N);
+            need(q->ld_in >= N && q->ld_in <= LD_MAX && q->ld_out3 >= N && q->ld_out3 <= LD_MAX, "ld_src and ld_dst in [cols, 2^20]");
+            need((int64_t)(M - 1) * q->ld_in + N <= q->in_floats, "the rows of src lie past in");
+            need((int64_t)(M - 1) * 3 * q->ld_out3 + 3 * (int64_t)N <= q->out3_elems, "the X3 rows lie past out3");
+            upload();
+            WLK_HIP(hipDeviceSynchronize());
+            launch_x3_pack(ctx, IN.f(), q->ld_in, OUT3.u(), q->ld_out3, M, N);
+        }
+        WLK_HIP(hipDeviceSynchronize());
+        download();
+        return WLK_OK;
+    } catch (const Refuse& e) {
+        g_diag_error = e.what();
+        return WLK_ERR_ARG;
+    } catch (const std::invalid_argument& e) {      // a launcher's own refusal: nothing was uploaded or launched
+        g_diag_error = e.what();
+        return WLK_ERR_ARG;
+    } catch (const std::exception& e) {
+        g_diag_error = e.what();
+        return WLK_ERR_HIP;
+    }
+}
+
+int wlk_diag_x3_plan(int m, int n, int k, int batch, int cus, char* out_text, int cap) {
+    if (!out_text || cap < 1) return WLK_ERR_ARG;
+    char text[256];
+    if (m < 1 || n < 1 || k < 64 || k % 64 != 0 || batch < 0 || batch > kMaxBatch || cus < 8) {
+        snprintf(text, sizeof text, "wlk_diag_x3_plan: m >= 1, n >= 1, k a multiple of 64, batch in [0, 8], cus >= 8");
+        g_diag_error = text;
+        snprintf(out_text, (size_t)cap, "%s", text);
+        return WLK_ERR_ARG;
+    }
+    const X3GemmPlan p = x3_gemm_plan(m, n, std::max(batch, 1), cus);
+    // the walk of gemm_x3_wide2_kernel, workgroup by workgroup: the tiles it takes and the empty slots between them
+    const int band_m = p.banded ? (p.tiles_m + 3) / 4 : p.tiles_m, band_n = p.banded ? (p.tiles_n + 1) / 2 : p.tiles_n;
+    const int per_session = band_m * band_n;
+    int max_tiles = 0, tiles_total = 0;
+    bool skips = false;
+    for (int wg = 0; wg < p.blocks; ++wg) {
+        const int xcd = p.banded ? wg & 7 : 0, first = p.banded ? wg >> 3 : wg, stride = p.banded ? p.blocks >> 3 : p.blocks;
+        const int band_m0 = p.banded ? (xcd >> 1) * band_m : 0, band_n0 = p.banded ? (xcd & 1) * band_n : 0;
+        int tiles = 0;
+        bool pending_gap = false;
+        for (int slot = first; slot < p.slots; slot += stride) {
+            const int r = slot % per_session;
+            const int rm = p.colmajor ? r % band_m : r / band_n, cn = p.colmajor ? r / band_m : r % band_n;
+            if (band_m0 + rm < p.tiles_m && band_n0 + cn < p.tiles_n) {
+                if (tiles > 0 && pending_gap) skips = true;
+                ++tiles;
+                pending_gap = false;
+            } else {
+                pending_gap = true;
+            }
+        }
+        max_tiles = std::max(max_tiles, tiles);
+        tiles_total += tiles;
+    }
+    snprintf(text, sizeof text, "bm=%d %s %s persist=%d tiles=%dx%d nslab=%d slots=%d blocks=%d walked=%d max_tiles_per_wg=%d skips_between=%d",
+             p.bm, p.banded ? "banded" : "plain", p.colmajor ? "colmajor" : "rowmajor", p.persist, p.tiles_m, p.tiles_n, k / 32,
+             p.slots, p.blocks, tiles_total, max_tiles, skips ? 1 : 0);
+    snprintf(out_text, (size_t)cap, "%s", text);
+    return WLK_OK;
+}
+
 }  // extern "C"

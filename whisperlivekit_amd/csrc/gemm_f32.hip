@@ -962,7 +962,7 @@ bool gemm_takes_kwave(int M, int N, int K) {
 
 bool gemm_takes_ksplit(int M, int N, int K) { return ksplit_tile(M, N, K).tm != 0; }
 
-void x3_refresh_env_switches();                          // gemm_x3.hip: WLK_X3_PERSIST
+void x3_refresh_env_switches();                          // gemm_x3.hip: WLK_X3_PERSIST, WLK_X3_BM, WLK_X3_COLMAJOR
 void refresh_env_switches() { x3_refresh_env_switches(); }   // wlk_diag_env_refresh: a test flips a switch inside one process
 
 void launch_gemm(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {

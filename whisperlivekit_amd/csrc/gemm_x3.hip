@@ -54,8 +54,12 @@ __global__ __launch_bounds__(256) void x3_pack_kernel(const float* __restrict__ 
     x3_store_chunk(dst + (long)row * 3 * ld_dst + (long)q * 24, v);
 }
 
-void launch_x3_pack(const LaunchCtx& ctx, const float* src, long ld_src, unsigned short* dst, long ld_dst, int rows, int cols) {
+void x3_pack_check(long ld_src, long ld_dst, int cols) {
     if (cols % 8 != 0 || ld_src % 4 != 0 || ld_dst % 8 != 0) throw std::invalid_argument("x3 pack: columns must be whole chunks of 8");
+}
+
+void launch_x3_pack(const LaunchCtx& ctx, const float* src, long ld_src, unsigned short* dst, long ld_dst, int rows, int cols) {
+    x3_pack_check(ld_src, ld_dst, cols);
     const long n = (long)rows * (cols / 8);
     if (n <= 0) return;
     KernelScope ks(ctx, "x3_pack");
@@ -235,6 +239,7 @@ __global__ __launch_bounds__(XK_THREADS) void gemm_x3_wide2_kernel(X3GemmArgs g)
     const int stride = banded ? (int)(gridDim.x >> 3) : (int)gridDim.x;
     const int limit = g.walk_slots;
     const int band_m0 = banded ? (xcd >> 1) * band_m : 0, band_n0 = banded ? (xcd & 1) * band_n : 0;
+    // (wlk_diag_x3_plan in diag.hip walks the same slots on the host - decode, advance, first and stride: keep it in step)
     auto decode = [&](int slot, int& tm, int& tn, int& b) -> bool {
         b = slot / per_session;
         const int r = slot - b * per_session;
@@ -575,13 +580,67 @@ bool gemm_x3_wide_applicable(int M, int N, int K, long lda) {
 
 static std::atomic<int> g_x3_persist{-1};                // -1: WLK_X3_PERSIST not read yet
 static std::atomic<int> g_x3_bm{-1};                     // -1: WLK_X3_BM not read yet (0: by the rounds x rows rule)
+static std::atomic<int> g_x3_colmajor{-2};               // -2: WLK_X3_COLMAJOR not read yet (-1: by the session count)
 void x3_refresh_env_switches() {
     g_x3_persist.store(-1, std::memory_order_relaxed);
     g_x3_bm.store(-1, std::memory_order_relaxed);
+    g_x3_colmajor.store(-2, std::memory_order_relaxed);
 }
 
-void launch_gemm_x3(const LaunchCtx& ctx, const X3GemmArgs& g, const char* tag) {
-    if (g.M <= 0 || g.N <= 0) return;
+// The launch geometry of the wide kernel for `batch` (>= 1) sessions of an M x N problem on `cus` compute units: what
+// launch_gemm_x3 launches, and what wlk_diag_x3_plan prints (no device needed).
+X3GemmPlan x3_gemm_plan(int M, int N, int batch, int cus) {
+    X3GemmPlan p;
+    // tile height: 64-row tiles where they cut the rounds x rows a CU works through by a tenth or more - the
+    // N = d projections of the d >= 1024 models (N = 1280: 160 tiles of 96 rows on 256 CUs, 240 of 64: 40.1 -> 31.7 us at K = 1280,
+    // 140.9 -> 120.0 at K = 5120) and large-v3's fc1 (640 tiles = 3 rounds of 96 rows, 960 = 4 rounds of 64: 137.4 -> 131.4 us); at
+    // equal rounds x rows the 96-row tile's loop wins (18 MFMAs per three weight loads against 12: base fc1 25.7 vs 31.1 us).
+    // profiles/r06l_x3_bm64_probe.txt.  WLK_X3_BM=64 / 96 forces either; an element's arithmetic does not depend on it.
+    int bm_env = g_x3_bm.load(std::memory_order_relaxed);
+    if (bm_env < 0) {
+        const char* e = getenv("WLK_X3_BM");
+        bm_env = e ? atoi(e) : 0;
+        g_x3_bm.store(bm_env, std::memory_order_relaxed);
+    }
+    p.tiles_n = (N + XW_BN - 1) / XW_BN;
+    auto rounds_rows = [&](int bm) { return (long)(((long)((M + bm - 1) / bm) * p.tiles_n * batch + cus - 1) / cus) * bm; };
+    p.bm = XW_BM;
+    if (bm_env == 64 || (bm_env == 0 && 10 * rounds_rows(64) <= 9 * rounds_rows(XW_BM))) p.bm = 64;
+    p.tiles_m = (M + p.bm - 1) / p.bm;
+    // WLK_X3_PERSIST=0: one workgroup per tile (the round-4 launch: same kernel, every list has one entry)
+    int persist = g_x3_persist.load(std::memory_order_relaxed);
+    if (persist < 0) {
+        const char* e = getenv("WLK_X3_PERSIST");
+        persist = !(e && e[0] == '0');
+        g_x3_persist.store(persist, std::memory_order_relaxed);
+    }
+    p.persist = persist;
+    // column-major walk inside a band: the workgroups resident at a time share weight blocks 4-fold and a persistent
+    // workgroup keeps its activation rows from tile to tile (cross-K|V 71 -> 67 us, large-v3 fc1 154 -> 147); with several
+    // sessions in one launch the row-major order measured better (212 vs 222 us at 8 sessions), so it is taken for one
+    // session only.  WLK_X3_COLMAJOR=0 / 1 forces either
+    int colmajor = g_x3_colmajor.load(std::memory_order_relaxed);
+    if (colmajor < -1) {
+        const char* e = getenv("WLK_X3_COLMAJOR");
+        colmajor = e ? atoi(e) : -1;
+        if (colmajor < -1) colmajor = -1;
+        g_x3_colmajor.store(colmajor, std::memory_order_relaxed);
+    }
+    p.colmajor = colmajor >= 0 ? colmajor : (batch <= 1);
+    p.banded = p.tiles_m >= 8;
+    if (p.banded) {           // per XCD: slots of its band, all sessions; at most one resident workgroup per CU of the XCD
+        p.slots = ((p.tiles_m + 3) / 4) * ((p.tiles_n + 1) / 2) * batch;
+        p.blocks = 8 * (persist ? std::min(p.slots, cus / 8) : p.slots);
+    } else {
+        p.slots = p.tiles_m * p.tiles_n * batch;
+        p.blocks = persist ? std::min(p.slots, cus) : p.slots;
+    }
+    return p;
+}
+
+// What launch_gemm_x3 refuses, as a host function of its own: the launcher calls it first, and wlk_diag_enc_op calls it on
+// the same arguments before it uploads anything (pointers: only their alignment is looked at).
+void x3_gemm_check(const X3GemmArgs& g) {
     if (g.K % 64 != 0 || g.lda % 8 != 0 || g.K < 64) throw std::invalid_argument("x3 gemm: K must be a multiple of 64, lda of 8");
     if (g.N % 4 != 0 || (!g.x3_out && g.ldc % 4 != 0) || ((g.flags & kGemmResidual) && g.ldr % 4 != 0))
         throw std::invalid_argument("x3 gemm: N, ldc and ldr must be multiples of 4 (16-byte epilogue accesses)");
@@ -592,6 +651,14 @@ void launch_gemm_x3(const LaunchCtx& ctx, const X3GemmArgs& g, const char* tag) 
     if (g.x3_out && ((g.flags & kGemmResidual) || g.vt_col0 % XW_BN != 0 || g.ldc3 % 8 != 0 || g.vt_ld % 32 != 0 ||
                      g.vt_ld < g.M))
         throw std::invalid_argument("x3 gemm: unsupported X3 result layout");
+    // the row image is stored in whole 8-column chunks: a last chunk of four columns would carry four values that belong to
+    // no column
+    if (g.x3_out && g.N % 8 != 0) throw std::invalid_argument("x3 gemm: an X3 result needs N % 8 == 0");
+}
+
+void launch_gemm_x3(const LaunchCtx& ctx, const X3GemmArgs& g, const char* tag) {
+    if (g.M <= 0 || g.N <= 0) return;
+    x3_gemm_check(g);
     static std::atomic<uint64_t> configured{0};
     int dev = 0;
     WLK_HIP(hipGetDevice(&dev));
@@ -608,48 +675,13 @@ void launch_gemm_x3(const LaunchCtx& ctx, const X3GemmArgs& g, const char* tag) 
         if (cus < 8) cus = 8;
         cu_count[dev & 63].store(cus, std::memory_order_relaxed);
     }
-    // tile height: 64-row tiles where they cut the rounds x rows a CU works through by a tenth or more - the
-    // N = d projections of the d >= 1024 models (N = 1280: 160 tiles of 96 rows on 256 CUs, 240 of 64: 40.1 -> 31.7 us at K = 1280,
-    // 140.9 -> 120.0 at K = 5120) and large-v3's fc1 (640 tiles = 3 rounds of 96 rows, 960 = 4 rounds of 64: 137.4 -> 131.4 us); at
-    // equal rounds x rows the 96-row tile's loop wins (18 MFMAs per three weight loads against 12: base fc1 25.7 vs 31.1 us).
-    // profiles/r06l_x3_bm64_probe.txt.  WLK_X3_BM=64 / 96 forces either; an element's arithmetic does not depend on it.
-    int bm_env = g_x3_bm.load(std::memory_order_relaxed);
-    if (bm_env < 0) {
-        const char* e = getenv("WLK_X3_BM");
-        bm_env = e ? atoi(e) : 0;
-        g_x3_bm.store(bm_env, std::memory_order_relaxed);
-    }
-    const int tiles_n = (g.N + XW_BN - 1) / XW_BN;
-    auto rounds_rows = [&](int bm) { return (long)(((long)((g.M + bm - 1) / bm) * tiles_n * batch + cus - 1) / cus) * bm; };
-    int bm = XW_BM;
-    if (bm_env == 64 || (bm_env == 0 && 10 * rounds_rows(64) <= 9 * rounds_rows(XW_BM))) bm = 64;
-    const int tiles_m = (g.M + bm - 1) / bm;
-    // WLK_X3_PERSIST=0: one workgroup per tile (the round-4 launch: same kernel, every list has one entry)
-    int persist = g_x3_persist.load(std::memory_order_relaxed);
-    if (persist < 0) {
-        const char* e = getenv("WLK_X3_PERSIST");
-        persist = !(e && e[0] == '0');
-        g_x3_persist.store(persist, std::memory_order_relaxed);
-    }
-    // column-major walk inside a band: the workgroups resident at a time share weight blocks 4-fold and a persistent
-    // workgroup keeps its activation rows from tile to tile (cross-K|V 71 -> 67 us, large-v3 fc1 154 -> 147); with several
-    // sessions in one launch the row-major order measured better (212 vs 222 us at 8 sessions), so it is taken for one
-    // session only.  WLK_X3_COLMAJOR=0 / 1 forces either
-    static const int colmajor = [] {
-        const char* e = getenv("WLK_X3_COLMAJOR");
-        return e ? atoi(e) : -1;
-    }();
+    const X3GemmPlan plan = x3_gemm_plan(g.M, g.N, batch, cus);
+    const int bm = plan.bm;
     X3GemmArgs gg = g;
-    gg.walk_colmajor = colmajor >= 0 ? colmajor : (batch <= 1);
-    gg.walk_banded = tiles_m >= 8;
-    int blocks;
-    if (gg.walk_banded) {           // per XCD: slots of its band, all sessions; at most one resident workgroup per CU of the XCD
-        gg.walk_slots = ((tiles_m + 3) / 4) * ((tiles_n + 1) / 2) * batch;
-        blocks = 8 * (persist ? std::min(gg.walk_slots, cus / 8) : gg.walk_slots);
-    } else {
-        gg.walk_slots = tiles_m * tiles_n * batch;
-        blocks = persist ? std::min(gg.walk_slots, cus) : gg.walk_slots;
-    }
+    gg.walk_colmajor = plan.colmajor;
+    gg.walk_banded = plan.banded;
+    gg.walk_slots = plan.slots;
+    const int blocks = plan.blocks;
     // algorithmic work (what the roofline fraction is computed from): 2 M N K flop, operands and result once
     KernelScope ks(ctx, tag, 2.0 * batch * (double)g.M * g.N * g.K,
                    batch * (6.0 * ((double)g.M * g.K) + 4.0 * (double)g.M * g.N) + 6.0 * (double)g.N * g.K);

@@ -161,10 +161,16 @@ static void launch_ln_by_width(int d, dim3 grid, hipStream_t stream, Args... arg
     else hipLaunchKernelGGL(layernorm_kernel<kLnMaxPerLane>, grid, dim3(256), 0, stream, args...);
 }
 
+// what the LayerNorm launchers refuse (they call it first; wlk_diag_enc_op before it uploads anything): x3 = the X3 forms
+void layernorm_check(int d, long ldx, long ldy3, bool x3, int batch) {
+    if (d > 64 * kLnMaxPerLane || batch > kMaxBatch) throw std::invalid_argument("layernorm: d or batch too large");
+    if (x3 && (d % 8 != 0 || ldx % 4 != 0 || ldy3 % 8 != 0)) throw std::invalid_argument("layernorm (x3): unsupported width");
+}
+
 void launch_layernorm(const LaunchCtx& ctx, const float* x, long ldx, const float* gamma, const float* beta,
                       float* y, long ldy, int rows, int d, const char* tag) {
     if (rows <= 0) return;
-    if (d > 64 * kLnMaxPerLane) throw std::invalid_argument("layernorm: d too large");
+    layernorm_check(d, ldx, 0, false, 0);
     KernelScope ks(ctx, tag);
     launch_ln_by_width(d, dim3((rows + 3) / 4), ctx.stream, x, ldx, gamma, beta, y, ldy, rows, d, PtrTable{}, 0);
     WLK_HIP(hipGetLastError());
@@ -173,7 +179,7 @@ void launch_layernorm(const LaunchCtx& ctx, const float* x, long ldx, const floa
 void launch_layernorm_batched(const LaunchCtx& ctx, const PtrTable& z, int batch, long ldx, const float* gamma,
                               const float* beta, long ldy, int rows, int d, const char* tag) {
     if (rows <= 0 || batch <= 0) return;
-    if (d > 64 * kLnMaxPerLane || batch > kMaxBatch) throw std::invalid_argument("layernorm: d or batch too large");
+    layernorm_check(d, ldx, 0, false, batch);
     KernelScope ks(ctx, tag);
     launch_ln_by_width(d, dim3((rows + 3) / 4, batch), ctx.stream, (const float*)nullptr, ldx, gamma, beta, (float*)nullptr,
                        ldy, rows, d, z, batch);
@@ -184,7 +190,7 @@ void launch_layernorm_batched(const LaunchCtx& ctx, const PtrTable& z, int batch
 void launch_layernorm_x3(const LaunchCtx& ctx, const float* x, long ldx, const float* gamma, const float* beta,
                          unsigned short* y3, long ldy3, int rows, int d, const char* tag) {
     if (rows <= 0) return;
-    if (d > 64 * kLnMaxPerLane || d % 8 != 0 || ldx % 4 != 0 || ldy3 % 8 != 0) throw std::invalid_argument("layernorm (x3): unsupported width");
+    layernorm_check(d, ldx, ldy3, true, 0);
     KernelScope ks(ctx, tag);
     launch_ln_x3_by_width(d, dim3((rows + 3) / 4), ctx.stream, x, ldx, gamma, beta, y3, ldy3, rows, d, PtrTable{});
     WLK_HIP(hipGetLastError());
@@ -193,8 +199,7 @@ void launch_layernorm_x3(const LaunchCtx& ctx, const float* x, long ldx, const f
 void launch_layernorm_x3_batched(const LaunchCtx& ctx, const PtrTable& z, int batch, long ldx, const float* gamma,
                                  const float* beta, long ldy3, int rows, int d, const char* tag) {
     if (rows <= 0 || batch <= 0) return;
-    if (d > 64 * kLnMaxPerLane || d % 8 != 0 || ldx % 4 != 0 || ldy3 % 8 != 0 || batch > kMaxBatch)
-        throw std::invalid_argument("layernorm (x3): unsupported width or batch");
+    layernorm_check(d, ldx, ldy3, true, batch);
     KernelScope ks(ctx, tag);
     launch_ln_x3_by_width(d, dim3((rows + 3) / 4, batch), ctx.stream, (const float*)nullptr, ldx, gamma, beta,
                           (unsigned short*)nullptr, ldy3, rows, d, z);

@@ -1,5 +1,12 @@
 // "X3": an fp32 tensor held as three bf16 planes, x = hi + mid + lo EXACTLY (each plane is the round-to-nearest bf16 of
-// what the planes before it left over; bf16 has fp32's exponent range, so nothing under- or overflows on the way).
+// what the planes before it left over; bf16 has fp32's exponent range).  The domain of "exactly"
+// (tests/test_enc_x3_reference_cpu.py; the device's split is the host's bit for bit, subnormals included - x3_pack is not
+// flushing - tests/test_gpu_enc_x3.py::test_pack):
+//   * |x| < 0x7F7F8000 = 3.3961775e38: from there to FLT_MAX hi rounds to infinity and the other planes are not finite;
+//   * x is a multiple of 2^-133, the spacing of bf16's subnormals (7 mantissa bits under 2^-126 against fp32's 23): every
+//     fp32 of magnitude 2^-110 or more is one; below that the bits of x under 2^-133 are rounded away (2^-126 (1 + 2^-23)
+//     comes back as 2^-126, 2^-149 as 0).
+// Activations and weights are many orders of magnitude inside both limits.  - 0 is split as (- 0, + 0, + 0).
 //
 // Why: gfx950's matrix cores run bf16 at 16x the fp32-input rate (v_mfma_f32_32x32x16_bf16: 32768 flop per 32 cycles per
 // SIMD against v_mfma_f32_32x32x2_f32's 4096 per 64), and an fp32 product is six bf16 products away:
