@@ -927,6 +927,53 @@ typedef struct wlk_diag_enc_op_args {
     uint16_t* out3;                 /* in / out, or NULL */
 } wlk_diag_enc_op_args;
 int wlk_diag_enc_op(const wlk_diag_enc_op_args* args);
+/* The device half of find_alignment behind the vocabulary projection (csrc/word_align.hip) on host data, through its
+ * production launcher launch_word_align, unchanged: token probabilities softmax(logits[i][:n_cols])[targets[i]] of the
+ * n_text = P - n_sot - 2 rows of logits (rows ld apart); w = softmax(qk_scale * ring[a][r][:F]) of the rows r < P of the raw
+ * scores ring [n_align][ring_rows][T]; in place its z-score over the P rows; cost [n_text + 1][F] = minus the head mean of
+ * the width-7 median of the rows n_sot .. P - 2; trace [(n_text + 2)][F + 1] = dtw's step codes.  last_stage stops the
+ * chain after WLK_WA_SOFTMAX, _ZSCORE (w holds z), _COST or _DTW; cost / trace may be NULL for the stages that do not write
+ * them.  Every buffer lives on the device in exactly the elements the caller passes and is copied back whole - inputs too.
+ * What a buffer cannot hold, or what the launcher's check function refuses (its own text), returns WLK_ERR_ARG with a
+ * message in wlk_diag_last_error() before anything is uploaded.  All pointers are host memory; the call is synchronous. */
+#define WLK_WA_SOFTMAX 0
+#define WLK_WA_ZSCORE 1
+#define WLK_WA_COST 2
+#define WLK_WA_DTW 3
+typedef struct wlk_diag_word_align_args {
+    int32_t P, F, T, ring_rows, n_align, n_sot, n_cols, last_stage;
+    float qk_scale;
+    int64_t ld;
+    int64_t ring_floats, logits_floats, targets_n, w_floats, cost_floats, probs_floats, trace_bytes;
+    float* ring;                    /* in / out */
+    float* logits;                  /* in / out */
+    int32_t* targets;               /* in / out [targets_n] */
+    float* w;                       /* in / out */
+    float* cost;                    /* in / out, or NULL */
+    float* probs;                   /* in / out */
+    int8_t* trace;                  /* in / out, or NULL */
+} wlk_diag_word_align_args;
+int wlk_diag_word_align(const wlk_diag_word_align_args* args);
+/* NLLB's ragged decoder cross-attention (csrc/nllb_batch.hip) on host data through launch_nllb_cross_attention_ragged
+ * (align = 0) or launch_nllb_cross_attention_ragged_align (align = 1), unchanged: q [n_rows][d], d = 64 n_head; row r
+ * attends to the lengths[r] (1 .. 512) key rows of its block kv + kv_at[r], which holds kv_rows[r] >= lengths[r] rows of
+ * ldkv floats with k at kv_off and v at kv_off + d; out [n_rows][d].  The align form (n_rows <= 8) also stores the weights
+ * of every head h with head_rank[h] >= 0 to align_probs[head_rank[h]][r][0 .. lengths[r]) ([n_rank][8][align_stride]).
+ * Buffers, refusals and synchronisation as wlk_diag_word_align. */
+typedef struct wlk_diag_nllb_cross_ragged_args {
+    int32_t n_rows, d, n_head, align, n_rank, align_stride;
+    int64_t kv_off, ldkv;
+    int64_t q_floats, kv_floats, out_floats, probs_floats;
+    const int32_t* lengths;         /* [n_rows] */
+    const int64_t* kv_at;           /* [n_rows] */
+    const int32_t* kv_rows;         /* [n_rows] */
+    int32_t* head_rank;             /* [n_head], or NULL */
+    float* q;                       /* in / out */
+    float* kv;                      /* in / out */
+    float* out;                     /* in / out */
+    float* align_probs;             /* in / out, or NULL */
+} wlk_diag_nllb_cross_ragged_args;
+int wlk_diag_nllb_cross_ragged(const wlk_diag_nllb_cross_ragged_args* args);
 /* The launch geometry launch_gemm_x3 takes for `batch` sessions (0 = plain pointers) of an m x n x k problem on a device of
  * `cus` compute units, as text: "bm=96|64 banded|plain colmajor|rowmajor persist=.. tiles=MxN nslab=.. slots=.. blocks=..
  * walked=.. max_tiles_per_wg=.. skips_between=0|1" - the answer of the function launch_gemm_x3 itself calls (the WLK_X3_*

@@ -57,8 +57,9 @@ def dtw(x: np.ndarray) -> np.ndarray:
 # Pinned by the matrices the reference's find_alignment handed to dtw (tests/golden/word_timing_kat.json.gz).
 # ---------------------------------------------------------------------------------------------------------------
 def alignment_cost(sd, dims, align_heads, mel, sot_sequence, no_timestamps, text_tokens, eot, num_frames,
-                   medfilt_width: int = 7, qk_scale: float = 1.0):
-    """-> (cost matrix [len(text_tokens) + 1, num_frames // 2] as handed to dtw, per-token probabilities)."""
+                   medfilt_width: int = 7, qk_scale: float = 1.0, dtype=np.float32):
+    """-> (cost matrix [len(text_tokens) + 1, num_frames // 2] as handed to dtw, per-token probabilities).  With a float64
+    state dict and mel the whole pass runs in float64; dtype=np.float64 then hands the matrix back unrounded."""
     import torch
 
     from . import whisper_oracle as wo
@@ -73,4 +74,4 @@ def alignment_cost(sd, dims, align_heads, mel, sot_sequence, no_timestamps, text
         std, mean = torch.std_mean(w, dim=-2, keepdim=True, unbiased=False)
         w = wo.median_filter((w - mean) / std, medfilt_width)
         matrix = w.mean(dim=0)[len(sot_sequence): -1]
-    return (-matrix).numpy().astype(np.float32), probs
+    return (-matrix).numpy().astype(dtype), probs

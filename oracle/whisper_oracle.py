@@ -71,8 +71,13 @@ def encoder_input_from_audio(audio: torch.Tensor, filters: torch.Tensor) -> Tupl
 # a14/a13/a4/a3  blocks                            whisperlivekit/whisper/model.py:39-254
 # ---------------------------------------------------------------------------------------
 
+def _f32(x):
+    """the reference's .float() (it may hold fp16 weights); a float64 run - the tests' high-precision form - stays float64"""
+    return x if x.dtype == torch.float64 else x.float()
+
+
 def _ln(x, sd, prefix):
-    return F.layer_norm(x.float(), (x.shape[-1],), sd[prefix + ".weight"], sd[prefix + ".bias"])  # model.py:39-41
+    return F.layer_norm(_f32(x), (x.shape[-1],), sd[prefix + ".weight"], sd[prefix + ".bias"])  # model.py:39-41
 
 
 def _lin(x, sd, prefix):
@@ -90,7 +95,7 @@ def qkv_attention(q, k, v, n_head, mask=None):
     qk = (q * scale) @ (k * scale).transpose(-1, -2)
     if mask is not None:
         qk = qk + mask[:n_ctx, :n_ctx]
-    qk = qk.float()
+    qk = _f32(qk)
     w = F.softmax(qk, dim=-1)
     out = (w @ v).permute(0, 2, 1, 3).flatten(start_dim=2)
     return out, qk
@@ -169,7 +174,7 @@ def decoder_forward(sd, dims, tokens: torch.Tensor, xa: torch.Tensor, cache: Dec
         cross_qk.append(qk)
         x = x + _mlp(_ln(x, sd, p + ".mlp_ln"), sd, p)
     x = _ln(x, sd, "decoder.ln")
-    logits = (x @ sd["decoder.token_embedding.weight"].transpose(0, 1)).float()  # model.py:326-328
+    logits = _f32(x @ sd["decoder.token_embedding.weight"].transpose(0, 1))  # model.py:326-328
     return logits, cross_qk
 
 

@@ -141,3 +141,45 @@ def test_hip_find_alignment_matches_the_reference(case):
     finally:
         sess.close()
         model.close()
+
+
+@pytest.mark.gpu
+def test_hip_find_alignment_multilingual_against_the_float64_oracle():
+    """The whole call on the multilingual micro model: a three-token sot sequence (row0 = 3), all its alignment heads, 40
+    and 440 text tokens (445 of the 448 rows of the text context), 5 and 1499 frames.  The cost against
+    timing_oracle.alignment_cost run in float64, within 4 x the error the float32 oracle has on the same case (floor: the
+    2e-5 of the test above); the trace is dtw_trace of the returned cost, cell by cell."""
+    import torch
+    from select_reference import abs_err
+    from whisperlivekit_amd.engine import HipWhisperModel
+    dims, heads = MODEL_DIMS["micro"], ALIGNMENT_HEADS["micro"]
+    sot_sequence, no_timestamps, eot = [50258, 50259, 50359], 50363, 50257
+    sd32 = H.oracle_sd("micro", 0)
+    sd64 = {k: v.double() if v.is_floating_point() else v for k, v in sd32.items()}
+    mel = np.random.default_rng(11).standard_normal((dims.n_mels, 3000)).astype(np.float32)
+    model = HipWhisperModel.from_state_dict(dims, helpers.synth_sd("micro", 0), heads, device=0)
+    sess = model.new_session(beam=1, batched=False)
+    fails = []
+    try:
+        sess.encode_mel(mel)
+        for n_text, num_frames in ((40, 10), (40, 2999), (440, 10), (440, 2999)):
+            text = np.random.default_rng(n_text + num_frames).integers(0, eot, n_text).tolist()
+            want, probs64 = timing_oracle.alignment_cost(sd64, dims, heads, torch.from_numpy(mel).double(), sot_sequence,
+                                                         no_timestamps, text, eot, num_frames, dtype=np.float64)
+            f32, _ = timing_oracle.alignment_cost(sd32, dims, heads, torch.from_numpy(mel), sot_sequence, no_timestamps, text,
+                                                  eot, num_frames)
+            trace, probs, cost = sess.find_alignment([*sot_sequence, no_timestamps, *text, eot], len(sot_sequence), eot,
+                                                     num_frames, want_cost=True)
+            assert cost.shape == want.shape == (n_text + 1, num_frames // 2)
+            e32, err = float(abs_err(f32, want).max()), float(abs_err(cost, want).max())
+            allowed = max(4 * e32, 2e-5)
+            print(f"n_text {n_text} num_frames {num_frames}: error {err:.3e}, float32 oracle {e32:.3e}, allowed {allowed:.3e}")
+            if not err <= allowed:
+                fails.append(f"n_text {n_text}, num_frames {num_frames}: cost error {err:.3e} > {allowed:.3e} (float32 oracle {e32:.3e})")
+            if not np.array_equal(trace, timing_oracle.dtw_trace(cost)):
+                fails.append(f"n_text {n_text}, num_frames {num_frames}: the trace is not dtw_trace of the returned cost")
+            np.testing.assert_allclose(probs, probs64, rtol=2e-4, atol=1e-9)
+    finally:
+        sess.close()
+        model.close()
+    assert not fails, "\n".join(fails)

@@ -129,7 +129,24 @@ class DiagEncOpArgs(C.Structure):
         (n, C.c_void_p) for n in ("in", "in3", "w", "bias", "r", "out", "out3")]
 
 
+class DiagWordAlignArgs(C.Structure):
+    """wlk_diag_word_align_args (include/wlk_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("P", "F", "T", "ring_rows", "n_align", "n_sot", "n_cols", "last_stage")] + [
+        ("qk_scale", C.c_float), ("ld", C.c_int64)] + [
+        (n, C.c_int64) for n in ("ring_floats", "logits_floats", "targets_n", "w_floats", "cost_floats", "probs_floats",
+                                 "trace_bytes")] + [
+        (n, C.c_void_p) for n in ("ring", "logits", "targets", "w", "cost", "probs", "trace")]
+
+
+class DiagNllbCrossRaggedArgs(C.Structure):
+    """wlk_diag_nllb_cross_ragged_args (include/wlk_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("n_rows", "d", "n_head", "align", "n_rank", "align_stride")] + [
+        (n, C.c_int64) for n in ("kv_off", "ldkv", "q_floats", "kv_floats", "out_floats", "probs_floats")] + [
+        (n, C.c_void_p) for n in ("lengths", "kv_at", "kv_rows", "head_rank", "q", "kv", "out", "align_probs")]
+
+
 ENC_X3_GEMM, ENC_LN, ENC_ATTENTION, ENC_PACK = range(4)
+WA_SOFTMAX, WA_ZSCORE, WA_COST, WA_DTW = range(4)
 SFK_ATTENTION, SFK_CONV0, SFK_DWCONV2D, SFK_GLU_DWCONV, SFK_HEAD, SFK_ASSEMBLE = range(6)
 DA_S0, DA_S1, DA_S2 = 0, 1, 2
 DA_C0, DA_C1, DA_C2, DA_C3, DA_C4, DA_C5 = 10, 11, 12, 13, 14, 15
@@ -343,6 +360,8 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_gemv_variant": (cint, [cint, cint, cint, cint, cint, C.c_char_p, cint]),
         "wlk_diag_enc_op": (cint, [C.POINTER(DiagEncOpArgs)]),
         "wlk_diag_x3_plan": (cint, [cint, cint, cint, cint, cint, C.c_char_p, cint]),
+        "wlk_diag_word_align": (cint, [C.POINTER(DiagWordAlignArgs)]),
+        "wlk_diag_nllb_cross_ragged": (cint, [C.POINTER(DiagNllbCrossRaggedArgs)]),
         "wlk_model_set_cif": (cint, [p, p, cint, C.c_float]),
         "wlk_cif_result": (cint, [p, C.POINTER(CifOut)]),
         "wlk_diag_cif": (cint, [p, cint, cint, p, C.c_float, cint, cint, p, p, p]),
@@ -397,7 +416,7 @@ EXPORTED_SYMBOLS = (
     "wlk_diag_encoder_attention_x3", "wlk_diag_encoder_attention_x3_time", "wlk_diag_qkv_x3_attention",
     "wlk_diag_select", "wlk_diag_dec_attention", "wlk_diag_topk", "wlk_diag_sf_kernel", "wlk_diag_nllb_align",
     "wlk_diag_nllb_align_rows", "wlk_diag_linear_ex", "wlk_diag_gemv_variant", "wlk_diag_enc_op",
-    "wlk_diag_x3_plan",
+    "wlk_diag_x3_plan", "wlk_diag_word_align", "wlk_diag_nllb_cross_ragged",
     "wlk_model_set_cif", "wlk_cif_result", "wlk_diag_cif",
 )
 

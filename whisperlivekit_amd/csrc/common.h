@@ -335,6 +335,30 @@ void launch_encoder_attention_x3(const LaunchCtx& ctx, const unsigned short* qk3
 void enc_attention_x3_check(long ldqk, long vt_ld, long ldo, int T, int d, int n_head, bool x3_out);   // throws for what the launcher refuses
 void launch_x3_pack_qkv(const LaunchCtx& ctx, const float* qkv, unsigned short* out, int T, int d, long vt_off, long vt_ld);
 
+// ---- word_align.hip ---------------------------------------------------------------------------
+// The device half of find_alignment behind the decoder pass: token probabilities, softmax over the first F frames, z-score
+// over the P token rows, median of 7 + head mean of the rows n_sot .. P - 2, dtw.  n_text = P - n_sot - 2 rows of logits.
+enum WordAlignStage { kWaSoftmax = 0, kWaZscore = 1, kWaCost = 2, kWaDtw = 3 };
+struct WordAlignArgs {
+    const float* logits = nullptr;      // [n_text][ld], the first n_cols columns count
+    long ld = 0;
+    int n_cols = 0;
+    const int* target = nullptr;        // [n_text] on the device
+    float* probs = nullptr;             // [n_text]
+    const float* ring = nullptr;        // raw scores [n_align][ring_rows][T], rows 0 .. P - 1
+    int ring_rows = 0, T = 0, n_align = 0, P = 0, F = 0, n_sot = 0;
+    float qk_scale = 1.f;
+    float* w = nullptr;                 // [n_align][P][F]: the softmax, then in place its z-score
+    float* cost = nullptr;              // [P - n_sot - 1][F]
+    signed char* trace_t = nullptr;     // dtw scratch and result, (P - n_sot)(F + 1) bytes each
+    signed char* trace = nullptr;
+};
+// throws std::invalid_argument for what launch_word_align refuses; target_host (may be null): the targets' values
+void word_align_check(const WordAlignArgs& a, const int* target_host, int last_stage);
+void launch_word_align(const LaunchCtx& ctx, const WordAlignArgs& a, const int* target_host, int last_stage);
+// wlk_diag_*: the calling thread's message for wlk_diag_last_error (diag.hip owns the storage)
+void set_diag_error(const std::string& msg);
+
 // ---- layernorm.hip --------------------------------------------------------------------------
 void layernorm_check(int d, long ldx, long ldy3, bool x3, int batch);        // throws for what the launchers below refuse
 void launch_layernorm(const LaunchCtx& ctx, const float* x, long ldx, const float* gamma, const float* beta,

@@ -39,6 +39,7 @@ int run(F&& f) {
 }
 }  // namespace
 
+void wlk::set_diag_error(const std::string& msg) { g_diag_error = msg; }
 
 // wave_ops.h against the __shfl_xor loops it replaces: out[0..9][lane] = VALU-butterfly results, ref[0..9][lane] = the
 // shuffle forms, on the same 64 floats (rows: sum, max, row16 sum 1-2-4-8, xor 1, 2, 4, 8, 16, 32, arg-max index)
@@ -1576,6 +1577,88 @@ int wlk_diag_enc_op(const wlk_diag_enc_op_args* q) {
         g_diag_error = e.what();
         return WLK_ERR_ARG;
     } catch (const std::invalid_argument& e) {      // a launcher's own refusal: nothing was uploaded or launched
+        g_diag_error = e.what();
+        return WLK_ERR_ARG;
+    } catch (const std::exception& e) {
+        g_diag_error = e.what();
+        return WLK_ERR_HIP;
+    }
+}
+
+/* The device half of find_alignment behind the vocabulary projection on host data, through launch_word_align, unchanged
+ * (see include/wlk_hip.h).  What a buffer cannot hold, and what word_align_check refuses (its own text), is WLK_ERR_ARG
+ * before anything is uploaded. */
+int wlk_diag_word_align(const wlk_diag_word_align_args* q) {
+    struct Refuse : std::invalid_argument {
+        using std::invalid_argument::invalid_argument;
+    };
+    struct Buf {        // a device copy of exactly `bytes` host bytes (never fewer than 64), copied back whole
+        char* p = nullptr;
+        void* host = nullptr;
+        size_t bytes = 0;
+        Buf() = default;
+        Buf(const Buf&) = delete;
+        void set(void* h, size_t n) {
+            host = h;
+            bytes = n;
+            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(bytes, 64)));
+            if (host && bytes) WLK_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+        }
+        float* f() const { return reinterpret_cast<float*>(p); }
+        void back() const { if (host && bytes) WLK_HIP(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost)); }
+        ~Buf() { (void)hipFree(p); }
+    };
+    try {
+        auto need = [](bool ok, const char* what) {
+            if (!ok) throw Refuse(std::string("wlk_diag_word_align: ") + what);
+        };
+        need(q != nullptr, "null arguments");
+        need(q->ring && q->logits && q->targets && q->w && q->probs, "null ring, logits, targets, w or probs");
+        const int64_t LIM = 1 << 20;
+        need(q->P >= 1 && q->P <= LIM && q->F >= 1 && q->F <= LIM && q->T >= 1 && q->T <= LIM && q->ring_rows >= 1 && q->ring_rows <= LIM &&
+                 q->n_align >= 1 && q->n_align <= 64 && q->n_sot >= 0 && q->n_sot <= LIM && q->n_cols >= 1 && q->n_cols <= LIM &&
+                 q->ld >= 1 && q->ld <= LIM,
+             "P, F, T, ring_rows, n_cols, ld in [1, 2^20], n_align in [1, 64], n_sot in [0, 2^20]");
+        const int last = q->last_stage;
+        const int64_t n_text = (int64_t)q->P - q->n_sot - 2, N = n_text + 1;
+        const int64_t nt = std::max<int64_t>(n_text, 1);
+        need(q->targets_n >= nt, "targets holds fewer than n_text entries");
+        WordAlignArgs a;
+        {   // the launcher's own refusals, by its own function, on stand-in pointers
+            float* const base = reinterpret_cast<float*>(uintptr_t(1) << 20);
+            a.logits = base; a.ld = q->ld; a.n_cols = q->n_cols; a.target = reinterpret_cast<const int*>(base); a.probs = base;
+            a.ring = base; a.ring_rows = q->ring_rows; a.T = q->T; a.n_align = q->n_align; a.P = q->P; a.F = q->F; a.n_sot = q->n_sot;
+            a.qk_scale = q->qk_scale; a.w = base; a.cost = q->cost ? base : nullptr;
+            a.trace_t = a.trace = q->trace ? reinterpret_cast<signed char*>(base) : nullptr;
+            word_align_check(a, q->targets, last);
+        }
+        need((int64_t)q->n_align * q->ring_rows * q->T <= q->ring_floats, "ring holds fewer than n_align x ring_rows x T floats");
+        need((n_text - 1) * q->ld + q->n_cols <= q->logits_floats, "the logit rows lie past their buffer");
+        need((int64_t)q->n_align * q->P * q->F <= q->w_floats, "w holds fewer than n_align x P x F floats");
+        need(n_text <= q->probs_floats, "probs holds fewer than n_text floats");
+        need(last < kWaCost || N * q->F <= q->cost_floats, "cost holds fewer than (n_text + 1) x F floats");
+        const int64_t n_trace = (N + 1) * ((int64_t)q->F + 1);
+        need(last < kWaDtw || n_trace <= q->trace_bytes, "trace holds fewer than (n_text + 2) x (F + 1) bytes");
+        Buf RING, LOG, TGT, W, COST, PROBS, TRACE, SCRATCH;
+        RING.set(q->ring, (size_t)q->ring_floats * 4);
+        LOG.set(q->logits, (size_t)q->logits_floats * 4);
+        TGT.set(q->targets, (size_t)q->targets_n * 4);
+        W.set(q->w, (size_t)q->w_floats * 4);
+        PROBS.set(q->probs, (size_t)q->probs_floats * 4);
+        if (q->cost) COST.set(q->cost, (size_t)q->cost_floats * 4);
+        if (q->trace) TRACE.set(q->trace, (size_t)q->trace_bytes);
+        SCRATCH.set(nullptr, (size_t)n_trace);
+        a.logits = LOG.f(); a.target = reinterpret_cast<const int*>(TGT.p); a.probs = PROBS.f(); a.ring = RING.f(); a.w = W.f();
+        a.cost = q->cost ? COST.f() : nullptr;
+        a.trace = q->trace ? reinterpret_cast<signed char*>(TRACE.p) : nullptr;
+        a.trace_t = q->trace ? reinterpret_cast<signed char*>(SCRATCH.p) : nullptr;
+        LaunchCtx ctx;
+        WLK_HIP(hipDeviceSynchronize());
+        launch_word_align(ctx, a, q->targets, last);
+        WLK_HIP(hipDeviceSynchronize());
+        RING.back(); LOG.back(); TGT.back(); W.back(); PROBS.back(); COST.back(); TRACE.back();
+        return WLK_OK;
+    } catch (const std::invalid_argument& e) {      // Refuse, or the launcher's own refusal: nothing was uploaded or launched
         g_diag_error = e.what();
         return WLK_ERR_ARG;
     } catch (const std::exception& e) {

@@ -28,9 +28,11 @@
 // from the table).  The row table is common.h's StepRow - the type the GEMV's cache append and the self-attention
 // launcher already index - with `content_len` holding the row's source length (its meaning for Whisper rows as well: the
 // number of valid encoder positions).  fp32 throughout.
+#include <algorithm>
 #include <climits>
 #include <cstring>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -224,8 +226,28 @@ __global__ __launch_bounds__(256) void nllb_cross_attention_ragged_kernel(const 
     }
 }
 
+// What the two launchers below refuse (std::invalid_argument).  lengths / head_rank (may be null): the host's copy of the
+// table's content_len and of the rank table, where the caller has one; n_rank = the ranks align_probs holds.
+static void nllb_cross_ragged_check(int n_rows, int d, int n_head, long kv_off, long ldkv, const int* lengths, bool align,
+                                    const int* head_rank, int n_rank, int align_stride) {
+    auto need = [](bool ok, const char* what) {
+        if (!ok) throw std::invalid_argument(std::string("NLLB ragged cross-attention: ") + what);
+    };
+    need(n_rows >= 1 && n_head >= 1 && d == 64 * n_head, "rows >= 1 and d = 64 n_head");
+    need(kv_off >= 0 && kv_off % 4 == 0 && ldkv % 4 == 0 && kv_off + 2L * d <= ldkv, "a key row does not hold k | v at kv_off");
+    if (lengths)
+        for (int r = 0; r < n_rows; ++r) need(lengths[r] >= 1 && lengths[r] <= kNlCrossMaxT, "a row has 1 .. 512 keys");
+    if (!align) return;
+    need(n_rows <= kNlBatchMaxRows && align_stride >= 1 && align_stride <= kNlCrossMaxT, "the alignment rows hold 8 rows of at most 512 positions");
+    if (lengths)
+        for (int r = 0; r < n_rows; ++r) need(lengths[r] <= align_stride, "a row has more keys than an alignment row holds");
+    if (head_rank)
+        for (int h = 0; h < n_head; ++h) need(head_rank[h] >= -1 && head_rank[h] < n_rank, "a head's rank lies outside the alignment rows");
+}
+
 static void launch_nllb_cross_attention_ragged(const LaunchCtx& ctx, const float* q, const StepRow* rows, long kv_off, long ldkv,
                                                float* out, int n_rows, int d, int n_head) {
+    nllb_cross_ragged_check(n_rows, d, n_head, kv_off, ldkv, nullptr, false, nullptr, 0, 0);
     KernelScope ks(ctx, "nllb_cross_attention_ragged");
     hipLaunchKernelGGL(nllb_cross_attention_ragged_kernel<false>, dim3(n_rows, n_head), dim3(256), 0, ctx.stream, q, rows, kv_off,
                        ldkv, d, out, (const int*)nullptr, (float*)nullptr, 0);
@@ -238,6 +260,7 @@ static void launch_nllb_cross_attention_ragged_align(const LaunchCtx& ctx, const
                                                      float* align_probs, int align_stride) {
     if (n_rows > kNlBatchMaxRows || !head_rank || !align_probs || align_stride < 1 || align_stride > kNlCrossMaxT)
         throw std::invalid_argument("NLLB ragged cross-attention: the alignment rows hold 8 rows of at most 512 positions");
+    nllb_cross_ragged_check(n_rows, d, n_head, kv_off, ldkv, nullptr, true, nullptr, 0, align_stride);
     KernelScope ks(ctx, "nllb_cross_attention_ragged_align");
     hipLaunchKernelGGL(nllb_cross_attention_ragged_kernel<true>, dim3(n_rows, n_head), dim3(256), 0, ctx.stream, q, rows, kv_off,
                        ldkv, d, out, head_rank, align_probs, align_stride);
@@ -877,6 +900,82 @@ int wlk_nllb_batch_cross_attention(wlk_nllb_batch* b, const int32_t* slots, int3
         WLK_HIP(hipStreamSynchronize(b->stream));
         return WLK_OK;
     });
+}
+
+/* The ragged cross-attention on host data through its launchers, unchanged (see include/wlk_hip.h): a StepRow table whose
+ * cross_kv / content_len are the caller's blocks and lengths.  Refusals (nllb_cross_ragged_check on the host's lengths and
+ * ranks, and what a buffer cannot hold) come before anything is uploaded. */
+int wlk_diag_nllb_cross_ragged(const wlk_diag_nllb_cross_ragged_args* g) {
+    struct Buf {        // a device copy of exactly `bytes` host bytes (never fewer than 64), copied back whole
+        char* p = nullptr;
+        void* host = nullptr;
+        size_t bytes = 0;
+        Buf() = default;
+        Buf(const Buf&) = delete;
+        void set(void* h, size_t n) {
+            host = h;
+            bytes = n;
+            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(bytes, 64)));
+            if (host && bytes) WLK_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+        }
+        float* f() const { return reinterpret_cast<float*>(p); }
+        void back() const { if (host && bytes) WLK_HIP(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost)); }
+        ~Buf() { (void)hipFree(p); }
+    };
+    try {
+        auto need = [](bool ok, const char* what) {
+            if (!ok) throw std::invalid_argument(std::string("wlk_diag_nllb_cross_ragged: ") + what);
+        };
+        need(g != nullptr, "null arguments");
+        need(g->q && g->kv && g->out && g->lengths && g->kv_at && g->kv_rows, "null q, kv, out, lengths, kv_at or kv_rows");
+        const bool align = g->align != 0;
+        need(g->n_rows >= 1 && g->n_rows <= 64 && g->n_head >= 1 && g->n_head <= 64 && g->d >= 1 && g->d <= 4096, "n_rows and n_head in [1, 64], d in [1, 4096]");
+        need(g->ldkv >= 1 && g->ldkv <= (1 << 20) && g->kv_off >= 0 && g->kv_off <= (1 << 20), "ldkv in [1, 2^20], kv_off in [0, 2^20]");
+        need(!align || (g->head_rank && g->align_probs && g->n_rank >= 1 && g->n_rank <= 64), "the align form needs head_rank, align_probs and 1 .. 64 ranks");
+        nllb_cross_ragged_check(g->n_rows, g->d, g->n_head, (long)g->kv_off, (long)g->ldkv, g->lengths, align, g->head_rank, g->n_rank,
+                                g->align_stride);
+        const int64_t d = g->d;
+        need((int64_t)g->n_rows * d <= g->q_floats && (int64_t)g->n_rows * d <= g->out_floats, "q / out hold fewer than n_rows x d floats");
+        for (int r = 0; r < g->n_rows; ++r) {
+            need(g->kv_rows[r] >= g->lengths[r], "a K/V block holds fewer rows than the row's length");
+            need(g->kv_at[r] >= 0 && g->kv_at[r] % 4 == 0 && g->kv_at[r] + (int64_t)g->kv_rows[r] * g->ldkv <= g->kv_floats,
+                 "a K/V block lies past kv (offsets are multiples of 4)");
+        }
+        need(!align || (int64_t)g->n_rank * kNlBatchMaxRows * g->align_stride <= g->probs_floats, "align_probs holds fewer than n_rank x 8 x align_stride floats");
+        Buf Q, KV, OUT, PROBS, RANK, ROWS;
+        Q.set(g->q, (size_t)g->q_floats * 4);
+        KV.set(g->kv, (size_t)g->kv_floats * 4);
+        OUT.set(g->out, (size_t)g->out_floats * 4);
+        if (align) {
+            PROBS.set(g->align_probs, (size_t)g->probs_floats * 4);
+            RANK.set(g->head_rank, (size_t)g->n_head * 4);
+        }
+        std::vector<StepRow> table((size_t)g->n_rows);
+        for (int r = 0; r < g->n_rows; ++r) {
+            table[r] = StepRow{};
+            table[r].cross_kv = KV.f() + g->kv_at[r];
+            table[r].content_len = g->lengths[r];
+        }
+        ROWS.set(nullptr, table.size() * sizeof(StepRow));
+        WLK_HIP(hipMemcpy(ROWS.p, table.data(), table.size() * sizeof(StepRow), hipMemcpyHostToDevice));
+        LaunchCtx ctx;
+        WLK_HIP(hipDeviceSynchronize());
+        const StepRow* rows = reinterpret_cast<const StepRow*>(ROWS.p);
+        if (align)
+            launch_nllb_cross_attention_ragged_align(ctx, Q.f(), rows, (long)g->kv_off, (long)g->ldkv, OUT.f(), g->n_rows, g->d, g->n_head,
+                                                     reinterpret_cast<const int*>(RANK.p), PROBS.f(), g->align_stride);
+        else
+            launch_nllb_cross_attention_ragged(ctx, Q.f(), rows, (long)g->kv_off, (long)g->ldkv, OUT.f(), g->n_rows, g->d, g->n_head);
+        WLK_HIP(hipDeviceSynchronize());
+        Q.back(); KV.back(); OUT.back(); PROBS.back();
+        return WLK_OK;
+    } catch (const std::invalid_argument& e) {      // nothing was uploaded or launched
+        set_diag_error(e.what());
+        return WLK_ERR_ARG;
+    } catch (const std::exception& e) {
+        set_diag_error(e.what());
+        return WLK_ERR_HIP;
+    }
 }
 
 int wlk_nllb_batch_sync(wlk_nllb_batch* b) {

@@ -20,6 +20,8 @@
 // it out of the whole file's log-mel (whisper/transcribe.py), find_alignment gets that segment.
 #include <algorithm>
 #include <cstring>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "common.h"
@@ -118,10 +120,11 @@ __device__ __forceinline__ float wa_median7(float v0, float v1, float v2, float 
     for (int i = 1; i < 7; ++i) {
 #pragma unroll
         for (int j = i; j > 0; --j) {
-            const float lo = fminf(v[j - 1], v[j]);
-            const float hi = fmaxf(v[j - 1], v[j]);
-            v[j - 1] = lo;
-            v[j] = hi;
+            // a NaN orders last, as in the reference's sort (fminf / fmaxf would drop it and double its neighbour)
+            const float lo = v[j - 1], hi = v[j];
+            const bool swap = hi < lo || lo != lo;
+            v[j - 1] = swap ? hi : lo;
+            v[j] = swap ? lo : hi;
         }
     }
     return v[3];
@@ -157,6 +160,39 @@ __global__ __launch_bounds__(256) void wa_cost_kernel(const float* __restrict__ 
 }
 
 }  // namespace
+
+void word_align_check(const WordAlignArgs& a, const int* target_host, int last_stage) {
+    auto need = [](bool ok, const char* what) {
+        if (!ok) throw std::invalid_argument(std::string("word alignment: ") + what);
+    };
+    const int n_text = a.P - a.n_sot - 2;
+    need(last_stage >= kWaSoftmax && last_stage <= kWaDtw, "last stage in [0, 3]");
+    need(a.n_sot >= 1 && n_text >= 1, "need [sot sequence, notimestamps, >= 1 text token, eot]");
+    need(a.n_align >= 1, "no alignment heads");
+    need(a.T >= 1 && a.ring_rows >= 1 && a.P <= a.ring_rows, "more token rows than the score window holds");
+    need(a.F >= 1 && a.F <= a.T, "frames outside [1, T]");
+    need(n_text + 1 <= 1024, "more than 1024 rows for the warping");
+    need(a.n_cols >= 1 && a.ld >= a.n_cols, "logit rows shorter than their columns");
+    need(a.logits && a.target && a.probs && a.ring && a.w, "null operand");
+    need(last_stage < kWaCost || a.cost, "null cost matrix");
+    need(last_stage < kWaDtw || (a.trace_t && a.trace), "null trace");
+    if (target_host)
+        for (int i = 0; i < n_text; ++i) need(target_host[i] >= 0 && target_host[i] < a.n_cols, "target outside the logit columns");
+}
+
+// the launches of find_alignment behind the vocabulary projection, in its order, up to and including `last_stage`
+void launch_word_align(const LaunchCtx& ctx, const WordAlignArgs& a, const int* target_host, int last_stage) {
+    word_align_check(a, target_host, last_stage);
+    const int n_text = a.P - a.n_sot - 2, N = n_text + 1;
+    hipLaunchKernelGGL(wa_token_prob_kernel, dim3(n_text), dim3(256), 0, ctx.stream, a.logits, a.ld, a.n_cols, a.target, a.probs);
+    // attention -> cost matrix
+    hipLaunchKernelGGL(wa_softmax_kernel, dim3(a.P, a.n_align), dim3(256), 0, ctx.stream, a.ring, a.ring_rows, a.T, a.F, a.qk_scale, a.w, a.P);
+    if (last_stage >= kWaZscore) hipLaunchKernelGGL(wa_zscore_kernel, dim3((a.F + 63) / 64, a.n_align), dim3(256), 0, ctx.stream, a.w, a.P, a.F);
+    if (last_stage >= kWaCost) hipLaunchKernelGGL(wa_cost_kernel, dim3(N), dim3(256), 0, ctx.stream, a.w, a.n_align, a.P, a.F, a.n_sot, a.cost);
+    WLK_HIP(hipGetLastError());
+    if (last_stage >= kWaDtw) launch_dtw(ctx.stream, a.cost, N, a.F, a.trace_t, a.trace);
+}
+
 }  // namespace wlk
 
 using namespace wlk;
@@ -281,13 +317,11 @@ int wlk_find_alignment(wlk_session* s, const int64_t* tokens, int32_t n_tokens, 
         GemmArgs lg;
         lg.A = hid; lg.lda = d; lg.W = m->w_tok_emb; lg.C = logits; lg.ldc = eot; lg.M = n_text; lg.N = eot; lg.K = d;
         launch_linear(c, lg, "wa_logits");
-        hipLaunchKernelGGL(wa_token_prob_kernel, dim3(n_text), dim3(256), 0, s->stream, logits, (long)eot, eot, target, probs);
-        // attention -> cost matrix
-        hipLaunchKernelGGL(wa_softmax_kernel, dim3(P, m->n_align), dim3(256), 0, s->stream, s->ring, s->ring_rows, T, F, qk_scale, w, P);
-        hipLaunchKernelGGL(wa_zscore_kernel, dim3((F + 63) / 64, m->n_align), dim3(256), 0, s->stream, w, P, F);
-        hipLaunchKernelGGL(wa_cost_kernel, dim3(N), dim3(256), 0, s->stream, w, m->n_align, P, F, n_sot, cost);
-        WLK_HIP(hipGetLastError());
-        launch_dtw(s->stream, cost, N, F, trace_t, trace);
+        WordAlignArgs wa;
+        wa.logits = logits; wa.ld = eot; wa.n_cols = eot; wa.target = target; wa.probs = probs;
+        wa.ring = s->ring; wa.ring_rows = s->ring_rows; wa.T = T; wa.n_align = m->n_align; wa.P = P; wa.F = F; wa.n_sot = n_sot;
+        wa.qk_scale = qk_scale; wa.w = w; wa.cost = cost; wa.trace_t = trace_t; wa.trace = trace;
+        launch_word_align(c, wa, stage, kWaDtw);
         // results: three copies behind one synchronisation (host buffers are the caller's: pageable, so synchronous)
         WLK_HIP(hipStreamSynchronize(s->stream));
         copy_sync(trace_host, trace, n_trace, hipMemcpyDeviceToHost);
