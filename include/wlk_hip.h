@@ -130,6 +130,37 @@ int wlk_pick_greedy(wlk_session* s, const wlk_pick_params* p, int32_t* token_hos
 int wlk_pick_topk(wlk_session* s, const wlk_pick_params* p /* [n_rows] */, int n_rows, int k,
                   float* logprobs_host /* [n_rows, k] */, int32_t* ids_host /* [n_rows, k] */);
 
+/* Window groups (batch `transcribe`, opt-in): the greedy temperature-0 steps of up to 8 windows that belong to DIFFERENT
+ * beam-1 sessions of one model as one launch chain - one pass over the decoder weights per token for all of them.  The
+ * group owns a stream and the workspace of an 8-row step; sessions are not bound to it, any prefilled session of the
+ * model may ride in any step.
+ * wlk_group_step_pick: one single-token decoder step + logit rules + greedy pick for n (1..max_rows) distinct sessions.
+ *   Row r feeds tokens[r] into sessions[r], applies that session's wlk_rules_set lists with p[r] and returns the token and
+ *   log-probability wlk_pick_greedy would return (bit-identical for the same logits row).  Every session is checked on
+ *   the host BEFORE anything is launched; a refused call has advanced no session: WLK_ERR_ARG for n outside 1..max_rows, a
+ *   session listed twice, a session of another model or with beam != 1, a token or rule parameter out of range;
+ *   WLK_ERR_STATE for a session before its prefill (the first wlk_decode of the window stays the session's own), before
+ *   wlk_rules_set, with self_len + 1 > n_text_ctx, or attached to the batch engine (wlk_engine_attach: its single-token
+ *   steps belong to the engine's loops).  The group's stream waits for what each session's stream has queued, the call
+ *   returns after the read-back, and each session is left as its own wlk_decode of that token leaves it (position, KV
+ *   cache, alignment window) - EXCEPT that the logits stay in the group: "logits_last" of wlk_export is not refreshed by
+ *   a group step (wlk_group_export_logits reads them), so wlk_pick_greedy / wlk_select after a group step see the
+ *   session's previous own decode.  A row's results do not depend on the rows beside it.  One step at a time per group;
+ *   the caller keeps the sessions of a step to itself for its duration. */
+typedef struct wlk_group wlk_group;
+int wlk_group_create(wlk_model* m, int max_rows /* 1..8 */, wlk_group** out);
+int wlk_group_destroy(wlk_group* g);   /* before the model */
+int wlk_group_step_pick(wlk_group* g, wlk_session* const* sessions, const int64_t* tokens /* [n] */,
+                        const wlk_pick_params* p /* [n] */, int n, int32_t* tokens_out /* [n] */, float* logprobs_out /* [n] */);
+int wlk_group_stats(wlk_group* g, uint64_t* steps, uint64_t* rows);   /* completed steps, and rows summed over them */
+/* tests: the logits row [n_vocab] of slot `row` of the last completed step (WLK_ERR_STATE: no such row) */
+int wlk_group_export_logits(wlk_group* g, int row, float* host, uint64_t capacity, uint64_t* n_written);
+/* Diagnostic (tests): the rows pick kernel alone on host data - logits [n][n_vocab], n_masks (1..8) rule masks
+ * [n_masks][n_vocab] (bit 0 = always suppressed, bit 1 = blank, as wlk_rules_set builds them), row r under
+ * masks[mask_of_row[r]] and p[r]; n in 1..8.  Synchronous. */
+int wlk_diag_pick_rows(const float* logits_host, int n_vocab, const uint8_t* masks_host, int n_masks, const int32_t* mask_of_row,
+                       const wlk_pick_params* p /* [n] */, int n, int32_t* tokens_out, float* logprobs_out);
+
 /* a6+a7+a8 in one launch group and ONE readback:
  *  - logits[row, ids[i]] += deltas[i] (-inf suppresses: SuppressTokens.apply whisper/decoding.py:427-432,
  *    _suppress_blank_tokens simul_whisper.py:379-381, DRY penalty align_att_base.py:492-537);

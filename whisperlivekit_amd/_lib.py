@@ -224,6 +224,12 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_rules_set": (cint, [p, p, cint, p, cint]),
         "wlk_pick_greedy": (cint, [p, p, p, p]),
         "wlk_pick_topk": (cint, [p, p, cint, cint, p, p]),
+        "wlk_group_create": (cint, [p, cint, C.POINTER(p)]),
+        "wlk_group_destroy": (cint, [p]),
+        "wlk_group_step_pick": (cint, [p, C.POINTER(p), p, p, cint, p, p]),
+        "wlk_group_stats": (cint, [p, C.POINTER(u64), C.POINTER(u64)]),
+        "wlk_group_export_logits": (cint, [p, cint, p, u64, C.POINTER(u64)]),
+        "wlk_diag_pick_rows": (cint, [p, cint, p, cint, p, p, cint, p, p]),
         "wlk_decode_ancestry": (cint, [p, p, p, cint]),
         "wlk_select": (cint, [p, p, p, p, cint, cint, cint, p, p, p]),
         "wlk_kv_reorder": (cint, [p, p, cint]),
@@ -418,6 +424,8 @@ EXPORTED_SYMBOLS = (
     "wlk_diag_nllb_align_rows", "wlk_diag_linear_ex", "wlk_diag_gemv_variant", "wlk_diag_enc_op",
     "wlk_diag_x3_plan", "wlk_diag_word_align", "wlk_diag_nllb_cross_ragged",
     "wlk_model_set_cif", "wlk_cif_result", "wlk_diag_cif",
+    "wlk_group_create", "wlk_group_destroy", "wlk_group_step_pick", "wlk_group_stats", "wlk_group_export_logits",
+    "wlk_diag_pick_rows",
 )
 
 
@@ -451,7 +459,9 @@ def load() -> C.CDLL:
 def check(rc: int) -> None:
     if rc != 0:
         msg = load().wlk_last_error()
-        raise WlkError(f"wlk_hip error {rc}: {msg.decode('utf-8', 'replace') if msg else '?'}")
+        err = WlkError(f"wlk_hip error {rc}: {msg.decode('utf-8', 'replace') if msg else '?'}")
+        err.code = int(rc)        # WLK_ERR_* of include/wlk_hip.h
+        raise err
 
 
 def device_count() -> int:

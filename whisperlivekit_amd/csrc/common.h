@@ -648,6 +648,15 @@ struct PickRulesRows {
 };
 void launch_rules_topk(const LaunchCtx& ctx, const float* logits, int n_vocab, int n_rows, const unsigned char* mask,
                        const PickRulesRows& rules, int k, float* out_lp, int* out_ids);
+// the greedy pick of launch_rules_pick for up to 8 rows that belong to DIFFERENT sessions (window_group.hip): row r takes its
+// rule mask and parameters from table[r] (device memory) and writes out[2 r] = token, out[2 r + 1] = log-probability (bits
+// of a float); a row's result is bit-identical to launch_rules_pick on the same logits, mask and parameters
+struct PickRowEntry {
+    const unsigned char* mask;
+    PickRules p;
+};
+void launch_rules_pick_rows(const LaunchCtx& ctx, const float* logits, int n_vocab, int n_rows, const PickRowEntry* table,
+                            int* out);
 struct AlignArgs {
     const float* ring;   // [n_align][n_beam][ring_rows][T]
     int n_align, n_beam, ring_rows, T;

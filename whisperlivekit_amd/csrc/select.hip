@@ -871,23 +871,51 @@ __device__ __forceinline__ bool rules_allowed(const unsigned char* __restrict__ 
 }
 }  // namespace
 
-__global__ __launch_bounds__(1024) void rules_pick_kernel(const float* __restrict__ logits, int n_vocab,
-                                                          const unsigned char* __restrict__ mask, PickRules p,
-                                                          int* __restrict__ out_token, float* __restrict__ out_logprob) {
+// The pick of one row by one 1024-thread workgroup: the one statement of it for wlk_pick_greedy's single row
+// (rules_pick_kernel) and for the rows of a window group (rules_pick_rows_kernel).  Thread t owns entries t, t + 1024, ... in
+// ascending order and every reduction folds in a fixed order, so the two kernels give the same bits for the same row.
+//   kRegs = false: two strided passes over memory (51 elements per thread).
+//   kRegs = true (rows of at most kRulesKeep * 1024 entries: every Whisper vocabulary): the row is read ONCE, all of a
+//     thread's loads issued ahead of the first reduction, an entry the rules forbid remembered in a 64-bit set.  The loads
+//     stay one dword per lane (a wave reads 256 contiguous bytes): a 16-byte load per lane would hand a thread four
+//     NEIGHBOURING entries, i.e. another summation order than the one-row kernel's, and its bits are the contract.
+constexpr int kRulesKeep = 52;
+template <bool kRegs>
+__device__ __forceinline__ void rules_pick_body(const float* __restrict__ logits, int n_vocab,
+                                                const unsigned char* __restrict__ mask, const PickRules& p,
+                                                int* __restrict__ out_token, float* __restrict__ out_logprob) {
     __shared__ PickBest s_all[16], s_ts[16];
     __shared__ float s_text[16], s_sum_all[16], s_sum_ts[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tb = p.timestamp_begin;
-    auto allowed = [&](int v) -> bool { return rules_allowed(mask, p, v); };
+    float xv[kRegs ? kRulesKeep : 1];
+    unsigned long long ok = 0ull;
+    if constexpr (kRegs) {
+#pragma unroll
+        for (int j = 0; j < kRulesKeep; ++j) {
+            const int v = tid + 1024 * j, vc = v < n_vocab ? v : 0;
+            xv[j] = logits[vc];
+            if (v < n_vocab && rules_allowed(mask, p, vc)) ok |= 1ull << j;
+        }
+    }
+    // f(index, logit) over this thread's allowed entries, ascending index
+    auto sweep = [&](auto&& f) {
+        if constexpr (kRegs) {
+#pragma unroll
+            for (int j = 0; j < kRulesKeep; ++j)
+                if ((ok >> j) & 1ull) f(tid + 1024 * j, xv[j]);
+        } else {
+            for (int v = tid; v < n_vocab; v += 1024)
+                if (rules_allowed(mask, p, v)) f(v, logits[v]);
+        }
+    };
     PickBest all{-INFINITY, 0x7fffffff}, ts{-INFINITY, 0x7fffffff};
     float text = -INFINITY;
-    for (int v = tid; v < n_vocab; v += 1024) {
-        if (!allowed(v)) continue;
-        const float x = logits[v];
+    sweep([&](int v, float x) {
         all = pick_better(all, PickBest{x, v});
         if (v >= tb) ts = pick_better(ts, PickBest{x, v});
         else text = fmaxf(text, x);
-    }
+    });
     all = pick_wave_best(all);
     ts = pick_wave_best(ts);
     text = wave_max(text);
@@ -907,12 +935,10 @@ __global__ __launch_bounds__(1024) void rules_pick_kernel(const float* __restric
         text = fmaxf(text, s_text[w]);
     }
     float sum_all = 0.f, sum_ts = 0.f;
-    for (int v = tid; v < n_vocab; v += 1024) {
-        if (!allowed(v)) continue;
-        const float x = logits[v];
+    sweep([&](int v, float x) {
         sum_all += expf(x - all.v);
         if (v >= tb) sum_ts += expf(x - ts.v);
-    }
+    });
     sum_all = wave_sum(sum_all);
     sum_ts = wave_sum(sum_ts);
     if (lane == 0) {
@@ -934,6 +960,32 @@ __global__ __launch_bounds__(1024) void rules_pick_kernel(const float* __restric
         out_token[0] = pick.i == 0x7fffffff ? 0 : pick.i;
         out_logprob[0] = -logf(ts_wins ? sum_ts : sum_all);
     }
+}
+
+__global__ __launch_bounds__(1024) void rules_pick_kernel(const float* __restrict__ logits, int n_vocab,
+                                                          const unsigned char* __restrict__ mask, PickRules p,
+                                                          int* __restrict__ out_token, float* __restrict__ out_logprob) {
+    rules_pick_body<false>(logits, n_vocab, mask, p, out_token, out_logprob);
+}
+
+// The same pick for the rows of a window group (window_group.hip): one workgroup per row, all rows in flight side by side.
+// Row r reads logits row r, its own rules and its own mask (two sessions may carry different wlk_rules_set lists) from the
+// device table and writes (token, log-probability) to slot r of `out` - one 8 n byte read-back for the host.
+__global__ __launch_bounds__(1024) void rules_pick_rows_kernel(const float* __restrict__ logits, int n_vocab,
+                                                               const PickRowEntry* __restrict__ table, int* __restrict__ out) {
+    const int row = blockIdx.x;
+    const PickRowEntry e = table[row];
+    const float* x = logits + (long)row * n_vocab;
+    int* o = out + 2 * row;
+    if (n_vocab <= kRulesKeep * 1024) rules_pick_body<true>(x, n_vocab, e.mask, e.p, o, reinterpret_cast<float*>(o + 1));
+    else rules_pick_body<false>(x, n_vocab, e.mask, e.p, o, reinterpret_cast<float*>(o + 1));
+}
+
+void launch_rules_pick_rows(const LaunchCtx& ctx, const float* logits, int n_vocab, int n_rows, const PickRowEntry* table, int* out) {
+    if (n_rows < 1 || n_rows > kMaxPickRows) throw std::invalid_argument("rules pick: 1..8 rows");
+    KernelScope ks(ctx, "rules_pick_rows", 0.0, 5.0 * n_rows * (double)n_vocab);
+    hipLaunchKernelGGL(rules_pick_rows_kernel, dim3(n_rows), dim3(1024), 0, ctx.stream, logits, n_vocab, table, out);
+    WLK_HIP(hipGetLastError());
 }
 
 void launch_rules_pick(const LaunchCtx& ctx, const float* logits, int n_vocab, const unsigned char* mask, const PickRules& p,
@@ -959,7 +1011,6 @@ void launch_rules_pick(const LaunchCtx& ctx, const float* logits, int n_vocab, c
 //     head, for rounds that here cost one 52-entry register scan in one thread.
 //   logprob = (x - max) - logf(sum); a row with fewer than k allowed (finite) entries fills up with (-inf, -1).
 // ---------------------------------------------------------------------------------------------
-constexpr int kRulesKeep = 52;
 namespace {
 // x comes strictly after w in the order (value descending, index ascending)
 __device__ __forceinline__ bool pick_after(float xv, int xi, PickBest w) { return xv < w.v || (xv == w.v && xi > w.i); }

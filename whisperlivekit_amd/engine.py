@@ -234,6 +234,9 @@ class HipWhisperModel:
         for rows in (self.__dict__.pop("_batch_rows", None) or {}).values():
             for sess in rows.sessions.values():
                 sess.close()
+        stacker = self.__dict__.pop("_window_stacker", None)      # transcribe.WindowStacker: its group holds this model
+        if stacker is not None:
+            stacker.close()
         if self._h:
             self.lib.wlk_model_destroy(self._h)
             self._h = C.c_void_p()
@@ -527,3 +530,71 @@ class HipSession:
             self.close()
         except Exception:
             pass
+
+
+class HipWindowGroup:
+    """A wlk_group (csrc/window_group.hip): the greedy temperature-0 steps of up to ``rows`` batch-Whisper windows, each in
+    its own prefilled beam-1 :class:`HipSession` of ``model``, as one launch chain per token.  One step at a time."""
+
+    def __init__(self, model: HipWhisperModel, rows: int = 8):
+        self.model = model
+        self.lib = model.lib
+        self.rows = int(rows)
+        self._h = C.c_void_p()
+        _lib.check(self.lib.wlk_group_create(model._h, self.rows, C.byref(self._h)))
+
+    def step_pick(self, sessions: Sequence[HipSession], tokens: Sequence[int], states: Sequence[dict]
+                  ) -> Tuple[np.ndarray, np.ndarray]:
+        """Feeds ``tokens[r]`` to ``sessions[r]`` and picks each row's next token under that session's rules and
+        ``states[r]`` (the keywords of :meth:`HipSession.pick_greedy`).  -> (token ids [n] int32, log-probabilities [n])."""
+        n = len(sessions)
+        handles = (C.c_void_p * max(n, 1))(*[s._h for s in sessions])
+        tok = np.ascontiguousarray(tokens, dtype=np.int64).reshape(-1)
+        prm = np.asarray([[int(st[f]) for f in HipSession.PICK_FIELDS] for st in states], dtype=np.int32).reshape(-1, 8)
+        if tok.size != n or prm.shape[0] != n:
+            raise ValueError("step_pick: one token and one rule state per session")
+        out = np.empty(max(n, 1), np.int32)
+        lp = np.empty(max(n, 1), np.float32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        _lib.check(self.lib.wlk_group_step_pick(self._h, handles, vp(tok), vp(prm), n, vp(out), vp(lp)))
+        return out[:n], lp[:n]
+
+    def stats(self) -> Dict[str, float]:
+        steps, rows = C.c_uint64(), C.c_uint64()
+        _lib.check(self.lib.wlk_group_stats(self._h, C.byref(steps), C.byref(rows)))
+        return dict(steps=int(steps.value), rows=int(rows.value),
+                    mean_rows_per_step=round(rows.value / steps.value, 3) if steps.value else None)
+
+    def export_logits(self, row: int) -> np.ndarray:
+        """The logits row of slot ``row`` of the last step (tests)."""
+        buf = np.empty(self.model.dims.n_vocab, np.float32)
+        n = C.c_uint64()
+        _lib.check(self.lib.wlk_group_export_logits(self._h, int(row), buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(n)))
+        return buf[: n.value]
+
+    def close(self) -> None:
+        if self._h:
+            self.lib.wlk_group_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pick_rows(logits: np.ndarray, masks: np.ndarray, mask_of_row: Sequence[int], states: Sequence[dict]
+              ) -> Tuple[np.ndarray, np.ndarray]:
+    """wlk_diag_pick_rows (tests): the rows pick kernel on host logits [n, V] and rule masks [n_masks, V] uint8."""
+    lib = _lib.load()
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    mk = np.ascontiguousarray(masks, dtype=np.uint8)
+    mo = np.ascontiguousarray(mask_of_row, dtype=np.int32)
+    prm = np.asarray([[int(st[f]) for f in HipSession.PICK_FIELDS] for st in states], dtype=np.int32).reshape(-1, 8)
+    n = lg.shape[0]
+    out = np.empty(n, np.int32)
+    lp = np.empty(n, np.float32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.wlk_diag_pick_rows(vp(lg), lg.shape[1], vp(mk), mk.shape[0], vp(mo), vp(prm), n, vp(out), vp(lp)))
+    return out, lp

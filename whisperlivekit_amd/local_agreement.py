@@ -19,7 +19,7 @@ from .backend import load_openai_checkpoint
 from .dims import ALIGNMENT_HEADS, MODEL_DIMS
 from .engine import HipWhisperModel
 from .policy import ASRToken
-from .transcribe import transcribe as hip_transcribe
+from .transcribe import resolve_stack, set_stack, transcribe as hip_transcribe
 
 logger = logging.getLogger(__name__)
 
@@ -29,7 +29,11 @@ class HipWhisperASR:
 
     def __init__(self, lan: str, model_size: Optional[str] = None, cache_dir: Optional[str] = None,
                  model_dir: Optional[str] = None, lora_path: Optional[str] = None, logfile=sys.stderr, *, device: int = 0,
-                 hip_model: Optional[HipWhisperModel] = None, state_dict=None, synthetic_seed: Optional[int] = None):
+                 hip_model: Optional[HipWhisperModel] = None, state_dict=None, synthetic_seed: Optional[int] = None,
+                 stack: Optional[int] = None):
+        """``stack``: rows of the model's window group - the greedy temperature-0 steps of up to that many concurrent
+        ``transcribe`` calls share each pass over the decoder weights (transcribe.WindowStacker; 0 = off, None = the
+        environment's ``WLK_TRANSCRIBE_STACK``, default off)."""
         self.logfile = logfile
         self.transcribe_kargs = {}
         self.lora_path = lora_path
@@ -47,6 +51,9 @@ class HipWhisperASR:
         else:
             self.model = self.load_model(model_size, cache_dir, model_dir, device=device, state_dict=state_dict,
                                          synthetic_seed=synthetic_seed)
+        self.stack = resolve_stack(stack)
+        if stack is not None:
+            set_stack(self.model, self.stack)       # an explicit argument wins over the environment
 
     def load_model(self, model_size=None, cache_dir=None, model_dir=None, *, device: int = 0, state_dict=None,
                    synthetic_seed: Optional[int] = None) -> HipWhisperModel:

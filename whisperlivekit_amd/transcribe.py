@@ -10,7 +10,9 @@ of masked fills and one log-softmax over the vocabulary row the step produced; t
 (single-threaded numpy; the sampling draw takes its random numbers from torch's global generator exactly as the reference's
 ``Categorical.sample()`` does, so a seeded run consumes the generator as the reference does); greedy decoding at temperature 0
 applies them on the device (``wlk_pick_greedy``), and so does beam search with 2-7 beams under WLK_TRANSCRIBE_DEVICE_BEAM=1
-(``wlk_pick_topk``, with single-token steps over the KV ancestry table: ``wlk_decode_ancestry``).  There is no CPU model path: without the library / a GPU the first call raises.
+(``wlk_pick_topk``, with single-token steps over the KV ancestry table: ``wlk_decode_ancestry``).  With WLK_TRANSCRIBE_STACK=n
+(or ``HipWhisperASR(stack=n)``; off by default) the greedy temperature-0 steps of up to n concurrent windows of one model
+ride in one launch chain per token (``WindowStacker`` / ``decode_many`` over ``wlk_group_step_pick``).  There is no CPU model path: without the library / a GPU the first call raises.
 
 Same keyword names, defaults and result dictionary as the reference; ``fp16`` is accepted and ignored (the path computes
 in fp32, as the reference does on its CPU).  Decoding a file name (ffmpeg) is outside the path: ``audio`` is samples.
@@ -127,6 +129,17 @@ class _Rows:
             s = self.sessions[rows] = self.model.new_session(beam=rows, max_audio_seconds=1.0, batched=False)
         return s
 
+    def windows(self, n: int) -> List[HipSession]:
+        """n one-row sessions for the windows of one `decode_many`: the thread's one-row session first, the further ones
+        under the keys -1, -2, ... (one-row sessions as well; released with the rest)."""
+        out = [self.get(1)]
+        for i in range(1, n):
+            s = self.sessions.get(-i)
+            if s is None:
+                s = self.sessions[-i] = self.model.new_session(beam=1, max_audio_seconds=1.0, batched=False)
+            out.append(s)
+        return out
+
 
 _ROWS_LOCK = threading.Lock()
 
@@ -154,6 +167,227 @@ def release_sessions(model: HipWhisperModel) -> None:
     for rows in per_thread.values():
         for sess in rows.sessions.values():
             sess.close()
+
+
+# ---- stacked greedy windows (opt-in; csrc/window_group.hip) -----------------------------------------------------------------
+def resolve_stack(stack: Optional[int]) -> int:
+    """``HipWhisperASR(stack=...)`` / :func:`set_stack`: an explicit value wins; ``None`` reads ``WLK_TRANSCRIBE_STACK``
+    (default 0 = off; 1..8 = rows of the window group)."""
+    if stack is None:
+        stack = int(os.environ.get("WLK_TRANSCRIBE_STACK", "0").strip() or 0)
+    stack = int(stack)
+    if stack < 0 or stack > 8:
+        raise ValueError("stack must be 0 (off) or 1..8 rows")
+    return stack
+
+
+def _greedy_take(tokens: np.ndarray, sum_logprobs: np.ndarray, nxt_id: int, picked: float, eot: int,
+                 n_ctx: int) -> Tuple[np.ndarray, bool]:
+    """GreedyDecoder.update (decoding.py:270-287) for the one sequence of a greedy window whose rules and pick ran on the
+    device: the log-probability counts unless the sequence had ended, the token is appended.  -> (tokens, the window is
+    over).  The one statement of it for the solo loop and the stacked one."""
+    if tokens[0, -1] != eot:
+        sum_logprobs[0] += np.float32(picked)
+    else:
+        nxt_id = eot
+    tokens = np.concatenate([tokens, np.asarray([[nxt_id]], np.int64)], axis=1)
+    return tokens, bool(nxt_id == eot or tokens.shape[-1] > n_ctx)
+
+
+class _GreedyWindow:
+    """One greedy temperature-0 window between its first pick and its end, as the stacked loop advances it: the session
+    that holds its caches, its tokens and log-probability sum, the steps it may still take."""
+
+    def __init__(self, decoder: "_WindowDecoder", session, tokens: np.ndarray, sum_logprobs: np.ndarray, steps_left: int):
+        self.decoder, self.session = decoder, session
+        self.tokens, self.sum_logprobs, self.steps_left = tokens, sum_logprobs, int(steps_left)
+
+    def feed(self) -> int:
+        return int(self.tokens[0, -1])
+
+    def state(self) -> dict:
+        return self.decoder._pick_state(self.tokens)
+
+    def take(self, nxt_id: int, picked: float) -> bool:
+        """-> the window is over (<|endoftext|>, sample_len or n_ctx)"""
+        self.tokens, over = _greedy_take(self.tokens, self.sum_logprobs, int(nxt_id), float(picked), self.decoder.tok.eot,
+                                         self.decoder.n_ctx)
+        self.steps_left -= 1
+        return over or self.steps_left <= 0
+
+
+def _refused(error: BaseException) -> bool:
+    """the group refused the call on the host (WLK_ERR_ARG / WLK_ERR_STATE): nothing was launched, no session advanced"""
+    return getattr(error, "code", None) in (-1, -3)
+
+
+class WindowStacker:
+    """Thread-safe front of one ``HipWindowGroup``, modelled on ``translation.NllbStacker``: any thread hands its greedy
+    window to :meth:`run`; the first caller becomes the runner and advances every window in flight with one
+    ``step_pick`` per token, callers that arrive while a pass is running queue their windows - the runner admits them at
+    its next step, up to the group's rows - and wait on a condition.  A window leaves at its end, the others go on; the
+    runner keeps running until nothing is in flight or queued.  A window the group refuses on the host (context full, no
+    rules, ...) fails alone: the refused call advanced nobody, so the others take that step without it.  A pass that fails
+    otherwise hands its error to every window in flight or queued, so no waiter blocks for ever, and the next caller
+    starts a fresh pass.
+
+    ``solo_single``: while ONE window is in flight it takes the session's own step (``decode`` + ``pick_greedy``, a graph
+    replay with the one-row folds) instead of a one-row group step, which measured 10 % slower; the two give
+    the same token and the same log-probability bits on every input the tests step."""
+
+    def __init__(self, model, rows: int = 8, group=None, solo_single: bool = True):
+        if not 1 <= int(rows) <= 8:
+            raise ValueError("a window stacker has 1..8 rows")
+        self.rows = int(rows)
+        if group is None:
+            from .engine import HipWindowGroup
+            group = HipWindowGroup(model, self.rows)
+        self.group = group
+        self.solo_single = bool(solo_single)
+        self.solo_steps = 0
+        self._cv = threading.Condition()
+        self._queue: List[Tuple[int, _GreedyWindow]] = []     # (ticket, window) not yet admitted
+        self._open: set = set()                               # tickets queued or in flight
+        self._outcome: dict = {}                              # ticket -> error or None
+        self._running = False
+        self._next_ticket = 0
+        self.passes = 0
+        self.windows = 0
+
+    def run(self, window: _GreedyWindow) -> None:
+        """Advances ``window`` to its end (its tokens and sum are updated in place); raises what stopped it."""
+        self.run_many([window])
+
+    def run_many(self, windows: Sequence[_GreedyWindow]) -> None:
+        if not windows:
+            return
+        with self._cv:
+            tickets = list(range(self._next_ticket, self._next_ticket + len(windows)))
+            self._next_ticket += len(windows)
+            for t, w in zip(tickets, windows):
+                self._queue.append((t, w))
+                self._open.add(t)
+        while True:
+            with self._cv:
+                while self._running and any(t not in self._outcome for t in tickets):
+                    self._cv.wait()
+                if all(t in self._outcome for t in tickets):
+                    for err in [self._outcome.pop(t) for t in tickets]:
+                        if err is not None:
+                            raise err
+                    return
+                self._running = True               # nobody is driving the group and this caller still waits: it drives
+            self._run()
+
+    def _settle(self, ticket: int, error: Optional[BaseException]) -> None:
+        with self._cv:
+            self._outcome[ticket] = error
+            self._open.discard(ticket)
+            self.windows += 1
+            self._cv.notify_all()
+
+    def _step(self, live: List[Tuple[int, _GreedyWindow]]) -> List[Tuple[int, _GreedyWindow]]:
+        """one token for every window in `live`; -> the windows still in flight"""
+        def step(part):
+            ids, lps = self.group.step_pick([w.session for _t, w in part], [w.feed() for _t, w in part],
+                                            [w.state() for _t, w in part])
+            return [(t, w) for (t, w), tok, lp in zip(part, ids, lps) if not self._taken(t, w, tok, lp)]
+        if len(live) == 1 and self.solo_single:
+            (t, w), = live
+            try:                                   # whatever stops a window on its own chain is that window's own error
+                w.session.decode(w.tokens[:, -1:], first=False)
+                tok, lp = w.session.pick_greedy(**w.state())
+            except Exception as e:
+                self._settle(t, e)
+                return []
+            self.solo_steps += 1
+            return [] if self._taken(t, w, tok, lp) else live
+        try:
+            return step(live)
+        except Exception as e:
+            if not _refused(e):
+                raise
+            if len(live) == 1:
+                self._settle(live[0][0], e)
+                return []
+        keep = []
+        for item in live:                          # the refused call advanced nobody: every window on its own
+            try:
+                keep += step([item])
+            except Exception as e:
+                if not _refused(e):
+                    raise
+                self._settle(item[0], e)
+        return keep
+
+    def _taken(self, ticket: int, window: _GreedyWindow, tok, lp) -> bool:
+        if window.take(int(tok), float(lp)):
+            self._settle(ticket, None)
+            return True
+        return False
+
+    def _run(self) -> None:
+        error: Optional[BaseException] = None
+        live: List[Tuple[int, _GreedyWindow]] = []
+        try:
+            while True:
+                with self._cv:
+                    while self._queue and len(live) < self.rows:
+                        live.append(self._queue.pop(0))
+                if not live:
+                    break
+                live = self._step(live)
+        except BaseException as e:                 # the pass is gone: everyone in it or queued behind it gets the error
+            error = e
+        finally:
+            with self._cv:
+                self.passes += 1
+                if error is not None:
+                    for t in self._open:
+                        self._outcome[t] = error
+                    self._open.clear()
+                    self._queue = []
+                self._running = False
+                self._cv.notify_all()
+        if error is not None and not isinstance(error, Exception):
+            raise error
+
+    def stats(self) -> dict:
+        """the group's steps and rows so far, and this front's passes, windows and solo steps"""
+        return dict(self.group.stats(), passes=self.passes, windows=self.windows, solo_steps=self.solo_steps)
+
+    def close(self) -> None:
+        self.group.close()
+
+
+_STACK_LOCK = threading.Lock()
+
+
+def set_stack(model, stack: Optional[int]) -> int:
+    """Switches the stacked greedy windows of ``model`` on (1..8 rows) or off (0); ``None`` leaves it to
+    ``WLK_TRANSCRIBE_STACK``.  -> the resolved value."""
+    rows = resolve_stack(stack)
+    with _STACK_LOCK:
+        model.__dict__["_window_stack_rows"] = rows
+    return rows
+
+
+def window_stacker(model, rows: Optional[int] = None) -> Optional[WindowStacker]:
+    """The model's stacker; created with ``rows`` rows when there is none yet (``rows`` None: never creates)."""
+    with _STACK_LOCK:
+        st = model.__dict__.get("_window_stacker")
+        if st is None and rows:
+            st = model.__dict__["_window_stacker"] = WindowStacker(model, rows)
+        return st
+
+
+def _run_stacker(model) -> Optional[WindowStacker]:
+    """What `_WindowDecoder.run` sends its greedy steps through: the model's stacker when stacking is switched on for it
+    (:func:`set_stack`, else ``WLK_TRANSCRIBE_STACK``), otherwise None - and then nothing is constructed."""
+    rows = model.__dict__.get("_window_stack_rows")
+    if rows is None:
+        rows = resolve_stack(None)
+    return window_stacker(model, rows) if rows > 0 else None
 
 
 def _tokenizer_for(model: HipWhisperModel, language: Optional[str], task: Optional[str]) -> WhisperTokenizer:
@@ -332,7 +566,11 @@ class _WindowDecoder:
         return self._pick_states(tokens[:1])[0]
 
     # -- the loop ------------------------------------------------------------------------------------------------------
-    def run(self, mel_segment: Optional[np.ndarray], session: Optional[HipSession] = None) -> DecodingResult:
+    def run(self, mel_segment: Optional[np.ndarray], session: Optional[HipSession] = None, *,
+            stacker: Optional[WindowStacker] = None, defer: bool = False):
+        """-> the window's DecodingResult.  ``stacker``: the greedy temperature-0 steps behind the first pick go through it
+        (default: the model's, when stacking is switched on).  ``defer`` (`decode_many`): a window that reaches those steps
+        comes back as ``(_GreedyWindow, finish)`` instead - the caller advances it and calls ``finish()`` for the result."""
         o, tok, V = self.o, self.tok, self.model.dims.n_vocab
         rows = self.n_group
         s = session or _rows_of(self.model).get(rows)
@@ -365,6 +603,34 @@ class _WindowDecoder:
                        and os.environ.get("WLK_TRANSCRIBE_DEVICE_BEAM", "0") == "1")
         if device_rules or device_beam:
             s.set_rules(self.suppressed or [], self.blank_ids or [])
+        if device_rules and stacker is None:
+            stacker = _run_stacker(self.model)
+        stacked = stacker if device_rules else None
+
+        def finish(tokens=None, sum_logprobs=None, window: Optional[_GreedyWindow] = None) -> DecodingResult:
+            # candidates of the group (decoding.py:289-292 / :378-399), cut between the first sampled token and <|endoftext|>
+            if window is not None:
+                tokens, sum_logprobs = window.tokens, window.sum_logprobs
+            if beam is not None:
+                finished = beam.finished[0]
+                if len(finished) < o.beam_size:
+                    for j in np.argsort(sum_logprobs)[::-1]:
+                        finished[tuple(tokens[j].tolist() + [tok.eot])] = float(sum_logprobs[j])
+                        if len(finished) >= o.beam_size:
+                            break
+                candidates = [list(seq) for seq in finished]
+                sums = [float(v) for v in finished.values()]
+            else:
+                candidates = [row.tolist() + [tok.eot] for row in tokens]
+                sums = [float(v) for v in sum_logprobs]
+            candidates = [c[self.sample_begin:c.index(tok.eot)] for c in candidates]
+            best = self._rank(candidates, sums)
+            out = candidates[best]
+            text = tok.decode(out).strip()
+            return DecodingResult(language=language, language_probs=language_probs, tokens=out, text=text,
+                                  avg_logprob=sums[best] / (len(out) + 1), no_speech_prob=no_speech,
+                                  temperature=o.temperature, compression_ratio=compression_ratio(text))
+
         sources = None
         for i in range(self.sample_len):
             if device_beam and i > 0:
@@ -381,13 +647,16 @@ class _WindowDecoder:
                 continue
             if device_rules:
                 nxt_id, picked = s.pick_greedy(**self._pick_state(tokens))
-                if tokens[0, -1] != tok.eot:
-                    sum_logprobs[0] += np.float32(picked)
-                else:
-                    nxt_id = tok.eot
-                tokens = np.concatenate([tokens, np.asarray([[nxt_id]], np.int64)], axis=1)
-                if nxt_id == tok.eot or tokens.shape[-1] > self.n_ctx:
+                tokens, over = _greedy_take(tokens, sum_logprobs, nxt_id, picked, tok.eot, self.n_ctx)
+                if over:
                     break
+                if stacked is not None and i + 1 < self.sample_len:
+                    # the prefill and its pick were this session's own; every further step rides in the group
+                    window = _GreedyWindow(self, s, tokens, sum_logprobs, self.sample_len - 1 - i)
+                    if defer:
+                        return window, lambda: finish(window=window)
+                    stacked.run(window)
+                    return finish(window=window)
                 continue
             logits = _logits(s, rows, V)
             logprobs = self._apply_rules(logits, tokens)
@@ -406,26 +675,7 @@ class _WindowDecoder:
             if done or tokens.shape[-1] > self.n_ctx:
                 break
 
-        # candidates of the group (decoding.py:289-292 / :378-399), cut between the first sampled token and <|endoftext|>
-        if beam is not None:
-            finished = beam.finished[0]
-            if len(finished) < o.beam_size:
-                for j in np.argsort(sum_logprobs)[::-1]:
-                    finished[tuple(tokens[j].tolist() + [tok.eot])] = float(sum_logprobs[j])
-                    if len(finished) >= o.beam_size:
-                        break
-            candidates = [list(seq) for seq in finished]
-            sums = [float(v) for v in finished.values()]
-        else:
-            candidates = [row.tolist() + [tok.eot] for row in tokens]
-            sums = [float(v) for v in sum_logprobs]
-        candidates = [c[self.sample_begin:c.index(tok.eot)] for c in candidates]
-        best = self._rank(candidates, sums)
-        out = candidates[best]
-        text = tok.decode(out).strip()
-        return DecodingResult(language=language, language_probs=language_probs, tokens=out, text=text,
-                              avg_logprob=sums[best] / (len(out) + 1), no_speech_prob=no_speech,
-                              temperature=o.temperature, compression_ratio=compression_ratio(text))
+        return finish(tokens, sum_logprobs)
 
     def _rank(self, candidates: List[List[int]], sums: List[float]) -> int:
         """MaximumLikelihoodRanker (decoding.py:184-207): log-probability over length, or over ((5 + length) / 6) ** alpha."""
@@ -440,6 +690,27 @@ def decode(model: HipWhisperModel, mel: Optional[np.ndarray], options: DecodingO
     if kwargs:
         options = replace(options, **kwargs)
     return _WindowDecoder(model, options).run(mel, session)
+
+
+def decode_many(model: HipWhisperModel, mels: Sequence[np.ndarray], options: DecodingOptions = DecodingOptions(), *,
+                stacker: Optional[WindowStacker] = None, **kwargs) -> List[DecodingResult]:
+    """decoding.py:787-820 for up to 8 segments [n, n_mels, 3000] at once, greedy at temperature 0: one result per window,
+    in order.  Encoder, language detection, prefill, first pick and no-speech probability are each window's own (one
+    session per window); from there every token of all windows still alive is ONE ``HipWindowGroup.step_pick``.  A window
+    leaves at <|endoftext|>, at sample_len or at n_ctx; the others go on."""
+    if kwargs:
+        options = replace(options, **kwargs)
+    if options.temperature != 0 or options.beam_size is not None or options.best_of is not None:
+        raise ValueError("decode_many decodes greedily at temperature 0 (sampling and beam search: decode())")
+    mels = [np.asarray(m) for m in mels]
+    if not 1 <= len(mels) <= 8:
+        raise ValueError("decode_many takes 1..8 windows")
+    if stacker is None:
+        stacker = window_stacker(model, 8)
+    sessions = _rows_of(model).windows(len(mels))
+    opened = [_WindowDecoder(model, options).run(mel, s, stacker=stacker, defer=True) for mel, s in zip(mels, sessions)]
+    stacker.run_many([r[0] for r in opened if isinstance(r, tuple)])
+    return [r[1]() if isinstance(r, tuple) else r for r in opened]
 
 
 # ---- the window loop (transcribe.py:21-494) ---------------------------------------------------------------------------------
@@ -731,3 +1002,42 @@ def _add_word_timestamps(segments: List[dict], encoded: Optional[HipSession], mo
         alignment = T.find_alignment(encoded, tokenizer, text_tokens, None, num_frames)
     T.attach_words(segments, alignment, per_segment, last_speech_timestamp=last_speech_timestamp,
                    prepend_punctuations=prepend, append_punctuations=append)
+
+
+def transcribe_many(model: HipWhisperModel, audios: Sequence, *, stack: int = 8, **kwargs) -> List[dict]:
+    """Offline convenience: one :func:`transcribe` per recording on worker threads (at most ``stack`` at a time) whose
+    greedy temperature-0 windows share the model's :class:`WindowStacker`; -> the result dictionaries, in order.  The
+    model's stack setting is switched to ``stack`` rows for the duration of the call and put back afterwards."""
+    rows = resolve_stack(stack)
+    if rows < 1:
+        raise ValueError("transcribe_many needs stack in 1..8")
+    audios = list(audios)
+    results: List[Optional[dict]] = [None] * len(audios)
+    errors: List[Optional[BaseException]] = [None] * len(audios)
+    gate = threading.Semaphore(rows)
+    before = model.__dict__.get("_window_stack_rows")
+    set_stack(model, rows)
+
+    def work(i: int) -> None:
+        with gate:
+            try:
+                results[i] = transcribe(model, audios[i], **kwargs)
+            except BaseException as e:
+                errors[i] = e
+
+    threads = [threading.Thread(target=work, args=(i,), name=f"wlk-transcribe-{i}") for i in range(len(audios))]
+    try:
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+    finally:
+        with _STACK_LOCK:
+            if before is None:
+                model.__dict__.pop("_window_stack_rows", None)
+            else:
+                model.__dict__["_window_stack_rows"] = before
+    for e in errors:
+        if e is not None:
+            raise e
+    return results
