@@ -155,6 +155,45 @@ int wlk_group_step_pick(wlk_group* g, wlk_session* const* sessions, const int64_
 int wlk_group_stats(wlk_group* g, uint64_t* steps, uint64_t* rows);   /* completed steps, and rows summed over them */
 /* tests: the logits row [n_vocab] of slot `row` of the last completed step (WLK_ERR_STATE: no such row) */
 int wlk_group_export_logits(wlk_group* g, int row, float* host, uint64_t capacity, uint64_t* n_written);
+/* Stacked word alignment (opt-in): what wlk_find_alignment computes for up to max_rows windows of DIFFERENT
+ * encoded beam-1 sessions of the group's model in one call - ONE teacher-forced decoder pass over the rows of all windows
+ * (the stacked prefill chain: a row goes through its session's own arithmetic), the token probabilities per window with the
+ * solo call's launches, the attention normalisation, the warping recurrence (one workgroup per window, side by side) and the
+ * path walk as six launches for all windows, and ONE read-back of about 1 KB per window.
+ *   starts[i], i = 0 .. n_text: the frame index at which the warping path enters text row i (the last entry is the
+ *     <|endoftext|> row) - time_indices[first element of text index i] of whisper/timing.py's backtrace, with its overrides
+ *     (row 0 only moves left, column 0 only moves up); all that word_timings reads of the path.
+ *   token_probs, cost, trace: as wlk_find_alignment returns them (cost and trace are optional and copied only where asked).
+ * Every window is checked on the host BEFORE anything is launched or any session is touched: WLK_ERR_ARG for n outside
+ * 1..max_rows, a session listed twice, of another model or with beam != 1, everything wlk_find_alignment refuses about the
+ * tokens, and a shape outside the stacked chain (wlk_group_align_fits); WLK_ERR_STATE for a session that is not encoded,
+ * attached to the batch engine, or in debug / profiling mode.  The group's stream waits for what each session's stream has
+ * queued; the call returns after one synchronisation of the group's stream.  Afterwards every session needs a new prefill
+ * (wlk_decode, first = 1), as after wlk_find_alignment.  A window's results do not depend on the windows beside it.
+ * The first call allocates the group's stacked-pass workspace for 8 x 256 rows (about 11 n_text_state + 1056 n_text_head
+ * floats per row: 0.12 GB for base, 0.29 GB for large) and a buffer for logits, normalised attention and traces that grows
+ * on demand; a group that never aligns allocates neither.
+ * wlk_group_align_fits: the shape conditions alone, a pure host function of (model, n_tokens, num_frames): 9 <= n_tokens <=
+ * min(256, n_text_ctx), every decoder GEMM of that many rows on the k-wave kernel (needs n_text_state >= 256), the
+ * cross-attention with key splits, 1 <= num_frames / 2 <= n_audio_ctx, and a model with alignment heads. */
+typedef struct wlk_align_window {
+    wlk_session* s;            /* encoded beam-1 session of the group's model, not attached to the batch engine */
+    const int64_t* tokens;     /* [sot sequence (n_sot) | <|notimestamps|> | text tokens | <|endoftext|>] */
+    int32_t n_tokens, n_sot, eot, num_frames;
+    float qk_scale;
+    int32_t* starts;           /* out [n_text + 1] */
+    float* token_probs;        /* out [n_text] */
+    float* cost;               /* optional out [n_text + 1][num_frames / 2] */
+    int8_t* trace;             /* optional out (n_text + 2) x (num_frames / 2 + 1) */
+} wlk_align_window;
+int wlk_group_find_alignment(wlk_group* g, const wlk_align_window* w, int n /* 1..max_rows */);
+int wlk_group_align_fits(wlk_group* g, int32_t n_tokens, int32_t num_frames, int32_t* fits);
+/* Diagnostic (tests): the ragged warping launches of wlk_group_find_alignment (recurrence, transposition, path walk) on n
+ * (1..8) host cost matrices; matrix i is [n_rows[i]][n_cols[i]] at costs + offsets[i] (1..1024 rows, 1..4095 columns).
+ * starts: n_rows[i] entries per matrix, concatenated; traces (optional): (n_rows[i] + 1) x (n_cols[i] + 1) step codes per
+ * matrix, concatenated.  Runs on the current device; needs no model.  Synchronous. */
+int wlk_diag_dtw_starts(const float* costs, const int64_t* offsets, const int32_t* n_rows, const int32_t* n_cols, int n,
+                        int32_t* starts, int8_t* traces);
 /* Diagnostic (tests): the rows pick kernel alone on host data - logits [n][n_vocab], n_masks (1..8) rule masks
  * [n_masks][n_vocab] (bit 0 = always suppressed, bit 1 = blank, as wlk_rules_set builds them), row r under
  * masks[mask_of_row[r]] and p[r]; n in 1..8.  Synchronous. */

@@ -145,6 +145,13 @@ class DiagNllbCrossRaggedArgs(C.Structure):
         (n, C.c_void_p) for n in ("lengths", "kv_at", "kv_rows", "head_rank", "q", "kv", "out", "align_probs")]
 
 
+class AlignWindow(C.Structure):
+    """wlk_align_window (include/wlk_hip.h)"""
+    _fields_ = [("s", C.c_void_p), ("tokens", C.c_void_p)] + [
+        (n, C.c_int32) for n in ("n_tokens", "n_sot", "eot", "num_frames")] + [("qk_scale", C.c_float)] + [
+        (n, C.c_void_p) for n in ("starts", "token_probs", "cost", "trace")]
+
+
 ENC_X3_GEMM, ENC_LN, ENC_ATTENTION, ENC_PACK = range(4)
 WA_SOFTMAX, WA_ZSCORE, WA_COST, WA_DTW = range(4)
 SFK_ATTENTION, SFK_CONV0, SFK_DWCONV2D, SFK_GLU_DWCONV, SFK_HEAD, SFK_ASSEMBLE = range(6)
@@ -230,6 +237,9 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_group_stats": (cint, [p, C.POINTER(u64), C.POINTER(u64)]),
         "wlk_group_export_logits": (cint, [p, cint, p, u64, C.POINTER(u64)]),
         "wlk_diag_pick_rows": (cint, [p, cint, p, cint, p, p, cint, p, p]),
+        "wlk_group_find_alignment": (cint, [p, C.POINTER(AlignWindow), cint]),
+        "wlk_group_align_fits": (cint, [p, i32, i32, C.POINTER(i32)]),
+        "wlk_diag_dtw_starts": (cint, [p, p, p, p, cint, p, p]),
         "wlk_decode_ancestry": (cint, [p, p, p, cint]),
         "wlk_select": (cint, [p, p, p, p, cint, cint, cint, p, p, p]),
         "wlk_kv_reorder": (cint, [p, p, cint]),
@@ -426,6 +436,7 @@ EXPORTED_SYMBOLS = (
     "wlk_model_set_cif", "wlk_cif_result", "wlk_diag_cif",
     "wlk_group_create", "wlk_group_destroy", "wlk_group_step_pick", "wlk_group_stats", "wlk_group_export_logits",
     "wlk_diag_pick_rows",
+    "wlk_group_find_alignment", "wlk_group_align_fits", "wlk_diag_dtw_starts",
 )
 
 

@@ -1237,27 +1237,40 @@ extern "C++" std::string wlk_prefill_precheck(const wlk_prefill_item& it, const 
     if (P > D.n_text_ctx) return "text context exceeded";
     for (int i = 0; i < P; ++i)
         if (it.tokens[i] < 0 || it.tokens[i] >= D.n_vocab) return "token id out of range";
-    // the stack runs every GEMM on the k-wave kernel and the cross-attention with key splits: only prompts whose own
-    // prefill would make exactly these choices ride in it (bit-identical results either way)
-    if (P <= 8 || P > ws.cap_session_rows) return "prompt length outside the stacked range";
-    if (!gemm_takes_kwave(P, 3 * d, d) || !gemm_takes_kwave(P, d, d) || !gemm_takes_kwave(P, 4 * d, d) ||
-        !gemm_takes_kwave(P, d, 4 * d))
-        return "prompt too long for the k-wave GEMMs";
-    if (((P + 31) / 32) * D.n_text_head >= 256) return "prompt too long for the key-split cross-attention";
+    const std::string shape = wlk_prefill_shape_check(s->m, P, ws.cap_session_rows);
+    if (!shape.empty()) return shape;
     if (!gemv_applicable(8, d)) return "model too wide for the stacked vocabulary projection";
     return std::string();
 }
 
-extern "C++" void wlk_prefill_group(const std::vector<wlk_prefill_item*>& items, const LaunchCtx& c, wlk_prefill_ws& ws) {
-    if (items.empty()) return;
+extern "C++" std::string wlk_prefill_shape_check(const wlk_model* m, int P, int cap_session_rows) {
+    const wlk_dims& D = m->D;
+    const int d = D.n_text_state;
+    // the stack runs every GEMM on the k-wave kernel and the cross-attention with key splits: only prompts whose own
+    // prefill would make exactly these choices ride in it (bit-identical results either way)
+    if (P <= 8 || P > cap_session_rows) return "prompt length outside the stacked range";
+    if (!gemm_takes_kwave(P, 3 * d, d) || !gemm_takes_kwave(P, d, d) || !gemm_takes_kwave(P, 4 * d, d) ||
+        !gemm_takes_kwave(P, d, 4 * d))
+        return "prompt too long for the k-wave GEMMs";
+    if (((P + 31) / 32) * D.n_text_head >= 256) return "prompt too long for the key-split cross-attention";
+    return std::string();
+}
+
+// The stacked chain up to the last layer's output: tables, embedding, the L layers - the flash cross-attention leaves the
+// alignment heads' raw scores in rows 0 .. P-1 of each session's score window.  The one statement of it for the stacked
+// prefills (wlk_prefill_group: read-out tail behind it) and the stacked alignment pass (wlk_group_find_alignment).
+// row0[i] = first stacked row of items[i] in ws.dx; touches no session bookkeeping.
+extern "C++" void wlk_prefill_chain(const std::vector<wlk_prefill_item*>& items, const LaunchCtx& c, wlk_prefill_ws& ws,
+                                    std::vector<int>& row0) {
     wlk_model* m = items[0]->s->m;
     const wlk_dims& D = m->D;
-    const int d = D.n_text_state, T = D.n_audio_ctx, H = D.n_text_head, V = D.n_vocab, L = D.n_text_layer;
+    const int d = D.n_text_state, T = D.n_audio_ctx, H = D.n_text_head, L = D.n_text_layer;
     const int B = (int)items.size();
     // ---- tables: one StepRow per stacked row; a session's rows are padded to whole 32-row tiles with copies of its
     // row 0 (same token, position, destinations: every write of a copy repeats row 0's write with the same value)
     StepRow* rows_h = reinterpret_cast<StepRow*>(ws.pinned);
-    std::vector<int> row0(B), padded(B);
+    std::vector<int> padded(B);
+    row0.assign(B, 0);
     int R = 0;
     for (int i = 0; i < B; ++i) {
         row0[i] = R;
@@ -1330,6 +1343,16 @@ extern "C++" void wlk_prefill_group(const std::vector<wlk_prefill_item*>& items,
         ln_linear(W.ln2w, W.ln2b, W.fc1w, W.fc1b, ws.dmlp, 4 * d, 4 * d, kGemmGelu, 1.f, 0, "dec_ln2", "dec_fc1");
         linear(ws.dmlp, 4 * d, W.fc2w, W.fc2b, ws.dx, d, d, 4 * d, kGemmResidual, ws.dx, 1.f, 0, "dec_fc2");
     }
+}
+
+extern "C++" void wlk_prefill_group(const std::vector<wlk_prefill_item*>& items, const LaunchCtx& c, wlk_prefill_ws& ws) {
+    if (items.empty()) return;
+    wlk_model* m = items[0]->s->m;
+    const wlk_dims& D = m->D;
+    const int d = D.n_text_state, T = D.n_audio_ctx, V = D.n_vocab;
+    const int B = (int)items.size();
+    std::vector<int> row0;
+    wlk_prefill_chain(items, c, ws, row0);
     // ---- per session: the alignment heads' raw scores softmaxed in place; final LayerNorm of the last and the sot row
     for (int i = 0; i < B; ++i) {
         wlk_session* s = items[i]->s;

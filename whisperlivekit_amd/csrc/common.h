@@ -356,6 +356,31 @@ struct WordAlignArgs {
 // throws std::invalid_argument for what launch_word_align refuses; target_host (may be null): the targets' values
 void word_align_check(const WordAlignArgs& a, const int* target_host, int last_stage);
 void launch_word_align(const LaunchCtx& ctx, const WordAlignArgs& a, const int* target_host, int last_stage);
+// ---- the same for up to 8 windows of different shapes at once (window_group.hip: wlk_group_find_alignment) ----------
+// One entry per window, read on the device: every ragged kernel takes the window index from a grid axis and its shape
+// and pointers from here; a workgroup beyond its window's shape leaves at once.
+struct AlignWin {
+    const float* ring;       // the session's score window [n_align][ring_rows][T], raw scores in rows 0 .. P - 1
+    float* w;                // [n_align][P][F]
+    float* cost;             // [N][F]
+    signed char* trace_t;    // dtw scratch, frame-major [(F + 1)][(N + 1)] (set to -1 by the launcher's caller)
+    signed char* trace;      // token-major [(N + 1)][(F + 1)]
+    int* starts;             // [N]: frame index at which the path enters each text row (dtw_walk_kernel)
+    int P, F, n_sot, N;      // token rows, frames, sot length, N = P - n_sot - 1 cost rows
+    float qk_scale;
+    int pad;
+};
+constexpr int kAlignWinMax = 8;
+constexpr int kDtwWalkMaxCols = 4095;   // the path walk's row masks: at most 64 words of 64 cells per row
+// softmax, z-score and cost matrix of n windows: three launches (the per-window arithmetic of launch_word_align)
+void launch_word_align_ragged(const LaunchCtx& ctx, const AlignWin* tab_dev, const AlignWin* tab_host, int n, int n_align,
+                              int ring_rows, int T);
+// recurrence (one workgroup per window), transposition and path walk of n cost matrices: three launches; every
+// window's trace_t must hold -1 in every byte
+void launch_dtw_ragged(const LaunchCtx& ctx, const AlignWin* tab_dev, const AlignWin* tab_host, int n);
+// softmax(logits[row, :n_cols])[target[row]] of n_text rows (the token probabilities of find_alignment)
+void launch_wa_token_prob(const LaunchCtx& ctx, const float* logits, long ld, int n_cols, const int* target, float* probs,
+                          int n_text);
 // wlk_diag_*: the calling thread's message for wlk_diag_last_error (diag.hip owns the storage)
 void set_diag_error(const std::string& msg);
 

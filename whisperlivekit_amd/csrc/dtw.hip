@@ -16,6 +16,8 @@
 #include <algorithm>
 #include <cstring>
 #include <mutex>
+#include <stdexcept>
+#include <vector>
 
 #include "../../include/wlk_hip.h"
 #include "common.h"
@@ -25,9 +27,10 @@ namespace wlk {
 
 constexpr int kDtwMaxRows = 1024;
 
-__global__ __launch_bounds__(kDtwMaxRows) void dtw_wavefront_kernel(const float* __restrict__ x, int N, int M,
-                                                                    signed char* __restrict__ trace_t /* [M+1][N+1] */) {
-    __shared__ float diag[3][kDtwMaxRows + 1];   // cost of row i on the anti-diagonals k-2, k-1, k
+// the recurrence of one cost matrix by one workgroup (thread = token row); diag = the three live anti-diagonals in LDS
+__device__ __forceinline__ void dtw_wavefront_body(const float* __restrict__ x, int N, int M,
+                                                   signed char* __restrict__ trace_t /* [M+1][N+1] */,
+                                                   float (*diag)[kDtwMaxRows + 1]) {
     const int i = threadIdx.x + 1;               // token row 1..N of the padded recurrence
     for (int r = threadIdx.x; r < 3 * (kDtwMaxRows + 1); r += blockDim.x) (&diag[0][0])[r] = INFINITY;
     __syncthreads();
@@ -57,10 +60,15 @@ __global__ __launch_bounds__(kDtwMaxRows) void dtw_wavefront_kernel(const float*
     }
 }
 
+__global__ __launch_bounds__(kDtwMaxRows) void dtw_wavefront_kernel(const float* __restrict__ x, int N, int M,
+                                                                    signed char* __restrict__ trace_t /* [M+1][N+1] */) {
+    __shared__ float diag[3][kDtwMaxRows + 1];   // cost of row i on the anti-diagonals k-2, k-1, k
+    dtw_wavefront_body(x, N, M, trace_t, diag);
+}
+
 // frame-major [M+1][N+1] -> token-major [N+1][M+1] (the layout dtw_cpu hands to backtrace), 32x32 tiles through LDS
-__global__ __launch_bounds__(256) void dtw_transpose_kernel(const signed char* __restrict__ in, signed char* __restrict__ out,
-                                                            int rows_in /* M+1 */, int cols_in /* N+1 */) {
-    __shared__ signed char tile[32][33];
+__device__ __forceinline__ void dtw_transpose_body(const signed char* __restrict__ in, signed char* __restrict__ out,
+                                                   int rows_in /* M+1 */, int cols_in /* N+1 */, signed char (*tile)[33]) {
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
     for (int r = ty; r < 32; r += 8)
@@ -68,6 +76,74 @@ __global__ __launch_bounds__(256) void dtw_transpose_kernel(const signed char* _
     __syncthreads();
     for (int r = ty; r < 32; r += 8)
         if (c0 + r < cols_in && r0 + tx < rows_in) out[(long)(c0 + r) * rows_in + r0 + tx] = tile[tx][r];
+}
+
+__global__ __launch_bounds__(256) void dtw_transpose_kernel(const signed char* __restrict__ in, signed char* __restrict__ out,
+                                                            int rows_in /* M+1 */, int cols_in /* N+1 */) {
+    __shared__ signed char tile[32][33];
+    dtw_transpose_body(in, out, rows_in, cols_in, tile);
+}
+
+// ---- up to 8 cost matrices of different shapes at once (wlk_group_find_alignment) ----------------------------------------
+// The recurrence is latency-bound on one CU, so the windows run side by side: workgroup = window, shape and pointers
+// from the table, the block sized for the tallest window (threads beyond a window's rows only keep its barriers).
+__global__ __launch_bounds__(kDtwMaxRows) void dtw_wavefront_ragged_kernel(const AlignWin* __restrict__ tab) {
+    __shared__ float diag[3][kDtwMaxRows + 1];
+    const AlignWin t = tab[blockIdx.x];
+    dtw_wavefront_body(t.cost, t.N, t.F, t.trace_t, diag);
+}
+__global__ __launch_bounds__(256) void dtw_transpose_ragged_kernel(const AlignWin* __restrict__ tab) {
+    __shared__ signed char tile[32][33];
+    const AlignWin t = tab[blockIdx.z];
+    if ((int)blockIdx.x * 32 > t.N || (int)blockIdx.y * 32 > t.F) return;      // tile outside this window's [F+1][N+1]
+    dtw_transpose_body(t.trace_t, t.trace, t.F + 1, t.N + 1, tile);
+}
+
+// The path walk of timing.backtrace, reduced to what word_timings reads: starts[i - 1] = frame index (column - 1) of the
+// cell at which the path, walked back from (N, M), LEAVES token row i = 1 .. N - the first path element of that text
+// index in forward order.  With backtrace's overrides (column 0 only moves up; row 0 only moves left and is not needed
+// for the starts) a row's exit is "the largest j' <= j whose code is not LEFT", and the next row is entered at j' - 1
+// (diagonal) or j' (up).  No thread follows the path cell by cell through memory: the waves of the workgroup turn the
+// codes of a band of rows into two bit masks per 64-cell chunk (one byte load per lane, two ballots: not-left, diagonal)
+// in LDS - 2 x 24 KB, 128 rows of a 1500-frame window per band - and one thread then resolves each row of the band with
+// a masked count-leading-zeros on LDS words: N + ceil(M / 64) dependent LDS look-ups at most, no dependent global load.
+constexpr int kWalkWords = 3072;                 // 64-cell words per mask in LDS
+__global__ __launch_bounds__(1024) void dtw_walk_kernel(const AlignWin* __restrict__ tab) {
+    __shared__ unsigned long long not_left[kWalkWords], diagonal[kWalkWords];
+    const AlignWin t = tab[blockIdx.x];
+    const int N = t.N, M = t.F;
+    const int W = (M + 64) / 64;                 // words of a row's columns 0 .. M
+    const int band = kWalkWords / W;             // rows per band (>= 48: M <= kDtwWalkMaxCols)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    int j = M;                                   // thread 0: the column at which the path enters the next row
+    for (int hi = N; hi >= 1; hi -= band) {
+        const int lo = hi - band + 1 > 1 ? hi - band + 1 : 1;
+        const int chunks = (hi - lo + 1) * W;
+        for (int c = wave; c < chunks; c += n_waves) {
+            const int i = lo + c / W, col = (c % W) * 64 + lane;
+            signed char code = 2;                // beyond column M: left, never an exit
+            if (col == 0) code = 1;              // column 0 only moves up
+            else if (col <= M) code = t.trace[(long)i * (M + 1) + col];
+            const unsigned long long nl = __ballot(code != 2), dg = __ballot(code == 0);
+            if (lane == 0) {
+                not_left[c] = nl;
+                diagonal[c] = dg;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int i = hi; i >= lo; --i) {
+                const unsigned long long* row = not_left + (i - lo) * W;
+                int w = j >> 6;
+                unsigned long long bits = row[w] & (~0ull >> (63 - (j & 63)));
+                while (bits == 0) bits = row[--w];           // ends at the latest in word 0: column 0 is always set
+                const int jp = w * 64 + 63 - __clzll((long long)bits);
+                t.starts[i - 1] = jp - 1;
+                j = jp - (int)((diagonal[(i - lo) * W + w] >> (jp & 63)) & 1ull);
+            }
+        }
+        __syncthreads();
+    }
 }
 
 // Per-device workspace of wlk_dtw: device buffers and pinned staging that only ever grow, and a non-blocking stream of
@@ -119,6 +195,24 @@ void launch_dtw(hipStream_t stream, const float* x_dev, int n_rows, int n_cols, 
     WLK_HIP(hipGetLastError());
 }
 
+void launch_dtw_ragged(const LaunchCtx& ctx, const AlignWin* tab_dev, const AlignWin* tab_host, int n) {
+    if (!tab_dev || !tab_host || n < 1 || n > kAlignWinMax) throw std::invalid_argument("ragged dtw: 1..8 windows");
+    int max_n = 0, max_f = 0;
+    for (int i = 0; i < n; ++i) {
+        const AlignWin& t = tab_host[i];
+        if (!t.cost || !t.trace_t || !t.trace || !t.starts) throw std::invalid_argument("ragged dtw: null operand");
+        if (t.N < 1 || t.N > kDtwMaxRows || t.F < 1 || t.F > kDtwWalkMaxCols)
+            throw std::invalid_argument("ragged dtw: 1..1024 rows and 1..4095 columns");
+        max_n = std::max(max_n, t.N); max_f = std::max(max_f, t.F);
+    }
+    const int threads = std::max(64, ((max_n + 63) / 64) * 64);
+    hipLaunchKernelGGL(dtw_wavefront_ragged_kernel, dim3(n), dim3(threads), 0, ctx.stream, tab_dev);
+    hipLaunchKernelGGL(dtw_transpose_ragged_kernel, dim3((max_n + 1 + 31) / 32, (max_f + 1 + 31) / 32, n), dim3(256), 0, ctx.stream,
+                       tab_dev);
+    hipLaunchKernelGGL(dtw_walk_kernel, dim3(n), dim3(1024), 0, ctx.stream, tab_dev);
+    WLK_HIP(hipGetLastError());
+}
+
 }  // namespace wlk
 
 using namespace wlk;
@@ -142,6 +236,62 @@ extern "C" int wlk_dtw(int device, const float* x, int32_t n_rows, int32_t n_col
         WLK_HIP(hipMemcpyAsync(ws.pinned, ws.tt, nt, hipMemcpyDeviceToHost, ws.stream));
         WLK_HIP(hipStreamSynchronize(ws.stream));
         std::memcpy(trace, ws.pinned, nt);
+        return WLK_OK;
+    });
+}
+
+// Tests: the production ragged launches (recurrence, transposition, path walk) on host-given cost matrices; no model.
+extern "C" int wlk_diag_dtw_starts(const float* costs, const int64_t* offsets, const int32_t* n_rows, const int32_t* n_cols, int n,
+                                   int32_t* starts, int8_t* traces) {
+    if (!costs || !offsets || !n_rows || !n_cols || !starts) return fail(WLK_ERR_ARG, "dtw starts: NULL argument");
+    if (n < 1 || n > kAlignWinMax) return fail(WLK_ERR_ARG, "dtw starts: 1..8 matrices");
+    size_t n_x = 0, n_t = 0, n_s = 0;
+    for (int i = 0; i < n; ++i) {
+        if (n_rows[i] < 1 || n_rows[i] > kDtwMaxRows || n_cols[i] < 1 || n_cols[i] > kDtwWalkMaxCols || offsets[i] < 0)
+            return fail(WLK_ERR_ARG, "dtw starts: 1..1024 rows, 1..4095 columns, offsets >= 0");
+        n_x = std::max(n_x, (size_t)offsets[i] + (size_t)n_rows[i] * n_cols[i]);
+        n_t += (size_t)(n_rows[i] + 1) * (n_cols[i] + 1);
+        n_s += (size_t)n_rows[i];
+    }
+    return guarded([&]() {
+        struct Scratch {
+            hipStream_t stream = nullptr;
+            float* x = nullptr;
+            signed char *tt = nullptr, *tr = nullptr;
+            int* st = nullptr;
+            AlignWin* tab = nullptr;
+            ~Scratch() {
+                for (void* p : {(void*)x, (void*)tt, (void*)tr, (void*)st, (void*)tab})
+                    if (p) (void)hipFree(p);
+                if (stream) (void)hipStreamDestroy(stream);
+            }
+        } w;
+        WLK_HIP(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+        WLK_HIP(hipMalloc(reinterpret_cast<void**>(&w.x), n_x * sizeof(float)));
+        WLK_HIP(hipMalloc(reinterpret_cast<void**>(&w.tt), n_t));
+        WLK_HIP(hipMalloc(reinterpret_cast<void**>(&w.tr), n_t));
+        WLK_HIP(hipMalloc(reinterpret_cast<void**>(&w.st), n_s * sizeof(int)));
+        WLK_HIP(hipMalloc(reinterpret_cast<void**>(&w.tab), sizeof(AlignWin) * kAlignWinMax));
+        AlignWin host[kAlignWinMax] = {};
+        size_t at_t = 0, at_s = 0;
+        for (int i = 0; i < n; ++i) {
+            AlignWin& t = host[i];
+            t.cost = w.x + offsets[i];
+            t.trace_t = w.tt + at_t;
+            t.trace = w.tr + at_t;
+            t.starts = w.st + at_s;
+            t.N = n_rows[i];
+            t.F = n_cols[i];
+            at_t += (size_t)(n_rows[i] + 1) * (n_cols[i] + 1);
+            at_s += (size_t)n_rows[i];
+        }
+        WLK_HIP(hipMemcpy(w.x, costs, n_x * sizeof(float), hipMemcpyHostToDevice));
+        WLK_HIP(hipMemcpy(w.tab, host, sizeof(AlignWin) * n, hipMemcpyHostToDevice));
+        WLK_HIP(hipMemsetAsync(w.tt, 0xff, n_t, w.stream));   // -1 like dtw_cpu's untouched border cells
+        launch_dtw_ragged(LaunchCtx{w.stream, nullptr}, w.tab, host, n);
+        WLK_HIP(hipStreamSynchronize(w.stream));
+        WLK_HIP(hipMemcpy(starts, w.st, n_s * sizeof(int), hipMemcpyDeviceToHost));
+        if (traces) WLK_HIP(hipMemcpy(traces, w.tr, n_t, hipMemcpyDeviceToHost));
         return WLK_OK;
     });
 }

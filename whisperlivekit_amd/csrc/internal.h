@@ -383,6 +383,11 @@ std::string wlk_encode_precheck(const wlk_session* s, const wlk_model* m);
 // caller runs wlk_decode).  Leaves each session as wlk_decode(first = 1) leaves it; throws on launch failures.
 std::string wlk_prefill_precheck(const wlk_prefill_item& it, const wlk_prefill_ws& ws);
 void wlk_prefill_group(const std::vector<wlk_prefill_item*>& items, const wlk::LaunchCtx& c, wlk_prefill_ws& ws);
+// the chain of wlk_prefill_group without its read-out tail and bookkeeping (api.hip); items must not be empty
+void wlk_prefill_chain(const std::vector<wlk_prefill_item*>& items, const wlk::LaunchCtx& c, wlk_prefill_ws& ws,
+                       std::vector<int>& row0);
+// the shape conditions of wlk_prefill_precheck alone: empty = a prompt of P tokens can ride in a stacked chain of model m
+std::string wlk_prefill_shape_check(const wlk_model* m, int P, int cap_session_rows);
 void wlk_prefill_ws_alloc(const wlk_model* m, wlk_prefill_ws& ws, int max_sessions, int session_rows);
 void wlk_prefill_ws_free(wlk_prefill_ws& ws);
 

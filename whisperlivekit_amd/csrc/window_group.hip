@@ -13,11 +13,19 @@
 // The layer chain restates wlk_engine::enqueue_decoder (engine.hip) with one difference: the cross-attention's query
 // projection is the multi-row GEMV for EVERY row count, also for one row (the engine folds it into the attention kernel
 // there).  A row therefore goes through the same kernels whether it steps alone or beside seven others.
+//
+// The same group also aligns the words of up to 8 windows in one call (wlk_group_find_alignment): one stacked
+// teacher-forced decoder pass (api.hip: wlk_prefill_chain), the token probabilities per window, the ragged normalisation
+// (word_align.hip), the warping recurrences side by side and the path walk on the device (dtw.hip), one read-back of the
+// starts and probabilities.  Its workspace is allocated by the first such call.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstring>
 #include <mutex>
+#include <stdexcept>
+#include <string>
+#include <vector>
 
 #include "common.h"
 #include "internal.h"
@@ -45,6 +53,13 @@ struct wlk_group {
     int last_rows = 0;                   // rows of the last completed step (wlk_group_export_logits)
     uint64_t n_steps = 0, n_rows = 0;
     std::mutex mu;                       // one step at a time
+    // stacked word alignment (wlk_group_find_alignment): nothing of it exists before the first such call
+    wlk_prefill_ws align_ws;             // the stacked decoder pass over 8 x 256 rows
+    bool align_ready = false;
+    char* align_buf = nullptr;           // grown on demand: [hidden | logits | w | cost | results | trace_t | trace]
+    size_t align_cap = 0;
+    char* align_up_dev = nullptr;        // [AlignWin x 8 | targets int x 8 x 256]
+    char* align_pinned = nullptr;        // [upload block | results: starts and token probabilities of all windows]
 
     ~wlk_group() {
         (void)hipSetDevice(m->device);
@@ -55,6 +70,10 @@ struct wlk_group {
         if (blk_dev) (void)hipFree(blk_dev);
         if (pick_dev) (void)hipFree(pick_dev);
         if (pinned) (void)hipHostFree(pinned);
+        if (align_ready) wlk_prefill_ws_free(align_ws);
+        if (align_buf) (void)hipFree(align_buf);
+        if (align_up_dev) (void)hipFree(align_up_dev);
+        if (align_pinned) (void)hipHostFree(align_pinned);
         for (hipEvent_t e : joined)
             if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
@@ -217,6 +236,175 @@ int wlk_group_step_pick(wlk_group* g, wlk_session* const* sessions, const int64_
         g->last_rows = n;
         g->n_steps += 1;
         g->n_rows += (uint64_t)n;
+        return WLK_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- stacked word alignment ----------------------------------------------------------------------------------
+namespace {
+constexpr int kAlignRowsMax = 256;       // longest token sequence of one window in the stacked pass
+constexpr size_t kAlignUpBytes = sizeof(AlignWin) * kGroupMaxRows + sizeof(int) * kGroupMaxRows * kAlignRowsMax;
+constexpr size_t kAlignResBytes = sizeof(int) * 2 * kGroupMaxRows * kAlignRowsMax;
+inline size_t up16(size_t n) { return (n + 15) / 16 * 16; }
+
+int align_session_rows(const wlk_model* m) { return std::min(kAlignRowsMax, (int)m->D.n_text_ctx); }
+
+// the shape conditions of a window in the stacked pass: a pure host function of (model, P, num_frames); empty = fits
+std::string align_shape_refusal(const wlk_model* m, int P, int num_frames) {
+    const int F = num_frames / 2;
+    if (m->n_align < 1) return "the model has no alignment heads";
+    if (F < 1 || F > m->D.n_audio_ctx) return "num_frames out of range";
+    return wlk_prefill_shape_check(m, P, align_session_rows(m));
+}
+}  // namespace
+
+extern "C" {
+
+int wlk_group_align_fits(wlk_group* g, int32_t n_tokens, int32_t num_frames, int32_t* fits) {
+    if (!g || !fits) return fail(WLK_ERR_ARG, "NULL argument");
+    *fits = align_shape_refusal(g->m, n_tokens, num_frames).empty() ? 1 : 0;
+    return WLK_OK;
+}
+
+int wlk_group_find_alignment(wlk_group* g, const wlk_align_window* w, int n) {
+    if (!g || !w) return fail(WLK_ERR_ARG, "NULL argument");
+    if (n < 1 || n > g->max_rows) return fail(WLK_ERR_ARG, "window group: 1..max_rows windows per alignment pass");
+    wlk_model* m = g->m;
+    const wlk_dims& D = m->D;
+    // every window is checked on the host before anything is launched or any session is touched
+    for (int r = 0; r < n; ++r) {
+        const wlk_align_window& a = w[r];
+        const wlk_session* s = a.s;
+        if (!s || !a.tokens || !a.starts || !a.token_probs) return fail(WLK_ERR_ARG, "window group: NULL argument in an alignment window");
+        for (int j = 0; j < r; ++j)
+            if (w[j].s == s) return fail(WLK_ERR_ARG, "window group: a session is listed twice");
+        if (s->m != m) return fail(WLK_ERR_ARG, "window group: a session of another model");
+        if (s->beam != 1) return fail(WLK_ERR_ARG, "find_alignment needs a beam-1 session");
+        if (s->engine) return fail(WLK_ERR_STATE, "window group: the session is attached to the batch engine");
+        if (!s->encoded) return fail(WLK_ERR_STATE, "find_alignment before an encode");
+        if (s->debug || s->prof_on) return fail(WLK_ERR_STATE, "window group: not a plain beam-1 session");
+        const int P = a.n_tokens, n_text = P - a.n_sot - 2;
+        if (a.n_sot < 1 || n_text < 1) return fail(WLK_ERR_ARG, "find_alignment: need [sot sequence, notimestamps, >= 1 text token, eot]");
+        if (a.eot < 1 || a.eot > D.n_vocab) return fail(WLK_ERR_ARG, "find_alignment: eot out of range");
+        const std::string shape = align_shape_refusal(m, P, a.num_frames);
+        if (!shape.empty()) return fail(WLK_ERR_ARG, "find_alignment: " + shape);
+        for (int i = 0; i < P; ++i)
+            if (a.tokens[i] < 0 || a.tokens[i] >= D.n_vocab) return fail(WLK_ERR_ARG, "token id out of range");
+        for (int i = 0; i < n_text; ++i)
+            if (a.tokens[a.n_sot + 1 + i] >= a.eot) return fail(WLK_ERR_ARG, "find_alignment: text token >= eot");
+    }
+    return guarded([&]() {
+        std::lock_guard<std::mutex> lk(g->mu);
+        WLK_HIP(hipSetDevice(m->device));
+        const LaunchCtx c{g->stream, nullptr};
+        const int d = D.n_text_state, T = D.n_audio_ctx;
+        if (!g->align_ready) {
+            wlk_prefill_ws_alloc(m, g->align_ws, kGroupMaxRows, align_session_rows(m));
+            g->align_ready = true;
+            g->align_up_dev = dev_alloc<char>(kAlignUpBytes);
+            WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&g->align_pinned), kAlignUpBytes + kAlignResBytes, hipHostMallocDefault));
+        }
+        // ---- workspace: [hidden max n_text x d | logits max n_text x eot | per window: w, cost | results | trace_t | trace]
+        size_t hid_b = 0, log_b = 0, wc_b = 0, tr_b = 0, n_res = 0;
+        for (int r = 0; r < n; ++r) {
+            const int P = w[r].n_tokens, n_text = P - w[r].n_sot - 2, N = n_text + 1, F = w[r].num_frames / 2;
+            hid_b = std::max(hid_b, up16((size_t)n_text * d * 4));
+            log_b = std::max(log_b, up16((size_t)n_text * w[r].eot * 4));
+            wc_b += up16((size_t)m->n_align * P * F * 4) + up16((size_t)N * F * 4);
+            tr_b += up16((size_t)(N + 1) * (F + 1));
+            n_res += (size_t)N + n_text;
+        }
+        const size_t res_b = up16(n_res * 4);
+        const size_t need = hid_b + log_b + wc_b + res_b + 2 * tr_b;
+        if (need > g->align_cap) {
+            WLK_HIP(hipStreamSynchronize(g->stream));
+            if (g->align_buf) WLK_HIP(hipFree(g->align_buf));
+            g->align_buf = nullptr; g->align_cap = 0;
+            g->align_buf = dev_alloc<char>(need);
+            g->align_cap = need;
+        }
+        float* hid = reinterpret_cast<float*>(g->align_buf);
+        float* logits = reinterpret_cast<float*>(g->align_buf + hid_b);
+        char* at = g->align_buf + hid_b + log_b;
+        int* res_dev = reinterpret_cast<int*>(at + wc_b);
+        signed char* trace_t0 = reinterpret_cast<signed char*>(at + wc_b + res_b);
+        signed char* trace0 = trace_t0 + tr_b;
+
+        // ---- tables: one AlignWin per window, the text tokens as the probability targets; results = [starts | probs] of
+        // window 0, then of window 1, ...
+        AlignWin* tab_h = reinterpret_cast<AlignWin*>(g->align_pinned);
+        int* tgt_h = reinterpret_cast<int*>(g->align_pinned + sizeof(AlignWin) * kGroupMaxRows);
+        AlignWin* tab_dev = reinterpret_cast<AlignWin*>(g->align_up_dev);
+        int* tgt_dev = reinterpret_cast<int*>(g->align_up_dev + sizeof(AlignWin) * kGroupMaxRows);
+        int* res_h = reinterpret_cast<int*>(g->align_pinned + kAlignUpBytes);
+        std::vector<wlk_prefill_item> items(n);
+        std::vector<wlk_prefill_item*> stack(n);
+        std::vector<size_t> res_at(n), tgt_at(n);
+        size_t tr_at = 0, r_at = 0, t_at = 0;
+        for (int r = 0; r < n; ++r) {
+            wlk_session* s = w[r].s;
+            const int P = w[r].n_tokens, n_sot = w[r].n_sot, n_text = P - n_sot - 2, N = n_text + 1, F = w[r].num_frames / 2;
+            AlignWin& t = tab_h[r];
+            t = AlignWin{};
+            t.ring = s->ring;
+            t.w = reinterpret_cast<float*>(at);
+            at += up16((size_t)m->n_align * P * F * 4);
+            t.cost = reinterpret_cast<float*>(at);
+            at += up16((size_t)N * F * 4);
+            t.trace_t = trace_t0 + tr_at;
+            t.trace = trace0 + tr_at;
+            tr_at += up16((size_t)(N + 1) * (F + 1));
+            t.starts = res_dev + r_at;
+            res_at[r] = r_at;
+            r_at += (size_t)N + n_text;
+            t.P = P; t.F = F; t.n_sot = n_sot; t.N = N; t.qk_scale = w[r].qk_scale;
+            tgt_at[r] = t_at;
+            for (int i = 0; i < n_text; ++i) tgt_h[t_at + i] = (int)w[r].tokens[n_sot + 1 + i];
+            t_at += n_text;
+            items[r].s = s; items[r].tokens = w[r].tokens; items[r].n_tok = P; items[r].sot_index = 0;
+            stack[r] = &items[r];
+            if (s->ring_rows != w[0].s->ring_rows) throw std::logic_error("window group: score windows of different heights");
+            // the chain overwrites the session's caches and score window: whatever happens from here on, its next decode
+            // must be a prefill (as after wlk_find_alignment)
+            s->n_steps = 0;
+            s->self_len = 0;
+            s->have_sot = false;
+            // what the session's own stream has queued (encode, its window's steps) is done before this stream touches it
+            WLK_HIP(hipEventRecord(g->joined[r], s->stream));
+            WLK_HIP(hipStreamWaitEvent(g->stream, g->joined[r], 0));
+        }
+        WLK_HIP(hipMemcpyAsync(g->align_up_dev, g->align_pinned, kAlignUpBytes, hipMemcpyHostToDevice, g->stream));
+
+        // ---- ONE decoder pass over the rows of all windows; raw alignment scores land in each session's score window
+        std::vector<int> row0;
+        wlk_prefill_chain(stack, c, g->align_ws, row0);
+        // ---- token probabilities, per window with the solo call's launches (M = n_text is compute-bound: stacking the rows
+        // would buy nothing and change the kernel choice) into one reused logits buffer
+        for (int r = 0; r < n; ++r) {
+            const int n_sot = w[r].n_sot, n_text = w[r].n_tokens - n_sot - 2, eot = w[r].eot;
+            launch_layernorm(c, g->align_ws.dx + (size_t)(row0[r] + n_sot) * d, d, m->w_ln_w, m->w_ln_b, hid, d, n_text, d, "wa_ln_f");
+            GemmArgs lg;
+            lg.A = hid; lg.lda = d; lg.W = m->w_tok_emb; lg.C = logits; lg.ldc = eot; lg.M = n_text; lg.N = eot; lg.K = d;
+            launch_linear(c, lg, "wa_logits");
+            launch_wa_token_prob(c, logits, eot, eot, tgt_dev + tgt_at[r],
+                                 reinterpret_cast<float*>(res_dev + res_at[r] + n_text + 1), n_text);
+        }
+        // ---- attention -> cost matrices -> warping -> path walk: six launches for all windows
+        launch_word_align_ragged(c, tab_dev, tab_h, n, m->n_align, w[0].s->ring_rows, T);
+        WLK_HIP(hipMemsetAsync(trace_t0, 0xff, tr_at, g->stream));   // -1 like dtw_cpu's untouched border cells
+        launch_dtw_ragged(c, tab_dev, tab_h, n);
+        WLK_HIP(hipMemcpyAsync(res_h, res_dev, r_at * sizeof(int), hipMemcpyDeviceToHost, g->stream));
+        WLK_HIP(hipStreamSynchronize(g->stream));
+        for (int r = 0; r < n; ++r) {
+            const int n_text = w[r].n_tokens - w[r].n_sot - 2, N = n_text + 1, F = w[r].num_frames / 2;
+            std::memcpy(w[r].starts, res_h + res_at[r], (size_t)N * sizeof(int));
+            std::memcpy(w[r].token_probs, res_h + res_at[r] + N, (size_t)n_text * sizeof(float));
+            // tests only (host buffers are the caller's: pageable, so synchronous)
+            if (w[r].cost) copy_sync(w[r].cost, tab_h[r].cost, (size_t)N * F * sizeof(float), hipMemcpyDeviceToHost);
+            if (w[r].trace) copy_sync(w[r].trace, tab_h[r].trace, (size_t)(N + 1) * (F + 1), hipMemcpyDeviceToHost);
+        }
         return WLK_OK;
     });
 }

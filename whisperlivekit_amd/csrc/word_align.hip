@@ -18,6 +18,8 @@
 // back and cutting it into words is integer bookkeeping and stays in Python (whisperlivekit_amd/timing.py).
 // The mel of a 30 s window can be handed in as the reference's callers have it (wlk_encode_mel): `transcribe()` slices
 // it out of the whole file's log-mel (whisper/transcribe.py), find_alignment gets that segment.
+// The three normalisation stages exist once as device bodies; the one-window kernels and the ragged ones (up to 8 windows of
+// different shapes per launch, window_group.hip: wlk_group_find_alignment) instantiate the same bodies.
 #include <algorithm>
 #include <cstring>
 #include <stdexcept>
@@ -68,13 +70,10 @@ __global__ __launch_bounds__(256) void wa_token_prob_kernel(const float* __restr
     if (threadIdx.x == 0) probs[blockIdx.x] = expf(x[target[blockIdx.x]] - mx) / sum;
 }
 
-// w[a][r][0 .. F) = softmax(qk_scale * raw[a][r][0 .. F)): one workgroup per (token row r, alignment rank a)
-__global__ __launch_bounds__(256) void wa_softmax_kernel(const float* __restrict__ ring, int ring_rows, int T, int F, float qk_scale,
-                                                         float* __restrict__ w, int P) {
-    __shared__ float red[4];
-    const int r = blockIdx.x, a = blockIdx.y;
-    const float* x = ring + ((long)a * ring_rows + r) * T;
-    float* y = w + ((long)a * P + r) * F;
+// ---- the device bodies: one statement of each stage for the one-window kernels and the ragged ones below --------------
+// y[0 .. F) = softmax(qk_scale * x[0 .. F)): one workgroup of 256
+__device__ __forceinline__ void wa_softmax_body(const float* __restrict__ x, float* __restrict__ y, int F, float qk_scale,
+                                                float* red) {
     float mx = -INFINITY;
     for (int j = threadIdx.x; j < F; j += 256) mx = fmaxf(mx, x[j] * qk_scale);
     mx = wa_block_max(mx, red);
@@ -88,14 +87,14 @@ __global__ __launch_bounds__(256) void wa_softmax_kernel(const float* __restrict
     for (int j = threadIdx.x; j < F; j += 256) y[j] = y[j] / sum;
 }
 
-// z-score over the token axis, in place: per (head a, frame f) mean and population std over the P rows in fp64 (as the
-// streaming read-out does: torch's CPU std_mean accumulates in double), z = (w - mean) / std - NO epsilon here
-__global__ __launch_bounds__(256) void wa_zscore_kernel(float* __restrict__ w, int P, int F) {
-    __shared__ double red[4][64];
+// z-score over the token axis, in place, of one head's [P][F] block for the 64 frames from f0 on: per frame mean and
+// population std over the P rows in fp64 (as the streaming read-out does: torch's CPU std_mean accumulates in double),
+// z = (w - mean) / std - NO epsilon here
+__device__ __forceinline__ void wa_zscore_body(float* __restrict__ wa, int P, int F, int f0, double (*red)[64]) {
     const int fx = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int f = blockIdx.x * 64 + fx, a = blockIdx.y;
+    const int f = f0 + fx;
     const bool ok = f < F;
-    float* base = w + (long)a * P * F + (ok ? f : 0);
+    float* base = wa + (ok ? f : 0);
     double sum = 0.0;
     for (int i = rg; i < P; i += 4) sum += (double)base[(long)i * F];
     red[rg][fx] = sum;
@@ -114,6 +113,20 @@ __global__ __launch_bounds__(256) void wa_zscore_kernel(float* __restrict__ w, i
         for (int i = rg; i < P; i += 4) base[(long)i * F] = (base[(long)i * F] - (float)mean) / stdv;
 }
 
+// w[a][r][0 .. F) = softmax(qk_scale * raw[a][r][0 .. F)): one workgroup per (token row r, alignment rank a)
+__global__ __launch_bounds__(256) void wa_softmax_kernel(const float* __restrict__ ring, int ring_rows, int T, int F, float qk_scale,
+                                                         float* __restrict__ w, int P) {
+    __shared__ float red[4];
+    const int r = blockIdx.x, a = blockIdx.y;
+    wa_softmax_body(ring + ((long)a * ring_rows + r) * T, w + ((long)a * P + r) * F, F, qk_scale, red);
+}
+
+// one workgroup per (64 frames, alignment rank a)
+__global__ __launch_bounds__(256) void wa_zscore_kernel(float* __restrict__ w, int P, int F) {
+    __shared__ double red[4][64];
+    wa_zscore_body(w + (long)blockIdx.y * P * F, P, F, blockIdx.x * 64, red);
+}
+
 __device__ __forceinline__ float wa_median7(float v0, float v1, float v2, float v3, float v4, float v5, float v6) {
     float v[7] = {v0, v1, v2, v3, v4, v5, v6};
 #pragma unroll
@@ -130,11 +143,9 @@ __device__ __forceinline__ float wa_median7(float v0, float v1, float v2, float 
     return v[3];
 }
 
-// cost[r - row0][f] = -(1 / n_align) sum_a median7(z[a][r][f-3 .. f+3], reflect padding): rows row0 .. row0 + N - 1.
+// out[f] = -(1 / n_align) sum_a median7(z[a][r][f-3 .. f+3], reflect padding) for token row r.
 // median_filter (timing.py:19-54) leaves rows no longer than the padding (F <= 3) untouched.
-__global__ __launch_bounds__(256) void wa_cost_kernel(const float* __restrict__ z, int n_align, int P, int F, int row0,
-                                                      float* __restrict__ cost) {
-    const int r = row0 + blockIdx.x;
+__device__ __forceinline__ void wa_cost_body(const float* __restrict__ z, int n_align, int P, int F, int r, float* __restrict__ out) {
     for (int f = threadIdx.x; f < F; f += 256) {
         float acc = 0.f;
         for (int a = 0; a < n_align; ++a) {
@@ -155,8 +166,34 @@ __global__ __launch_bounds__(256) void wa_cost_kernel(const float* __restrict__ 
             }
             acc += m;
         }
-        cost[(long)blockIdx.x * F + f] = -(acc / (float)n_align);
+        out[f] = -(acc / (float)n_align);
     }
+}
+
+// cost[r - row0][..]: rows row0 .. row0 + N - 1, one workgroup each
+__global__ __launch_bounds__(256) void wa_cost_kernel(const float* __restrict__ z, int n_align, int P, int F, int row0,
+                                                      float* __restrict__ cost) {
+    wa_cost_body(z, n_align, P, F, row0 + blockIdx.x, cost + (long)blockIdx.x * F);
+}
+
+// ---- ragged forms: window blockIdx.z (.y for the cost) of the table; workgroups beyond the window's shape leave --------
+__global__ __launch_bounds__(256) void wa_softmax_ragged_kernel(const AlignWin* __restrict__ tab, int ring_rows, int T) {
+    __shared__ float red[4];
+    const AlignWin t = tab[blockIdx.z];
+    const int r = blockIdx.x, a = blockIdx.y;
+    if (r >= t.P) return;
+    wa_softmax_body(t.ring + ((long)a * ring_rows + r) * T, t.w + ((long)a * t.P + r) * t.F, t.F, t.qk_scale, red);
+}
+__global__ __launch_bounds__(256) void wa_zscore_ragged_kernel(const AlignWin* __restrict__ tab) {
+    __shared__ double red[4][64];
+    const AlignWin t = tab[blockIdx.z];
+    if ((int)blockIdx.x * 64 >= t.F) return;
+    wa_zscore_body(t.w + (long)blockIdx.y * t.P * t.F, t.P, t.F, blockIdx.x * 64, red);
+}
+__global__ __launch_bounds__(256) void wa_cost_ragged_kernel(const AlignWin* __restrict__ tab, int n_align) {
+    const AlignWin t = tab[blockIdx.y];
+    if ((int)blockIdx.x >= t.N) return;
+    wa_cost_body(t.w, n_align, t.P, t.F, t.n_sot + blockIdx.x, t.cost + (long)blockIdx.x * t.F);
 }
 
 }  // namespace
@@ -178,6 +215,36 @@ void word_align_check(const WordAlignArgs& a, const int* target_host, int last_s
     need(last_stage < kWaDtw || (a.trace_t && a.trace), "null trace");
     if (target_host)
         for (int i = 0; i < n_text; ++i) need(target_host[i] >= 0 && target_host[i] < a.n_cols, "target outside the logit columns");
+}
+
+void launch_wa_token_prob(const LaunchCtx& ctx, const float* logits, long ld, int n_cols, const int* target, float* probs,
+                          int n_text) {
+    if (n_text < 1 || n_cols < 1 || ld < n_cols || !logits || !target || !probs)
+        throw std::invalid_argument("word alignment: token probabilities of an empty or null operand");
+    hipLaunchKernelGGL(wa_token_prob_kernel, dim3(n_text), dim3(256), 0, ctx.stream, logits, ld, n_cols, target, probs);
+    WLK_HIP(hipGetLastError());
+}
+
+void launch_word_align_ragged(const LaunchCtx& ctx, const AlignWin* tab_dev, const AlignWin* tab_host, int n, int n_align,
+                              int ring_rows, int T) {
+    auto need = [](bool ok, const char* what) {
+        if (!ok) throw std::invalid_argument(std::string("ragged word alignment: ") + what);
+    };
+    need(tab_dev && tab_host && n >= 1 && n <= kAlignWinMax, "1..8 windows");
+    need(n_align >= 1 && T >= 1 && ring_rows >= 1, "no alignment heads or no score window");
+    int max_p = 0, max_f = 0, max_n = 0;
+    for (int i = 0; i < n; ++i) {
+        const AlignWin& t = tab_host[i];
+        need(t.ring && t.w && t.cost, "null operand");
+        need(t.n_sot >= 1 && t.N >= 2 && t.N == t.P - t.n_sot - 1, "need [sot sequence, notimestamps, >= 1 text token, eot]");
+        need(t.P <= ring_rows, "more token rows than the score window holds");
+        need(t.F >= 1 && t.F <= T, "frames outside [1, T]");
+        max_p = std::max(max_p, t.P); max_f = std::max(max_f, t.F); max_n = std::max(max_n, t.N);
+    }
+    hipLaunchKernelGGL(wa_softmax_ragged_kernel, dim3(max_p, n_align, n), dim3(256), 0, ctx.stream, tab_dev, ring_rows, T);
+    hipLaunchKernelGGL(wa_zscore_ragged_kernel, dim3((max_f + 63) / 64, n_align, n), dim3(256), 0, ctx.stream, tab_dev);
+    hipLaunchKernelGGL(wa_cost_ragged_kernel, dim3(max_n, n), dim3(256), 0, ctx.stream, tab_dev, n_align);
+    WLK_HIP(hipGetLastError());
 }
 
 // the launches of find_alignment behind the vocabulary projection, in its order, up to and including `last_stage`

@@ -559,6 +559,40 @@ class HipWindowGroup:
         _lib.check(self.lib.wlk_group_step_pick(self._h, handles, vp(tok), vp(prm), n, vp(out), vp(lp)))
         return out[:n], lp[:n]
 
+    def find_alignment(self, windows: Sequence[tuple], want_cost: bool = False, want_trace: bool = False) -> List[tuple]:
+        """wlk_group_find_alignment: the device half of whisper/timing.py:find_alignment for up to ``rows`` windows in one
+        stacked pass.  ``windows``: (session, tokens, n_sot, eot, num_frames[, qk_scale]) each, ``tokens`` = [sot sequence,
+        <|notimestamps|>, text tokens, <|endoftext|>] and the session encoded.  -> per window (starts [n_text + 1] int32 -
+        the frame at which the path enters each text row, the last one <|endoftext|>'s -, token probabilities [n_text],
+        cost matrix or None, dtw step codes or None).  Afterwards every session needs a new prefill."""
+        n = len(windows)
+        arr = (_lib.AlignWindow * max(n, 1))()
+        keep, out = [], []
+        vp = lambda a: a.ctypes.data_as(C.c_void_p).value
+        for a, win in zip(arr, windows):
+            sess, tokens, n_sot, eot, num_frames = win[:5]
+            toks = np.ascontiguousarray(np.asarray(tokens, dtype=np.int64).reshape(-1))
+            n_text, f = max(len(toks) - int(n_sot) - 2, 0), max(int(num_frames) // 2, 0)
+            starts = np.empty(n_text + 1, np.int32)
+            probs = np.empty(max(n_text, 1), np.float32)
+            cost = np.empty((n_text + 1, f), np.float32) if want_cost else None
+            trace = np.empty((n_text + 2, f + 1), np.int8) if want_trace else None
+            a.s, a.tokens, a.n_tokens, a.n_sot, a.eot, a.num_frames = sess._h, vp(toks), len(toks), int(n_sot), int(eot), int(num_frames)
+            a.qk_scale = float(win[5]) if len(win) > 5 else 1.0
+            a.starts, a.token_probs = vp(starts), vp(probs)
+            a.cost, a.trace = (vp(cost) if want_cost else None), (vp(trace) if want_trace else None)
+            keep.append(toks)
+            out.append((starts, probs[:n_text], cost, trace))
+        _lib.check(self.lib.wlk_group_find_alignment(self._h, arr, n))
+        return out
+
+    def fits(self, n_tokens: int, num_frames: int) -> bool:
+        """wlk_group_align_fits: can a window of ``n_tokens`` tokens (sot sequence, <|notimestamps|>, text, <|endoftext|>) over
+        ``num_frames`` mel frames ride in :meth:`find_alignment`?  A pure host function of the shape and the model."""
+        ok = C.c_int32()
+        _lib.check(self.lib.wlk_group_align_fits(self._h, int(n_tokens), int(num_frames), C.byref(ok)))
+        return bool(ok.value)
+
     def stats(self) -> Dict[str, float]:
         steps, rows = C.c_uint64(), C.c_uint64()
         _lib.check(self.lib.wlk_group_stats(self._h, C.byref(steps), C.byref(rows)))

@@ -19,7 +19,7 @@ from .backend import load_openai_checkpoint
 from .dims import ALIGNMENT_HEADS, MODEL_DIMS
 from .engine import HipWhisperModel
 from .policy import ASRToken
-from .transcribe import resolve_stack, set_stack, transcribe as hip_transcribe
+from .transcribe import resolve_align_stack, resolve_stack, set_align_stack, set_stack, transcribe as hip_transcribe
 
 logger = logging.getLogger(__name__)
 
@@ -30,10 +30,12 @@ class HipWhisperASR:
     def __init__(self, lan: str, model_size: Optional[str] = None, cache_dir: Optional[str] = None,
                  model_dir: Optional[str] = None, lora_path: Optional[str] = None, logfile=sys.stderr, *, device: int = 0,
                  hip_model: Optional[HipWhisperModel] = None, state_dict=None, synthetic_seed: Optional[int] = None,
-                 stack: Optional[int] = None):
+                 stack: Optional[int] = None, align_stack: Optional[bool] = None):
         """``stack``: rows of the model's window group - the greedy temperature-0 steps of up to that many concurrent
         ``transcribe`` calls share each pass over the decoder weights (transcribe.WindowStacker; 0 = off, None = the
-        environment's ``WLK_TRANSCRIBE_STACK``, default off)."""
+        environment's ``WLK_TRANSCRIBE_STACK``, default off).  ``align_stack``: the word-timestamp alignment of those
+        calls' windows shares one stacked pass as well (transcribe.AlignStacker; needs ``stack`` >= 1; None = the
+        environment's ``WLK_TRANSCRIBE_ALIGN_STACK``, default off)."""
         self.logfile = logfile
         self.transcribe_kargs = {}
         self.lora_path = lora_path
@@ -54,6 +56,12 @@ class HipWhisperASR:
         self.stack = resolve_stack(stack)
         if stack is not None:
             set_stack(self.model, self.stack)       # an explicit argument wins over the environment
+        self.align_stack = resolve_align_stack(align_stack)
+        if align_stack is not None:
+            if self.align_stack and self.stack < 1:
+                raise ValueError("align_stack needs stack >= 1: the stacked alignment runs on the window group")
+            set_align_stack(self.model, self.align_stack)
+        self.align_stack = self.align_stack and self.stack >= 1
 
     def load_model(self, model_size=None, cache_dir=None, model_dir=None, *, device: int = 0, state_dict=None,
                    synthetic_seed: Optional[int] = None) -> HipWhisperModel:

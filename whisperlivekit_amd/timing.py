@@ -61,7 +61,7 @@ def dtw(x, device: int = 0) -> np.ndarray:
 # Everything below is integer / float bookkeeping on a few hundred words per window; it stays in Python next to the
 # reference's own.  Pinned by tests/golden/word_timing_kat.json (scripts/gen_golden_word_timing.py runs the reference).
 from dataclasses import dataclass, field  # noqa: E402
-from typing import List, Sequence  # noqa: E402
+from typing import List, Optional, Sequence, Tuple  # noqa: E402
 
 TOKENS_PER_SECOND = 50            # whisper/audio.py: 20 ms per encoder position
 HOP_LENGTH, SAMPLE_RATE = 160, 16000
@@ -124,6 +124,48 @@ def find_alignment(session, tokenizer, text_tokens: Sequence[int], mel, num_fram
     text_indices, time_indices = backtrace(trace)
     words, word_tokens = tokenizer.split_to_word_tokens(text_tokens + [int(tokenizer.eot)])
     return word_timings(text_indices, time_indices, words, word_tokens, probs.tolist())
+
+
+def word_timings_from_starts(starts, words: Sequence[str], word_tokens: Sequence[Sequence[int]],
+                             text_token_probs: Sequence[float]) -> List[WordTiming]:
+    """:func:`word_timings` from what it reads of the path alone: ``starts[i]`` = the frame index at which the path
+    enters text row i (i = 0 .. n_text, the last one <|endoftext|>'s) - ``time_indices[first_of_token]`` of
+    ``backtrace``, as the device's path walk returns it (wlk_group_find_alignment)."""
+    if len(word_tokens) <= 1:
+        return []
+    token_start = np.asarray(starts).astype(np.int64) / TOKENS_PER_SECOND
+    bounds = np.concatenate([[0], np.cumsum([len(t) for t in word_tokens[:-1]])]).astype(np.int64)
+    return [WordTiming(words[w], list(word_tokens[w]), token_start[lo], token_start[hi], np.mean(text_token_probs[lo:hi]))
+            for w, (lo, hi) in enumerate(zip(bounds[:-1], bounds[1:]))]
+
+
+def alignment_tokens(tokenizer, text_tokens: Sequence[int]) -> Tuple[List[int], int]:
+    """-> ([sot sequence, <|notimestamps|>, text tokens, <|endoftext|>], length of the sot sequence): timing.py:175-182"""
+    sot = [int(t) for t in tokenizer.sot_sequence]
+    return [*sot, int(tokenizer.no_timestamps), *[int(t) for t in text_tokens], int(tokenizer.eot)], len(sot)
+
+
+def find_alignment_many(group, items: Sequence[tuple], *, qk_scale: float = 1.0) -> List[List[WordTiming]]:
+    """:func:`find_alignment` for up to ``group.rows`` windows in ONE stacked pass (engine.HipWindowGroup.find_alignment):
+    ``items`` = (session, tokenizer, text_tokens, num_frames) each, every session already encoded and a different one.
+    The path is walked on the device; what comes back per window is one frame number per token and the token
+    probabilities.  -> one WordTiming list per item, equal to ``find_alignment(session, tokenizer, text_tokens, None,
+    num_frames)`` of each."""
+    out: List[Optional[List[WordTiming]]] = [None] * len(items)
+    windows, where = [], []
+    for k, (session, tokenizer, text_tokens, num_frames) in enumerate(items):
+        text_tokens = [int(t) for t in text_tokens]
+        if len(text_tokens) == 0:
+            out[k] = []
+            continue
+        tokens, n_sot = alignment_tokens(tokenizer, text_tokens)
+        windows.append((session, tokens, n_sot, int(tokenizer.eot), int(num_frames), float(qk_scale)))
+        where.append((k, tokenizer, text_tokens))
+    if windows:
+        for (k, tokenizer, text_tokens), (starts, probs, _c, _t) in zip(where, group.find_alignment(windows)):
+            words, word_tokens = tokenizer.split_to_word_tokens(text_tokens + [int(tokenizer.eot)])
+            out[k] = word_timings_from_starts(starts, words, word_tokens, probs.tolist())
+    return out
 
 
 def merge_punctuations(alignment: List[WordTiming], prepended: str = PREPEND_PUNCTUATIONS,

@@ -12,7 +12,10 @@ of masked fills and one log-softmax over the vocabulary row the step produced; t
 applies them on the device (``wlk_pick_greedy``), and so does beam search with 2-7 beams under WLK_TRANSCRIBE_DEVICE_BEAM=1
 (``wlk_pick_topk``, with single-token steps over the KV ancestry table: ``wlk_decode_ancestry``).  With WLK_TRANSCRIBE_STACK=n
 (or ``HipWhisperASR(stack=n)``; off by default) the greedy temperature-0 steps of up to n concurrent windows of one model
-ride in one launch chain per token (``WindowStacker`` / ``decode_many`` over ``wlk_group_step_pick``).  There is no CPU model path: without the library / a GPU the first call raises.
+ride in one launch chain per token (``WindowStacker`` / ``decode_many`` over ``wlk_group_step_pick``); with
+WLK_TRANSCRIBE_ALIGN_STACK=1 on top of it (or ``HipWhisperASR(stack=n, align_stack=True)``; off by default) the word alignment of
+the windows those calls have waiting shares one stacked pass as well (``AlignStacker`` over ``wlk_group_find_alignment``).
+There is no CPU model path: without the library / a GPU the first call raises.
 
 Same keyword names, defaults and result dictionary as the reference; ``fp16`` is accepted and ignored (the path computes
 in fp32, as the reference does on its CPU).  Decoding a file name (ffmpeg) is outside the path: ``audio`` is samples.
@@ -221,32 +224,21 @@ def _refused(error: BaseException) -> bool:
     return getattr(error, "code", None) in (-1, -3)
 
 
-class WindowStacker:
-    """Thread-safe front of one ``HipWindowGroup``, modelled on ``translation.NllbStacker``: any thread hands its greedy
-    window to :meth:`run`; the first caller becomes the runner and advances every window in flight with one
-    ``step_pick`` per token, callers that arrive while a pass is running queue their windows - the runner admits them at
-    its next step, up to the group's rows - and wait on a condition.  A window leaves at its end, the others go on; the
-    runner keeps running until nothing is in flight or queued.  A window the group refuses on the host (context full, no
-    rules, ...) fails alone: the refused call advanced nobody, so the others take that step without it.  A pass that fails
-    otherwise hands its error to every window in flight or queued, so no waiter blocks for ever, and the next caller
-    starts a fresh pass.
+class _StackerFront:
+    """The thread-safe queue in front of one ``HipWindowGroup``, modelled on ``translation.NllbStacker`` and shared by
+    :class:`WindowStacker` and :class:`AlignStacker`: any thread hands its items to :meth:`run_many`; the first caller
+    becomes the runner and calls ``_advance`` on everything in flight until nothing is in flight or queued, callers that
+    arrive while a pass is running queue their items - the runner admits them before its next ``_advance``, up to the
+    group's rows - and wait on a condition.  ``_advance(live) -> still live`` settles each item that is over (or failed
+    alone) with :meth:`_settle`.  A pass that raises hands its error to every item in flight or queued, so no waiter
+    blocks for ever, and the next caller starts a fresh pass."""
 
-    ``solo_single``: while ONE window is in flight it takes the session's own step (``decode`` + ``pick_greedy``, a graph
-    replay with the one-row folds) instead of a one-row group step, which measured 10 % slower (DESIGN 26); the two give
-    the same token and the same log-probability bits on every input the tests step."""
-
-    def __init__(self, model, rows: int = 8, group=None, solo_single: bool = True):
+    def __init__(self, rows: int):
         if not 1 <= int(rows) <= 8:
             raise ValueError("a window stacker has 1..8 rows")
         self.rows = int(rows)
-        if group is None:
-            from .engine import HipWindowGroup
-            group = HipWindowGroup(model, self.rows)
-        self.group = group
-        self.solo_single = bool(solo_single)
-        self.solo_steps = 0
         self._cv = threading.Condition()
-        self._queue: List[Tuple[int, _GreedyWindow]] = []     # (ticket, window) not yet admitted
+        self._queue: List[Tuple[int, object]] = []            # (ticket, item) not yet admitted
         self._open: set = set()                               # tickets queued or in flight
         self._outcome: dict = {}                              # ticket -> error or None
         self._running = False
@@ -254,11 +246,10 @@ class WindowStacker:
         self.passes = 0
         self.windows = 0
 
-    def run(self, window: _GreedyWindow) -> None:
-        """Advances ``window`` to its end (its tokens and sum are updated in place); raises what stopped it."""
-        self.run_many([window])
+    def _advance(self, live: list) -> list:
+        raise NotImplementedError
 
-    def run_many(self, windows: Sequence[_GreedyWindow]) -> None:
+    def run_many(self, windows: Sequence) -> None:
         if not windows:
             return
         with self._cv:
@@ -285,6 +276,60 @@ class WindowStacker:
             self._open.discard(ticket)
             self.windows += 1
             self._cv.notify_all()
+
+    def _run(self) -> None:
+        error: Optional[BaseException] = None
+        live: list = []
+        try:
+            while True:
+                with self._cv:
+                    while self._queue and len(live) < self.rows:
+                        live.append(self._queue.pop(0))
+                if not live:
+                    break
+                live = self._advance(live)
+        except BaseException as e:                 # the pass is gone: everyone in it or queued behind it gets the error
+            error = e
+        finally:
+            with self._cv:
+                self.passes += 1
+                if error is not None:
+                    for t in self._open:
+                        self._outcome[t] = error
+                    self._open.clear()
+                    self._queue = []
+                self._running = False
+                self._cv.notify_all()
+        if error is not None and not isinstance(error, Exception):
+            raise error
+
+
+class WindowStacker(_StackerFront):
+    """Thread-safe front of one ``HipWindowGroup`` for the greedy steps (the queue: :class:`_StackerFront`): any thread
+    hands its greedy window to :meth:`run`; the runner advances every window in flight with one ``step_pick`` per token
+    and admits queued windows at its next step.  A window leaves at its end, the others go on.  A window the group refuses
+    on the host (context full, no rules, ...) fails alone: the refused call advanced nobody, so the others take that step
+    without it.
+
+    ``solo_single``: while ONE window is in flight it takes the session's own step (``decode`` + ``pick_greedy``, a graph
+    replay with the one-row folds) instead of a one-row group step, which measured 10 % slower (DESIGN 26); the two give
+    the same token and the same log-probability bits on every input the tests step."""
+
+    def __init__(self, model, rows: int = 8, group=None, solo_single: bool = True):
+        super().__init__(rows)
+        if group is None:
+            from .engine import HipWindowGroup
+            group = HipWindowGroup(model, self.rows)
+        self.group = group
+        self.solo_single = bool(solo_single)
+        self.solo_steps = 0
+
+    def run(self, window: _GreedyWindow) -> None:
+        """Advances ``window`` to its end (its tokens and sum are updated in place); raises what stopped it."""
+        self.run_many([window])
+
+    def _advance(self, live):
+        return self._step(live)
 
     def _step(self, live: List[Tuple[int, _GreedyWindow]]) -> List[Tuple[int, _GreedyWindow]]:
         """one token for every window in `live`; -> the windows still in flight"""
@@ -326,32 +371,6 @@ class WindowStacker:
             return True
         return False
 
-    def _run(self) -> None:
-        error: Optional[BaseException] = None
-        live: List[Tuple[int, _GreedyWindow]] = []
-        try:
-            while True:
-                with self._cv:
-                    while self._queue and len(live) < self.rows:
-                        live.append(self._queue.pop(0))
-                if not live:
-                    break
-                live = self._step(live)
-        except BaseException as e:                 # the pass is gone: everyone in it or queued behind it gets the error
-            error = e
-        finally:
-            with self._cv:
-                self.passes += 1
-                if error is not None:
-                    for t in self._open:
-                        self._outcome[t] = error
-                    self._open.clear()
-                    self._queue = []
-                self._running = False
-                self._cv.notify_all()
-        if error is not None and not isinstance(error, Exception):
-            raise error
-
     def stats(self) -> dict:
         """the group's steps and rows so far, and this front's passes, windows and solo steps"""
         return dict(self.group.stats(), passes=self.passes, windows=self.windows, solo_steps=self.solo_steps)
@@ -388,6 +407,134 @@ def _run_stacker(model) -> Optional[WindowStacker]:
     if rows is None:
         rows = resolve_stack(None)
     return window_stacker(model, rows) if rows > 0 else None
+
+
+# ---- stacked word alignment (opt-in; wlk_group_find_alignment) --------------------------------------------------------------
+class _AlignWindow:
+    """One window's word-alignment request: the encoded 1-row session, what :func:`timing.find_alignment` takes, and the
+    WordTiming list once it is served."""
+
+    def __init__(self, session, tokenizer, text_tokens: Sequence[int], num_frames: int):
+        self.session, self.tokenizer = session, tokenizer
+        self.text_tokens, self.num_frames = [int(t) for t in text_tokens], int(num_frames)
+        self.result: Optional[list] = None
+
+    def item(self) -> tuple:
+        return (self.session, self.tokenizer, self.text_tokens, self.num_frames)
+
+
+class AlignStacker(_StackerFront):
+    """Thread-safe front of ``HipWindowGroup.find_alignment`` (the queue: :class:`_StackerFront`): any thread hands its
+    window's alignment to :meth:`align`; the first caller drives, everything queued at that moment - up to the group's
+    rows - is aligned by ONE stacked pass, windows that arrive during a pass ride the next one.  A window the group refuses
+    on the host fails alone - the refused call touched nobody - and is then aligned by the solo ``timing.find_alignment``;
+    the others go through without it.  A pass that fails otherwise hands its error to everyone in flight or queued.
+
+    ``solo_single``: a window that is alone in its pass takes the solo ``timing.find_alignment`` instead of a group of
+    one (DESIGN 27 says which was measured faster); both give the same words."""
+
+    def __init__(self, model, rows: int = 8, group=None, solo_single: bool = False):
+        super().__init__(rows)
+        if group is None:
+            from .engine import HipWindowGroup
+            group = HipWindowGroup(model, self.rows)
+        self.group = group
+        self.solo_single = bool(solo_single)
+        self.group_passes = 0          # stacked passes, and the windows they served
+        self.stacked = 0
+        self.solo = 0                  # windows served by the solo call (refused by the group, or alone with solo_single)
+
+    def align(self, session, tokenizer, text_tokens: Sequence[int], num_frames: int) -> list:
+        """-> the WordTiming list ``timing.find_alignment(session, tokenizer, text_tokens, None, num_frames)`` returns"""
+        window = _AlignWindow(session, tokenizer, text_tokens, num_frames)
+        self.run_many([window])
+        return window.result
+
+    def _solo(self, ticket: int, w: _AlignWindow) -> None:
+        try:                                       # whatever stops a window on its own chain is that window's own error
+            w.result = T.find_alignment(*w.item()[:3], None, w.num_frames)
+            self.solo += 1
+        except Exception as e:
+            self._settle(ticket, e)
+        else:
+            self._settle(ticket, None)
+
+    def _pass(self, part: list) -> None:
+        results = T.find_alignment_many(self.group, [w.item() for _t, w in part])
+        self.group_passes += 1
+        self.stacked += len(part)
+        for (t, w), res in zip(part, results):
+            w.result = res
+            self._settle(t, None)
+
+    def _advance(self, live: list) -> list:
+        if len(live) == 1 and self.solo_single:
+            self._solo(*live[0])
+            return []
+        try:
+            self._pass(live)
+            return []
+        except Exception as e:
+            if not _refused(e):
+                raise
+        for item in live:                          # the refused call touched nobody: every window on its own
+            try:
+                self._pass([item])
+            except Exception as e:
+                if not _refused(e):
+                    raise
+                self._solo(*item)
+        return []
+
+    def stats(self) -> dict:
+        """this front's drives and windows, the stacked passes with the windows they served, the solo windows"""
+        return dict(passes=self.passes, windows=self.windows, group_passes=self.group_passes, stacked=self.stacked,
+                    solo=self.solo, mean_windows_per_pass=round(self.stacked / self.group_passes, 3) if self.group_passes else None)
+
+
+def resolve_align_stack(flag: Optional[bool]) -> bool:
+    """``HipWhisperASR(align_stack=...)`` / :func:`set_align_stack`: an explicit value wins; ``None`` reads
+    ``WLK_TRANSCRIBE_ALIGN_STACK`` (default off)."""
+    if flag is None:
+        return os.environ.get("WLK_TRANSCRIBE_ALIGN_STACK", "0").strip().lower() in ("1", "true", "on", "yes")
+    return bool(flag)
+
+
+def set_align_stack(model, flag: Optional[bool]) -> bool:
+    """Switches the stacked word alignment of ``model`` on or off; ``None`` leaves it to ``WLK_TRANSCRIBE_ALIGN_STACK``.
+    It only acts while the stacked windows are on as well (:func:`set_stack` / ``WLK_TRANSCRIBE_STACK`` >= 1).  -> the
+    resolved value."""
+    on = resolve_align_stack(flag)
+    with _STACK_LOCK:
+        if flag is None:
+            model.__dict__.pop("_align_stack", None)
+        else:
+            model.__dict__["_align_stack"] = on
+    return on
+
+
+def align_stacker(model) -> Optional[AlignStacker]:
+    """The model's alignment stacker, if one was ever constructed (never creates)."""
+    with _STACK_LOCK:
+        return model.__dict__.get("_align_stacker")
+
+
+def _align_stacker(model) -> Optional[AlignStacker]:
+    """What `_add_word_timestamps` sends a window's alignment through: the model's alignment stacker - over the
+    :class:`WindowStacker`'s group - when both switches are on, otherwise None, and then nothing is constructed."""
+    on = model.__dict__.get("_align_stack")
+    if on is None:
+        on = resolve_align_stack(None)
+    if not on:
+        return None
+    windows = _run_stacker(model)
+    if windows is None:
+        return None
+    with _STACK_LOCK:
+        st = model.__dict__.get("_align_stacker")
+        if st is None:
+            st = model.__dict__["_align_stacker"] = AlignStacker(model, windows.rows, group=windows.group)
+        return st
 
 
 def _tokenizer_for(model: HipWhisperModel, language: Optional[str], task: Optional[str]) -> WhisperTokenizer:
@@ -999,7 +1146,11 @@ def _add_word_timestamps(segments: List[dict], encoded: Optional[HipSession], mo
         encoded = _rows_of(model).get(1)
         alignment = T.find_alignment(encoded, tokenizer, text_tokens, mel_segment, num_frames)
     else:                                         # the 1-row session still holds this window's encoder output
-        alignment = T.find_alignment(encoded, tokenizer, text_tokens, None, num_frames)
+        stacker = _align_stacker(model) if text_tokens else None
+        if stacker is not None and stacker.group.fits(len(tokenizer.sot_sequence) + 2 + len(text_tokens), num_frames):
+            alignment = stacker.align(encoded, tokenizer, text_tokens, num_frames)      # beside the other calls' windows
+        else:
+            alignment = T.find_alignment(encoded, tokenizer, text_tokens, None, num_frames)
     T.attach_words(segments, alignment, per_segment, last_speech_timestamp=last_speech_timestamp,
                    prepend_punctuations=prepend, append_punctuations=append)
 
