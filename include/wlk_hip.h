@@ -152,7 +152,23 @@ int wlk_group_create(wlk_model* m, int max_rows /* 1..8 */, wlk_group** out);
 int wlk_group_destroy(wlk_group* g);   /* before the model */
 int wlk_group_step_pick(wlk_group* g, wlk_session* const* sessions, const int64_t* tokens /* [n] */,
                         const wlk_pick_params* p /* [n] */, int n, int32_t* tokens_out /* [n] */, float* logprobs_out /* [n] */);
-int wlk_group_stats(wlk_group* g, uint64_t* steps, uint64_t* rows);   /* completed steps, and rows summed over them */
+/* wlk_group_run_pick (opt-in): up to `burst` (1..16) such steps of every row behind ONE call - one upload, `burst`
+ *   launch chains back to back with a one-wave kernel between them that derives each row's next step from its pick on the
+ *   device (the next position and alignment-window row, the next ts_mode / ts_bound, first_step = 0), one read-back, one
+ *   synchronisation.  Row r feeds tokens[r], then its own picks, for at most min(max_steps[r], burst, n_text_ctx - self_len)
+ *   steps, and stops early after the step that picks p[r].eot.  steps_out[r] (>= 1) is the number of steps it took;
+ *   tokens_out[r][0 .. steps - 1] and logprobs_out[r][0 .. steps - 1] are what that many successive wlk_group_step_pick calls
+ *   return, bit for bit; entries at index >= steps are left as the caller passed them.  Afterwards every session is as
+ *   after steps_out[r] single steps.  A row that has ended repeats its last step in the remaining chains, which rewrites
+ *   the values already there.  The host checks are wlk_group_step_pick's, plus WLK_ERR_ARG for burst outside 1..16 and for
+ *   a max_steps[r] < 1; a refused call has launched nothing and advanced nobody.  wlk_group_step_pick is the one-step
+ *   case of the same routine. */
+int wlk_group_run_pick(wlk_group* g, wlk_session* const* sessions, const int64_t* tokens /* [n] */,
+                       const wlk_pick_params* p /* [n] */, const int32_t* max_steps /* [n], >= 1 */, int n, int burst /* 1..16 */,
+                       int32_t* tokens_out /* [n][burst] */, float* logprobs_out /* [n][burst] */, int32_t* steps_out /* [n] */);
+/* steps: launch chains enqueued; rows: row-steps actually taken (wlk_group_run_pick: chains x rows minus rows is what rows
+ * that had ended took up) */
+int wlk_group_stats(wlk_group* g, uint64_t* steps, uint64_t* rows);
 /* tests: the logits row [n_vocab] of slot `row` of the last completed step (WLK_ERR_STATE: no such row) */
 int wlk_group_export_logits(wlk_group* g, int row, float* host, uint64_t capacity, uint64_t* n_written);
 /* Stacked word alignment (opt-in): what wlk_find_alignment computes for up to max_rows windows of DIFFERENT
@@ -199,6 +215,9 @@ int wlk_diag_dtw_starts(const float* costs, const int64_t* offsets, const int32_
  * masks[mask_of_row[r]] and p[r]; n in 1..8.  Synchronous. */
 int wlk_diag_pick_rows(const float* logits_host, int n_vocab, const uint8_t* masks_host, int n_masks, const int32_t* mask_of_row,
                        const wlk_pick_params* p /* [n] */, int n, int32_t* tokens_out, float* logprobs_out);
+/* Diagnostic (tests): the device form of the rule transition of wlk_group_run_pick alone - out[i] = the parameter block of
+ * the step after tokens[i] was picked under p[i].  Needs no model; any n >= 1.  Synchronous. */
+int wlk_diag_pick_advance(const wlk_pick_params* p /* [n] */, const int32_t* tokens /* [n] */, int n, wlk_pick_params* out /* [n] */);
 
 /* a6+a7+a8 in one launch group and ONE readback:
  *  - logits[row, ids[i]] += deltas[i] (-inf suppresses: SuppressTokens.apply whisper/decoding.py:427-432,

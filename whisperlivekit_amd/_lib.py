@@ -234,6 +234,8 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_group_create": (cint, [p, cint, C.POINTER(p)]),
         "wlk_group_destroy": (cint, [p]),
         "wlk_group_step_pick": (cint, [p, C.POINTER(p), p, p, cint, p, p]),
+        "wlk_group_run_pick": (cint, [p, C.POINTER(p), p, p, p, cint, cint, p, p, p]),
+        "wlk_diag_pick_advance": (cint, [p, p, cint, p]),
         "wlk_group_stats": (cint, [p, C.POINTER(u64), C.POINTER(u64)]),
         "wlk_group_export_logits": (cint, [p, cint, p, u64, C.POINTER(u64)]),
         "wlk_diag_pick_rows": (cint, [p, cint, p, cint, p, p, cint, p, p]),
@@ -437,6 +439,7 @@ EXPORTED_SYMBOLS = (
     "wlk_group_create", "wlk_group_destroy", "wlk_group_step_pick", "wlk_group_stats", "wlk_group_export_logits",
     "wlk_diag_pick_rows",
     "wlk_group_find_alignment", "wlk_group_align_fits", "wlk_diag_dtw_starts",
+    "wlk_group_run_pick", "wlk_diag_pick_advance",
 )
 
 

@@ -96,6 +96,22 @@ struct StepRow {
     int prefill_rows, n_single, newest_row, content_len;   // AlignArgs of this row's read-out
     int pad;
 };
+// The scalars of the StepRow of the single-token step a beam-1 session is about to take, from its counters before that step
+// (n_steps >= 1 steps since the window opened, the prefill included; self_len cached positions).  The one statement of
+// the arithmetic: the host derives a row from a session with it (internal.h: next_step_row) and the window group's advance
+// kernel derives the next row from the previous one on the device (window_group.hip).  The pointers of `r` are left alone.
+__host__ __device__ inline void step_row_scalars(StepRow& r, int n_steps, int self_len, int prefill_rows, int n_text_ctx,
+                                                 int token, int content_len) {
+    const int after = n_steps + 1;
+    r.token = token;
+    r.offset = self_len;
+    r.ring_row = n_text_ctx + ((n_steps - 1) % kAlignWindow);
+    r.prefill_rows = after <= kAlignWindow ? prefill_rows : 0;
+    r.n_single = after - 1 < kAlignWindow ? after - 1 : kAlignWindow;
+    r.newest_row = n_text_ctx + ((after - 2) % kAlignWindow);
+    r.content_len = content_len;
+    r.pad = 0;
+}
 
 // ---- single-token step of one beam-1 session as ONE graph replay (api.hip: wlk_step_select) -----------
 // The host writes a StepBlock into pinned (host-coherent) memory and replays the graph; the graph's first kernel reads
@@ -664,6 +680,24 @@ void launch_token_prob(const LaunchCtx& ctx, const float* logits, int n_vocab, i
 struct PickRules {
     int first_step, without_timestamps, timestamp_begin, eot, no_timestamps, ts_mode, ts_bound, max_initial;
 };
+// The rule state of the step after `token` was picked under `p`: what transcribe._pick_states derives from the sampled
+// history, as a function of the previous state and the pick alone (window_group.hip advances a row's rules on the device
+// with it).  The last timestamp of the history is recovered from the old state: ts_bound itself when the last token opened
+// a pair (ts_mode 2), ts_bound - 1 when there is a bound at all, none otherwise.
+__host__ __device__ inline PickRules pick_rules_advance(const PickRules& p, int token) {
+    const int tb = p.timestamp_begin;
+    const bool last_ts = token >= tb;
+    const bool before_last_ts = p.first_step ? true : p.ts_mode != 0;
+    const bool had_stamp = p.ts_mode == 2 || p.ts_bound > tb;
+    const int old_stamp = p.ts_mode == 2 ? p.ts_bound : p.ts_bound - 1;
+    const bool has_stamp = last_ts || had_stamp;
+    const int stamp = last_ts ? token : old_stamp;
+    PickRules q = p;
+    q.first_step = 0;
+    q.ts_mode = !last_ts ? 0 : (before_last_ts ? 1 : 2);
+    q.ts_bound = !has_stamp ? tb : (q.ts_mode == 2 ? stamp : stamp + 1);
+    return q;
+}
 void launch_rules_pick(const LaunchCtx& ctx, const float* logits, int n_vocab, const unsigned char* mask, const PickRules& p,
                        int* out_token, float* out_logprob);
 // the same rules for up to 8 rows with a history each, and the k <= 8 best log-probabilities / ids of every row ([n_rows][k])

@@ -292,21 +292,12 @@ struct wlk_session {
 // cross K|V, alignment window, and the window scalars after this step.  The one place they are derived: the solo step
 // (wlk_step_select) and the engine's batched steps must stay decision-identical.
 inline wlk::StepRow next_step_row(const wlk_session* s, int token, int content_len) {
-    const int ctx_len = s->m->D.n_text_ctx;
-    const int after = s->n_steps + 1;
     wlk::StepRow r;
     r.kcache = s->kcache[s->kv_cur];
     r.vcache = s->vcache[s->kv_cur];
     r.cross_kv = s->cross_kv;
     r.ring = s->ring;
-    r.token = token;
-    r.offset = s->self_len;
-    r.ring_row = ctx_len + ((s->n_steps - 1) % wlk::kAlignWindow);
-    r.prefill_rows = after <= wlk::kAlignWindow ? s->prefill_rows : 0;
-    r.n_single = std::min(after - 1, wlk::kAlignWindow);
-    r.newest_row = ctx_len + ((after - 2) % wlk::kAlignWindow);
-    r.content_len = content_len;
-    r.pad = 0;
+    wlk::step_row_scalars(r, s->n_steps, s->self_len, s->prefill_rows, s->m->D.n_text_ctx, token, content_len);
     return r;
 }
 

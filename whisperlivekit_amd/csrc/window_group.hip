@@ -10,6 +10,11 @@
 // per token for all rows, no thread, no wait on host-coherent flags and no graph inside the library (the chain as one graph
 // replay per row count was measured and did not pay: DESIGN 26).
 //
+// wlk_group_run_pick takes up to 16 such steps behind one call: everything the next step needs from the host - the
+// next StepRow, the next rule state, whether the row goes on - is a pure function of the previous pick, so a one-wave kernel
+// (group_advance_rows_kernel) derives it on the device between two chains.  The host enqueues `burst` chains back to back,
+// reads the picks and the per-row step counts back once and synchronises once.  wlk_group_step_pick is its one-step case.
+//
 // The layer chain restates wlk_engine::enqueue_decoder (engine.hip) with one difference: the cross-attention's query
 // projection is the multi-row GEMV for EVERY row count, also for one row (the engine folds it into the attention kernel
 // there).  A row therefore goes through the same kernels whether it steps alone or beside seven others.
@@ -34,11 +39,67 @@ using namespace wlk;
 
 namespace {
 constexpr int kGroupMaxRows = 8;
-// what one step uploads, in one copy: the row table the layer kernels index and the rule table of the pick
+constexpr int kGroupMaxBurst = 16;
+// a row's state across the chains of one call (wlk_group_run_pick), advanced on the device
+struct BurstRow {
+    int alive;                             // the row takes the next chain as a step of its own
+    int taken;                             // own steps so far in this call
+    int limit;                             // own steps at most: min(max_steps, burst, free text positions)
+    int n_steps, self_len, prefill_rows;   // the session's counters before the row's next own step (step_row_scalars)
+};
+// what one call uploads, in one copy: the row table the layer kernels index, the rule table of the pick and - for a call of
+// more than one chain - the burst records
 struct GroupBlock {
     StepRow rows[kGroupMaxRows];
     PickRowEntry pick[kGroupMaxRows];
+    BurstRow burst[kGroupMaxRows];
 };
+// what a call of more than one chain reads back, in one copy
+struct GroupResults {
+    int picks[kGroupMaxRows][kGroupMaxBurst][2];   // [row][own step][token | log-probability bits]
+    int taken[kGroupMaxRows];                      // own steps of every row
+};
+
+// Between two chains of a call: one wave, lane r = row r.  A live row's pick goes to its next result slot; unless that pick
+// was <|endoftext|> or the row's last allowed step, its StepRow and rule state become those of its next step.
+// A row that has ended is left untouched, and so is its table entry: in the remaining chains of the call it REPEATS its last
+// step - the same token at the same offset, into the same cache slot and the same alignment-window row.  Every kernel of
+// the chain is a deterministic function of its row's inputs, and a step reads the cache positions below its offset and
+// writes the one at it, so the repeat rewrites the values that are already there (the argument of the padded tile rows of
+// wlk_prefill_group).  A dead row therefore needs no guard in any layer kernel, its logits row
+// (wlk_group_export_logits) and its pick slot keep showing its last own step, and nothing its session owns differs from
+// what `taken` single steps leave.
+__global__ __launch_bounds__(64) void group_advance_rows_kernel(GroupBlock* __restrict__ blk, const int* __restrict__ pick,
+                                                                 GroupResults* __restrict__ res, int n, int n_text_ctx) {
+    const int r = threadIdx.x;
+    if (r >= n || r >= kGroupMaxRows) return;
+    BurstRow b = blk->burst[r];
+    if (!b.alive || b.taken < 0 || b.taken >= kGroupMaxBurst) return;
+    const int token = pick[2 * r];
+    res->picks[r][b.taken][0] = token;
+    res->picks[r][b.taken][1] = pick[2 * r + 1];
+    b.taken += 1;
+    res->taken[r] = b.taken;
+    const PickRules p = blk->pick[r].p;
+    if (token == p.eot || b.taken >= b.limit) {
+        b.alive = 0;
+    } else {
+        b.n_steps += 1;
+        b.self_len += 1;
+        StepRow row = blk->rows[r];
+        step_row_scalars(row, b.n_steps, b.self_len, b.prefill_rows, n_text_ctx, token, row.content_len);
+        blk->rows[r] = row;
+        blk->pick[r].p = pick_rules_advance(p, token);
+    }
+    blk->burst[r] = b;
+}
+
+// wlk_diag_pick_advance: pick_rules_advance alone
+__global__ __launch_bounds__(256) void pick_advance_kernel(const PickRules* __restrict__ in, const int* __restrict__ tokens, int n,
+                                                            PickRules* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = pick_rules_advance(in[i], tokens[i]);
+}
 }  // namespace
 
 struct wlk_group {
@@ -48,7 +109,8 @@ struct wlk_group {
     float *x = nullptr, *qkv = nullptr, *att = nullptr, *q = nullptr, *mlp = nullptr, *logits = nullptr, *xsplit = nullptr;
     GroupBlock* blk_dev = nullptr;
     int* pick_dev = nullptr;             // [R][token | log-probability]
-    char* pinned = nullptr;              // [GroupBlock | R x 8 bytes of results]
+    GroupResults* results_dev = nullptr; // a call of more than one chain: every row's picks and step count
+    char* pinned = nullptr;              // [GroupBlock | GroupResults (a one-chain call: R x 8 bytes of it)]
     hipEvent_t joined[kGroupMaxRows] = {};
     int last_rows = 0;                   // rows of the last completed step (wlk_group_export_logits)
     uint64_t n_steps = 0, n_rows = 0;
@@ -69,6 +131,7 @@ struct wlk_group {
             if (p) (void)hipFree(p);
         if (blk_dev) (void)hipFree(blk_dev);
         if (pick_dev) (void)hipFree(pick_dev);
+        if (results_dev) (void)hipFree(results_dev);
         if (pinned) (void)hipHostFree(pinned);
         if (align_ready) wlk_prefill_ws_free(align_ws);
         if (align_buf) (void)hipFree(align_buf);
@@ -80,6 +143,8 @@ struct wlk_group {
     }
 
     void enqueue_step(int R);
+    int run_pick(wlk_session* const* sessions, const int64_t* tokens, const wlk_pick_params* p, const int32_t* max_steps, int n,
+                 int burst, int32_t* tokens_out, float* logprobs_out, int32_t* steps_out);
 };
 
 // embed .. logits of R rows + every row's pick: wlk_engine::enqueue_decoder's operators in its order (see the file comment)
@@ -173,7 +238,9 @@ int wlk_group_create(wlk_model* m, int max_rows, wlk_group** out) {
         g->xsplit = dev_alloc<float>(cross_split_scratch_floats(8, D.n_text_head, (int)T));
         g->blk_dev = reinterpret_cast<GroupBlock*>(dev_alloc<char>(sizeof(GroupBlock)));
         g->pick_dev = dev_alloc<int>(2 * R);
-        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&g->pinned), sizeof(GroupBlock) + 8 * R, hipHostMallocDefault));
+        g->results_dev = reinterpret_cast<GroupResults*>(dev_alloc<char>(sizeof(GroupResults)));
+        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&g->pinned), sizeof(GroupBlock) + sizeof(GroupResults), hipHostMallocDefault));
+        std::memset(g->pinned, 0, sizeof(GroupBlock) + sizeof(GroupResults));
         for (hipEvent_t& e : g->joined) WLK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         *out = g.release();
         return WLK_OK;
@@ -188,7 +255,26 @@ int wlk_group_destroy(wlk_group* g) {
 int wlk_group_step_pick(wlk_group* g, wlk_session* const* sessions, const int64_t* tokens, const wlk_pick_params* p, int n,
                         int32_t* tokens_out, float* logprobs_out) {
     if (!g || !sessions || !tokens || !p || !tokens_out || !logprobs_out) return fail(WLK_ERR_ARG, "NULL argument");
+    return g->run_pick(sessions, tokens, p, nullptr, n, 1, tokens_out, logprobs_out, nullptr);
+}
+
+int wlk_group_run_pick(wlk_group* g, wlk_session* const* sessions, const int64_t* tokens, const wlk_pick_params* p,
+                       const int32_t* max_steps, int n, int burst, int32_t* tokens_out, float* logprobs_out, int32_t* steps_out) {
+    if (!g || !sessions || !tokens || !p || !max_steps || !tokens_out || !logprobs_out || !steps_out)
+        return fail(WLK_ERR_ARG, "NULL argument");
+    return g->run_pick(sessions, tokens, p, max_steps, n, burst, tokens_out, logprobs_out, steps_out);
+}
+
+}  // extern "C"
+
+// Up to `burst` single-token steps of n sessions behind one upload, one read-back and one synchronisation: the body of
+// wlk_group_step_pick (max_steps == nullptr: one step of every row, results [n]) and of wlk_group_run_pick (results
+// [n][burst], entries behind a row's last own step untouched).
+int wlk_group::run_pick(wlk_session* const* sessions, const int64_t* tokens, const wlk_pick_params* p, const int32_t* max_steps,
+                        int n, int burst, int32_t* tokens_out, float* logprobs_out, int32_t* steps_out) {
+    wlk_group* g = this;
     if (n < 1 || n > g->max_rows) return fail(WLK_ERR_ARG, "window group: 1..max_rows sessions per step");
+    if (burst < 1 || burst > kGroupMaxBurst) return fail(WLK_ERR_ARG, "window group: 1..16 steps per call");
     const wlk_dims& D = g->m->D;
     // every session is checked on the host before anything is launched: a refused call has advanced nobody
     for (int r = 0; r < n; ++r) {
@@ -200,6 +286,7 @@ int wlk_group_step_pick(wlk_group* g, wlk_session* const* sessions, const int64_
         if (s->beam != 1) return fail(WLK_ERR_ARG, "window group: only sessions of one row");
         if (tokens[r] < 0 || tokens[r] >= D.n_vocab) return fail(WLK_ERR_ARG, "token id out of range");
         if (!pick_params_ok(p[r], D.n_vocab)) return fail(WLK_ERR_ARG, "rule parameters out of range");
+        if (max_steps && max_steps[r] < 1) return fail(WLK_ERR_ARG, "window group: a row's step budget is at least 1");
         if (s->engine) return fail(WLK_ERR_STATE, "window group: the session is attached to the batch engine (its steps belong to the engine's loops)");
         if (!s->encoded || s->n_steps < 1) return fail(WLK_ERR_STATE, "window group: step before the session's prefill");
         if (!s->rules_mask) return fail(WLK_ERR_STATE, "window group: step before wlk_rules_set");
@@ -209,38 +296,68 @@ int wlk_group_step_pick(wlk_group* g, wlk_session* const* sessions, const int64_
         std::lock_guard<std::mutex> lk(g->mu);
         WLK_HIP(hipSetDevice(g->m->device));
         GroupBlock* blk = reinterpret_cast<GroupBlock*>(g->pinned);
-        int* res = reinterpret_cast<int*>(g->pinned + sizeof(GroupBlock));
+        GroupResults* res = reinterpret_cast<GroupResults*>(g->pinned + sizeof(GroupBlock));
         for (int r = 0; r < n; ++r) {
             wlk_session* s = sessions[r];
             blk->rows[r] = next_step_row(s, (int)tokens[r], D.n_audio_ctx);
             blk->pick[r] = PickRowEntry{s->rules_mask, pick_rules_of(p[r])};
+            const int limit = std::min(std::min(max_steps ? (int)max_steps[r] : 1, burst), (int)D.n_text_ctx - s->self_len);
+            blk->burst[r] = BurstRow{1, 0, limit, s->n_steps, s->self_len, s->prefill_rows};
             // encode, prefill and an earlier step of the session's own chain have finished before this stream touches its caches
             WLK_HIP(hipEventRecord(g->joined[r], s->stream));
             WLK_HIP(hipStreamWaitEvent(g->stream, g->joined[r], 0));
         }
-        const size_t up = offsetof(GroupBlock, pick) + (size_t)n * sizeof(PickRowEntry);
-        WLK_HIP(hipMemcpyAsync(g->blk_dev, blk, up, hipMemcpyHostToDevice, g->stream));
-        g->enqueue_step(n);
-        WLK_HIP(hipMemcpyAsync(res, g->pick_dev, (size_t)8 * n, hipMemcpyDeviceToHost, g->stream));
-        WLK_HIP(hipStreamSynchronize(g->stream));
+        uint64_t rows_taken = 0;
+        if (burst == 1) {
+            // one chain: the pick slots are the results and nothing has to be advanced on the device
+            const size_t up = offsetof(GroupBlock, pick) + (size_t)n * sizeof(PickRowEntry);
+            WLK_HIP(hipMemcpyAsync(g->blk_dev, blk, up, hipMemcpyHostToDevice, g->stream));
+            g->enqueue_step(n);
+            WLK_HIP(hipMemcpyAsync(res->picks, g->pick_dev, (size_t)8 * n, hipMemcpyDeviceToHost, g->stream));
+            WLK_HIP(hipStreamSynchronize(g->stream));
+        } else {
+            const size_t up = offsetof(GroupBlock, burst) + (size_t)n * sizeof(BurstRow);
+            WLK_HIP(hipMemcpyAsync(g->blk_dev, blk, up, hipMemcpyHostToDevice, g->stream));
+            for (int k = 0; k < burst; ++k) {      // nothing from the host goes between the chains
+                g->enqueue_step(n);
+                hipLaunchKernelGGL(group_advance_rows_kernel, dim3(1), dim3(64), 0, g->stream, g->blk_dev, g->pick_dev,
+                                   g->results_dev, n, (int)D.n_text_ctx);
+                WLK_HIP(hipGetLastError());
+            }
+            WLK_HIP(hipMemcpyAsync(res, g->results_dev, sizeof(GroupResults), hipMemcpyDeviceToHost, g->stream));
+            WLK_HIP(hipStreamSynchronize(g->stream));
+            for (int r = 0; r < n; ++r)
+                if (res->taken[r] < 1 || res->taken[r] > blk->burst[r].limit)
+                    throw std::logic_error("window group: a row's step count is out of range");
+        }
         for (int r = 0; r < n; ++r) {
             wlk_session* s = sessions[r];
-            s->self_len += 1;
-            s->n_steps += 1;
+            int steps = 1;
+            if (burst == 1) {
+                const int* one = &res->picks[0][0][0] + 2 * r;     // the pick slots, [n][2]
+                tokens_out[r] = one[0];
+                std::memcpy(&logprobs_out[r], &one[1], 4);
+            } else {
+                steps = res->taken[r];
+                for (int k = 0; k < steps; ++k) {
+                    tokens_out[(size_t)r * burst + k] = res->picks[r][k][0];
+                    std::memcpy(&logprobs_out[(size_t)r * burst + k], &res->picks[r][k][1], 4);
+                }
+            }
+            if (steps_out) steps_out[r] = steps;
+            s->self_len += steps;
+            s->n_steps += steps;
             s->have_sot = false;
             s->last_rows = 1;
             s->last_ntok = 1;
-            tokens_out[r] = res[2 * r];
-            std::memcpy(&logprobs_out[r], &res[2 * r + 1], 4);
+            rows_taken += (uint64_t)steps;
         }
         g->last_rows = n;
-        g->n_steps += 1;
-        g->n_rows += (uint64_t)n;
+        g->n_steps += (uint64_t)burst;       // chains enqueued
+        g->n_rows += rows_taken;             // row-steps taken: the rest of burst x n went to rows that had ended
         return WLK_OK;
     });
 }
-
-}  // extern "C"
 
 // ---- stacked word alignment ----------------------------------------------------------------------------------
 namespace {
@@ -464,6 +581,45 @@ int wlk_diag_pick_rows(const float* logits_host, int n_vocab, const uint8_t* mas
             for (int r = 0; r < n; ++r) {
                 tokens_out[r] = res[2 * r];
                 std::memcpy(&logprobs_out[r], &res[2 * r + 1], 4);
+            }
+        } catch (...) {
+            release();
+            throw;
+        }
+        release();
+        return WLK_OK;
+    });
+}
+
+// Tests: the device form of the rule transition alone (pick_rules_advance), out[i] = the state after tokens[i] was picked
+// under p[i].  No model, any n >= 1.
+int wlk_diag_pick_advance(const wlk_pick_params* p, const int32_t* tokens, int n, wlk_pick_params* out) {
+    if (!p || !tokens || !out) return fail(WLK_ERR_ARG, "NULL argument");
+    if (n < 1) return fail(WLK_ERR_ARG, "pick advance: n >= 1");
+    return guarded([&]() {
+        std::vector<PickRules> host(n);
+        for (int i = 0; i < n; ++i) host[i] = pick_rules_of(p[i]);
+        PickRules* in_dev = reinterpret_cast<PickRules*>(dev_alloc<char>(sizeof(PickRules) * n));
+        PickRules* out_dev = nullptr;
+        int* tok_dev = nullptr;
+        auto release = [&] {
+            (void)hipFree(in_dev);
+            if (out_dev) (void)hipFree(out_dev);
+            if (tok_dev) (void)hipFree(tok_dev);
+        };
+        try {
+            out_dev = reinterpret_cast<PickRules*>(dev_alloc<char>(sizeof(PickRules) * n));
+            tok_dev = dev_alloc<int>(n);
+            copy_sync(in_dev, host.data(), sizeof(PickRules) * n, hipMemcpyHostToDevice);
+            copy_sync(tok_dev, tokens, sizeof(int) * (size_t)n, hipMemcpyHostToDevice);
+            hipLaunchKernelGGL(pick_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, in_dev, tok_dev, n, out_dev);
+            WLK_HIP(hipGetLastError());
+            WLK_HIP(hipStreamSynchronize(nullptr));
+            copy_sync(host.data(), out_dev, sizeof(PickRules) * n, hipMemcpyDeviceToHost);
+            for (int i = 0; i < n; ++i) {
+                const PickRules& q = host[i];
+                out[i] = wlk_pick_params{q.first_step, q.without_timestamps, q.timestamp_begin, q.eot, q.no_timestamps, q.ts_mode,
+                                         q.ts_bound, q.max_initial};
             }
         } catch (...) {
             release();

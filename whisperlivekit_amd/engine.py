@@ -559,6 +559,27 @@ class HipWindowGroup:
         _lib.check(self.lib.wlk_group_step_pick(self._h, handles, vp(tok), vp(prm), n, vp(out), vp(lp)))
         return out[:n], lp[:n]
 
+    def run_pick(self, sessions: Sequence[HipSession], tokens: Sequence[int], states: Sequence[dict],
+                 max_steps: Sequence[int], burst: int) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """wlk_group_run_pick: up to ``burst`` (1..16) steps of every row behind one call.  Row r feeds ``tokens[r]``, then
+        its own picks, for at most ``max_steps[r]`` steps (and no further than <|endoftext|> or the text context); the rule
+        states advance on the device from ``states[r]``.  -> per row (token ids int32 [steps_r], log-probabilities float32
+        [steps_r]): what ``steps_r`` successive :meth:`step_pick` calls return."""
+        n, burst = len(sessions), int(burst)
+        handles = (C.c_void_p * max(n, 1))(*[s._h for s in sessions])
+        tok = np.ascontiguousarray(tokens, dtype=np.int64).reshape(-1)
+        prm = np.asarray([[int(st[f]) for f in HipSession.PICK_FIELDS] for st in states], dtype=np.int32).reshape(-1, 8)
+        lim = np.ascontiguousarray(max_steps, dtype=np.int32).reshape(-1)
+        if tok.size != n or prm.shape[0] != n or lim.size != n:
+            raise ValueError("run_pick: one token, one rule state and one step budget per session")
+        width = max(burst, 1)
+        out = np.zeros((max(n, 1), width), np.int32)
+        lp = np.zeros((max(n, 1), width), np.float32)
+        steps = np.zeros(max(n, 1), np.int32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        _lib.check(self.lib.wlk_group_run_pick(self._h, handles, vp(tok), vp(prm), vp(lim), n, burst, vp(out), vp(lp), vp(steps)))
+        return [(out[r, :steps[r]].copy(), lp[r, :steps[r]].copy()) for r in range(n)]
+
     def find_alignment(self, windows: Sequence[tuple], want_cost: bool = False, want_trace: bool = False) -> List[tuple]:
         """wlk_group_find_alignment: the device half of whisper/timing.py:find_alignment for up to ``rows`` windows in one
         stacked pass.  ``windows``: (session, tokens, n_sot, eot, num_frames[, qk_scale]) each, ``tokens`` = [sot sequence,
@@ -632,3 +653,17 @@ def pick_rows(logits: np.ndarray, masks: np.ndarray, mask_of_row: Sequence[int],
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
     _lib.check(lib.wlk_diag_pick_rows(vp(lg), lg.shape[1], vp(mk), mk.shape[0], vp(mo), vp(prm), n, vp(out), vp(lp)))
     return out, lp
+
+
+def pick_advance(states: Sequence[dict], tokens: Sequence[int]) -> List[dict]:
+    """wlk_diag_pick_advance (tests): the device form of the rule transition, one (state, picked token) pair per entry.
+    -> the next states, integers throughout (``first_step`` and ``without_timestamps`` as 0 / 1)."""
+    lib = _lib.load()
+    prm = np.asarray([[int(st[f]) for f in HipSession.PICK_FIELDS] for st in states], dtype=np.int32).reshape(-1, 8)
+    tok = np.ascontiguousarray(tokens, dtype=np.int32).reshape(-1)
+    if tok.size != prm.shape[0]:
+        raise ValueError("pick_advance: one token per state")
+    out = np.zeros_like(prm)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.wlk_diag_pick_advance(vp(prm), vp(tok), tok.size, vp(out)))
+    return [dict(zip(HipSession.PICK_FIELDS, (int(v) for v in row))) for row in out]

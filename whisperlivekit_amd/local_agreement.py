@@ -19,7 +19,8 @@ from .backend import load_openai_checkpoint
 from .dims import ALIGNMENT_HEADS, MODEL_DIMS
 from .engine import HipWhisperModel
 from .policy import ASRToken
-from .transcribe import resolve_align_stack, resolve_stack, set_align_stack, set_stack, transcribe as hip_transcribe
+from .transcribe import (resolve_align_stack, resolve_burst, resolve_stack, set_align_stack, set_burst, set_stack,
+                         transcribe as hip_transcribe)
 
 logger = logging.getLogger(__name__)
 
@@ -30,12 +31,14 @@ class HipWhisperASR:
     def __init__(self, lan: str, model_size: Optional[str] = None, cache_dir: Optional[str] = None,
                  model_dir: Optional[str] = None, lora_path: Optional[str] = None, logfile=sys.stderr, *, device: int = 0,
                  hip_model: Optional[HipWhisperModel] = None, state_dict=None, synthetic_seed: Optional[int] = None,
-                 stack: Optional[int] = None, align_stack: Optional[bool] = None):
+                 stack: Optional[int] = None, align_stack: Optional[bool] = None, burst: Optional[int] = None):
         """``stack``: rows of the model's window group - the greedy temperature-0 steps of up to that many concurrent
         ``transcribe`` calls share each pass over the decoder weights (transcribe.WindowStacker; 0 = off, None = the
         environment's ``WLK_TRANSCRIBE_STACK``, default off).  ``align_stack``: the word-timestamp alignment of those
         calls' windows shares one stacked pass as well (transcribe.AlignStacker; needs ``stack`` >= 1; None = the
-        environment's ``WLK_TRANSCRIBE_ALIGN_STACK``, default off)."""
+        environment's ``WLK_TRANSCRIBE_ALIGN_STACK``, default off).  ``burst``: steps of the window group per library call
+        (transcribe.WindowStacker(burst=...), 1..16; needs ``stack`` >= 1; None = the environment's
+        ``WLK_TRANSCRIBE_STACK_BURST``, default 1 = one step per call)."""
         self.logfile = logfile
         self.transcribe_kargs = {}
         self.lora_path = lora_path
@@ -62,6 +65,11 @@ class HipWhisperASR:
                 raise ValueError("align_stack needs stack >= 1: the stacked alignment runs on the window group")
             set_align_stack(self.model, self.align_stack)
         self.align_stack = self.align_stack and self.stack >= 1
+        self.burst = resolve_burst(burst)
+        if burst is not None:
+            if self.burst > 1 and self.stack < 1:
+                raise ValueError("burst needs stack >= 1: the steps per call are the window group's")
+            set_burst(self.model, self.burst)       # an explicit argument wins over the environment
 
     def load_model(self, model_size=None, cache_dir=None, model_dir=None, *, device: int = 0, state_dict=None,
                    synthetic_seed: Optional[int] = None) -> HipWhisperModel:

@@ -184,6 +184,37 @@ def resolve_stack(stack: Optional[int]) -> int:
     return stack
 
 
+def resolve_burst(burst: Optional[int]) -> int:
+    """``HipWhisperASR(burst=...)`` / :func:`set_burst` / ``WindowStacker(burst=...)``: an explicit value wins; ``None`` reads
+    ``WLK_TRANSCRIBE_STACK_BURST`` (default 1 = one step per library call; 2..16 = steps of a window group per call)."""
+    if burst is None:
+        burst = int(os.environ.get("WLK_TRANSCRIBE_STACK_BURST", "1").strip() or 1)
+    burst = int(burst)
+    if burst < 1 or burst > 16:
+        raise ValueError("burst must be 1..16 steps per call")
+    return burst
+
+
+def _next_pick_state(state: dict, token: int) -> dict:
+    """The rule state of the step after ``token`` was picked under ``state``: `_pick_state(history + [token])` as a function
+    of `_pick_state(history)` and the pick alone - the host statement of what ``wlk_group_run_pick`` advances on the device
+    (csrc/common.h: pick_rules_advance).  The last timestamp of the history is recovered from the old state: ``ts_bound``
+    itself when the last token opened a pair (``ts_mode`` 2), ``ts_bound - 1`` when there is a bound at all, none otherwise."""
+    tb = state["timestamp_begin"]
+    last_ts = token >= tb
+    before_last_ts = True if state["first_step"] else state["ts_mode"] != 0
+    stamp = None
+    if state["ts_mode"] == 2:
+        stamp = state["ts_bound"]
+    elif state["ts_bound"] > tb:
+        stamp = state["ts_bound"] - 1
+    if last_ts:
+        stamp = int(token)
+    mode = 0 if not last_ts else (1 if before_last_ts else 2)
+    bound = tb if stamp is None else (stamp if mode == 2 else stamp + 1)
+    return dict(state, first_step=False, ts_mode=mode, ts_bound=bound)
+
+
 def _greedy_take(tokens: np.ndarray, sum_logprobs: np.ndarray, nxt_id: int, picked: float, eot: int,
                  n_ctx: int) -> Tuple[np.ndarray, bool]:
     """GreedyDecoder.update (decoding.py:270-287) for the one sequence of a greedy window whose rules and pick ran on the
@@ -313,16 +344,23 @@ class WindowStacker(_StackerFront):
 
     ``solo_single``: while ONE window is in flight it takes the session's own step (``decode`` + ``pick_greedy``, a graph
     replay with the one-row folds) instead of a one-row group step, which measured 10 % slower; the two give
-    the same token and the same log-probability bits on every input the tests step."""
+    the same token and the same log-probability bits on every input the tests step.
 
-    def __init__(self, model, rows: int = 8, group=None, solo_single: bool = True):
+    ``burst`` (1..16, default ``WLK_TRANSCRIBE_STACK_BURST`` or 1): with more than 1, a pass over the windows in flight is
+    ONE ``run_pick`` of up to that many tokens per window (``wlk_group_run_pick``): each window's budget is its
+    ``steps_left``, the call is no longer than the longest budget, every row's picks are taken in order, and windows that
+    arrive meanwhile are admitted before the next call.  With 1 the front calls ``step_pick`` as before."""
+
+    def __init__(self, model, rows: int = 8, group=None, solo_single: bool = True, burst: Optional[int] = None):
         super().__init__(rows)
+        self.burst = resolve_burst(burst)
         if group is None:
             from .engine import HipWindowGroup
             group = HipWindowGroup(model, self.rows)
         self.group = group
         self.solo_single = bool(solo_single)
         self.solo_steps = 0
+        self.row_slots = 0             # rows x chains over the group calls: what is not in the group's `rows` went to dead rows
 
     def run(self, window: _GreedyWindow) -> None:
         """Advances ``window`` to its end (its tokens and sum are updated in place); raises what stopped it."""
@@ -332,10 +370,15 @@ class WindowStacker(_StackerFront):
         return self._step(live)
 
     def _step(self, live: List[Tuple[int, _GreedyWindow]]) -> List[Tuple[int, _GreedyWindow]]:
-        """one token for every window in `live`; -> the windows still in flight"""
+        """one token (``burst`` > 1: up to that many) for every window in `live`; -> the windows still in flight"""
+        burst = self.burst
+
         def step(part):
+            if burst > 1:
+                return self._burst(part, burst)
             ids, lps = self.group.step_pick([w.session for _t, w in part], [w.feed() for _t, w in part],
                                             [w.state() for _t, w in part])
+            self.row_slots += len(part)
             return [(t, w) for (t, w), tok, lp in zip(part, ids, lps) if not self._taken(t, w, tok, lp)]
         if len(live) == 1 and self.solo_single:
             (t, w), = live
@@ -365,6 +408,24 @@ class WindowStacker(_StackerFront):
                 self._settle(item[0], e)
         return keep
 
+    def _burst(self, part: List[Tuple[int, _GreedyWindow]], burst: int) -> List[Tuple[int, _GreedyWindow]]:
+        """one ``run_pick`` for the windows of `part`: no chain is enqueued that no row can use"""
+        budgets = [w.steps_left for _t, w in part]
+        chains = min(burst, max(budgets))
+        res = self.group.run_pick([w.session for _t, w in part], [w.feed() for _t, w in part],
+                                  [w.state() for _t, w in part], budgets, chains)
+        self.row_slots += len(part) * chains
+        keep = []
+        for (t, w), (ids, lps) in zip(part, res):
+            over = False
+            for tok, lp in zip(ids, lps):
+                over = w.take(int(tok), float(lp))
+            if over:
+                self._settle(t, None)
+            else:
+                keep.append((t, w))
+        return keep
+
     def _taken(self, ticket: int, window: _GreedyWindow, tok, lp) -> bool:
         if window.take(int(tok), float(lp)):
             self._settle(ticket, None)
@@ -372,8 +433,10 @@ class WindowStacker(_StackerFront):
         return False
 
     def stats(self) -> dict:
-        """the group's steps and rows so far, and this front's passes, windows and solo steps"""
-        return dict(self.group.stats(), passes=self.passes, windows=self.windows, solo_steps=self.solo_steps)
+        """the group's steps (chains) and rows so far, and this front's passes, windows, solo steps and row slots (rows x
+        chains of its group calls)"""
+        return dict(self.group.stats(), passes=self.passes, windows=self.windows, solo_steps=self.solo_steps,
+                    row_slots=self.row_slots)
 
     def close(self) -> None:
         self.group.close()
@@ -391,6 +454,24 @@ def set_stack(model, stack: Optional[int]) -> int:
     return rows
 
 
+def set_burst(model, burst: Optional[int]) -> int:
+    """Steps per library call of ``model``'s stacked greedy windows (1..16; 1 = one ``step_pick`` per token); ``None``
+    leaves it to ``WLK_TRANSCRIBE_STACK_BURST``.  It only acts while the stacked windows are on (:func:`set_stack` /
+    ``WLK_TRANSCRIBE_STACK`` >= 1).  -> the resolved value."""
+    k = resolve_burst(burst)
+    with _STACK_LOCK:
+        if burst is None:
+            model.__dict__.pop("_window_stack_burst", None)
+        else:
+            model.__dict__["_window_stack_burst"] = k
+    return k
+
+
+def _model_burst(model) -> int:
+    k = model.__dict__.get("_window_stack_burst")
+    return resolve_burst(None) if k is None else k
+
+
 def window_stacker(model, rows: Optional[int] = None) -> Optional[WindowStacker]:
     """The model's stacker; created with ``rows`` rows when there is none yet (``rows`` None: never creates)."""
     with _STACK_LOCK:
@@ -400,13 +481,22 @@ def window_stacker(model, rows: Optional[int] = None) -> Optional[WindowStacker]
         return st
 
 
+def _with_model_burst(model, st):
+    """the model's stacker with the model's burst (:func:`set_burst`, else ``WLK_TRANSCRIBE_STACK_BURST``) from its next pass on"""
+    burst = _model_burst(model)
+    if getattr(st, "burst", burst) != burst:
+        st.burst = burst
+    return st
+
+
 def _run_stacker(model) -> Optional[WindowStacker]:
     """What `_WindowDecoder.run` sends its greedy steps through: the model's stacker when stacking is switched on for it
-    (:func:`set_stack`, else ``WLK_TRANSCRIBE_STACK``), otherwise None - and then nothing is constructed."""
+    (:func:`set_stack`, else ``WLK_TRANSCRIBE_STACK``), otherwise None - and then nothing is constructed.  The stacker takes
+    the model's burst (:func:`set_burst`, else ``WLK_TRANSCRIBE_STACK_BURST``) from its next pass on."""
     rows = model.__dict__.get("_window_stack_rows")
     if rows is None:
         rows = resolve_stack(None)
-    return window_stacker(model, rows) if rows > 0 else None
+    return _with_model_burst(model, window_stacker(model, rows)) if rows > 0 else None
 
 
 # ---- stacked word alignment (opt-in; wlk_group_find_alignment) --------------------------------------------------------------
@@ -853,8 +943,8 @@ def decode_many(model: HipWhisperModel, mels: Sequence[np.ndarray], options: Dec
     if not 1 <= len(mels) <= 8:
         raise ValueError("decode_many takes 1..8 windows")
     if stacker is None:
-        stacker = window_stacker(model, 8)
-    sessions = _rows_of(model).windows(len(mels))
+        stacker = _with_model_burst(model, window_stacker(model, 8))
+    sessions =_rows_of(model).windows(len(mels))
     opened = [_WindowDecoder(model, options).run(mel, s, stacker=stacker, defer=True) for mel, s in zip(mels, sessions)]
     stacker.run_many([r[0] for r in opened if isinstance(r, tuple)])
     return [r[1]() if isinstance(r, tuple) else r for r in opened]
@@ -1155,10 +1245,12 @@ def _add_word_timestamps(segments: List[dict], encoded: Optional[HipSession], mo
                    prepend_punctuations=prepend, append_punctuations=append)
 
 
-def transcribe_many(model: HipWhisperModel, audios: Sequence, *, stack: int = 8, **kwargs) -> List[dict]:
+def transcribe_many(model: HipWhisperModel, audios: Sequence, *, stack: int = 8, burst: Optional[int] = None,
+                    **kwargs) -> List[dict]:
     """Offline convenience: one :func:`transcribe` per recording on worker threads (at most ``stack`` at a time) whose
     greedy temperature-0 windows share the model's :class:`WindowStacker`; -> the result dictionaries, in order.  The
-    model's stack setting is switched to ``stack`` rows for the duration of the call and put back afterwards."""
+    model's stack setting is switched to ``stack`` rows - and, when ``burst`` is given, its steps per library call to
+    ``burst`` - for the duration of the call and put back afterwards."""
     rows = resolve_stack(stack)
     if rows < 1:
         raise ValueError("transcribe_many needs stack in 1..8")
@@ -1167,6 +1259,9 @@ def transcribe_many(model: HipWhisperModel, audios: Sequence, *, stack: int = 8,
     errors: List[Optional[BaseException]] = [None] * len(audios)
     gate = threading.Semaphore(rows)
     before = model.__dict__.get("_window_stack_rows")
+    burst_before = model.__dict__.get("_window_stack_burst")
+    if burst is not None:
+        set_burst(model, burst)
     set_stack(model, rows)
 
     def work(i: int) -> None:
@@ -1188,6 +1283,11 @@ def transcribe_many(model: HipWhisperModel, audios: Sequence, *, stack: int = 8,
                 model.__dict__.pop("_window_stack_rows", None)
             else:
                 model.__dict__["_window_stack_rows"] = before
+            if burst is not None:
+                if burst_before is None:
+                    model.__dict__.pop("_window_stack_burst", None)
+                else:
+                    model.__dict__["_window_stack_burst"] = burst_before
     for e in errors:
         if e is not None:
             raise e
