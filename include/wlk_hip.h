@@ -204,6 +204,52 @@ typedef struct wlk_align_window {
 } wlk_align_window;
 int wlk_group_find_alignment(wlk_group* g, const wlk_align_window* w, int n /* 1..max_rows */);
 int wlk_group_align_fits(wlk_group* g, int32_t n_tokens, int32_t num_frames, int32_t* fits);
+/* Draft verification (opt-in): how much of a draft - the tokens the previous call of a growing buffer produced -
+ * greedy decoding at temperature 0 would produce again, and the token behind it, for up to max_rows windows of DIFFERENT
+ * encoded beam-1 sessions in one call: ONE teacher-forced decoder pass over [initial tokens | draft] of all windows (the
+ * stacked prefill chain), per window the final LayerNorm and vocabulary projection of the n_draft + 1 candidate rows (row
+ * n_initial - 1 + j predicts what follows draft[0 .. j)) and of the sot row, the greedy pick of every candidate row under the
+ * rule state its position has (derived on the device from p, the state of the window's FIRST pick, and the draft), and
+ *   accepted k   = the first j with pick(j) != draft[j] (n_draft when there is none),
+ *   next_token, next_logprob = the pick at position k (the bits wlk_pick_greedy gives on that logits row),
+ *   sum_logprob  = the log-probabilities of positions 0 .. k added in ascending order in fp32 (nothing is added, and
+ *                  next_token is p.eot, when tokens[n_initial - 1] is p.eot already),
+ *   no_speech_prob = softmax(logits of row sot_index)[no_speech_token] (NaN for no_speech_token < 0).
+ * Afterwards every session is what its own prefill of [initial | draft[0 .. k)] leaves - position n_initial + k, its K/V rows
+ * below that, wlk_no_speech_prob, wlk_pick_greedy and wlk_export("logits_last") included (the logits row of position k) -
+ * and the caller goes on by feeding next_token (wlk_decode first = 0, wlk_group_step_pick, wlk_group_run_pick).  K/V rows at
+ * and behind n_initial + k hold the rejected draft; every step overwrites its own position before anything reads it.
+ * Every window is checked on the host BEFORE anything is launched or any session is touched: WLK_ERR_ARG for n outside
+ * 1..max_rows, a session listed twice, of another model or with beam != 1, n_initial < 1, an empty draft, a draft token equal
+ * to p.eot, a token or rule parameter out of range, sot_index outside the initial tokens, n_tokens > n_text_ctx or outside the
+ * stacked chain's shapes (wlk_group_verify_fits), a score window shorter than n_tokens rows; WLK_ERR_STATE for a session that is
+ * not encoded, has no wlk_rules_set lists, is attached to the batch engine or in debug / profiling mode.  A window's results do
+ * not depend on the windows beside it.  The pass shares wlk_group_find_alignment's stacked workspace (allocated by the first
+ * call of either) and a logits buffer of (longest draft + 2) x n_vocab floats that grows on demand.
+ * wlk_group_verify_fits: the shape conditions alone, a pure host function of (model, n_initial, n_draft): n_initial >= 1,
+ * n_draft >= 1, 9 <= n_initial + n_draft <= min(256, n_text_ctx), the decoder GEMMs of that many rows on the k-wave kernel,
+ * the cross-attention with key splits. */
+typedef struct wlk_verify_result {
+    int32_t accepted, next_token;
+    float next_logprob, sum_logprob, no_speech_prob;
+} wlk_verify_result;
+typedef struct wlk_verify_window {
+    wlk_session* s;            /* encoded beam-1 session of the group's model with wlk_rules_set lists */
+    const int64_t* tokens;     /* [initial tokens (n_initial) | draft (n_tokens - n_initial)] */
+    int32_t n_initial, n_tokens, sot_index, no_speech_token /* -1 = none */;
+    wlk_pick_params p;         /* the rule state of the window's first pick (position 0) */
+    wlk_verify_result* result; /* out */
+    int32_t* picks;            /* optional out (tests) [n_draft + 1][2]: token and log-probability bits of every position */
+} wlk_verify_window;
+int wlk_group_verify(wlk_group* g, const wlk_verify_window* w, int n /* 1..max_rows */);
+int wlk_group_verify_fits(wlk_group* g, int32_t n_initial, int32_t n_draft, int32_t* fits);
+/* Diagnostic (tests): the two kernels behind wlk_group_verify's decoder pass alone on host data - logits [n_draft + 1][n_vocab],
+ * one rule mask [n_vocab] (as wlk_rules_set builds it), p0 = the first position's state, `ended` != 0: the token in front of
+ * position 0 is <|endoftext|>.  tokens_out / logprobs_out [n_draft + 1]: every position's pick; result: accepted, next_token,
+ * next_logprob, sum_logprob.  n_draft in 1..256.  Runs on the current device; needs no model.  Synchronous. */
+int wlk_diag_draft_pick(const float* logits_host, int n_vocab, const uint8_t* mask_host, const wlk_pick_params* p0,
+                        const int32_t* draft, int n_draft, int ended, int32_t* tokens_out, float* logprobs_out,
+                        wlk_verify_result* result);
 /* Diagnostic (tests): the ragged warping launches of wlk_group_find_alignment (recurrence, transposition, path walk) on n
  * (1..8) host cost matrices; matrix i is [n_rows[i]][n_cols[i]] at costs + offsets[i] (1..1024 rows, 1..4095 columns).
  * starts: n_rows[i] entries per matrix, concatenated; traces (optional): (n_rows[i] + 1) x (n_cols[i] + 1) step codes per

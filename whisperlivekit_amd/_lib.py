@@ -152,6 +152,19 @@ class AlignWindow(C.Structure):
         (n, C.c_void_p) for n in ("starts", "token_probs", "cost", "trace")]
 
 
+class VerifyResult(C.Structure):
+    """wlk_verify_result (include/wlk_hip.h)"""
+    _fields_ = [("accepted", C.c_int32), ("next_token", C.c_int32), ("next_logprob", C.c_float), ("sum_logprob", C.c_float),
+                ("no_speech_prob", C.c_float)]
+
+
+class VerifyWindow(C.Structure):
+    """wlk_verify_window (include/wlk_hip.h); ``p`` = the eight wlk_pick_params fields in order"""
+    _fields_ = [("s", C.c_void_p), ("tokens", C.c_void_p)] + [
+        (n, C.c_int32) for n in ("n_initial", "n_tokens", "sot_index", "no_speech_token")] + [("p", C.c_int32 * 8)] + [
+        ("result", C.POINTER(VerifyResult)), ("picks", C.c_void_p)]
+
+
 ENC_X3_GEMM, ENC_LN, ENC_ATTENTION, ENC_PACK = range(4)
 WA_SOFTMAX, WA_ZSCORE, WA_COST, WA_DTW = range(4)
 SFK_ATTENTION, SFK_CONV0, SFK_DWCONV2D, SFK_GLU_DWCONV, SFK_HEAD, SFK_ASSEMBLE = range(6)
@@ -242,6 +255,9 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_group_find_alignment": (cint, [p, C.POINTER(AlignWindow), cint]),
         "wlk_group_align_fits": (cint, [p, i32, i32, C.POINTER(i32)]),
         "wlk_diag_dtw_starts": (cint, [p, p, p, p, cint, p, p]),
+        "wlk_group_verify": (cint, [p, C.POINTER(VerifyWindow), cint]),
+        "wlk_group_verify_fits": (cint, [p, i32, i32, C.POINTER(i32)]),
+        "wlk_diag_draft_pick": (cint, [p, cint, p, p, p, cint, cint, p, p, C.POINTER(VerifyResult)]),
         "wlk_decode_ancestry": (cint, [p, p, p, cint]),
         "wlk_select": (cint, [p, p, p, p, cint, cint, cint, p, p, p]),
         "wlk_kv_reorder": (cint, [p, p, cint]),
@@ -440,6 +456,7 @@ EXPORTED_SYMBOLS = (
     "wlk_diag_pick_rows",
     "wlk_group_find_alignment", "wlk_group_align_fits", "wlk_diag_dtw_starts",
     "wlk_group_run_pick", "wlk_diag_pick_advance",
+    "wlk_group_verify", "wlk_group_verify_fits", "wlk_diag_draft_pick",
 )
 
 

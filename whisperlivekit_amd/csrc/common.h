@@ -716,6 +716,16 @@ struct PickRowEntry {
 };
 void launch_rules_pick_rows(const LaunchCtx& ctx, const float* logits, int n_vocab, int n_rows, const PickRowEntry* table,
                             int* out);
+// Draft verification (window_group.hip: wlk_group_verify): the greedy pick at the n_draft + 1 candidate positions of one
+// teacher-forced window - logits [n_draft + 1][n_vocab], the rule state of position j derived on the device from p0 (the
+// window's first pick) and draft[0 .. j) - and how far greedy decoding would have followed the draft.  All pointers are
+// device memory.  picks [n_draft + 1][3] = (token, log-probability bits, token == draft[j]), a position's first two the
+// bits of launch_rules_pick on the same row, mask and state; res [4] = (accepted k, the pick at k, its log-probability
+// bits, bits of the sum over positions 0 .. k added in ascending order).  ended: the token in front of position 0 is
+// <|endoftext|>.  keep_row (optional): receives logits row k.
+constexpr int kMaxDraft = 256;
+void launch_draft_pick(const LaunchCtx& ctx, const float* logits, int n_vocab, const unsigned char* mask, const PickRules& p0,
+                       const int* draft, int n_draft, int ended, int* picks, int* res, float* keep_row);
 struct AlignArgs {
     const float* ring;   // [n_align][n_beam][ring_rows][T]
     int n_align, n_beam, ring_rows, T;

@@ -988,6 +988,101 @@ void launch_rules_pick_rows(const LaunchCtx& ctx, const float* logits, int n_voc
     WLK_HIP(hipGetLastError());
 }
 
+// Draft verification (window_group.hip: wlk_group_verify): the greedy pick at EVERY candidate position of a
+// teacher-forced window in one launch.  Workgroup j = the position behind draft[0 .. j): logits row j, the session's mask,
+// and the rule state that position has - the window's first-pick state walked through pick_rules_advance over draft[0 .. j)
+// by one lane (at most 255 steps of a dozen integer operations; the one statement of the transition stays common.h's).
+// The pick itself is rules_pick_body in the form rules_pick_rows_kernel takes (same loads, same fold order), so a
+// position's (token, log-probability) are the bits wlk_pick_greedy gives on that row, mask and state.
+//   out[3 j] = token, out[3 j + 1] = log-probability bits, out[3 j + 2] = j < n_draft && token == draft[j]
+__global__ __launch_bounds__(1024) void draft_pick_rows_kernel(const float* __restrict__ logits, int n_vocab,
+                                                               const unsigned char* __restrict__ mask, PickRules p0,
+                                                               const int* __restrict__ draft, int n_draft,
+                                                               int* __restrict__ out) {
+    __shared__ PickRules s_rules;
+    __shared__ int s_token;
+    __shared__ float s_logprob;
+    const int j = blockIdx.x;
+    if (threadIdx.x == 0) {
+        PickRules q = p0;
+        for (int i = 0; i < j && i < n_draft; ++i) q = pick_rules_advance(q, draft[i]);
+        s_rules = q;
+    }
+    __syncthreads();
+    const PickRules p = s_rules;
+    const float* x = logits + (long)j * n_vocab;
+    if (n_vocab <= kRulesKeep * 1024) rules_pick_body<true>(x, n_vocab, mask, p, &s_token, &s_logprob);
+    else rules_pick_body<false>(x, n_vocab, mask, p, &s_token, &s_logprob);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int token = s_token;
+        out[3 * j] = token;
+        out[3 * j + 1] = __float_as_int(s_logprob);
+        out[3 * j + 2] = (j < n_draft && token == draft[j]) ? 1 : 0;
+    }
+}
+
+// One wave per window behind draft_pick_rows_kernel: k = the first position whose pick is not the draft's token (a ballot
+// over the match flags, 64 positions a round; n_draft when every one matches), next = the pick at k, and the sum of the
+// log-probabilities of positions 0 .. k, added in ascending order by one lane, one fp32 add after the other - the order
+// in which transcribe._greedy_take accumulates, so the sum has the host loop's bits for the same addends.  `ended`: the
+// token in front of position 0 was <|endoftext|> already; _greedy_take then takes <|endoftext|> whatever was picked and
+// adds nothing (a draft token never is <|endoftext|>, so no later position can be in that state).
+//   res[0] = k, res[1] = next token, res[2] = its log-probability bits, res[3] = the sum's bits
+__global__ __launch_bounds__(64) void draft_accept_kernel(const int* __restrict__ picks, int n_draft, int eot, int ended,
+                                                          int* __restrict__ res) {
+    const int lane = threadIdx.x;
+    int k = n_draft;
+    for (int base = 0; base < n_draft; base += 64) {
+        const int j = base + lane;
+        const bool miss = j < n_draft && (picks[3 * j + 2] == 0 || (ended && j == 0));
+        const unsigned long long m = __ballot(miss);
+        if (m != 0ull) {
+            k = base + __ffsll((long long)m) - 1;
+            break;
+        }
+    }
+    if (lane == 0) {
+        float sum = 0.f;
+        for (int j = ended ? 1 : 0; j <= k; ++j) sum += __int_as_float(picks[3 * j + 1]);
+        res[0] = k;
+        res[1] = (ended && k == 0) ? eot : picks[3 * k];
+        res[2] = picks[3 * k + 1];
+        res[3] = __float_as_int(sum);
+    }
+}
+
+// the logits row wlk_group_verify leaves in the session: row res[0] (the accepted count, known on the device only while the
+// logits buffer is reused by the next window) of `logits` to `dst`, a plain copy
+__global__ __launch_bounds__(256) void draft_keep_row_kernel(const float* __restrict__ logits, int n_vocab,
+                                                             const int* __restrict__ res, int n_rows, float* __restrict__ dst) {
+    const int k = res[0];
+    if (k < 0 || k >= n_rows) return;
+    const float* src = logits + (long)k * n_vocab;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n_vocab; i += gridDim.x * 256) dst[i] = src[i];
+}
+
+void launch_draft_pick(const LaunchCtx& ctx, const float* logits, int n_vocab, const unsigned char* mask, const PickRules& p0,
+                       const int* draft, int n_draft, int ended, int* picks, int* res, float* keep_row) {
+    if (n_draft < 1 || n_draft > kMaxDraft) throw std::invalid_argument("draft pick: 1..256 draft tokens");
+    {
+        KernelScope ks(ctx, "draft_pick_rows", 0.0, 5.0 * (n_draft + 1) * (double)n_vocab);
+        hipLaunchKernelGGL(draft_pick_rows_kernel, dim3(n_draft + 1), dim3(1024), 0, ctx.stream, logits, n_vocab, mask, p0, draft,
+                           n_draft, picks);
+        WLK_HIP(hipGetLastError());
+    }
+    {
+        KernelScope ks(ctx, "draft_accept");
+        hipLaunchKernelGGL(draft_accept_kernel, dim3(1), dim3(64), 0, ctx.stream, picks, n_draft, p0.eot, ended, res);
+        WLK_HIP(hipGetLastError());
+    }
+    if (keep_row) {
+        KernelScope ks(ctx, "draft_keep_row", 0.0, 8.0 * n_vocab);
+        hipLaunchKernelGGL(draft_keep_row_kernel, dim3(32), dim3(256), 0, ctx.stream, logits, n_vocab, res, n_draft + 1, keep_row);
+        WLK_HIP(hipGetLastError());
+    }
+}
+
 void launch_rules_pick(const LaunchCtx& ctx, const float* logits, int n_vocab, const unsigned char* mask, const PickRules& p,
                        int* out_token, float* out_logprob) {
     KernelScope ks(ctx, "rules_pick", 0.0, 8.0 * n_vocab);

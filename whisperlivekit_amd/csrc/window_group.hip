@@ -23,6 +23,11 @@
 // teacher-forced decoder pass (api.hip: wlk_prefill_chain), the token probabilities per window, the ragged normalisation
 // (word_align.hip), the warping recurrences side by side and the path walk on the device (dtw.hip), one read-back of the
 // starts and probabilities.  Its workspace is allocated by the first such call.
+//
+// And it verifies drafts (wlk_group_verify): the same stacked pass over [initial tokens | draft] of up to 8
+// windows, the greedy pick of every candidate position with the rule state its history gives, the accepted prefix and the
+// token behind it on the device (select.hip: draft_pick_rows_kernel, draft_accept_kernel), 32 bytes back per window; each
+// session is left as its own prefill of the accepted tokens leaves it.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -122,6 +127,12 @@ struct wlk_group {
     size_t align_cap = 0;
     char* align_up_dev = nullptr;        // [AlignWin x 8 | targets int x 8 x 256]
     char* align_pinned = nullptr;        // [upload block | results: starts and token probabilities of all windows]
+    // draft verification (wlk_group_verify): shares the stacked decoder pass's workspace; nothing of it exists before the
+    // first such call
+    char* verify_buf = nullptr;          // grown on demand: [hidden (n_d + 2) x d | logits (n_d + 2) x V] of the longest draft
+    size_t verify_cap = 0;
+    int* verify_dev = nullptr;           // [drafts int x 8 x 256 | picks int x 8 x 257 x 3 | results int x 8 x 8]
+    int* verify_pinned = nullptr;        // [drafts | results]
 
     ~wlk_group() {
         (void)hipSetDevice(m->device);
@@ -137,6 +148,9 @@ struct wlk_group {
         if (align_buf) (void)hipFree(align_buf);
         if (align_up_dev) (void)hipFree(align_up_dev);
         if (align_pinned) (void)hipHostFree(align_pinned);
+        if (verify_buf) (void)hipFree(verify_buf);
+        if (verify_dev) (void)hipFree(verify_dev);
+        if (verify_pinned) (void)hipHostFree(verify_pinned);
         for (hipEvent_t e : joined)
             if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
@@ -420,6 +434,8 @@ int wlk_group_find_alignment(wlk_group* g, const wlk_align_window* w, int n) {
         if (!g->align_ready) {
             wlk_prefill_ws_alloc(m, g->align_ws, kGroupMaxRows, align_session_rows(m));
             g->align_ready = true;
+        }
+        if (!g->align_up_dev) {
             g->align_up_dev = dev_alloc<char>(kAlignUpBytes);
             WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&g->align_pinned), kAlignUpBytes + kAlignResBytes, hipHostMallocDefault));
         }
@@ -526,6 +542,194 @@ int wlk_group_find_alignment(wlk_group* g, const wlk_align_window* w, int n) {
     });
 }
 
+}  // extern "C"
+
+// ---- draft verification --------------------------------------------------------------------------------------
+namespace {
+constexpr int kVerifyResInts = 8;        // per window: accepted, next token, its log-probability, the sum, no-speech probability
+constexpr size_t kVerifyDraftInts = (size_t)kGroupMaxRows * kMaxDraft;
+constexpr size_t kVerifyPickInts = (size_t)kGroupMaxRows * (kMaxDraft + 1) * 3;
+constexpr size_t kVerifyResAll = (size_t)kGroupMaxRows * kVerifyResInts;
+
+// the shape conditions of a window in the verify pass: a pure host function of (model, P0, n_d); empty = fits
+std::string verify_shape_refusal(const wlk_model* m, int n_initial, int n_draft) {
+    if (n_initial < 1) return "no initial tokens";
+    if (n_draft < 1) return "an empty draft";
+    if (n_draft > kMaxDraft || n_initial > kAlignRowsMax) return "prompt length outside the stacked range";
+    const int P = n_initial + n_draft;
+    if (P > m->D.n_text_ctx) return "text context exceeded";
+    return wlk_prefill_shape_check(m, P, align_session_rows(m));
+}
+}  // namespace
+
+extern "C" {
+
+int wlk_group_verify_fits(wlk_group* g, int32_t n_initial, int32_t n_draft, int32_t* fits) {
+    if (!g || !fits) return fail(WLK_ERR_ARG, "NULL argument");
+    *fits = verify_shape_refusal(g->m, n_initial, n_draft).empty() ? 1 : 0;
+    return WLK_OK;
+}
+
+int wlk_group_verify(wlk_group* g, const wlk_verify_window* w, int n) {
+    if (!g || !w) return fail(WLK_ERR_ARG, "NULL argument");
+    if (n < 1 || n > g->max_rows) return fail(WLK_ERR_ARG, "window group: 1..max_rows windows per verify pass");
+    wlk_model* m = g->m;
+    const wlk_dims& D = m->D;
+    const int V = D.n_vocab;
+    // every window is checked on the host before anything is launched or any session is touched
+    for (int r = 0; r < n; ++r) {
+        const wlk_verify_window& a = w[r];
+        const wlk_session* s = a.s;
+        if (!s || !a.tokens || !a.result) return fail(WLK_ERR_ARG, "window group: NULL argument in a verify window");
+        for (int j = 0; j < r; ++j)
+            if (w[j].s == s) return fail(WLK_ERR_ARG, "window group: a session is listed twice");
+        if (s->m != m) return fail(WLK_ERR_ARG, "window group: a session of another model");
+        if (s->beam != 1) return fail(WLK_ERR_ARG, "verify needs a beam-1 session");
+        if (s->engine) return fail(WLK_ERR_STATE, "window group: the session is attached to the batch engine");
+        if (!s->encoded) return fail(WLK_ERR_STATE, "verify before an encode");
+        if (!s->rules_mask) return fail(WLK_ERR_STATE, "verify before wlk_rules_set");
+        if (s->debug || s->prof_on || s->align_raw_scores) return fail(WLK_ERR_STATE, "window group: not a plain beam-1 session");
+        const int P0 = a.n_initial, P = a.n_tokens, n_d = P - P0;
+        if (n_d < 1) return fail(WLK_ERR_ARG, "verify: an empty draft");
+        const std::string shape = verify_shape_refusal(m, P0, n_d);
+        if (!shape.empty()) return fail(WLK_ERR_ARG, "verify: " + shape);
+        if (a.sot_index < 0 || a.sot_index >= P0) return fail(WLK_ERR_ARG, "sot_index out of range");
+        if (!pick_params_ok(a.p, V)) return fail(WLK_ERR_ARG, "rule parameters out of range");
+        if (a.no_speech_token >= V) return fail(WLK_ERR_ARG, "token out of range");
+        for (int i = 0; i < P; ++i)
+            if (a.tokens[i] < 0 || a.tokens[i] >= V) return fail(WLK_ERR_ARG, "token id out of range");
+        for (int i = P0; i < P; ++i)
+            if (a.tokens[i] == a.p.eot) return fail(WLK_ERR_ARG, "verify: <|endoftext|> inside the draft");
+        if (s->ring_rows < P) return fail(WLK_ERR_ARG, "verify: the session's score window is shorter than the pass");
+        if (s->ring_rows != w[0].s->ring_rows) return fail(WLK_ERR_ARG, "window group: score windows of different heights");
+    }
+    return guarded([&]() {
+        std::lock_guard<std::mutex> lk(g->mu);
+        WLK_HIP(hipSetDevice(m->device));
+        const LaunchCtx c{g->stream, nullptr};
+        const int d = D.n_text_state, T = D.n_audio_ctx;
+        if (!g->align_ready) {
+            wlk_prefill_ws_alloc(m, g->align_ws, kGroupMaxRows, align_session_rows(m));
+            g->align_ready = true;
+        }
+        if (!g->verify_dev) {
+            g->verify_dev = dev_alloc<int>(kVerifyDraftInts + kVerifyPickInts + kVerifyResAll);
+            WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&g->verify_pinned), (kVerifyDraftInts + kVerifyResAll) * sizeof(int),
+                                  hipHostMallocDefault));
+        }
+        // ---- workspace: [hidden | logits] of the longest window: its n_d + 1 candidate rows and the sot row behind them
+        int rows_max = 0;
+        for (int r = 0; r < n; ++r) rows_max = std::max(rows_max, w[r].n_tokens - w[r].n_initial + 2);
+        const size_t hid_b = up16((size_t)rows_max * d * 4), need = hid_b + up16((size_t)rows_max * V * 4);
+        if (need > g->verify_cap) {
+            WLK_HIP(hipStreamSynchronize(g->stream));
+            if (g->verify_buf) WLK_HIP(hipFree(g->verify_buf));
+            g->verify_buf = nullptr; g->verify_cap = 0;
+            g->verify_buf = dev_alloc<char>(need);
+            g->verify_cap = need;
+        }
+        float* hid = reinterpret_cast<float*>(g->verify_buf);
+        float* logits = reinterpret_cast<float*>(g->verify_buf + hid_b);
+        int* draft_dev = g->verify_dev;
+        int* picks_dev = draft_dev + kVerifyDraftInts;
+        int* res_dev = picks_dev + kVerifyPickInts;
+        int* draft_h = g->verify_pinned;
+        int* res_h = draft_h + kVerifyDraftInts;
+
+        std::vector<wlk_prefill_item> items(n);
+        std::vector<wlk_prefill_item*> stack(n);
+        for (int r = 0; r < n; ++r) {
+            wlk_session* s = w[r].s;
+            const int P0 = w[r].n_initial, n_d = w[r].n_tokens - P0;
+            for (int i = 0; i < n_d; ++i) draft_h[(size_t)r * kMaxDraft + i] = (int)w[r].tokens[P0 + i];
+            items[r].s = s; items[r].tokens = w[r].tokens; items[r].n_tok = w[r].n_tokens; items[r].sot_index = w[r].sot_index;
+            stack[r] = &items[r];
+            // the chain overwrites the session's caches and score window: should anything fail from here on, its next
+            // decode must be a prefill
+            s->n_steps = 0;
+            s->self_len = 0;
+            s->have_sot = false;
+            // what the session's own stream has queued (encode, an earlier window's steps) is done before this stream touches it
+            WLK_HIP(hipEventRecord(g->joined[r], s->stream));
+            WLK_HIP(hipStreamWaitEvent(g->stream, g->joined[r], 0));
+        }
+        WLK_HIP(hipMemcpyAsync(draft_dev, draft_h, (size_t)n * kMaxDraft * sizeof(int), hipMemcpyHostToDevice, g->stream));
+        WLK_HIP(hipMemsetAsync(res_dev, 0, kVerifyResAll * sizeof(int), g->stream));
+
+        // ---- ONE teacher-forced decoder pass over [initial | draft] of all windows.  It writes K/V rows 0 .. P - 1 of every
+        // session.  Of those, rows at and behind P0 + k (k = the accepted count) belong to draft tokens greedy decoding would
+        // not have produced; they stay where they are, stale: a step at offset o reads the cache positions below o and
+        // writes position o (the argument of group_advance_rows_kernel's dead rows and of the padded tile rows),
+        // and the session goes on at offset P0 + k - so every stale row is overwritten by the step that owns its position
+        // before any step reads it.  Rows below P0 + k depend on tokens below P0 + k only (causal self-attention, row-wise
+        // operators elsewhere): they are the rows a prefill of [initial | draft[0 .. k)] writes.
+        std::vector<int> row0;
+        wlk_prefill_chain(stack, c, g->align_ws, row0);
+        for (int r = 0; r < n; ++r) {
+            wlk_session* s = w[r].s;
+            const int P0 = w[r].n_initial, P = w[r].n_tokens, n_d = P - P0, n_pos = n_d + 1;
+            // the alignment heads' raw scores softmaxed in place, as a prefill leaves them (row-wise: rows below P0 + k are
+            // those of the shorter prefill)
+            if (m->n_align > 0)
+                launch_ring_softmax(c, s->ring, g->align_ws.ring_row_dev + row0[r], g->align_ws.zeros_dev, m->all_ranks, m->n_align, P,
+                                    s->ring_rows, 1, T);
+            // ---- final LayerNorm of the candidate rows P0 - 1 .. P - 1 and of the sot row, projected onto the vocabulary
+            // by one launch into the reused logits buffer (rows 0 .. n_d: the candidates; row n_d + 1: the sot row)
+            const float* x0 = g->align_ws.dx + (size_t)row0[r] * d;
+            launch_layernorm(c, x0 + (size_t)(P0 - 1) * d, d, m->w_ln_w, m->w_ln_b, hid, d, n_pos, d, "dv_ln_f");
+            launch_layernorm(c, x0 + (size_t)w[r].sot_index * d, d, m->w_ln_w, m->w_ln_b, hid + (size_t)n_pos * d, d, 1, d, "dv_ln_f");
+            GemmArgs lg;
+            lg.A = hid; lg.lda = d; lg.W = m->w_tok_emb; lg.C = logits; lg.ldc = V; lg.M = n_pos + 1; lg.N = V; lg.K = d;
+            launch_linear(c, lg, "dv_logits");
+            int* res = res_dev + (size_t)r * kVerifyResInts;
+            if (w[r].no_speech_token >= 0)
+                launch_token_prob(c, logits + (size_t)n_pos * V, V, 1, w[r].no_speech_token, reinterpret_cast<float*>(res + 4));
+            const int ended = w[r].tokens[P0 - 1] == w[r].p.eot ? 1 : 0;
+            launch_draft_pick(c, logits, V, s->rules_mask, pick_rules_of(w[r].p), draft_dev + (size_t)r * kMaxDraft, n_d, ended,
+                              picks_dev + (size_t)r * (kMaxDraft + 1) * 3, res, s->logits_last);
+            WLK_HIP(hipMemcpyAsync(s->logits_sot, logits + (size_t)n_pos * V, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice,
+                                   g->stream));
+        }
+        WLK_HIP(hipMemcpyAsync(res_h, res_dev, (size_t)n * kVerifyResInts * sizeof(int), hipMemcpyDeviceToHost, g->stream));
+        WLK_HIP(hipStreamSynchronize(g->stream));
+        for (int r = 0; r < n; ++r) {
+            const int n_d = w[r].n_tokens - w[r].n_initial;
+            if (res_h[r * kVerifyResInts] < 0 || res_h[r * kVerifyResInts] > n_d)
+                throw std::logic_error("window group: an accepted count is out of range");
+        }
+        for (int r = 0; r < n; ++r) {
+            const wlk_verify_window& o = w[r];
+            wlk_session* s = o.s;
+            const int* res = res_h + (size_t)r * kVerifyResInts;
+            const int P0 = o.n_initial, n_d = o.n_tokens - P0, k = res[0];
+            o.result->accepted = k;
+            o.result->next_token = res[1];
+            std::memcpy(&o.result->next_logprob, &res[2], 4);
+            std::memcpy(&o.result->sum_logprob, &res[3], 4);
+            if (o.no_speech_token >= 0) std::memcpy(&o.result->no_speech_prob, &res[4], 4);
+            else o.result->no_speech_prob = NAN;
+            // tests only (the host buffer is the caller's: pageable, so synchronous)
+            if (o.picks) {
+                std::vector<int> pk((size_t)(n_d + 1) * 3);
+                copy_sync(pk.data(), picks_dev + (size_t)r * (kMaxDraft + 1) * 3, pk.size() * sizeof(int), hipMemcpyDeviceToHost);
+                for (int j = 0; j <= n_d; ++j) {
+                    o.picks[2 * j] = pk[3 * j];
+                    o.picks[2 * j + 1] = pk[3 * j + 1];
+                }
+            }
+            // the session is what a prefill of [initial | draft[0 .. k)] leaves
+            s->self_len = P0 + k;
+            s->n_steps = 1;
+            s->have_sot = true;
+            s->prefill_rows = P0 + k;
+            s->last_rows = 1;
+            s->last_ntok = P0 + k;
+            s->anc_live = false;
+        }
+        return WLK_OK;
+    });
+}
+
 int wlk_group_stats(wlk_group* g, uint64_t* steps, uint64_t* rows) {
     if (!g) return fail(WLK_ERR_ARG, "group is NULL");
     std::lock_guard<std::mutex> lk(g->mu);
@@ -621,6 +825,56 @@ int wlk_diag_pick_advance(const wlk_pick_params* p, const int32_t* tokens, int n
                 out[i] = wlk_pick_params{q.first_step, q.without_timestamps, q.timestamp_begin, q.eot, q.no_timestamps, q.ts_mode,
                                          q.ts_bound, q.max_initial};
             }
+        } catch (...) {
+            release();
+            throw;
+        }
+        release();
+        return WLK_OK;
+    });
+}
+
+// Tests: the two kernels behind wlk_group_verify's decoder pass alone (select.hip: draft_pick_rows_kernel,
+// draft_accept_kernel) on host logits [n_draft + 1][n_vocab], one rule mask [n_vocab] and the first-pick state p0.
+int wlk_diag_draft_pick(const float* logits_host, int n_vocab, const uint8_t* mask_host, const wlk_pick_params* p0,
+                        const int32_t* draft, int n_draft, int ended, int32_t* tokens_out, float* logprobs_out,
+                        wlk_verify_result* result) {
+    if (!logits_host || !mask_host || !p0 || !draft || !tokens_out || !logprobs_out || !result) return fail(WLK_ERR_ARG, "NULL argument");
+    if (n_draft < 1 || n_draft > kMaxDraft || n_vocab < 1) return fail(WLK_ERR_ARG, "draft pick: 1..256 draft tokens");
+    if (!pick_params_ok(*p0, n_vocab)) return fail(WLK_ERR_ARG, "draft pick: rule parameters out of range");
+    return guarded([&]() {
+        const size_t V = (size_t)n_vocab, n_pos = (size_t)n_draft + 1;
+        float* logits = dev_alloc<float>(V * n_pos);
+        unsigned char* mask = nullptr;
+        int* ints = nullptr;                    // [draft n_draft | picks n_pos x 3 | result 4]
+        auto release = [&] {
+            (void)hipFree(logits);
+            if (mask) (void)hipFree(mask);
+            if (ints) (void)hipFree(ints);
+        };
+        try {
+            mask = dev_alloc<unsigned char>(V);
+            ints = dev_alloc<int>((size_t)n_draft + n_pos * 3 + 4);
+            int* picks = ints + n_draft;
+            int* res = picks + n_pos * 3;
+            copy_sync(logits, logits_host, V * n_pos * sizeof(float), hipMemcpyHostToDevice);
+            copy_sync(mask, mask_host, V, hipMemcpyHostToDevice);
+            copy_sync(ints, draft, sizeof(int) * (size_t)n_draft, hipMemcpyHostToDevice);
+            launch_draft_pick(LaunchCtx{nullptr, nullptr}, logits, n_vocab, mask, pick_rules_of(*p0), ints, n_draft, ended ? 1 : 0,
+                              picks, res, nullptr);
+            WLK_HIP(hipStreamSynchronize(nullptr));
+            std::vector<int> host(n_pos * 3 + 4);
+            copy_sync(host.data(), picks, host.size() * sizeof(int), hipMemcpyDeviceToHost);
+            for (size_t j = 0; j < n_pos; ++j) {
+                tokens_out[j] = host[3 * j];
+                std::memcpy(&logprobs_out[j], &host[3 * j + 1], 4);
+            }
+            const int* r4 = host.data() + n_pos * 3;
+            result->accepted = r4[0];
+            result->next_token = r4[1];
+            std::memcpy(&result->next_logprob, &r4[2], 4);
+            std::memcpy(&result->sum_logprob, &r4[3], 4);
+            result->no_speech_prob = NAN;
         } catch (...) {
             release();
             throw;

@@ -614,6 +614,49 @@ class HipWindowGroup:
         _lib.check(self.lib.wlk_group_align_fits(self._h, int(n_tokens), int(num_frames), C.byref(ok)))
         return bool(ok.value)
 
+    def verify(self, windows: Sequence[tuple], want_picks: bool = False) -> List[dict]:
+        """wlk_group_verify: how far greedy decoding at temperature 0 follows each window's draft, in ONE teacher-forced
+        decoder pass over all windows.  ``windows``: (session, initial tokens, draft tokens, sot_index, first-pick state,
+        no_speech_token or None) each, the session encoded and with ``set_rules`` lists.  -> per window a dict: ``accepted``
+        (k), ``next_token`` and ``next_logprob`` (the pick behind draft[:k]), ``sum_logprob`` (positions 0..k, added in that
+        order in float32), ``no_speech_prob``, and with ``want_picks`` (tests) ``picks`` = (token ids int32 [n_d + 1],
+        log-probabilities float32 [n_d + 1]) of every candidate position.  Afterwards each session is what its own prefill
+        of initial + draft[:k] leaves."""
+        n = len(windows)
+        arr = (_lib.VerifyWindow * max(n, 1))()
+        res = (_lib.VerifyResult * max(n, 1))()
+        keep, picks = [], []
+        vp = lambda a: a.ctypes.data_as(C.c_void_p).value
+        for i, (a, win) in enumerate(zip(arr, windows)):
+            sess, initial, draft, sot_index, state, no_speech = win
+            initial = [int(t) for t in initial]
+            draft = [int(t) for t in draft]
+            toks = np.ascontiguousarray(np.asarray(initial + draft, dtype=np.int64).reshape(-1))
+            a.s, a.tokens, a.n_initial, a.n_tokens = sess._h, vp(toks), len(initial), len(toks)
+            a.sot_index, a.no_speech_token = int(sot_index), -1 if no_speech is None else int(no_speech)
+            a.p = (C.c_int32 * 8)(*[int(state[f]) for f in HipSession.PICK_FIELDS])
+            a.result = C.pointer(res[i])
+            pk = np.zeros((len(draft) + 1, 2), np.int32) if want_picks else None
+            a.picks = vp(pk) if want_picks else None
+            keep.append(toks)
+            picks.append(pk)
+        _lib.check(self.lib.wlk_group_verify(self._h, arr, n))
+        out = []
+        for r, pk in zip(res[:n], picks):
+            o = dict(accepted=int(r.accepted), next_token=int(r.next_token), next_logprob=np.float32(r.next_logprob),
+                     sum_logprob=np.float32(r.sum_logprob), no_speech_prob=float(r.no_speech_prob))
+            if pk is not None:
+                o["picks"] = (pk[:, 0].copy(), pk[:, 1].copy().view(np.float32))
+            out.append(o)
+        return out
+
+    def verify_fits(self, n_initial: int, n_draft: int) -> bool:
+        """wlk_group_verify_fits: can a window of ``n_initial`` initial and ``n_draft`` draft tokens ride in :meth:`verify`?
+        A pure host function of the shape and the model."""
+        ok = C.c_int32()
+        _lib.check(self.lib.wlk_group_verify_fits(self._h, int(n_initial), int(n_draft), C.byref(ok)))
+        return bool(ok.value)
+
     def stats(self) -> Dict[str, float]:
         steps, rows = C.c_uint64(), C.c_uint64()
         _lib.check(self.lib.wlk_group_stats(self._h, C.byref(steps), C.byref(rows)))
@@ -653,6 +696,28 @@ def pick_rows(logits: np.ndarray, masks: np.ndarray, mask_of_row: Sequence[int],
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
     _lib.check(lib.wlk_diag_pick_rows(vp(lg), lg.shape[1], vp(mk), mk.shape[0], vp(mo), vp(prm), n, vp(out), vp(lp)))
     return out, lp
+
+
+def draft_pick(logits: np.ndarray, mask: np.ndarray, state: dict, draft: Sequence[int], ended: bool = False
+               ) -> Tuple[np.ndarray, np.ndarray, dict]:
+    """wlk_diag_draft_pick (tests): the two kernels behind ``HipWindowGroup.verify``'s decoder pass on host logits
+    [len(draft) + 1, V], one rule mask [V] uint8 and the first position's rule state.  -> (token ids, log-probabilities
+    of every position, dict(accepted, next_token, next_logprob, sum_logprob))."""
+    lib = _lib.load()
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    mk = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+    dr = np.ascontiguousarray(draft, dtype=np.int32).reshape(-1)
+    if lg.ndim != 2 or lg.shape[0] != dr.size + 1 or mk.size != lg.shape[1]:
+        raise ValueError("draft_pick: logits [len(draft) + 1, V] and a mask [V]")
+    prm = np.asarray([int(state[f]) for f in HipSession.PICK_FIELDS], dtype=np.int32)
+    out = np.empty(lg.shape[0], np.int32)
+    lp = np.empty(lg.shape[0], np.float32)
+    res = _lib.VerifyResult()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.wlk_diag_draft_pick(vp(lg), lg.shape[1], vp(mk), vp(prm), vp(dr), dr.size, int(bool(ended)), vp(out), vp(lp),
+                                       C.byref(res)))
+    return out, lp, dict(accepted=int(res.accepted), next_token=int(res.next_token), next_logprob=np.float32(res.next_logprob),
+                         sum_logprob=np.float32(res.sum_logprob))
 
 
 def pick_advance(states: Sequence[dict], tokens: Sequence[int]) -> List[dict]:

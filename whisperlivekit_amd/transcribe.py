@@ -15,6 +15,9 @@ applies them on the device (``wlk_pick_greedy``), and so does beam search with 2
 ride in one launch chain per token (``WindowStacker`` / ``decode_many`` over ``wlk_group_step_pick``); with
 WLK_TRANSCRIBE_ALIGN_STACK=1 on top of it (or ``HipWhisperASR(stack=n, align_stack=True)``; off by default) the word alignment of
 the windows those calls have waiting shares one stacked pass as well (``AlignStacker`` over ``wlk_group_find_alignment``).
+With a ``draft`` (``DecodingOptions.draft``, ``decode_many(drafts=...)``, ``transcribe(draft=WindowDraft)``; off unless given) a
+stacked greedy window opens with ONE teacher-forced pass that verifies the tokens an earlier call sampled
+(``wlk_group_verify``) instead of a prefill and one step per token already known.
 There is no CPU model path: without the library / a GPU the first call raises.
 
 Same keyword names, defaults and result dictionary as the reference; ``fp16`` is accepted and ignored (the path computes
@@ -62,6 +65,9 @@ class DecodingOptions:
     without_timestamps: bool = False
     max_initial_timestamp: Optional[float] = 1.0
     fp16: bool = False            # accepted for signature compatibility; the HIP path is fp32
+    # not in the reference: the tokens an earlier decode of (a prefix of) this window sampled; the greedy temperature-0
+    # path verifies them in one decoder pass instead of re-deriving them token by token
+    draft: Optional[Sequence[int]] = None
 
 
 @dataclass(frozen=True)
@@ -226,6 +232,76 @@ def _greedy_take(tokens: np.ndarray, sum_logprobs: np.ndarray, nxt_id: int, pick
         nxt_id = eot
     tokens = np.concatenate([tokens, np.asarray([[nxt_id]], np.int64)], axis=1)
     return tokens, bool(nxt_id == eot or tokens.shape[-1] > n_ctx)
+
+
+def _accept_draft(picks: Sequence[Tuple[int, float]], draft: Sequence[int], eot: Optional[int] = None,
+                  ended: bool = False) -> Tuple[int, int, np.float32, np.float32]:
+    """How far the greedy loop follows ``draft``: the host statement of ``draft_accept_kernel`` (csrc/select.hip).
+    ``picks[j]`` = (token, log-probability) of the greedy pick behind ``draft[:j]``, j = 0 .. len(draft).  -> (k, next
+    token, its log-probability, sum): k = the first position whose pick is not the draft's token (len(draft) when there
+    is none), next = the pick at k, sum = the log-probabilities of positions 0 .. k added in that order in float32 - the
+    order in which `_greedy_take` accumulates.  ``ended``: the token in front of position 0 is ``eot`` already; as in
+    `_greedy_take` the sequence then takes ``eot`` whatever was picked and nothing is added."""
+    n = len(draft)
+    if len(picks) != n + 1:
+        raise ValueError("one pick per draft position and one behind the draft")
+    k = n
+    for j in range(n):
+        if int(picks[j][0]) != int(draft[j]) or (ended and j == 0):
+            k = j
+            break
+    total = np.float32(0.0)
+    for j in range(1 if ended else 0, k + 1):
+        total = np.float32(total + np.float32(picks[j][1]))
+    nxt = int(eot) if (ended and k == 0) else int(picks[k][0])
+    return k, nxt, np.float32(picks[k][1]), total
+
+
+def clamp_draft(draft: Optional[Sequence[int]], n_initial: int, sample_len: int, n_ctx: int, eot: int) -> List[int]:
+    """The part of ``draft`` a verify pass may carry behind ``n_initial`` initial tokens: cut in front of its first
+    <|endoftext|> (a sampled history never holds one), then to min(sample_len - 1, n_ctx - n_initial - 1, 256 - n_initial)
+    tokens - the window samples at most ``sample_len`` tokens and the pick behind the draft is one of them, that pick's
+    token still needs a text position, and the stacked pass takes 256 rows."""
+    out = []
+    for t in draft or []:
+        if int(t) == eot:
+            break
+        out.append(int(t))
+    room = min(sample_len - 1, n_ctx - n_initial - 1, 256 - n_initial)
+    return out[:max(room, 0)]
+
+
+class WindowDraft:
+    """What one LocalAgreement session remembers between two ``transcribe`` calls on its growing buffer: the tokens the
+    first window of the last call sampled, and the audio that call saw.  :meth:`begin` hands the tokens out as the next
+    call's draft when the new audio begins with the remembered audio sample for sample; a buffer that was trimmed (or any
+    other audio) gets none.  Not shared between sessions and not thread-safe: one per session."""
+
+    def __init__(self):
+        self.tokens: List[int] = []
+        self.audio: Optional[np.ndarray] = None
+        self.offered = 0               # calls that were handed a draft
+        self.dropped = 0               # calls whose audio did not extend the remembered audio
+
+    def begin(self, audio: np.ndarray) -> List[int]:
+        """-> the draft for a call over ``audio`` (may be empty); the memory now holds ``audio`` and no tokens."""
+        audio = np.asarray(audio, dtype=np.float32).reshape(-1)
+        prev, tokens = self.audio, self.tokens
+        self.audio, self.tokens = audio.copy(), []
+        if prev is None or not tokens:
+            return []
+        n = min(len(prev), len(audio))
+        if n == 0 or not np.array_equal(prev[:n], audio[:n]):
+            self.dropped += 1
+            return []
+        self.offered += 1
+        return list(tokens)
+
+    def remember(self, tokens: Sequence[int]) -> None:
+        self.tokens = [int(t) for t in tokens]
+
+    def reset(self) -> None:
+        self.tokens, self.audio = [], None
 
 
 class _GreedyWindow:
@@ -590,6 +666,13 @@ def resolve_align_stack(flag: Optional[bool]) -> bool:
     return bool(flag)
 
 
+def resolve_draft(flag: Optional[bool]) -> bool:
+    """``HipWhisperASR(draft=...)``: an explicit value wins; ``None`` reads ``WLK_TRANSCRIBE_DRAFT`` (default off)."""
+    if flag is None:
+        return os.environ.get("WLK_TRANSCRIBE_DRAFT", "0").strip().lower() in ("1", "true", "on", "yes")
+    return bool(flag)
+
+
 def set_align_stack(model, flag: Optional[bool]) -> bool:
     """Switches the stacked word alignment of ``model`` on or off; ``None`` leaves it to ``WLK_TRANSCRIBE_ALIGN_STACK``.
     It only acts while the stacked windows are on as well (:func:`set_stack` / ``WLK_TRANSCRIBE_STACK`` >= 1).  -> the
@@ -802,12 +885,34 @@ class _WindowDecoder:
         """The one sequence of the greedy loop: row 0 of `_pick_states`."""
         return self._pick_states(tokens[:1])[0]
 
+    # -- draft verification (DESIGN 29) --------------------------------------------------------------------------------
+    def draft_window(self, session, initial: Sequence[int], group) -> Optional[tuple]:
+        """The ``HipWindowGroup.verify`` window of this decoder's draft behind ``initial`` in ``session`` (encoded, rules
+        set), or None: no draft is left after clamping, or the range is outside the stacked pass."""
+        draft = clamp_draft(self.o.draft, len(initial), self.sample_len, self.n_ctx, self.tok.eot)
+        if not draft or not group.verify_fits(len(initial), len(draft)):
+            return None
+        state = self._pick_state(np.asarray([list(initial)], np.int64))
+        return (session, list(initial), draft, self.sot_index, state, self.tok.no_speech)
+
+    def takes_draft(self, session) -> bool:
+        """the conditions of `run`'s device-rules greedy path, for a caller (`decode_many`) that verifies ahead of `run`"""
+        o = self.o
+        return (o.draft is not None and o.beam_size is None and self.n_group == 1 and o.temperature == 0
+                and o.language is not None and o.task != "lang_id" and hasattr(session, "pick_greedy")
+                and os.environ.get("WLK_TRANSCRIBE_DEVICE_RULES", "1") != "0")
+
+    def set_rules(self, session) -> None:
+        session.set_rules(self.suppressed or [], self.blank_ids or [])
+
     # -- the loop ------------------------------------------------------------------------------------------------------
     def run(self, mel_segment: Optional[np.ndarray], session: Optional[HipSession] = None, *,
-            stacker: Optional[WindowStacker] = None, defer: bool = False):
+            stacker: Optional[WindowStacker] = None, defer: bool = False, verified: Optional[dict] = None):
         """-> the window's DecodingResult.  ``stacker``: the greedy temperature-0 steps behind the first pick go through it
         (default: the model's, when stacking is switched on).  ``defer`` (`decode_many`): a window that reaches those steps
-        comes back as ``(_GreedyWindow, finish)`` instead - the caller advances it and calls ``finish()`` for the result."""
+        comes back as ``(_GreedyWindow, finish)`` instead - the caller advances it and calls ``finish()`` for the result.
+        ``verified`` (`decode_many`): what ``HipWindowGroup.verify`` returned for this window's `draft_window`, with that
+        window's draft under the key ``draft`` - the session is encoded and verified already."""
         o, tok, V = self.o, self.tok, self.model.dims.n_vocab
         rows = self.n_group
         s = session or _rows_of(self.model).get(rows)
@@ -839,7 +944,7 @@ class _WindowDecoder:
         device_beam = (beam is not None and 2 <= o.beam_size <= 7 and o.temperature == 0 and hasattr(s, "pick_topk")
                        and os.environ.get("WLK_TRANSCRIBE_DEVICE_BEAM", "0") == "1")
         if device_rules or device_beam:
-            s.set_rules(self.suppressed or [], self.blank_ids or [])
+            self.set_rules(s)
         if device_rules and stacker is None:
             stacker = _run_stacker(self.model)
         stacked = stacker if device_rules else None
@@ -867,6 +972,33 @@ class _WindowDecoder:
             return DecodingResult(language=language, language_probs=language_probs, tokens=out, text=text,
                                   avg_logprob=sums[best] / (len(out) + 1), no_speech_prob=no_speech,
                                   temperature=o.temperature, compression_ratio=compression_ratio(text))
+
+        if stacked is not None and verified is None and o.draft is not None:
+            # ONE teacher-forced pass over [initial | draft] instead of the prefill, the first pick and a step per
+            # accepted token; a range the group refuses on the host (nothing launched, the session untouched) and an
+            # unusable draft take the statements below
+            win = self.draft_window(s, initial, stacked.group)
+            if win is not None:
+                try:
+                    verified = dict(stacked.group.verify([win])[0], draft=win[2])
+                except Exception as e:
+                    if not _refused(e):
+                        raise
+        if stacked is not None and verified is not None:
+            k = int(verified["accepted"])
+            taken = initial + [int(t) for t in verified["draft"][:k]] + [int(verified["next_token"])]
+            tokens = np.asarray([taken], np.int64)
+            sum_logprobs[0] = np.float32(verified["sum_logprob"])
+            if tok.no_speech is not None:
+                no_speech = float(verified["no_speech_prob"])
+            # the loop below, entered behind its iteration k: k + 1 tokens are sampled
+            if tokens[0, -1] == tok.eot or tokens.shape[-1] > self.n_ctx or k + 1 >= self.sample_len:
+                return finish(tokens, sum_logprobs)
+            window = _GreedyWindow(self, s, tokens, sum_logprobs, self.sample_len - 1 - k)
+            if defer:
+                return window, lambda: finish(window=window)
+            stacked.run(window)
+            return finish(window=window)
 
         sources = None
         for i in range(self.sample_len):
@@ -922,19 +1054,24 @@ class _WindowDecoder:
 
 
 def decode(model: HipWhisperModel, mel: Optional[np.ndarray], options: DecodingOptions = DecodingOptions(), *,
-           session: Optional[HipSession] = None, **kwargs) -> DecodingResult:
-    """decoding.py:787-820 for one 30 s segment [n_mels, 3000] (None: the session already holds the encoded window)."""
+           session: Optional[HipSession] = None, stacker: Optional[WindowStacker] = None, **kwargs) -> DecodingResult:
+    """decoding.py:787-820 for one 30 s segment [n_mels, 3000] (None: the session already holds the encoded window).
+    ``stacker``: the window stacker of the greedy temperature-0 steps (default: the model's, when stacking is switched on);
+    ``options.draft`` acts only where there is one."""
     if kwargs:
         options = replace(options, **kwargs)
-    return _WindowDecoder(model, options).run(mel, session)
+    return _WindowDecoder(model, options).run(mel, session, stacker=stacker)
 
 
 def decode_many(model: HipWhisperModel, mels: Sequence[np.ndarray], options: DecodingOptions = DecodingOptions(), *,
-                stacker: Optional[WindowStacker] = None, **kwargs) -> List[DecodingResult]:
+                stacker: Optional[WindowStacker] = None, drafts: Optional[Sequence[Optional[Sequence[int]]]] = None,
+                **kwargs) -> List[DecodingResult]:
     """decoding.py:787-820 for up to 8 segments [n, n_mels, 3000] at once, greedy at temperature 0: one result per window,
     in order.  Encoder, language detection, prefill, first pick and no-speech probability are each window's own (one
     session per window); from there every token of all windows still alive is ONE ``HipWindowGroup.step_pick``.  A window
-    leaves at <|endoftext|>, at sample_len or at n_ctx; the others go on."""
+    leaves at <|endoftext|>, at sample_len or at n_ctx; the others go on.  ``drafts`` (one entry per window, None = none):
+    after their encodes, the windows with a usable draft open with ONE ``HipWindowGroup.verify`` for all of them instead of
+    a prefill and a first pick each; the others open as before."""
     if kwargs:
         options = replace(options, **kwargs)
     if options.temperature != 0 or options.beam_size is not None or options.best_of is not None:
@@ -942,10 +1079,42 @@ def decode_many(model: HipWhisperModel, mels: Sequence[np.ndarray], options: Dec
     mels = [np.asarray(m) for m in mels]
     if not 1 <= len(mels) <= 8:
         raise ValueError("decode_many takes 1..8 windows")
+    if drafts is not None and len(drafts) != len(mels):
+        raise ValueError("decode_many: one draft (or None) per window")
     if stacker is None:
         stacker = _with_model_burst(model, window_stacker(model, 8))
     sessions =_rows_of(model).windows(len(mels))
+    if drafts is not None and any(d is not None for d in drafts):
+        return _decode_many_drafts(model, mels, sessions, options, stacker, drafts)
     opened = [_WindowDecoder(model, options).run(mel, s, stacker=stacker, defer=True) for mel, s in zip(mels, sessions)]
+    stacker.run_many([r[0] for r in opened if isinstance(r, tuple)])
+    return [r[1]() if isinstance(r, tuple) else r for r in opened]
+
+
+def _decode_many_drafts(model, mels, sessions, options, stacker, drafts) -> List[DecodingResult]:
+    """`decode_many` with drafts: every window is encoded first, the windows with a usable draft share one verify pass, then
+    each window opens (from its verify result, or with its own prefill and first pick) and all go on in the stacker."""
+    decoders = [_WindowDecoder(model, replace(options, draft=d)) for d in drafts]
+    windows: List[Optional[tuple]] = []
+    for dec, mel, s in zip(decoders, mels, sessions):
+        s.encode_mel(pad_or_trim(mel))
+        win = None
+        if dec.takes_draft(s):
+            dec.set_rules(s)
+            win = dec.draft_window(s, dec.initial, stacker.group)
+        windows.append(win)
+    verified: List[Optional[dict]] = [None] * len(mels)
+    riding = [i for i, w in enumerate(windows) if w is not None]
+    if riding:
+        try:
+            for i, res in zip(riding, stacker.group.verify([windows[i] for i in riding])):
+                verified[i] = dict(res, draft=windows[i][2])
+        except Exception as e:                     # refused on the host: nothing was launched, every window opens on its own
+            if not _refused(e):
+                raise
+    # a window without a verify result still carries its draft into `run`, which then tries it alone (a refusal of the
+    # joint call may have been another window's)
+    opened = [dec.run(None, s, stacker=stacker, defer=True, verified=v) for dec, s, v in zip(decoders, sessions, verified)]
     stacker.run_many([r[0] for r in opened if isinstance(r, tuple)])
     return [r[1]() if isinstance(r, tuple) else r for r in opened]
 
@@ -992,9 +1161,15 @@ def transcribe(model: HipWhisperModel, audio, *, verbose: Optional[bool] = None,
                initial_prompt: Optional[str] = None, carry_initial_prompt: bool = False, word_timestamps: bool = False,
                prepend_punctuations: str = T.PREPEND_PUNCTUATIONS, append_punctuations: str = T.APPEND_PUNCTUATIONS,
                clip_timestamps: Union[str, List[float]] = "0", hallucination_silence_threshold: Optional[float] = None,
-               **decode_options) -> dict:
+               draft: Optional[WindowDraft] = None, **decode_options) -> dict:
     """-> {"text", "segments": [{"id", "seek", "start", "end", "text", "tokens", "temperature", "avg_logprob",
-    "compression_ratio", "no_speech_prob", ("words")}], "language"}."""
+    "compression_ratio", "no_speech_prob", ("words")}], "language"}.
+
+    ``draft`` (not in the reference): one session's memory across the calls on its growing buffer.  The first
+    window of the call (seek 0) at the first temperature of the ladder, when that is 0, verifies the tokens the same
+    window sampled in the previous call, provided this call's audio begins with that call's audio; on return the memory
+    holds this call's audio and first window.  Fallback temperatures, later windows, beam search and sampling never see
+    it, and the result is the one the call gives without it."""
     if isinstance(audio, str):
         raise TypeError("transcribe: pass samples (float32, 16 kHz); decoding a file is outside the accelerated path")
     if hasattr(audio, "detach"):
@@ -1002,6 +1177,7 @@ def transcribe(model: HipWhisperModel, audio, *, verbose: Optional[bool] = None,
     audio = np.ascontiguousarray(audio, dtype=np.float32).reshape(-1)
     decode_options = dict(decode_options)
     decode_options["fp16"] = False
+    draft_tokens = draft.begin(audio) if draft is not None else []
     dims = model.dims
     session = _rows_of(model).get(1)
 
@@ -1037,10 +1213,12 @@ def transcribe(model: HipWhisperModel, audio, *, verbose: Optional[bool] = None,
 
     temperatures = [temperature] if isinstance(temperature, (int, float)) else list(temperature)
 
-    def decode_with_fallback(segment: np.ndarray) -> DecodingResult:
+    def decode_with_fallback(segment: np.ndarray, window_draft: Optional[List[int]] = None) -> DecodingResult:
         result = None
         for n, t in enumerate(temperatures):
             kw = dict(decode_options)
+            if window_draft and n == 0 and t == 0 and kw.get("beam_size") is None:
+                kw["draft"] = window_draft
             if t > 0:
                 kw.pop("beam_size", None)         # sampling: no beam
                 kw.pop("patience", None)
@@ -1083,6 +1261,7 @@ def transcribe(model: HipWhisperModel, audio, *, verbose: Optional[bool] = None,
     last_speech_timestamp = 0.0
     clip_idx = 0
     seek = clips[0][0]
+    n_windows = 0
     while clip_idx < len(clips):
         clip_start, clip_end = clips[clip_idx]
         if seek < clip_start:
@@ -1105,7 +1284,11 @@ def transcribe(model: HipWhisperModel, audio, *, verbose: Optional[bool] = None,
             decode_options["prompt"] = all_tokens[prompt_reset_since:]
 
         encoded_in[0] = None
-        result = decode_with_fallback(mel_segment)
+        first_window = draft is not None and n_windows == 0 and seek == 0
+        n_windows += 1
+        result = decode_with_fallback(mel_segment, draft_tokens if first_window else None)
+        if first_window:
+            draft.remember(result.tokens)
         tokens = np.asarray(result.tokens, dtype=np.int64)
 
         if no_speech_threshold is not None:
