@@ -986,7 +986,10 @@ typedef struct wlk_diag_sf_kernel_args {
 int wlk_diag_sf_kernel(const wlk_diag_sf_kernel_args* args);
 /* ONE linear layer C = epilogue(LayerNorm?(A) W^T + bias) on host data through a production launcher, unchanged, with
  * every operand a launch can carry.  route: 0 = launch_linear's own choice, 1 = launch_gemv, 2 / 3 / 4 = launch_gemm
- * with force_kernel (k-wave, 64x64, k-pipe), 5 .. 8 = launch_gemm_kp as wlk_diag_linear encodes them.
+ * with force_kernel (k-wave, 64x64, k-pipe), 5 .. 8 = launch_gemm_kp as wlk_diag_linear encodes them (5 = its own choice,
+ * 6 = 16 x 16 k-wave tiles, 7 / 8 = 32 x 32 k-wave tiles with two buffers / one), 500 + 10 tm + tn = launch_gemm_kp with the
+ * k-pipe kernel's tile tm x tn: an instantiated tile and a shape the kp family gives to the k-pipe kernel (k % 128 == 0,
+ * k >= 256, m >= 512), anything else is refused.
  *   a [a_floats] rows lda apart, w [n][k], bias [n] or NULL, ln_gamma / ln_beta [k] or NULL (fused LayerNorm of the rows),
  *   c [c_floats] rows ldc apart, arriving as the caller filled it.  Residual (flags & 2): r [r_floats] rows ldr apart, or
  *   with r_is_c the output buffer itself (its preloaded values; ldr = ldc).
@@ -1023,6 +1026,13 @@ int wlk_diag_linear_ex(const wlk_diag_linear_args* args);
  * function launch_gemv itself switches on; needs no device.  A shape launch_gemv refuses returns WLK_ERR_ARG and the
  * refusal as text. */
 int wlk_diag_gemv_variant(int m, int n, int k, int has_ln, int kv_mode, char* out_text, int cap);
+/* Which tiled GEMM kernel a launch of m x n x k takes on route `route` of wlk_diag_linear_ex (0, 2 .. 8, 500 + 10 tm + tn;
+ * batch operand sets, has_cache: the fused cache append), as text: "gemm<64,64>", "gemm<32,64>", "kwave<gemm>",
+ * "kwave16<gemm>" (launch_gemm), "kwave<kp,2>", "kwave<kp,1>", "kwave16<kp>" (launch_gemm_kp's k-wave forms with two buffers
+ * / one / 16 x 16 tiles), "kpipe<tm,tn>" (either launcher).  The answer of the function both launchers launch; needs no
+ * device.  What a launcher refuses, a launch the GEMV kernels take and a tile route wlk_diag_linear_ex refuses return
+ * WLK_ERR_ARG and the refusal as text. */
+int wlk_diag_gemm_plan(int m, int n, int k, int route, int batch, int has_cache, char* out_text, int cap);
 /* ONE encoder operator on host data through its production launcher, unchanged.  kind:
  *   WLK_ENC_X3_GEMM    launch_gemm_x3: C = epilogue(A W^T + bias), m x n x k.  a = `in` (fp32 rows ld_in apart, packed on the
  *                      device with launch_x3_pack) or `in3` (an X3 row image, rows 3 ld_in apart); w [n][k] (launch_x3_pack_w);

@@ -25,8 +25,8 @@ def _add(name, m, n, k, routes=(1,), table=None, **kw):
     table = SPECS if table is None else table
     spec = dict(m=m, n=n, k=k, routes=tuple(routes), ln=False, bias=True, flags=0, scale=0.125, scale_cols=0,
                 scale_period=0, r_is_c=False, kv_mode=0, kv_d=0, kv_pos=0, kv_ctx=0, kv_ntok=1, kv_rows=None, n_caches=0,
-                kv_layer_off=0, batch=0, rows=("normal",), spread=False, res_scale=1.0)
-    assert name not in SPECS and name not in REFUSED_SPECS and set(kw) <= set(spec), (name, kw)
+                kv_layer_off=0, batch=0, rows=("normal",), spread=False, res_scale=1.0, lda=0, ldr=0)
+    assert name not in table and name not in SPECS and name not in REFUSED_SPECS and set(kw) <= set(spec), (name, kw)
     spec.update(kw)
     table[name] = spec
 
@@ -97,6 +97,8 @@ _add("gemm_period_kp", 40, 120, 256, routes=(6, 7, 8), **_P)
 # the decoder prefill's append: rows [beam][token]
 _add("gemm_prefill_2x7", 14, 120, 256, routes=(0,), flags=SCALE, scale_cols=80, kv_mode=1, kv_d=40, kv_ctx=12, kv_pos=3, kv_ntok=7)
 _add("gemm_prefill_2x70", 140, 120, 256, routes=(0,), flags=SCALE, scale_cols=80, kv_mode=1, kv_d=40, kv_ctx=75, kv_pos=3, kv_ntok=70)
+# rows of a further apart than k and rows of r at another distance than the rows of c (lda, ldr: 0 = k, the distance of c's rows)
+_add("gemm_strides_32x64", 37, 70, 36, routes=(3,), flags=RESIDUAL, lda=44, ldr=70 + 12)
 # operand tables
 _add("gemm_batch3_64x64", 512, 513, 36, routes=(3,), batch=3, flags=GELU | RESIDUAL, spread=True)
 _add("gemm_batch3_kpipe", 512, 120, 256, routes=(4,), batch=3, flags=RESIDUAL, r_is_c=True)
@@ -147,16 +149,34 @@ def _rows(rng, kinds, z, m, k, ln):
     return a
 
 
+PAD = 4                                 # pad columns of the rows of c
+
+
 def case(name):
     """-> the spec of `name` plus its arrays: a [Z][m][k], w [n][k], bias [n] / None, gamma, beta [k] / None, r [Z][m][n] /
     None (with r_is_c: what the output buffer holds on arrival), and the cache geometry"""
-    s = dict(SPECS[name] if name in SPECS else REFUSED_SPECS[name])
+    return build(name, SPECS[name] if name in SPECS else REFUSED_SPECS[name])
+
+
+def build(name, spec):
+    """the arrays of spec `spec`, seeded by `name`.  lda = 0: the rows of a lie k (rounded up to 4) apart.  lda < k: the rows
+    overlap - a_flat [Z][(m - 1) lda + k] is the signal and a its strided view.  ldr = 0: the rows of r lie as far apart as
+    the rows of c (ldc = n + PAD)."""
+    s = dict(spec)
     rng = np.random.default_rng(zlib.crc32(name.encode()))
     m, n, k = s["m"], s["n"], s["k"]
     z = max(s["batch"], 1)
     c = s
     c["name"] = name
-    c["a"] = _rows(rng, s["rows"], z, m, k, s["ln"])
+    c["ldc"] = n + PAD
+    c["ldr"] = c["ldc"] if s["r_is_c"] or not s["ldr"] else s["ldr"]
+    if s["lda"] and s["lda"] < k:
+        assert not s["ln"] and s["lda"] % 4 == 0, name
+        c["a_flat"] = rng.standard_normal((z, (m - 1) * s["lda"] + k)).astype(np.float32)
+        c["a"] = np.lib.stride_tricks.as_strided(c["a_flat"], (z, m, k), (c["a_flat"].strides[0], 4 * s["lda"], 4), writeable=False)
+    else:
+        c["a_flat"] = None
+        c["a"] = _rows(rng, s["rows"], z, m, k, s["ln"])
     w = (rng.standard_normal((n, k)) / np.sqrt(k)).astype(np.float32)
     if s["spread"]:
         w *= np.float32(0.25)
@@ -198,6 +218,7 @@ def alone(c, z, row):
     s = dict(c)
     s.update(m=1, batch=0, kv_mode=0, kv_rows=None, cache_floats=0, cache_stride=0, name=f"{c['name']}[{z}][{row}]")
     s["a"] = c["a"][z:z + 1, row:row + 1]
+    s["a_flat"], s["lda"] = None, 0
     s["r"] = c["r"][z:z + 1, row:row + 1] if c["r"] is not None else None
     return s
 
@@ -224,4 +245,12 @@ def mutants(c):
         out.append("residual_before_act")
     if c["bias"] is not None:
         out.append("bias_drop_last")
+    if c.get("lda") and c["lda"] != c["k"]:
+        out.append("lda_is_k")
+    if f & RESIDUAL and not c["r_is_c"] and c.get("ldr") and c["ldr"] != c["n"] + PAD:
+        out.append("ldr_is_ldc")
+    if c["k"] % 32:
+        out.append("k_tail_dropped")
+    if c["m"] >= 2:
+        out.append("tail_row_clamped")
     return out

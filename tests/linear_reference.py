@@ -7,7 +7,7 @@ One function, `linear`, evaluates the whole operation in a given dtype, in a fix
   5 exact-erf GELU   6 ReLU   7 x / (1 + exp(-x))   8 + R   9 the self-attention cache image after the append
 float64 (`dt=np.float64`) is what the kernels are compared with; float32 (`dt=np.float32`, numpy float32 throughout) is
 the restatement whose distance from the float64 form sizes the tolerance, nothing else.  `mutant` names a deliberate
-mistake (tests/test_linear_reference_cpu.py shows that the cases tell each from the reference); the GPU test never passes
+mistake (tests/test_linear_reference_cpu.py shows that the cases tell each from the reference); the GPU tests never pass
 one.  No torch in here.
 
 Cache image (step 9): columns [kv_d, 2 kv_d) of an output row go to the K cache, [2 kv_d, 3 kv_d) to the V cache, at float
@@ -27,7 +27,8 @@ from select_reference import FLOOR, KERNEL_FACTOR, abs_err, value_tolerance  # n
 GELU, RESIDUAL, SCALE, RELU, SWISH = 1, 2, 4, 8, 16          # GemmFlags (csrc/common.h)
 
 MUTANTS = ("scale_boundary", "scale_no_period", "append_pos1", "append_ntok1", "steprow_row0", "ln_eps6", "ln_unbiased",
-           "gelu_tanh", "residual_before_act", "bias_drop_last")
+           "gelu_tanh", "residual_before_act", "bias_drop_last", "lda_is_k", "ldr_is_ldc", "k_tail_dropped",
+           "tail_row_clamped")
 
 # Factor that an output may use instead of KERNEL_FACTOR, keyed by kernel family (linear_cases.family): twice the largest
 # kernel_err / restatement_err ratio measured on an MI355X over the whole table, rounded up to a power of two, for a kernel
@@ -79,10 +80,33 @@ def cache_indices(c, mutant=None):
     return base[:, None].astype(np.int64) + np.arange(d)[None, :]
 
 
+def a_signal(c):
+    """-> float32 [Z][(m - 1) lda + k]: the floats of every operand set of a as they lie in memory, rows lda apart -
+    c["a_flat"] where the rows overlap (lda < k), else the rows of c["a"] with zeros between them"""
+    if c.get("a_flat") is not None:
+        return np.asarray(c["a_flat"], np.float32)
+    z, m, k = c["a"].shape
+    lda = c.get("lda") or k
+    flat = np.zeros((z, (m - 1) * lda + k), np.float32)
+    flat[:, np.arange(m)[:, None] * lda + np.arange(k)[None, :]] = c["a"]
+    return flat
+
+
+def _misread(flat, rows, cols, ld):
+    """element (i, j) of every set taken from flat[i * ld + j] (wrapping at the end): rows read with the wrong stride"""
+    return flat[:, (np.arange(rows)[:, None] * ld + np.arange(cols)[None, :]) % flat.shape[1]]
+
+
 def linear(c, dt=np.float64, mutant=None):
-    """c: a case of tests/linear_cases.py.  -> out [Z][m][n] in dt (Z = max(batch, 1))."""
+    """c: a case of tests/linear_cases.py or tests/gemm_tile_cases.py.  -> out [Z][m][n] in dt (Z = max(batch, 1)).
+    c["a"] holds the rows whatever their distance in memory (with lda < k: a strided view of the flat signal)."""
     one = dt(1.0)
-    a = np.asarray(c["a"], np.float32).astype(dt)                         # [Z][m][k]
+    a = np.asarray(c["a"], np.float32)                                    # [Z][m][k]
+    if mutant == "lda_is_k":                                              # the rows read as if they lay k apart
+        a = _misread(a_signal(c), c["m"], c["k"], c["k"])
+    a = a.astype(dt)
+    if mutant == "k_tail_dropped":                                        # the last k % 32 columns never reach the product
+        a[..., c["k"] - c["k"] % 32:] = 0
     w = np.asarray(c["w"], np.float32).astype(dt)
     flags = c["flags"]
     with np.errstate(over="ignore", under="ignore"):
@@ -104,6 +128,11 @@ def linear(c, dt=np.float64, mutant=None):
             cols = scaled_columns(c["n"], c["scale_cols"], c["scale_period"], mutant)
             y = np.where(cols, y * dt(np.float32(c["scale"])), y).astype(dt)
         res = c["r"].astype(dt) if flags & RESIDUAL else None
+        if res is not None and mutant == "ldr_is_ldc":                    # r read with the rows of c's distance
+            ldr, m, n = c["ldr"], c["m"], c["n"]
+            flat = np.zeros((res.shape[0], m * ldr), dt)
+            flat[:, np.arange(m)[:, None] * ldr + np.arange(n)[None, :]] = res
+            res = _misread(flat, m, n, c["ldc"])
         if res is not None and mutant == "residual_before_act":
             y, res = (y + res).astype(dt), None
         if flags & GELU:
@@ -114,6 +143,9 @@ def linear(c, dt=np.float64, mutant=None):
             y = (y / (one + np.exp(-y, dtype=dt))).astype(dt)
         if res is not None:
             y = (y + res).astype(dt)
+        if mutant == "tail_row_clamped":                                  # the clamp of a tail row's loads leaking into its store
+            y = y.copy()
+            y[:, -1] = y[:, -2]
     return y
 
 

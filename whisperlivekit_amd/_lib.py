@@ -392,6 +392,7 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_sf_kernel": (cint, [C.POINTER(DiagSfKernelArgs)]),
         "wlk_diag_linear_ex": (cint, [C.POINTER(DiagLinearArgs)]),
         "wlk_diag_gemv_variant": (cint, [cint, cint, cint, cint, cint, C.c_char_p, cint]),
+        "wlk_diag_gemm_plan": (cint, [cint, cint, cint, cint, cint, cint, C.c_char_p, cint]),
         "wlk_diag_enc_op": (cint, [C.POINTER(DiagEncOpArgs)]),
         "wlk_diag_x3_plan": (cint, [cint, cint, cint, cint, cint, C.c_char_p, cint]),
         "wlk_diag_word_align": (cint, [C.POINTER(DiagWordAlignArgs)]),
@@ -449,7 +450,7 @@ EXPORTED_SYMBOLS = (
     "wlk_diag_linear_x3", "wlk_diag_linear_x3_time", "wlk_diag_layernorm_x3",
     "wlk_diag_encoder_attention_x3", "wlk_diag_encoder_attention_x3_time", "wlk_diag_qkv_x3_attention",
     "wlk_diag_select", "wlk_diag_dec_attention", "wlk_diag_topk", "wlk_diag_sf_kernel", "wlk_diag_nllb_align",
-    "wlk_diag_nllb_align_rows", "wlk_diag_linear_ex", "wlk_diag_gemv_variant", "wlk_diag_enc_op",
+    "wlk_diag_nllb_align_rows", "wlk_diag_linear_ex", "wlk_diag_gemv_variant", "wlk_diag_gemm_plan", "wlk_diag_enc_op",
     "wlk_diag_x3_plan", "wlk_diag_word_align", "wlk_diag_nllb_cross_ragged",
     "wlk_model_set_cif", "wlk_cif_result", "wlk_diag_cif",
     "wlk_group_create", "wlk_group_destroy", "wlk_group_step_pick", "wlk_group_stats", "wlk_group_export_logits",

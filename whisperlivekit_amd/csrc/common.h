@@ -240,7 +240,8 @@ struct GemmArgs {
     const AlignArgs* side_align = nullptr;
     int side_blocks = 0, side_zf = 0;
     bool force_kwave = false;            // diagnostics: take the k-wave kernel (under-filled grids) whatever the shape
-    int force_kernel = 0;                // diagnostics / A-B: 0 = by shape, 2 = k-wave, 3 = the 64x64 kernel, 4 = the one-tile-per-CU k-pipe kernel
+    int force_kernel = 0;                // diagnostics / A-B: 0 = by shape, 2 = k-wave, 3 = the 64x64 kernel, 4 = the one-tile-per-CU k-pipe kernel;
+                                         // launch_gemm_kp: 6 / 7 / 8 = its k-wave forms, 500 + 10 tm + tn = the k-pipe tile tm x tn
     bool gemm_plain_loop = false;        // A/B switch: LDS fragment reads right before use instead of a group ahead
 };
 // First statement of every kernel that takes GemmArgs by value: the hot block above is requested together and held in
@@ -258,6 +259,24 @@ void launch_gemm(const LaunchCtx& ctx, const GemmArgs& g, const char* tag);
 // the "kp" family: one per-element arithmetic (the k-pipe kernel's) for every tile, so stacked rows keep their solo results
 void launch_gemm_kp(const LaunchCtx& ctx, const GemmArgs& g, const char* tag);
 bool gemm_kp_takes_kpipe(int M, int N, int K);
+bool gemm_kpipe_has_tile(int tm, int tn);     // is gemm_nt_f32_kpipe_kernel<tm, tn> instantiated?
+// What launch_gemm (kp_family false) or launch_gemm_kp (true) launches for a set of arguments: the kernel and, for the
+// k-pipe kernel, its tile - or why the launcher refuses.  A pure host function of the shape, the force_* fields and of
+// which operands are present (gemm_f32.hip); both launchers launch its answer and wlk_diag_gemm_plan prints it, so a
+// test can ask which instantiation a shape reaches.
+struct GemmPlan {
+    enum Kernel {
+        kRefused,
+        kTiled64, kTiled32,                 // gemm_nt_f32_kernel<64,64> / <32,64>
+        kKwave, kKwave16,                   // gemm_nt_f32_kwave_kernel<false>, gemm_nt_f32_kwave16_kernel<>
+        kKpipe,                             // gemm_nt_f32_kpipe_kernel<tm, tn>
+        kKpKwave2, kKpKwave1, kKpKwave16    // gemm_nt_f32_kwave_kernel<true> / <true, 1>, gemm_nt_f32_kwave16_kernel<true>
+    };
+    Kernel kernel = kRefused;
+    int tm = 0, tn = 0;             // kKpipe: the tile in units of 32 rows / columns
+    const char* refusal = nullptr;  // kRefused: the text the launcher throws
+};
+GemmPlan gemm_plan(const GemmArgs& g, bool kp_family);
 bool gemm_takes_kwave(int M, int N, int K);
 bool gemm_takes_ksplit(int M, int N, int K);  // ... for the one-tile-per-CU k-pipe kernel (encoder-sized problems)   // launch_gemm's shape rule for the k-wave kernel (under-filled grids)
 // weight-streaming path for M <= 8 rows (decode steps); same contract as launch_gemm

@@ -1167,6 +1167,13 @@ int wlk_diag_sf_kernel(const wlk_diag_sf_kernel_args* q) {
     }
 }
 
+/* Routes of wlk_diag_linear_ex and wlk_diag_gemm_plan above 8: 500 + 10 tm + tn, the k-pipe kernel's tile tm x tn through
+ * launch_gemm_kp (force_kernel carries the route). */
+static const char kRouteRule[] = "route in [0, 8], or 500 + 10 tm + tn for an instantiated k-pipe tile (3x4 3x3 3x2 3x1 2x4 2x2 2x1 4x2)";
+static const char kTileShapeRule[] =
+    "a k-pipe tile route needs a shape the kp family gives to the k-pipe kernel (k % 128 == 0, k >= 256, m >= 512)";
+static bool kp_tile_route(int route) { return route >= 500 && route < 600 && gemm_kpipe_has_tile((route - 500) / 10, (route - 500) % 10); }
+
 /* One linear layer on host data through launch_linear / launch_gemv / launch_gemm / launch_gemm_kp, unchanged (see
  * include/wlk_hip.h).  Everything a kernel of the chosen route may address is checked against the caller's buffer sizes
  * here, before anything is uploaded; the launchers' own refusals follow before anything is launched. */
@@ -1195,8 +1202,10 @@ int wlk_diag_linear_ex(const wlk_diag_linear_args* q) {
         };
         need(q != nullptr, "null arguments");
         const int route = q->route, M = q->m, N = q->n, K = q->k, batch = q->batch;
-        need(route >= 0 && route <= 8, "route in [0, 8]");
+        need((route >= 0 && route <= 8) || kp_tile_route(route), kRouteRule);
         need(M >= 1 && M <= (1 << 16) && N >= 1 && N <= (1 << 20) && K >= 1 && K <= (1 << 16), "m in [1, 2^16], n in [1, 2^20], k in [1, 2^16]");
+        // a tile probe on a shape the k-pipe kernel of the kp family does not take would run another kernel: refused here
+        need(route <= 8 || gemm_kp_takes_kpipe(M, N, K), kTileShapeRule);
         need((q->flags & ~31) == 0, "unknown flag bits");
         need(q->a && q->w && q->c, "null a / w / c");
         need(q->lda >= 1 && q->lda <= (1 << 20) && q->ldc >= N && q->ldc <= (1 << 21), "lda in [1, 2^20], ldc in [n, 2^21]");
@@ -1289,7 +1298,7 @@ int wlk_diag_linear_ex(const wlk_diag_linear_args* q) {
             g.kv_layer_off = q->kv_layer_off; g.kv_d = q->kv_d; g.kv_ctx = q->kv_ctx;
         }
         g.force_kwave = route == 2;
-        g.force_kernel = (route >= 2 && route <= 4) || (route >= 6 && route <= 8) ? route : 0;
+        g.force_kernel = (route >= 2 && route <= 4) || route >= 6 ? route : 0;      // > 8: the tile probe of launch_gemm_kp
         LaunchCtx ctx;
         WLK_HIP(hipDeviceSynchronize());
         if (route == 0) launch_linear(ctx, g, "diag_linear");
@@ -1338,6 +1347,50 @@ int wlk_diag_gemv_variant(int m, int n, int k, int has_ln, int kv_mode, char* ou
             snprintf(text, sizeof text, "gemv1_mgl<%d>", p.width);
         } else {
             snprintf(text, sizeof text, "gemv1<%d,%d,%s,%s>", p.width, p.rpw, p.mg ? "mg" : p.ln ? "ln" : "plain", p.full ? "full" : "part");
+        }
+    }
+    if (rc != WLK_OK) g_diag_error = text;
+    snprintf(out_text, (size_t)cap, "%s", text);
+    return rc;
+}
+
+int wlk_diag_gemm_plan(int m, int n, int k, int route, int batch, int has_cache, char* out_text, int cap) {
+    if (!out_text || cap < 1) return WLK_ERR_ARG;
+    // operands that are present are marked by a non-null pointer; gemm_plan dereferences none
+    static const float present = 0.f;
+    static float cache_present = 0.f;
+    char text[200];
+    int rc = WLK_OK;
+    const bool tile_route = kp_tile_route(route);
+    if (m < 1 || n < 1 || k < 1 || batch < 0 || batch > kMaxBatch) {
+        snprintf(text, sizeof text, "wlk_diag_gemm_plan: m >= 1, n >= 1, k >= 1, batch in [0, 8]");
+        rc = WLK_ERR_ARG;
+    } else if (!((route >= 0 && route <= 8) || tile_route)) {
+        snprintf(text, sizeof text, "wlk_diag_gemm_plan: %s", kRouteRule);
+        rc = WLK_ERR_ARG;
+    } else if (route == 1 || (route == 0 && gemv_applicable(m, k))) {
+        snprintf(text, sizeof text, "wlk_diag_gemm_plan: launch_gemv takes this launch (wlk_diag_gemv_variant)");
+        rc = WLK_ERR_ARG;
+    } else if (tile_route && !gemm_kp_takes_kpipe(m, n, k)) {
+        snprintf(text, sizeof text, "wlk_diag_gemm_plan: %s", kTileShapeRule);
+        rc = WLK_ERR_ARG;
+    } else {
+        GemmArgs g;
+        g.A = &present; g.W = &present; g.lda = k; g.M = m; g.N = n; g.K = k; g.batch = batch;
+        if (has_cache) { g.kcache = &cache_present; g.vcache = &cache_present; }
+        g.force_kwave = route == 2;                                                  // (as wlk_diag_linear_ex sets them)
+        g.force_kernel = (route >= 2 && route <= 4) || route >= 6 ? route : 0;
+        const GemmPlan p = gemm_plan(g, route >= 5);
+        switch (p.kernel) {
+        case GemmPlan::kRefused: snprintf(text, sizeof text, "%s", p.refusal); rc = WLK_ERR_ARG; break;
+        case GemmPlan::kTiled64: snprintf(text, sizeof text, "gemm<64,64>"); break;
+        case GemmPlan::kTiled32: snprintf(text, sizeof text, "gemm<32,64>"); break;
+        case GemmPlan::kKwave: snprintf(text, sizeof text, "kwave<gemm>"); break;
+        case GemmPlan::kKwave16: snprintf(text, sizeof text, "kwave16<gemm>"); break;
+        case GemmPlan::kKpKwave2: snprintf(text, sizeof text, "kwave<kp,2>"); break;
+        case GemmPlan::kKpKwave1: snprintf(text, sizeof text, "kwave<kp,1>"); break;
+        case GemmPlan::kKpKwave16: snprintf(text, sizeof text, "kwave16<kp>"); break;
+        case GemmPlan::kKpipe: snprintf(text, sizeof text, "kpipe<%d,%d>", p.tm, p.tn); break;
         }
     }
     if (rc != WLK_OK) g_diag_error = text;

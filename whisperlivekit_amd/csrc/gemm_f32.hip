@@ -910,9 +910,17 @@ static void launch_kpipe(const LaunchCtx& ctx, const GemmArgs& g) {
                        ctx.stream, g);
 }
 
+// the instantiated k-pipe tiles (TM, TN), in the order ksplit_tile tries them
+#define WLK_KPIPE_TILES(X) X(3, 4) X(3, 3) X(3, 2) X(3, 1) X(2, 4) X(2, 2) X(2, 1) X(4, 2)
+bool gemm_kpipe_has_tile(int tm, int tn) {
+#define WLK_KP(a, b) if (tm == a && tn == b) return true;
+    WLK_KPIPE_TILES(WLK_KP)
+#undef WLK_KP
+    return false;
+}
 static bool dispatch_kpipe(const LaunchCtx& ctx, const GemmArgs& g, int tm, int tn) {
 #define WLK_KP(a, b) if (tm == a && tn == b) { launch_kpipe<a, b>(ctx, g); return true; }
-    WLK_KP(3, 4) WLK_KP(3, 3) WLK_KP(3, 2) WLK_KP(3, 1) WLK_KP(2, 4) WLK_KP(2, 2) WLK_KP(2, 1) WLK_KP(4, 2)
+    WLK_KPIPE_TILES(WLK_KP)
 #undef WLK_KP
     return false;
 }
@@ -934,7 +942,9 @@ static KSplitTile ksplit_tile(int M, int N, int K, bool forced = false) {
     // K >= 512: with fewer than 16 slabs the fixed cost of a launch dominates either kernel, and the one measured case
     // (large-v3 conv1, K = 384, M = 3000) favours the 64x64 kernel (36 vs 44 us)
     if (!forced && (N > 1536 || K < 512)) return {0, 0};
-    static const KSplitTile cand[] = {{3, 4}, {3, 3}, {3, 2}, {3, 1}, {2, 4}, {2, 2}, {2, 1}, {4, 2}};
+#define WLK_KP(a, b) {a, b},
+    static const KSplitTile cand[] = {WLK_KPIPE_TILES(WLK_KP)};
+#undef WLK_KP
     KSplitTile best{0, 0};
     double best_cost = 0.0;
     for (const KSplitTile& c : cand) {
@@ -965,49 +975,90 @@ bool gemm_takes_ksplit(int M, int N, int K) { return ksplit_tile(M, N, K).tm != 
 void x3_refresh_env_switches();                          // gemm_x3.hip: WLK_X3_PERSIST, WLK_X3_BM, WLK_X3_COLMAJOR
 void refresh_env_switches() { x3_refresh_env_switches(); }   // wlk_diag_env_refresh: a test flips a switch inside one process
 
-void launch_gemm(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
-    if (g.M <= 0 || g.N <= 0) return;
-    if (g.K % 4 != 0 || g.lda % 4 != 0) throw std::invalid_argument("gemm: K and lda must be multiples of 4");
+// launch_gemm's part of gemm_plan
+static GemmPlan gemm_plan_tiled(const GemmArgs& g) {
+    GemmPlan p;
+    auto refuse = [&](const char* why) {
+        p = GemmPlan{};
+        p.refusal = why;
+        return p;
+    };
+    if (g.K % 4 != 0 || g.lda % 4 != 0) return refuse("gemm: K and lda must be multiples of 4");
     if ((((long)g.M - 1) * g.lda + g.K) * 4 >= (1L << 31) || (long)g.N * g.K * 4 >= (1L << 31))
-        throw std::invalid_argument("gemm: operand larger than 2 GiB");
-    if (g.ln_gamma) throw std::invalid_argument("gemm: only the GEMV kernels (rows <= 8) take the LayerNorm; launch it separately");
-    const double nb = std::max(g.batch, 1);
-    KernelScope ks(ctx, tag, nb * 2.0 * g.M * g.N * g.K,
-                   4.0 * (nb * (double)g.M * g.K + (double)g.N * g.K + nb * (double)g.M * g.N));
-    if (g.batch > kMaxBatch) throw std::invalid_argument("gemm: batch too large");
+        return refuse("gemm: operand larger than 2 GiB");
+    if (g.ln_gamma) return refuse("gemm: only the GEMV kernels (rows <= 8) take the LayerNorm; launch it separately");
+    if (g.batch > kMaxBatch) return refuse("gemm: batch too large");
     const bool want_kwave = g.force_kwave || g.force_kernel == 2;
     // encoder-sized problems: one tile per compute unit, K split over the waves (force_kernel 3 = the 64x64 kernel)
     const KSplitTile kt = (want_kwave || g.kcache || g.force_kernel == 3) ? KSplitTile{0, 0} : ksplit_tile(g.M, g.N, g.K, g.force_kernel == 4);
-    if (g.force_kernel == 4 && !kt.tm) throw std::invalid_argument("gemm: the k-pipe kernel does not take this shape");
+    if (g.force_kernel == 4 && !kt.tm) return refuse("gemm: the k-pipe kernel does not take this shape");
     if (kt.tm) {
-        if (!dispatch_kpipe(ctx, g, kt.tm, kt.tn)) throw std::logic_error("gemm: k-pipe tile without an instantiation");
-        WLK_HIP(hipGetLastError());
-        return;
+        p.kernel = GemmPlan::kKpipe;
+        p.tm = kt.tm;
+        p.tn = kt.tn;
+        return p;
     }
-    if (g.batch > 0 && (gemm_takes_kwave(g.M, g.N, g.K) || want_kwave || (long)((g.N + 63) / 64) * ((g.M + 63) / 64) < 64))
-        throw std::invalid_argument("gemm: batched launches are only available on the tiled paths");
     const long tiles64 = (long)((g.N + 63) / 64) * ((g.M + 63) / 64);
+    if (g.batch > 0 && (gemm_takes_kwave(g.M, g.N, g.K) || want_kwave || tiles64 < 64))
+        return refuse("gemm: batched launches are only available on the tiled paths");
+    if (g.kcache && !(gemm_takes_kwave(g.M, g.N, g.K) || want_kwave))
+        return refuse("gemm: fused KV-cache append is only available on the k-wave path");
+    if ((gemm_takes_kwave(g.M, g.N, g.K) && g.force_kernel != 3) || (want_kwave && g.K >= 256))
+        p.kernel = g.M <= 128 && g.force_kernel != 2 ? GemmPlan::kKwave16 : GemmPlan::kKwave;   // prompt-sized row counts (decoder prefill): 16 x 16 tiles
+    else
+        p.kernel = tiles64 >= 64 ? GemmPlan::kTiled64 : GemmPlan::kTiled32;   // few tiles (decoder prefill): half the tile height, more CUs get a workgroup
+    return p;
+}
+
+// Launches what gemm_plan decided: the kernel, its grid and its workgroup size follow from the plan and the shape alone.
+static void launch_gemm_plan(const LaunchCtx& ctx, const GemmArgs& g, const GemmPlan& p, const char* tag) {
+    if (p.kernel == GemmPlan::kRefused) throw std::invalid_argument(p.refusal);
+    const double nb = std::max(g.batch, 1);
+    KernelScope ks(ctx, tag, nb * 2.0 * g.M * g.N * g.K,
+                   4.0 * (nb * (double)g.M * g.K + (double)g.N * g.K + nb * (double)g.M * g.N));
     const int tiles_n = (g.N + 63) / 64;
     const long tiles32 = (long)((g.N + 31) / 32) * ((g.M + 31) / 32);
-    if (g.kcache && !(gemm_takes_kwave(g.M, g.N, g.K) || want_kwave))
-        throw std::invalid_argument("gemm: fused KV-cache append is only available on the k-wave path");
-    if ((gemm_takes_kwave(g.M, g.N, g.K) && g.force_kernel != 3) || (want_kwave && g.K >= 256)) {
-        if (g.M <= 128 && g.force_kernel != 2) {   // prompt-sized row counts (decoder prefill): 16 x 16 tiles
-            const long tiles16 = (long)((g.N + 15) / 16) * ((g.M + 15) / 16);
-            hipLaunchKernelGGL(gemm_nt_f32_kwave16_kernel<>, dim3((unsigned)tiles16), dim3(256), 0, ctx.stream, g);
-        } else {
-            hipLaunchKernelGGL(gemm_nt_f32_kwave_kernel<false>, dim3((unsigned)tiles32), dim3(256), 0, ctx.stream, g);
-        }
-    } else if (tiles64 >= 64) {
+    const long tiles16 = (long)((g.N + 15) / 16) * ((g.M + 15) / 16);
+    switch (p.kernel) {
+    case GemmPlan::kKpipe:
+        if (!dispatch_kpipe(ctx, g, p.tm, p.tn)) throw std::logic_error("gemm: k-pipe tile without an instantiation");
+        break;
+    case GemmPlan::kKwave16:
+        hipLaunchKernelGGL(gemm_nt_f32_kwave16_kernel<>, dim3((unsigned)tiles16), dim3(256), 0, ctx.stream, g);
+        break;
+    case GemmPlan::kKwave:
+        hipLaunchKernelGGL(gemm_nt_f32_kwave_kernel<false>, dim3((unsigned)tiles32), dim3(256), 0, ctx.stream, g);
+        break;
+    case GemmPlan::kTiled64: {
         const int tiles_m = (g.M + 63) / 64;
         const int blocks = tiles_m >= 8 ? 8 * ((tiles_m + 3) / 4) * ((tiles_n + 1) / 2) : tiles_m * tiles_n;
         hipLaunchKernelGGL((gemm_nt_f32_kernel<64, 64>), dim3(blocks, std::max(g.batch, 1)), dim3(256), 0, ctx.stream, g);
-    } else {  // few tiles (decoder prefill): halve the tile height so that more CUs get a workgroup
+        break;
+    }
+    case GemmPlan::kTiled32: {
         const int tiles_m = (g.M + 31) / 32;
         const int blocks = tiles_m >= 8 ? 8 * ((tiles_m + 3) / 4) * ((tiles_n + 1) / 2) : tiles_m * tiles_n;
         hipLaunchKernelGGL((gemm_nt_f32_kernel<32, 64>), dim3(blocks), dim3(128), 0, ctx.stream, g);
+        break;
+    }
+    case GemmPlan::kKpKwave16:
+        hipLaunchKernelGGL((gemm_nt_f32_kwave16_kernel<true>), dim3((unsigned)tiles16), dim3(256), 0, ctx.stream, g);
+        break;
+    case GemmPlan::kKpKwave1:
+        hipLaunchKernelGGL((gemm_nt_f32_kwave_kernel<true, 1>), dim3((unsigned)tiles32), dim3(256), 0, ctx.stream, g);
+        break;
+    case GemmPlan::kKpKwave2:
+        hipLaunchKernelGGL(gemm_nt_f32_kwave_kernel<true>, dim3((unsigned)tiles32), dim3(256), 0, ctx.stream, g);
+        break;
+    case GemmPlan::kRefused:
+        break;
     }
     WLK_HIP(hipGetLastError());
+}
+
+void launch_gemm(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
+    if (g.M <= 0 || g.N <= 0) return;
+    launch_gemm_plan(ctx, g, gemm_plan(g, false), tag);
 }
 
 // The "kp" family (round 6): kernels that share ONE per-element arithmetic - the k-pipe's - whatever their tile, so that
@@ -1062,31 +1113,36 @@ static bool kp_takes_16(int M, int N, int K, int force) {
     return kp16_rule(M, N, K, tiles16);
 }
 bool gemm_kp_takes_kpipe(int M, int N, int K) { return K % 128 == 0 && K >= 256 && M >= 512 && ksplit_tile(M, N, K, true).tm != 0; }
-void launch_gemm_kp(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
-    if (g.M <= 0 || g.N <= 0) return;
-    if (g.K % 4 != 0 || g.lda % 4 != 0) throw std::invalid_argument("gemm: K and lda must be multiples of 4");
-    if (g.batch > 0 || g.kcache) throw std::invalid_argument("gemm (kp family): plain projections only");
-    if (g.ln_gamma) throw std::invalid_argument("gemm (kp family): the LayerNorm is a launch of its own");
+// launch_gemm_kp's part of gemm_plan
+static GemmPlan gemm_plan_kp(const GemmArgs& g) {
+    GemmPlan p;
+    auto refuse = [&](const char* why) {
+        p = GemmPlan{};
+        p.refusal = why;
+        return p;
+    };
+    if (g.K % 4 != 0 || g.lda % 4 != 0) return refuse("gemm: K and lda must be multiples of 4");
+    if (g.batch > 0 || g.kcache) return refuse("gemm (kp family): plain projections only");
+    if (g.ln_gamma) return refuse("gemm (kp family): the LayerNorm is a launch of its own");
     // K = 192 (the Sortformer's Transformer width; any multiple of 32 from 128 to 255): the k-wave tiles too, at EVERY row count -
     // the last 128-deep slab is half zeros, a row's arithmetic (wave w: k = 32 t + 8 w .. + 7, partials folded in wave order) does
     // not depend on M.  Until round 6 these shapes took the 64 x 64 family, where ONE wave walks K (7.9 us per launch for 64 MFLOP).
     const bool short_k_kwave = g.K % 32 == 0 && g.K >= 128 && g.K < 256;
     if (!short_k_kwave && (g.K % 128 != 0 || g.K < 256)) {
-        GemmArgs p = g;
-        p.force_kernel = 3;
-        launch_gemm(ctx, p, tag);
-        return;
+        GemmArgs t = g;
+        t.force_kernel = 3;
+        return gemm_plan_tiled(t);
     }
     if ((((long)g.M - 1) * g.lda + g.K) * 4 >= (1L << 31) || (long)g.N * g.K * 4 >= (1L << 31))
-        throw std::invalid_argument("gemm: operand larger than 2 GiB");
-    KernelScope ks(ctx, tag, 2.0 * g.M * g.N * g.K, 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));
+        return refuse("gemm: operand larger than 2 GiB");
     if (!short_k_kwave && gemm_kp_takes_kpipe(g.M, g.N, g.K)) {
         KSplitTile kt = kp_tile(g.M, g.N, g.K);
         if (g.force_kernel >= 500) kt = KSplitTile{(g.force_kernel - 500) / 10, (g.force_kernel - 500) % 10};   // tile probe
-        if (!dispatch_kpipe(ctx, g, kt.tm, kt.tn)) throw std::logic_error("gemm: k-pipe tile without an instantiation");
+        p.kernel = GemmPlan::kKpipe;
+        p.tm = kt.tm;
+        p.tn = kt.tn;
     } else if ((!short_k_kwave || g.M < 512) && kp_takes_16(g.M, g.N, g.K, g.force_kernel)) {
-        const long tiles16 = (long)((g.N + 15) / 16) * ((g.M + 15) / 16);
-        hipLaunchKernelGGL((gemm_nt_f32_kwave16_kernel<true>), dim3((unsigned)tiles16), dim3(256), 0, ctx.stream, g);
+        p.kernel = GemmPlan::kKpKwave16;
     } else {
         const long tiles32 = (long)((g.N + 31) / 32) * ((g.M + 31) / 32);
         // more than two tiles per compute unit: the one-buffer form (36.9 KB of LDS, three to four workgroups per CU) keeps them all
@@ -1094,10 +1150,19 @@ void launch_gemm_kp(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
         // 401 rows 16.8 -> 14.0; below that the extra barrier per slab costs 0-3 % (profiles/r06q_kwave_nbuf1_probe.txt).  Same bits.
         // force_kernel 7 / 8 (diagnostics): two buffers / one buffer whatever the grid.
         const bool one_buf = g.force_kernel == 8 || (g.force_kernel != 7 && tiles32 > 512);
-        if (one_buf) hipLaunchKernelGGL((gemm_nt_f32_kwave_kernel<true, 1>), dim3((unsigned)tiles32), dim3(256), 0, ctx.stream, g);
-        else hipLaunchKernelGGL(gemm_nt_f32_kwave_kernel<true>, dim3((unsigned)tiles32), dim3(256), 0, ctx.stream, g);
+        p.kernel = one_buf ? GemmPlan::kKpKwave1 : GemmPlan::kKpKwave2;
     }
-    WLK_HIP(hipGetLastError());
+    return p;
+}
+
+// The ONE place that decides which tiled GEMM kernel a launch takes (launch_gemm and launch_gemm_kp launch its answer,
+// wlk_diag_gemm_plan prints it).  Host arithmetic on the shape, the force_* fields and on which operands are present; no
+// pointer is dereferenced.
+GemmPlan gemm_plan(const GemmArgs& g, bool kp_family) { return kp_family ? gemm_plan_kp(g) : gemm_plan_tiled(g); }
+
+void launch_gemm_kp(const LaunchCtx& ctx, const GemmArgs& g, const char* tag) {
+    if (g.M <= 0 || g.N <= 0) return;
+    launch_gemm_plan(ctx, g, gemm_plan(g, true), tag);
 }
 
 // -------------------------------------------------------------------------------------------------
