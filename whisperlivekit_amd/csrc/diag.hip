@@ -519,17 +519,10 @@ int wlk_diag_select(const wlk_diag_select_args* q) {
         DevBuf L((size_t)R * V, q->logits), NL(ns ? (size_t)R * V : 1, ns ? q->ns_logits : nullptr), NP(R), TV((size_t)R * k),
             RG(ring_floats, q->ring), Z((size_t)R * A * T + 2 * kGuard), AL((size_t)R * T), PT((size_t)R * 64 * 2),
             SC(topk_scratch_bytes(R) / sizeof(float) + 1);
-        struct IntBuf {
-            int* p = nullptr;
-            IntBuf(size_t n, const int32_t* host = nullptr) {
-                WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(int)));
-                if (host) WLK_HIP(hipMemcpy(p, host, n * sizeof(int), hipMemcpyHostToDevice));
-            }
-            ~IntBuf() { (void)hipFree(p); }
-        } TI((size_t)R * k), FR(R), AR(q->n_adj, q->adj_row), AI(q->n_adj, q->adj_ids);
+        DevBytes TI((size_t)R * k * sizeof(int)), FR(R * sizeof(int)), AR(q->n_adj * sizeof(int), q->adj_row), AI(q->n_adj * sizeof(int), q->adj_ids);
         DevBuf AD(q->n_adj, q->adj_deltas);
         WLK_HIP(hipMemset(Z.p, 0, ((size_t)R * A * T + 2 * kGuard) * sizeof(float)));
-        WLK_HIP(hipMemset(FR.p, 0xff, R * sizeof(int)));
+        WLK_HIP(hipMemset(FR.i(), 0xff, R * sizeof(int)));
         WLK_HIP(hipDeviceSynchronize());   // the uploads and fills above ran on the legacy stream; st does not wait for it
         LaunchCtx ctx;
         ctx.stream = st.s;
@@ -537,8 +530,8 @@ int wlk_diag_select(const wlk_diag_select_args* q) {
         a.ring = RG.p; a.n_align = A; a.n_beam = R; a.ring_rows = q->ring_rows; a.T = T;
         a.prefill_rows = q->prefill_rows[0]; a.n_single = q->n_single[0]; a.newest_row = q->newest_row[0];
         a.single_base = q->single_base; a.content_len = q->content_len[0];
-        a.z = Z.p + kGuard; a.attn_last = AL.p; a.frames = FR.p;
-        const int *adj_row = q->n_adj ? AR.p : nullptr, *adj_ids = q->n_adj ? AI.p : nullptr;
+        a.z = Z.p + kGuard; a.attn_last = AL.p; a.frames = FR.i();
+        const int *adj_row = q->n_adj ? AR.i() : nullptr, *adj_ids = q->n_adj ? AI.i() : nullptr;
         const float* adj_deltas = q->n_adj ? AD.p : nullptr;
         StepRow* rows_dev = nullptr;
         struct RowsFree {
@@ -548,7 +541,7 @@ int wlk_diag_select(const wlk_diag_select_args* q) {
         switch (q->route) {
         case 0:
         case 1:
-            launch_logsoftmax_topk(ctx, L.p, V, R, k, TV.p, TI.p, SC.p, adj_row, adj_ids, adj_deltas, q->n_adj);
+            launch_logsoftmax_topk(ctx, L.p, V, R, k, TV.p, TI.i(), SC.p, adj_row, adj_ids, adj_deltas, q->n_adj);
             if (q->route == 0) {
                 launch_alignatt(ctx, a);
             } else {
@@ -558,7 +551,7 @@ int wlk_diag_select(const wlk_diag_select_args* q) {
             if (ns) launch_token_prob(ctx, NL.p, V, R, q->ns_token, NP.p);
             break;
         case 2:
-            refused = !launch_select_fused(ctx, L.p, V, R, k, TV.p, TI.p, SC.p, adj_row, adj_ids, adj_deltas, q->n_adj, a, StepHostOut{},
+            refused = !launch_select_fused(ctx, L.p, V, R, k, TV.p, TI.i(), SC.p, adj_row, adj_ids, adj_deltas, q->n_adj, a, StepHostOut{},
                                            ns ? NL.p : nullptr, ns ? q->ns_token : 0, ns ? NP.p : nullptr, false);
             break;
         case 3:
@@ -568,7 +561,7 @@ int wlk_diag_select(const wlk_diag_select_args* q) {
                 break;
             }
             launch_align_zscore(ctx, a);
-            refused = !launch_select_fused(ctx, L.p, V, R, k, TV.p, TI.p, SC.p, adj_row, adj_ids, adj_deltas, q->n_adj, a, StepHostOut{},
+            refused = !launch_select_fused(ctx, L.p, V, R, k, TV.p, TI.i(), SC.p, adj_row, adj_ids, adj_deltas, q->n_adj, a, StepHostOut{},
                                            nullptr, 0, nullptr, true);
             break;
         default: {
@@ -586,7 +579,7 @@ int wlk_diag_select(const wlk_diag_select_args* q) {
             WLK_HIP(hipMemcpy(rows_dev, rows.data(), sizeof(StepRow) * R, hipMemcpyHostToDevice));
             a.ring = nullptr;
             a.ring_rows = R * q->ring_rows;
-            launch_logsoftmax_topk(ctx, L.p, V, R, k, TV.p, TI.p, SC.p, adj_row, adj_ids, adj_deltas, q->n_adj);
+            launch_logsoftmax_topk(ctx, L.p, V, R, k, TV.p, TI.i(), SC.p, adj_row, adj_ids, adj_deltas, q->n_adj);
             launch_alignatt_rows(ctx, a, rows_dev);
             if (ns) launch_token_prob(ctx, NL.p, V, R, q->ns_token, NP.p);
             break;
@@ -595,8 +588,8 @@ int wlk_diag_select(const wlk_diag_select_args* q) {
         WLK_HIP(hipStreamSynchronize(st.s));
         if (refused) return;
         WLK_HIP(hipMemcpy(q->top_logprobs, TV.p, (size_t)R * k * sizeof(float), hipMemcpyDeviceToHost));
-        WLK_HIP(hipMemcpy(q->top_ids, TI.p, (size_t)R * k * sizeof(int), hipMemcpyDeviceToHost));
-        WLK_HIP(hipMemcpy(q->frames, FR.p, (size_t)R * sizeof(int), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(q->top_ids, TI.i(), (size_t)R * k * sizeof(int), hipMemcpyDeviceToHost));
+        WLK_HIP(hipMemcpy(q->frames, FR.i(), (size_t)R * sizeof(int), hipMemcpyDeviceToHost));
         WLK_HIP(hipMemcpy(q->attn_last, AL.p, (size_t)R * T * sizeof(float), hipMemcpyDeviceToHost));
         WLK_HIP(hipMemcpy(q->z, Z.p + kGuard, (size_t)R * A * T * sizeof(float), hipMemcpyDeviceToHost));
         WLK_HIP(hipMemcpy(q->logits_out, L.p, (size_t)R * V * sizeof(float), hipMemcpyDeviceToHost));
@@ -732,22 +725,6 @@ int wlk_diag_dec_attention(const wlk_diag_dec_attention_args* q) {
     struct Refuse : std::invalid_argument {
         using std::invalid_argument::invalid_argument;
     };
-    struct Bytes {      // device allocation, optionally filled from the host
-        char* p = nullptr;
-        size_t n = 0;
-        Bytes() = default;
-        Bytes(size_t bytes, const void* host = nullptr) { alloc(bytes, host); }
-        Bytes(const Bytes&) = delete;
-        void alloc(size_t bytes, const void* host = nullptr) {
-            n = bytes;
-            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(bytes, 16)));
-            if (host && bytes) WLK_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
-        }
-        void back(void* host) const { if (n) WLK_HIP(hipMemcpy(host, p, n, hipMemcpyDeviceToHost)); }
-        float* f() const { return reinterpret_cast<float*>(p); }
-        int* i() const { return reinterpret_cast<int*>(p); }
-        ~Bytes() { (void)hipFree(p); }
-    };
     try {
         auto need = [](bool ok, const char* what) {
             if (!ok) throw Refuse(std::string("wlk_diag_dec_attention: ") + what);
@@ -764,7 +741,7 @@ int wlk_diag_dec_attention(const wlk_diag_dec_attention_args* q) {
         if (route == WLK_DA_A0) {
             need(ctx_len >= 1 && q->anc && q->anc_rows >= R && q->n_updates >= 0, "A0: a table of at least n_rows rows");
             need(q->n_updates == 0 || (q->ctl && q->upd_offsets), "A0: null update list");
-            Bytes A((size_t)q->anc_rows * ctx_len, q->anc), CT(8 * sizeof(int)), OF(sizeof(int));
+            DevBytes A((size_t)q->anc_rows * ctx_len, q->anc), CT(8 * sizeof(int)), OF(sizeof(int));
             for (int u = 0; u < q->n_updates; ++u) {
                 WLK_HIP(hipMemcpy(CT.p, q->ctl + 8 * u, 8 * sizeof(int), hipMemcpyHostToDevice));
                 WLK_HIP(hipMemcpy(OF.p, q->upd_offsets + u, sizeof(int), hipMemcpyHostToDevice));
@@ -806,11 +783,11 @@ int wlk_diag_dec_attention(const wlk_diag_dec_attention_args* q) {
                 need(q->out && q->out_floats >= (int64_t)R * n_tok * d, "out holds fewer than the query rows");
             }
             const size_t QR = (size_t)R * n_tok;
-            Bytes QKV(route == WLK_DA_G0 ? 0 : QR * 3 * d * F, q->qkv), KC, VC, OUT(attends ? (size_t)q->out_floats * F : 0, q->out),
+            DevBytes QKV(route == WLK_DA_G0 ? 0 : QR * 3 * d * F, q->qkv), KC, VC, OUT(attends ? (size_t)q->out_floats * F : 0, q->out),
                 OFF((rows_form ? R : 1) * sizeof(int), route == WLK_DA_G0 ? nullptr : q->offsets), ROWS, ANC, SRC;
             // the caches sit layer_off floats into their allocations; what lies in front of them is NaN
             std::vector<float> front((size_t)layer_off, nanf_v);
-            for (Bytes* c : {&KC, &VC}) {
+            for (DevBytes* c : {&KC, &VC}) {
                 c->alloc(((size_t)layer_off + (size_t)q->cache_floats) * F);
                 if (layer_off) WLK_HIP(hipMemcpy(c->p, front.data(), (size_t)layer_off * F, hipMemcpyHostToDevice));
                 WLK_HIP(hipMemcpy(c->f() + layer_off, c == &KC ? q->kcache : q->vcache, (size_t)q->cache_floats * F, hipMemcpyHostToDevice));
@@ -894,13 +871,13 @@ int wlk_diag_dec_attention(const wlk_diag_dec_attention_args* q) {
                 memcpy(row + d, q->v + ((size_t)s * T + t) * d, d * F);
             }
         const size_t ring_floats = align ? (size_t)q->n_align * q->n_beam * q->ring_rows * T : 0;
-        Bytes KV(kv.size() * F, kv.data()), Q(q->q ? (size_t)R * d * F : 0, q->q), OUT((size_t)q->out_floats * F, q->out),
+        DevBytes KV(kv.size() * F, kv.data()), Q(q->q ? (size_t)R * d * F : 0, q->q), OUT((size_t)q->out_floats * F, q->out),
             RING(ring_floats * F, q->ring), SC(std::max(score_floats, (size_t)(q->scores ? q->scores_floats : 0)) * F, q->scores),
             HR(align ? H * sizeof(int) : 0, q->head_rank), RR(align ? R * sizeof(int) : 0, q->ring_row),
             BR(align ? R * sizeof(int) : 0, q->beam_of_row), SH(side_heads.size() * sizeof(int), side_heads.data()),
             RK(ranks.size() * sizeof(int), ranks.data());
-        Bytes PM((size_t)R * H * kCrossSplitWays * F), PL((size_t)R * H * kCrossSplitWays * F), PO((size_t)R * H * kCrossSplitWays * 64 * F);
-        Bytes X, WQ, BQ, GA, BE, WO, BO, ROWS, PART;
+        DevBytes PM((size_t)R * H * kCrossSplitWays * F), PL((size_t)R * H * kCrossSplitWays * F), PO((size_t)R * H * kCrossSplitWays * 64 * F);
+        DevBytes X, WQ, BQ, GA, BE, WO, BO, ROWS, PART;
         CrossAttnArgs ca{};
         ca.q = Q.f(); ca.k = KV.f() + 2 * d; ca.v = ca.k + d; ca.ldkv = ldkv; ca.out = OUT.f();
         ca.rows = R; ca.d = d; ca.n_head = H; ca.T = T;
@@ -997,26 +974,11 @@ int wlk_diag_sf_kernel(const wlk_diag_sf_kernel_args* q) {
     struct Refuse : std::invalid_argument {
         using std::invalid_argument::invalid_argument;
     };
-    struct Buf {        // a device copy of exactly `n` host floats, copied back whole on request
-        float* p = nullptr;
-        float* host = nullptr;
-        size_t n = 0;
-        Buf() = default;
-        Buf(const float* h, size_t floats) { set(h, floats); }
-        Buf(const Buf&) = delete;
-        void set(const float* h, size_t floats) {
-            host = const_cast<float*>(h);
-            n = floats;
-            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 4) * sizeof(float)));
-            if (host && n) WLK_HIP(hipMemcpy(p, host, n * sizeof(float), hipMemcpyHostToDevice));
-        }
-        void back() const { if (host && n) WLK_HIP(hipMemcpy(host, p, n * sizeof(float), hipMemcpyDeviceToHost)); }
-        ~Buf() { (void)hipFree(p); }
-    };
     try {
         auto need = [](bool ok, const char* what) {
             if (!ok) throw Refuse(std::string("wlk_diag_sf_kernel: ") + what);
         };
+        constexpr size_t kF = sizeof(float);
         need(q != nullptr, "null arguments");
         const int kind = q->kind;
         need(kind >= WLK_SFK_ATTENTION && kind <= WLK_SFK_ASSEMBLE, "unknown kind");
@@ -1056,15 +1018,17 @@ int wlk_diag_sf_kernel(const wlk_diag_sf_kernel_args* q) {
                 need(q->ldp >= W && q->ldp % 4 == 0 && q->ldp <= (1 << 20), "ldp a multiple of 4, at least n_head dh");
                 need((int64_t)(q->pos_rows - 1) * q->ldp + W <= q->pos_floats, "the pos table lies past its buffer");
             }
-            Buf Q(q->q, q->q_floats), K(q->k, q->k_floats), V(q->v, q->v_floats), O(q->out, q->out_floats), P, U, Vb;
-            if (q->pos) P.set(q->pos, q->pos_floats);
-            if (q->bias_u) U.set(q->bias_u, W);
-            if (q->bias_v) Vb.set(q->bias_v, W);
+            DevBytes Q, K, V, O, P, U, Vb;
+            Q.mirror(q->q, q->q_floats * kF); K.mirror(q->k, q->k_floats * kF); V.mirror(q->v, q->v_floats * kF);
+            O.mirror(q->out, q->out_floats * kF);
+            if (q->pos) P.mirror(q->pos, q->pos_floats * kF);
+            if (q->bias_u) U.alloc(W * kF, q->bias_u);
+            if (q->bias_v) Vb.alloc(W * kF, q->bias_v);
             SfAttnArgs a;
-            a.q = Q.p; a.k = K.p; a.v = V.p; a.ldq = q->ldq; a.ldk = q->ldk; a.ldv = q->ldv; a.out = O.p; a.ldo = q->ldo;
+            a.q = Q.f(); a.k = K.f(); a.v = V.f(); a.ldq = q->ldq; a.ldk = q->ldk; a.ldv = q->ldv; a.out = O.f(); a.ldo = q->ldo;
             a.T = T; a.n_head = H; a.dh = dh; a.scale = q->scale;
-            a.pos = q->pos ? P.p : nullptr; a.ldp = q->ldp; a.pos_row0 = q->pos_row0;
-            a.bias_u = q->bias_u ? U.p : nullptr; a.bias_v = q->bias_v ? Vb.p : nullptr;
+            a.pos = q->pos ? P.f() : nullptr; a.ldp = q->ldp; a.pos_row0 = q->pos_row0;
+            a.bias_u = q->bias_u ? U.f() : nullptr; a.bias_v = q->bias_v ? Vb.f() : nullptr;
             a.n_seg = n_seg;
             for (int s = 0; s < n_seg; ++s) { a.seg_start[s] = q->seg_start[s]; a.seg_T[s] = q->seg_T[s]; }
             WLK_HIP(hipDeviceSynchronize());
@@ -1080,9 +1044,10 @@ int wlk_diag_sf_kernel(const wlk_diag_sf_kernel_args* q) {
             need(T >= 1 && T <= 4096 && d >= 1 && d <= 4096 && ns >= 1 && ns <= 64, "T in [1, 4096], d in [1, 4096], n_spk in [1, 64]");
             need(q->w2 && q->b2, "null w2 / b2");
             need((int64_t)T * d <= q->in_floats && (int64_t)T * ns <= q->out_floats, "the rows lie past in / out");
-            Buf X(q->in, q->in_floats), W1(q->w, (size_t)d * d), B1(q->b, d), W2(q->w2, (size_t)ns * d), B2(q->b2, ns), O(q->out, q->out_floats);
+            DevBytes X, W1((size_t)d * d * kF, q->w), B1(d * kF, q->b), W2((size_t)ns * d * kF, q->w2), B2(ns * kF, q->b2), O;
+            X.mirror(q->in, q->in_floats * kF); O.mirror(q->out, q->out_floats * kF);
             WLK_HIP(hipDeviceSynchronize());
-            launch_sf_head(ctx, X.p, W1.p, B1.p, W2.p, B2.p, O.p, T, d, ns);
+            launch_sf_head(ctx, X.f(), W1.f(), B1.f(), W2.f(), B2.f(), O.f(), T, d, ns);
             WLK_HIP(hipDeviceSynchronize());
             X.back(); O.back();
             return WLK_OK;
@@ -1106,10 +1071,11 @@ int wlk_diag_sf_kernel(const wlk_diag_sf_kernel_args* q) {
             sg.in_total = f0; sg.out_total = t0;
             const int64_t per_in = kind == WLK_SFK_CONV0 ? F : (int64_t)F * C;
             need(f0 * per_in <= q->in_floats && (int64_t)t0 * sf_sub_len(F) * C <= q->out_floats, "the sessions lie past in / out");
-            Buf X(q->in, q->in_floats), Wt(q->w, (size_t)9 * C), B(q->b, C), O(q->out, q->out_floats);
+            DevBytes X, Wt((size_t)9 * C * kF, q->w), B(C * kF, q->b), O;
+            X.mirror(q->in, q->in_floats * kF); O.mirror(q->out, q->out_floats * kF);
             WLK_HIP(hipDeviceSynchronize());
-            if (kind == WLK_SFK_CONV0) launch_sf_conv0(ctx, X.p, Wt.p, B.p, O.p, sg, F, C);
-            else launch_sf_dwconv2d(ctx, X.p, Wt.p, B.p, O.p, sg, F, C);
+            if (kind == WLK_SFK_CONV0) launch_sf_conv0(ctx, X.f(), Wt.f(), B.f(), O.f(), sg, F, C);
+            else launch_sf_dwconv2d(ctx, X.f(), Wt.f(), B.f(), O.f(), sg, F, C);
             WLK_HIP(hipDeviceSynchronize());
             X.back(); O.back();
             return WLK_OK;
@@ -1129,10 +1095,11 @@ int wlk_diag_sf_kernel(const wlk_diag_sf_kernel_args* q) {
             need(taps >= 1 && taps % 2 == 1 && taps <= 255, "taps odd in [1, 255]");
             need(q->bn_mean && q->bn_invstd && q->bn_w && q->bn_b, "null batch norm");
             need((int64_t)r0 * 2 * d <= q->in_floats && (int64_t)r0 * d <= q->out_floats, "the sessions lie past in / out");
-            Buf X(q->in, q->in_floats), Wt(q->w, (size_t)taps * d), B(q->b, d), M(q->bn_mean, d), I(q->bn_invstd, d), G(q->bn_w, d),
-                Bb(q->bn_b, d), O(q->out, q->out_floats);
+            DevBytes X, Wt((size_t)taps * d * kF, q->w), B(d * kF, q->b), M(d * kF, q->bn_mean), I(d * kF, q->bn_invstd), G(d * kF, q->bn_w),
+                Bb(d * kF, q->bn_b), O;
+            X.mirror(q->in, q->in_floats * kF); O.mirror(q->out, q->out_floats * kF);
             WLK_HIP(hipDeviceSynchronize());
-            launch_sf_glu_dwconv(ctx, X.p, Wt.p, B.p, M.p, I.p, G.p, Bb.p, O.p, rows, d, taps);
+            launch_sf_glu_dwconv(ctx, X.f(), Wt.f(), B.f(), M.f(), I.f(), G.f(), Bb.f(), O.f(), rows, d, taps);
             WLK_HIP(hipDeviceSynchronize());
             X.back(); O.back();
             return WLK_OK;
@@ -1146,11 +1113,12 @@ int wlk_diag_sf_kernel(const wlk_diag_sf_kernel_args* q) {
         }
         need(c0 == 0 || (q->in2 && (int64_t)c0 * d <= q->in2_floats), "the chunk rows lie past in2");
         need((int64_t)r0 * d <= q->in_floats && (int64_t)r0 * d <= q->out_floats, "the sessions lie past in / out");
-        Buf X(q->in, q->in_floats), X2, O(q->out, q->out_floats);
-        if (q->in2 && q->in2_floats > 0) X2.set(q->in2, q->in2_floats);
-        else X2.set(nullptr, 4);
+        DevBytes X, X2, O;
+        X.mirror(q->in, q->in_floats * kF); O.mirror(q->out, q->out_floats * kF);
+        if (q->in2 && q->in2_floats > 0) X2.mirror(q->in2, q->in2_floats * kF);
+        else X2.alloc(0);
         WLK_HIP(hipDeviceSynchronize());
-        launch_sf_assemble(ctx, X.p, X2.p, O.p, rows, chunks, d, q->scale);
+        launch_sf_assemble(ctx, X.f(), X2.f(), O.f(), rows, chunks, d, q->scale);
         WLK_HIP(hipDeviceSynchronize());
         X.back(); X2.back(); O.back();
         return WLK_OK;
@@ -1180,21 +1148,6 @@ static bool kp_tile_route(int route) { return route >= 500 && route < 600 && gem
 int wlk_diag_linear_ex(const wlk_diag_linear_args* q) {
     struct Refuse : std::invalid_argument {
         using std::invalid_argument::invalid_argument;
-    };
-    struct Buf {        // a device copy of exactly `n` host floats (never fewer than 16 allocated), copied back whole
-        float* p = nullptr;
-        float* host = nullptr;
-        size_t n = 0;
-        Buf() = default;
-        Buf(const Buf&) = delete;
-        void set(float* h, size_t floats) {
-            host = h;
-            n = floats;
-            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 16) * sizeof(float)));
-            if (host && n) WLK_HIP(hipMemcpy(p, host, n * sizeof(float), hipMemcpyHostToDevice));
-        }
-        void back() const { if (host && n) WLK_HIP(hipMemcpy(host, p, n * sizeof(float), hipMemcpyDeviceToHost)); }
-        ~Buf() { (void)hipFree(p); }
     };
     try {
         auto need = [](bool ok, const char* what) {
@@ -1257,44 +1210,42 @@ int wlk_diag_linear_ex(const wlk_diag_linear_args* q) {
             }
         }
 
-        Buf A, W, B, G, Bt, R, Cc, KC, VC, POS, ROWS;
-        A.set(q->a, q->a_floats);
-        W.set(q->w, q->w_floats);
-        if (q->bias) B.set(q->bias, q->bias_floats);
-        if (q->ln_gamma) { G.set(q->ln_gamma, q->ln_floats); Bt.set(q->ln_beta, q->ln_floats); }
-        if (has_res && !r_is_c) R.set(q->r, q->r_floats);
-        Cc.set(q->c, q->c_floats);
-        if (kv_mode != 0) { KC.set(q->kcache, q->cache_floats); VC.set(q->vcache, q->cache_floats); }
+        constexpr size_t kF = sizeof(float);
+        DevBytes A, W, B, G, Bt, R, Cc, KC, VC, POS, ROWS;
+        A.mirror(q->a, q->a_floats * kF);
+        W.mirror(q->w, q->w_floats * kF);
+        if (q->bias) B.mirror(q->bias, q->bias_floats * kF);
+        if (q->ln_gamma) { G.mirror(q->ln_gamma, q->ln_floats * kF); Bt.mirror(q->ln_beta, q->ln_floats * kF); }
+        if (has_res && !r_is_c) R.mirror(q->r, q->r_floats * kF);
+        Cc.mirror(q->c, q->c_floats * kF);
+        if (kv_mode != 0) { KC.mirror(q->kcache, q->cache_floats * kF); VC.mirror(q->vcache, q->cache_floats * kF); }
         GemmArgs g;
-        g.A = A.p; g.lda = q->lda; g.W = W.p; g.bias = q->bias ? B.p : nullptr; g.C = Cc.p; g.ldc = q->ldc;
-        g.R = has_res ? (r_is_c ? Cc.p : R.p) : nullptr; g.ldr = ldr;
+        g.A = A.f(); g.lda = q->lda; g.W = W.f(); g.bias = q->bias ? B.f() : nullptr; g.C = Cc.f(); g.ldc = q->ldc;
+        g.R = has_res ? (r_is_c ? Cc.f() : R.f()) : nullptr; g.ldr = ldr;
         g.M = M; g.N = N; g.K = K; g.flags = q->flags; g.scale = q->scale; g.scale_cols = q->scale_cols;
         g.scale_period = q->scale_period;
-        g.ln_gamma = q->ln_gamma ? G.p : nullptr; g.ln_beta = q->ln_gamma ? Bt.p : nullptr;
+        g.ln_gamma = q->ln_gamma ? G.f() : nullptr; g.ln_beta = q->ln_gamma ? Bt.f() : nullptr;
         g.batch = batch;
         for (int z = 0; z < batch; ++z) {
-            g.z.in[z] = A.p + q->a_off[z];
-            g.z.out[z] = Cc.p + q->c_off[z];
-            g.z.res[z] = has_res ? (r_is_c ? Cc.p + q->c_off[z] : R.p + q->r_off[z]) : nullptr;
+            g.z.in[z] = A.f() + q->a_off[z];
+            g.z.out[z] = Cc.f() + q->c_off[z];
+            g.z.res[z] = has_res ? (r_is_c ? Cc.f() + q->c_off[z] : R.f() + q->r_off[z]) : nullptr;
         }
         for (int z = batch; z < kMaxBatch; ++z) { g.z.in[z] = nullptr; g.z.out[z] = nullptr; g.z.res[z] = nullptr; }
-        static_assert(sizeof(StepRow) % sizeof(float) == 0 && sizeof(int) == sizeof(float), "tables are uploaded through float buffers");
         if (kv_mode == 1) {
-            float pos_bits = __builtin_bit_cast(float, (int)q->kv_pos);
-            POS.set(&pos_bits, 1);
-            POS.host = nullptr;
-            g.kcache = KC.p; g.vcache = VC.p; g.kv_pos = reinterpret_cast<const int*>(POS.p);
+            const int pos = (int)q->kv_pos;
+            POS.alloc(sizeof(int), &pos);
+            g.kcache = KC.f(); g.vcache = VC.f(); g.kv_pos = POS.i();
             g.kv_d = q->kv_d; g.kv_ctx = q->kv_ctx; g.kv_ntok = q->kv_ntok;
         } else if (kv_mode == 2) {
             StepRow table[8] = {};
             for (int r = 0; r < M; ++r) {
-                table[r].kcache = KC.p + (size_t)q->kv_row_cache[r] * q->cache_stride;
-                table[r].vcache = VC.p + (size_t)q->kv_row_cache[r] * q->cache_stride;
+                table[r].kcache = KC.f() + (size_t)q->kv_row_cache[r] * q->cache_stride;
+                table[r].vcache = VC.f() + (size_t)q->kv_row_cache[r] * q->cache_stride;
                 table[r].offset = q->kv_row_offset[r];
             }
-            ROWS.set(reinterpret_cast<float*>(table), 8 * (sizeof(StepRow) / sizeof(float)));
-            ROWS.host = nullptr;
-            g.kv_rows = reinterpret_cast<const StepRow*>(ROWS.p);
+            ROWS.alloc(sizeof(table), table);
+            g.kv_rows = ROWS.as<const StepRow>();
             g.kv_layer_off = q->kv_layer_off; g.kv_d = q->kv_d; g.kv_ctx = q->kv_ctx;
         }
         g.force_kwave = route == 2;
@@ -1406,23 +1357,6 @@ int wlk_diag_enc_op(const wlk_diag_enc_op_args* q) {
     struct Refuse : std::invalid_argument {
         using std::invalid_argument::invalid_argument;
     };
-    struct Buf {        // a device copy of exactly `n` host elements of `esz` bytes (never fewer than 64 bytes), copied back whole
-        char* p = nullptr;
-        void* host = nullptr;
-        size_t bytes = 0;
-        Buf() = default;
-        Buf(const Buf&) = delete;
-        void set(void* h, size_t n, size_t esz) {
-            host = h;
-            bytes = n * esz;
-            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(bytes, 64)));
-            if (host && bytes) WLK_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
-        }
-        float* f() const { return reinterpret_cast<float*>(p); }
-        unsigned short* u() const { return reinterpret_cast<unsigned short*>(p); }
-        void back() const { if (host && bytes) WLK_HIP(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost)); }
-        ~Buf() { (void)hipFree(p); }
-    };
     try {
         auto need = [](bool ok, const char* what) {
             if (!ok) throw Refuse(std::string("wlk_diag_enc_op: ") + what);
@@ -1440,15 +1374,15 @@ int wlk_diag_enc_op(const wlk_diag_enc_op_args* q) {
             for (int z = 0; z < nz; ++z) need(off(o, z) >= 0 && off(o, z) % align == 0 && off(o, z) + span <= cap, what);
         };
         const bool in_is_x3 = q->in3 != nullptr;
-        Buf IN, IN3, W, B, R, OUT, OUT3;
+        DevBytes IN, IN3, W, B, R, OUT, OUT3;
         auto upload = [&]() {
-            if (q->in) IN.set(q->in, q->in_floats, 4);
-            if (q->in3) IN3.set(q->in3, q->in3_elems, 2);
-            if (q->w) W.set(q->w, q->w_floats, 4);
-            if (q->bias) B.set(q->bias, q->bias_floats, 4);
-            if (q->r) R.set(q->r, q->r_floats, 4);
-            if (q->out) OUT.set(q->out, q->out_floats, 4);
-            if (q->out3) OUT3.set(q->out3, q->out3_elems, 2);
+            if (q->in) IN.mirror(q->in, q->in_floats * 4);
+            if (q->in3) IN3.mirror(q->in3, q->in3_elems * 2);
+            if (q->w) W.mirror(q->w, q->w_floats * 4);
+            if (q->bias) B.mirror(q->bias, q->bias_floats * 4);
+            if (q->r) R.mirror(q->r, q->r_floats * 4);
+            if (q->out) OUT.mirror(q->out, q->out_floats * 4);
+            if (q->out3) OUT3.mirror(q->out3, q->out3_elems * 2);
         };
         auto download = [&]() { IN.back(); IN3.back(); W.back(); B.back(); R.back(); OUT.back(); OUT3.back(); };
         std::vector<unsigned short*> scratch;      // packed operands (device only)
@@ -1521,13 +1455,13 @@ int wlk_diag_enc_op(const wlk_diag_enc_op_args* q) {
             for (int i = 0; i < nz; ++i) {
                 const unsigned short* a3;
                 if (in_is_x3) {
-                    a3 = IN3.u() + off(q->in3_off, i);
+                    a3 = IN3.as<unsigned short>() + off(q->in3_off, i);
                 } else {
                     unsigned short* p = dev_u16((size_t)M * 3 * q->ld_in);
                     launch_x3_pack(ctx, IN.f() + off(q->in_off, i), q->ld_in, p, q->ld_in, M, K);
                     a3 = p;
                 }
-                float* c = form == 0 ? OUT.f() + off(q->out_off, i) : reinterpret_cast<float*>(OUT3.u() + off(q->out3_off, i));
+                float* c = form == 0 ? OUT.f() + off(q->out_off, i) : reinterpret_cast<float*>(OUT3.as<unsigned short>() + off(q->out3_off, i));
                 const float* r = has_res ? (r_is_c ? c : R.f() + off(q->r_off, i)) : nullptr;
                 if (batch) {        // exactly run_encode_group's table: in = the X3 image, out = the result (fp32 or X3), res
                     z.in[i] = reinterpret_cast<const float*>(a3); z.out[i] = c; z.res[i] = r;
@@ -1558,7 +1492,7 @@ int wlk_diag_enc_op(const wlk_diag_enc_op_args* q) {
             upload();
             for (int i = 0; i < nz; ++i) {
                 z.in[i] = IN.f() + off(q->in_off, i);
-                z.out[i] = form == 0 ? OUT.f() + off(q->out_off, i) : reinterpret_cast<float*>(OUT3.u() + off(q->out3_off, i));
+                z.out[i] = form == 0 ? OUT.f() + off(q->out_off, i) : reinterpret_cast<float*>(OUT3.as<unsigned short>() + off(q->out3_off, i));
             }
             WLK_HIP(hipDeviceSynchronize());
             if (form == 0 && batch) launch_layernorm_batched(ctx, z, batch, q->ld_in, W.f(), B.f(), q->ld_out, M, d, "diag_enc_ln");
@@ -1597,13 +1531,13 @@ int wlk_diag_enc_op(const wlk_diag_enc_op_args* q) {
                     continue;
                 }
                 if (in_is_x3) {
-                    z.in[i] = reinterpret_cast<const float*>(IN3.u() + off(q->in3_off, i));
+                    z.in[i] = reinterpret_cast<const float*>(IN3.as<unsigned short>() + off(q->in3_off, i));
                 } else {
                     unsigned short* img = dev_u16(x3_attn_image_elems(T, d));
                     launch_x3_pack_qkv(ctx, IN.f() + off(q->in_off, i), img, T, d, x3_attn_vt_off(T, d), x3_attn_vt_ld(T));
                     z.in[i] = reinterpret_cast<const float*>(img);
                 }
-                z.out[i] = x3_out ? reinterpret_cast<float*>(OUT3.u() + off(q->out3_off, i)) : OUT.f() + off(q->out_off, i);
+                z.out[i] = x3_out ? reinterpret_cast<float*>(OUT3.as<unsigned short>() + off(q->out3_off, i)) : OUT.f() + off(q->out_off, i);
             }
             WLK_HIP(hipDeviceSynchronize());
             if (form == 0 && batch) launch_encoder_attention_batched(ctx, z, batch, T, d, H);
@@ -1621,7 +1555,7 @@ int wlk_diag_enc_op(const wlk_diag_enc_op_args* q) {
             need((int64_t)(M - 1) * 3 * q->ld_out3 + 3 * (int64_t)N <= q->out3_elems, "the X3 rows lie past out3");
             upload();
             WLK_HIP(hipDeviceSynchronize());
-            launch_x3_pack(ctx, IN.f(), q->ld_in, OUT3.u(), q->ld_out3, M, N);
+            launch_x3_pack(ctx, IN.f(), q->ld_in, OUT3.as<unsigned short>(), q->ld_out3, M, N);
         }
         WLK_HIP(hipDeviceSynchronize());
         download();
@@ -1644,22 +1578,6 @@ int wlk_diag_enc_op(const wlk_diag_enc_op_args* q) {
 int wlk_diag_word_align(const wlk_diag_word_align_args* q) {
     struct Refuse : std::invalid_argument {
         using std::invalid_argument::invalid_argument;
-    };
-    struct Buf {        // a device copy of exactly `bytes` host bytes (never fewer than 64), copied back whole
-        char* p = nullptr;
-        void* host = nullptr;
-        size_t bytes = 0;
-        Buf() = default;
-        Buf(const Buf&) = delete;
-        void set(void* h, size_t n) {
-            host = h;
-            bytes = n;
-            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(bytes, 64)));
-            if (host && bytes) WLK_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
-        }
-        float* f() const { return reinterpret_cast<float*>(p); }
-        void back() const { if (host && bytes) WLK_HIP(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost)); }
-        ~Buf() { (void)hipFree(p); }
     };
     try {
         auto need = [](bool ok, const char* what) {
@@ -1692,15 +1610,15 @@ int wlk_diag_word_align(const wlk_diag_word_align_args* q) {
         need(last < kWaCost || N * q->F <= q->cost_floats, "cost holds fewer than (n_text + 1) x F floats");
         const int64_t n_trace = (N + 1) * ((int64_t)q->F + 1);
         need(last < kWaDtw || n_trace <= q->trace_bytes, "trace holds fewer than (n_text + 2) x (F + 1) bytes");
-        Buf RING, LOG, TGT, W, COST, PROBS, TRACE, SCRATCH;
-        RING.set(q->ring, (size_t)q->ring_floats * 4);
-        LOG.set(q->logits, (size_t)q->logits_floats * 4);
-        TGT.set(q->targets, (size_t)q->targets_n * 4);
-        W.set(q->w, (size_t)q->w_floats * 4);
-        PROBS.set(q->probs, (size_t)q->probs_floats * 4);
-        if (q->cost) COST.set(q->cost, (size_t)q->cost_floats * 4);
-        if (q->trace) TRACE.set(q->trace, (size_t)q->trace_bytes);
-        SCRATCH.set(nullptr, (size_t)n_trace);
+        DevBytes RING, LOG, TGT, W, COST, PROBS, TRACE, SCRATCH;
+        RING.mirror(q->ring, (size_t)q->ring_floats * 4);
+        LOG.mirror(q->logits, (size_t)q->logits_floats * 4);
+        TGT.mirror(q->targets, (size_t)q->targets_n * 4);
+        W.mirror(q->w, (size_t)q->w_floats * 4);
+        PROBS.mirror(q->probs, (size_t)q->probs_floats * 4);
+        if (q->cost) COST.mirror(q->cost, (size_t)q->cost_floats * 4);
+        if (q->trace) TRACE.mirror(q->trace, (size_t)q->trace_bytes);
+        SCRATCH.alloc((size_t)n_trace);
         a.logits = LOG.f(); a.target = reinterpret_cast<const int*>(TGT.p); a.probs = PROBS.f(); a.ring = RING.f(); a.w = W.f();
         a.cost = q->cost ? COST.f() : nullptr;
         a.trace = q->trace ? reinterpret_cast<signed char*>(TRACE.p) : nullptr;

@@ -59,8 +59,8 @@ struct wlk_engine {
     hipStream_t stream = nullptr;
     // device workspace of one batched step
     StepRow* rows_dev = nullptr;   // = blk_dev->rows
-    float *x = nullptr, *qkv = nullptr, *att = nullptr, *q = nullptr, *mlp = nullptr, *logits = nullptr, *xsplit = nullptr,
-          *z = nullptr, *attn_last = nullptr;
+    wlk_step_ws ws;                // the activations of the step chain
+    float *z = nullptr, *attn_last = nullptr;
     float* res_dev = nullptr;      // [top log-probs R*2 | top ids R*2 | frames R]
     void* topk_scratch = nullptr;
     int* adj_dev = nullptr;        // [rows n | ids n | deltas n]
@@ -120,42 +120,67 @@ struct wlk_engine {
     void enqueue_select(int R, int n_adj);  // logit adjustments + log-softmax top-2 + AlignAtt read-out per row
 };
 
-// ---- one batched step ----------------------------------------------------------------------------------------
-void wlk_engine::enqueue_decoder(int R, bool from_block, const AlignArgs* side_align, int side_blocks, int side_zf) {
+// ---- the step chain ------------------------------------------------------------------------------------------
+void wlk_step_ws_alloc(const wlk_model* m, wlk_step_ws& ws) {
+    const wlk_dims& D = m->D;
+    const size_t R = 8, d = D.n_text_state, V = D.n_vocab;
+    ws.x = dev_alloc<float>(R * d);
+    ws.qkv = dev_alloc<float>(R * 3 * d);
+    ws.att = dev_alloc<float>(R * d);
+    ws.q = dev_alloc<float>(R * d);
+    ws.mlp = dev_alloc<float>(R * 4 * d);
+    ws.logits = dev_alloc<float>(R * V);
+    ws.xsplit = dev_alloc<float>(cross_split_scratch_floats(8, D.n_text_head, D.n_audio_ctx));
+}
+
+void wlk_step_ws_free(wlk_step_ws& ws) {
+    float* fl[] = {ws.x, ws.qkv, ws.att, ws.q, ws.mlp, ws.logits, ws.xsplit};
+    for (float* p : fl)
+        if (p) (void)hipFree(p);
+    ws = wlk_step_ws{};
+}
+
+void wlk_enqueue_step_rows(const wlk_model* m, const LaunchCtx& c, const wlk_step_ws& ws, const StepRow* rows_dev, int R,
+                           const wlk_step_opts& o) {
     const wlk_dims& D = m->D;
     const int d = D.n_text_state, T = D.n_audio_ctx, H = D.n_text_head, V = D.n_vocab, ctx_len = D.n_text_ctx;
-    const LaunchCtx c{stream, nullptr};
     const float scale = std::pow((float)kHeadDim, -0.25f);
-    if (from_block) launch_embed_rows_step(c, blk_host_dev, blk_dev, m->w_tok_emb, m->w_dec_pos, x, R, d);
+    float *x = ws.x, *att = ws.att;
+    // C[R][N] = A[R][K] W^T + bias, both operands dense
+    auto gemm = [R](const float* A, int K, const float* W, const float* bias, float* C, int N) {
+        GemmArgs g;
+        g.A = A; g.lda = K; g.W = W; g.bias = bias; g.C = C; g.ldc = N; g.M = R; g.N = N; g.K = K;
+        return g;
+    };
+    auto residual_gemv = [&](GemmArgs g, const char* tag) {       // x += ...
+        g.flags = kGemmResidual; g.R = x; g.ldr = d;
+        launch_gemv(c, g, tag);
+    };
+    if (o.block_host) launch_embed_rows_step(c, o.block_host, o.block_dev, m->w_tok_emb, m->w_dec_pos, x, R, d);
     else launch_embed_rows(c, rows_dev, m->w_tok_emb, m->w_dec_pos, x, R, d);
-    float* sc = xsplit;
+    float* sc = ws.xsplit;
     float* pm = sc + (size_t)8 * H * T;
     float* pl = pm + (size_t)8 * H * 8;
     float* po = pl + (size_t)8 * H * 8;
     for (int i = 0; i < D.n_text_layer; ++i) {
         const LayerW& L = m->dec_layers[i];
         const long layer_off = (long)i * ctx_len * d;       // beam 1: [L][ctx][d]
-        GemmArgs g;
-        g.A = x; g.lda = d; g.W = L.qkvw; g.bias = L.qkvb; g.C = qkv; g.ldc = 3 * d; g.M = R; g.N = 3 * d; g.K = d;
+        GemmArgs g = gemm(x, d, L.qkvw, L.qkvb, ws.qkv, 3 * d);
         g.flags = kGemmScaleCols; g.scale = scale; g.scale_cols = 2 * d;
         g.ln_gamma = L.ln1w; g.ln_beta = L.ln1b;
         g.kv_rows = rows_dev; g.kv_layer_off = layer_off; g.kv_d = d; g.kv_ctx = ctx_len;
         launch_gemv(c, g, "dec_ln1_qkv_kv");
-        launch_decoder_self_attention_rows(c, qkv, rows_dev, layer_off, att, R, d, H, ctx_len);
-        GemmArgs o;
-        o.A = att; o.lda = d; o.W = L.outw; o.bias = L.outb; o.C = x; o.ldc = d; o.M = R; o.N = d; o.K = d;
-        o.flags = kGemmResidual; o.R = x; o.ldr = d;
-        launch_gemv(c, o, "dec_out");
-        GemmArgs qq;
-        qq.A = x; qq.lda = d; qq.W = L.xqw; qq.bias = L.xqb; qq.C = q; qq.ldc = d; qq.M = R; qq.N = d; qq.K = d;
+        launch_decoder_self_attention_rows(c, ws.qkv, rows_dev, layer_off, att, R, d, H, ctx_len);
+        residual_gemv(gemm(att, d, L.outw, L.outb, x, d), "dec_out");
+        GemmArgs qq = gemm(x, d, L.xqw, L.xqb, ws.q, d);
         qq.flags = kGemmScaleCols; qq.scale = scale; qq.scale_cols = d; qq.ln_gamma = L.lnxw; qq.ln_beta = L.lnxb;
         // batched steps keep the query projection as ONE multi-row GEMV (weights streamed once for all rows): folded into the
         // split cross-attention every row's 64 workgroups would stream Wq again (19 us per launch at 8 streams,
         // profiles/r04_trace8_busy.txt) - the fold only pays for a single row, where it saves a launch
-        const bool fold_xq = R == 1 && cross_split_folds_query(d);
+        const bool fold_xq = o.fold_one_row_query && R == 1 && cross_split_folds_query(d);
         if (!fold_xq) launch_gemv(c, qq, "dec_lnx_xq");
         CrossAttnArgs ca{};
-        ca.q = q; ca.k = nullptr; ca.v = nullptr; ca.ldkv = (long)D.n_text_layer * 2 * d; ca.out = att;
+        ca.q = ws.q; ca.k = nullptr; ca.v = nullptr; ca.ldkv = (long)D.n_text_layer * 2 * d; ca.out = att;
         ca.rows = R; ca.d = d; ca.n_head = H; ca.T = T;
         ca.head_rank = m->n_align > 0 ? m->head_rank + (size_t)i * H : nullptr;
         ca.ring = nullptr; ca.ring_row = nullptr; ca.beam_of_row = nullptr;
@@ -165,24 +190,25 @@ void wlk_engine::enqueue_decoder(int R, bool from_block, const AlignArgs* side_a
             ca.xq_x = x; ca.xq_w = L.xqw; ca.xq_b = L.xqb; ca.xq_gamma = L.lnxw; ca.xq_beta = L.lnxb; ca.xq_scale = scale;
         }
         launch_decoder_cross_attention_split(c, ca, sc, pm, pl, po, true);
-        GemmArgs xo;
-        xo.A = att; xo.lda = d; xo.W = L.xoutw; xo.bias = L.xoutb; xo.C = x; xo.ldc = d; xo.M = R; xo.N = d; xo.K = d;
-        xo.flags = kGemmResidual; xo.R = x; xo.ldr = d;
-        launch_gemv(c, xo, "dec_xout");
-        GemmArgs f1;
-        f1.A = x; f1.lda = d; f1.W = L.fc1w; f1.bias = L.fc1b; f1.C = mlp; f1.ldc = 4 * d; f1.M = R; f1.N = 4 * d; f1.K = d;
+        residual_gemv(gemm(att, d, L.xoutw, L.xoutb, x, d), "dec_xout");
+        GemmArgs f1 = gemm(x, d, L.fc1w, L.fc1b, ws.mlp, 4 * d);
         f1.flags = kGemmGelu; f1.ln_gamma = L.ln2w; f1.ln_beta = L.ln2b;
         launch_gemv(c, f1, "dec_ln2_fc1");
-        GemmArgs f2;
-        f2.A = mlp; f2.lda = 4 * d; f2.W = L.fc2w; f2.bias = L.fc2b; f2.C = x; f2.ldc = d; f2.M = R; f2.N = d; f2.K = 4 * d;
-        f2.flags = kGemmResidual; f2.R = x; f2.ldr = d;
-        launch_gemv(c, f2, "dec_fc2");
+        residual_gemv(gemm(ws.mlp, 4 * d, L.fc2w, L.fc2b, x, d), "dec_fc2");
     }
-    GemmArgs lg;
-    lg.A = x; lg.lda = d; lg.W = m->w_tok_emb; lg.C = logits; lg.ldc = V; lg.M = R; lg.N = V; lg.K = d;
+    GemmArgs lg = gemm(x, d, m->w_tok_emb, nullptr, ws.logits, V);
     lg.ln_gamma = m->w_ln_w; lg.ln_beta = m->w_ln_b;
-    lg.side_align = side_align; lg.side_blocks = side_blocks; lg.side_zf = side_zf;   // fused replay: the rows' z-scores ride here
+    lg.side_align = o.side_align; lg.side_blocks = o.side_blocks; lg.side_zf = o.side_zf;   // fused replay: the rows' z-scores ride here
     launch_gemv(c, lg, "dec_lnf_logits");
+}
+
+// ---- one batched step ----------------------------------------------------------------------------------------
+void wlk_engine::enqueue_decoder(int R, bool from_block, const AlignArgs* side_align, int side_blocks, int side_zf) {
+    wlk_step_opts o;
+    if (from_block) { o.block_host = blk_host_dev; o.block_dev = blk_dev; }
+    o.side_align = side_align; o.side_blocks = side_blocks; o.side_zf = side_zf;
+    o.fold_one_row_query = true;
+    wlk_enqueue_step_rows(m, LaunchCtx{stream, nullptr}, ws, rows_dev, R, o);
 }
 
 void wlk_engine::enqueue_select(int R, int n_adj) {
@@ -199,8 +225,8 @@ void wlk_engine::enqueue_select(int R, int n_adj) {
     a.rows = rows_dev;
     int* adj_ids = adj_dev + n_adj;
     float* adj_deltas = reinterpret_cast<float*>(adj_dev + 2 * n_adj);
-    if (launch_select_fused(c, logits, V, R, 2, top_vals, top_ids, topk_scratch, adj_dev, adj_ids, adj_deltas, n_adj, a)) return;
-    launch_logsoftmax_topk(c, logits, V, R, 2, top_vals, top_ids, topk_scratch, adj_dev, adj_ids, adj_deltas, n_adj);
+    if (launch_select_fused(c, ws.logits, V, R, 2, top_vals, top_ids, topk_scratch, adj_dev, adj_ids, adj_deltas, n_adj, a)) return;
+    launch_logsoftmax_topk(c, ws.logits, V, R, 2, top_vals, top_ids, topk_scratch, adj_dev, adj_ids, adj_deltas, n_adj);
     if (m->n_align > 0) launch_alignatt(c, a);
     else WLK_HIP(hipMemsetAsync(frames, 0, sizeof(int) * R, stream));
 }
@@ -268,7 +294,7 @@ bool wlk_engine::step_batched_one_replay(std::vector<EngineJob*>& group, std::ve
             ho.seq = &blk_dev->seq;
             float* top_vals = res_dev;
             int* top_ids = reinterpret_cast<int*>(res_dev) + 2 * max_rows;
-            if (!launch_select_fused(c, logits, V, R, 2, top_vals, top_ids, topk_scratch, blk_dev->adj_row, blk_dev->adj_ids,
+            if (!launch_select_fused(c, ws.logits, V, R, 2, top_vals, top_ids, topk_scratch, blk_dev->adj_row, blk_dev->adj_ids,
                                      blk_dev->adj_deltas, 0, a, ho, nullptr, 0, nullptr, early_z))
                 throw std::runtime_error("batched step: read-out not available");
         });
@@ -599,14 +625,8 @@ static wlk_engine* engine_create(wlk_model* m) {
     if (const char* g = std::getenv("WLK_PREFILL_MIN_SESSIONS")) e->pre_min_sessions = std::max(2, std::atoi(g));
     WLK_HIP(hipStreamCreateWithPriority(&e->pre_stream, hipStreamNonBlocking, prio ? prio_hi : prio_lo));
     if (e->batch_prefills) wlk_prefill_ws_alloc(m, e->pre_ws, kMaxBatch, std::min(256, (int)D.n_text_ctx));
-    const size_t R = 8, d = D.n_text_state, T = D.n_audio_ctx, V = D.n_vocab;
-    e->x = dev_alloc<float>(R * d);
-    e->qkv = dev_alloc<float>(R * 3 * d);
-    e->att = dev_alloc<float>(R * d);
-    e->q = dev_alloc<float>(R * d);
-    e->mlp = dev_alloc<float>(R * 4 * d);
-    e->logits = dev_alloc<float>(R * V);
-    e->xsplit = dev_alloc<float>(cross_split_scratch_floats(8, D.n_text_head, (int)T));
+    const size_t R = 8, T = D.n_audio_ctx;
+    wlk_step_ws_alloc(m, e->ws);
     e->z = dev_alloc<float>(R * std::max(m->n_align, 1) * T + R * 128);   // + the read-out's per-block (value, frame) pairs
     e->align_dev = reinterpret_cast<AlignArgs*>(dev_alloc<char>(9 * sizeof(AlignArgs)));
     e->attn_last = dev_alloc<float>(R * T);
@@ -657,7 +677,8 @@ void wlk_engine_destroy_for_model(wlk_model* m) {
     (void)hipSetDevice(m->device);
     if (e->pre_stream) (void)hipStreamDestroy(e->pre_stream);
     wlk_prefill_ws_free(e->pre_ws);
-    float* fl[] = {e->x, e->qkv, e->att, e->q, e->mlp, e->logits, e->xsplit, e->z, e->attn_last, e->res_dev};
+    wlk_step_ws_free(e->ws);
+    float* fl[] = {e->z, e->attn_last, e->res_dev};
     for (float* p : fl)
         if (p) (void)hipFree(p);
     if (e->topk_scratch) (void)hipFree(e->topk_scratch);

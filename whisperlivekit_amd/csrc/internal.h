@@ -96,6 +96,33 @@ inline T* dev_alloc_zero(size_t n, hipStream_t s) {
     return p;
 }
 
+// A device byte buffer of the test entry points (synchronous copies on the legacy stream), freed with its scope.  Never
+// fewer than 64 bytes are allocated, so a kernel may be handed an empty operand.
+struct DevBytes {
+    char* p = nullptr;
+    size_t bytes = 0;
+    void* host = nullptr;      // where back() copies to: mirror()'s host block
+    DevBytes() = default;
+    explicit DevBytes(size_t n, const void* from = nullptr) { alloc(n, from); }
+    DevBytes(const DevBytes&) = delete;
+    DevBytes& operator=(const DevBytes&) = delete;
+    ~DevBytes() { (void)hipFree(p); }
+    void alloc(size_t n, const void* from = nullptr) {      // n bytes, the copy of `from` where given
+        bytes = n;
+        WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 64)));
+        if (from && n) WLK_HIP(hipMemcpy(p, from, n, hipMemcpyHostToDevice));
+    }
+    void mirror(const void* h, size_t n) {                  // alloc + back() copies the n bytes back to h
+        alloc(n, h);
+        host = const_cast<void*>(h);
+    }
+    void back() const { if (host) back(host); }
+    void back(void* to) const { if (bytes) WLK_HIP(hipMemcpy(to, p, bytes, hipMemcpyDeviceToHost)); }
+    template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+    float* f() const { return as<float>(); }
+    int* i() const { return as<int>(); }
+};
+
 }  // namespace wlk
 
 struct wlk_engine;
@@ -388,6 +415,29 @@ void wlk_cif_session_free(wlk_session* s);
 void wlk_cif_enqueue(const std::vector<wlk_session*>& group, const wlk::LaunchCtx& c, const std::vector<int>& content);
 
 // engine.hip
+// ---- the single-token step of up to 8 rows over a StepRow table: the batch engine's steps and the window group's --------
+// Activations of one such step, 8 rows each (xsplit: the split cross-attention's scratch).
+struct wlk_step_ws {
+    float *x = nullptr, *qkv = nullptr, *att = nullptr, *q = nullptr, *mlp = nullptr, *logits = nullptr, *xsplit = nullptr;
+};
+void wlk_step_ws_alloc(const wlk_model* m, wlk_step_ws& ws);
+void wlk_step_ws_free(wlk_step_ws& ws);
+// what a caller's chain may differ in
+struct wlk_step_opts {
+    // embedding: the tokens and offsets come out of the host-coherent block `block_host` (its device-side address), which the
+    // first kernel also copies into `block_dev`, whose `rows` is then the table (launch_embed_rows_step); nullptr = the table
+    const wlk::EngineBlock* block_host = nullptr;
+    wlk::EngineBlock* block_dev = nullptr;
+    // riders of the vocabulary GEMV (GemmArgs::side_align): the rows' z-scores of a fused replay
+    const wlk::AlignArgs* side_align = nullptr;
+    int side_blocks = 0, side_zf = 0;
+    // a step of ONE row folds the cross-attention's query projection into the attention kernel where that kernel can
+    bool fold_one_row_query = false;
+};
+// embed .. logits of R rows on c.stream: the one statement of the chain, whoever takes the step
+void wlk_enqueue_step_rows(const wlk_model* m, const wlk::LaunchCtx& c, const wlk_step_ws& ws, const wlk::StepRow* rows_dev, int R,
+                           const wlk_step_opts& o = wlk_step_opts{});
+
 // the prefill of an attached session through the engine's prefill lane (stacked with the prefills other sessions have
 // waiting); 1 = not taken (the caller runs wlk_decode itself); blocks until this session's prefill is done
 int wlk_engine_prefill(wlk_session* s, const int64_t* tokens, int n_tok, int sot_index);

@@ -38,6 +38,7 @@
 
 #include "../../include/wlk_hip.h"
 #include "common.h"
+#include "internal.h"
 #include "nllb_internal.h"
 #include "wave_ops.h"
 
@@ -906,22 +907,6 @@ int wlk_nllb_batch_cross_attention(wlk_nllb_batch* b, const int32_t* slots, int3
  * cross_kv / content_len are the caller's blocks and lengths.  Refusals (nllb_cross_ragged_check on the host's lengths and
  * ranks, and what a buffer cannot hold) come before anything is uploaded. */
 int wlk_diag_nllb_cross_ragged(const wlk_diag_nllb_cross_ragged_args* g) {
-    struct Buf {        // a device copy of exactly `bytes` host bytes (never fewer than 64), copied back whole
-        char* p = nullptr;
-        void* host = nullptr;
-        size_t bytes = 0;
-        Buf() = default;
-        Buf(const Buf&) = delete;
-        void set(void* h, size_t n) {
-            host = h;
-            bytes = n;
-            WLK_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(bytes, 64)));
-            if (host && bytes) WLK_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
-        }
-        float* f() const { return reinterpret_cast<float*>(p); }
-        void back() const { if (host && bytes) WLK_HIP(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost)); }
-        ~Buf() { (void)hipFree(p); }
-    };
     try {
         auto need = [](bool ok, const char* what) {
             if (!ok) throw std::invalid_argument(std::string("wlk_diag_nllb_cross_ragged: ") + what);
@@ -942,13 +927,13 @@ int wlk_diag_nllb_cross_ragged(const wlk_diag_nllb_cross_ragged_args* g) {
                  "a K/V block lies past kv (offsets are multiples of 4)");
         }
         need(!align || (int64_t)g->n_rank * kNlBatchMaxRows * g->align_stride <= g->probs_floats, "align_probs holds fewer than n_rank x 8 x align_stride floats");
-        Buf Q, KV, OUT, PROBS, RANK, ROWS;
-        Q.set(g->q, (size_t)g->q_floats * 4);
-        KV.set(g->kv, (size_t)g->kv_floats * 4);
-        OUT.set(g->out, (size_t)g->out_floats * 4);
+        DevBytes Q, KV, OUT, PROBS, RANK;
+        Q.mirror(g->q, (size_t)g->q_floats * 4);
+        KV.mirror(g->kv, (size_t)g->kv_floats * 4);
+        OUT.mirror(g->out, (size_t)g->out_floats * 4);
         if (align) {
-            PROBS.set(g->align_probs, (size_t)g->probs_floats * 4);
-            RANK.set(g->head_rank, (size_t)g->n_head * 4);
+            PROBS.mirror(g->align_probs, (size_t)g->probs_floats * 4);
+            RANK.alloc((size_t)g->n_head * 4, g->head_rank);
         }
         std::vector<StepRow> table((size_t)g->n_rows);
         for (int r = 0; r < g->n_rows; ++r) {
@@ -956,14 +941,13 @@ int wlk_diag_nllb_cross_ragged(const wlk_diag_nllb_cross_ragged_args* g) {
             table[r].cross_kv = KV.f() + g->kv_at[r];
             table[r].content_len = g->lengths[r];
         }
-        ROWS.set(nullptr, table.size() * sizeof(StepRow));
-        WLK_HIP(hipMemcpy(ROWS.p, table.data(), table.size() * sizeof(StepRow), hipMemcpyHostToDevice));
+        DevBytes ROWS(table.size() * sizeof(StepRow), table.data());
         LaunchCtx ctx;
         WLK_HIP(hipDeviceSynchronize());
-        const StepRow* rows = reinterpret_cast<const StepRow*>(ROWS.p);
+        const StepRow* rows = ROWS.as<const StepRow>();
         if (align)
             launch_nllb_cross_attention_ragged_align(ctx, Q.f(), rows, (long)g->kv_off, (long)g->ldkv, OUT.f(), g->n_rows, g->d, g->n_head,
-                                                     reinterpret_cast<const int*>(RANK.p), PROBS.f(), g->align_stride);
+                                                     RANK.i(), PROBS.f(), g->align_stride);
         else
             launch_nllb_cross_attention_ragged(ctx, Q.f(), rows, (long)g->kv_off, (long)g->ldkv, OUT.f(), g->n_rows, g->d, g->n_head);
         WLK_HIP(hipDeviceSynchronize());

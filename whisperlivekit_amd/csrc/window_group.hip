@@ -15,9 +15,8 @@
 // (group_advance_rows_kernel) derives it on the device between two chains.  The host enqueues `burst` chains back to back,
 // reads the picks and the per-row step counts back once and synchronises once.  wlk_group_step_pick is its one-step case.
 //
-// The layer chain restates wlk_engine::enqueue_decoder (engine.hip) with one difference: the cross-attention's query
-// projection is the multi-row GEMV for EVERY row count, also for one row (the engine folds it into the attention kernel
-// there).  A row therefore goes through the same kernels whether it steps alone or beside seven others.
+// The layer chain is the batch engine's, wlk_enqueue_step_rows (engine.hip), without the one-row fold of the
+// cross-attention's query projection: a row goes through the same kernels whether it steps alone or beside seven others.
 //
 // The same group also aligns the words of up to 8 windows in one call (wlk_group_find_alignment): one stacked
 // teacher-forced decoder pass (api.hip: wlk_prefill_chain), the token probabilities per window, the ragged normalisation
@@ -63,6 +62,22 @@ struct GroupBlock {
 struct GroupResults {
     int picks[kGroupMaxRows][kGroupMaxBurst][2];   // [row][own step][token | log-probability bits]
     int taken[kGroupMaxRows];                      // own steps of every row
+};
+// a device block that grows on demand and is freed with its owner
+struct GrowBuf {
+    char* p = nullptr;
+    size_t cap = 0;
+    GrowBuf() = default;
+    GrowBuf(const GrowBuf&) = delete;
+    ~GrowBuf() { if (p) (void)hipFree(p); }
+    void reserve(size_t bytes, hipStream_t stream) {
+        if (bytes <= cap) return;
+        WLK_HIP(hipStreamSynchronize(stream));     // what the stream still has queued reads the old block
+        if (p) WLK_HIP(hipFree(p));
+        p = nullptr; cap = 0;
+        p = dev_alloc<char>(bytes);
+        cap = bytes;
+    }
 };
 
 // Between two chains of a call: one wave, lane r = row r.  A live row's pick goes to its next result slot; unless that pick
@@ -111,7 +126,7 @@ struct wlk_group {
     wlk_model* m = nullptr;
     int max_rows = 1;
     hipStream_t stream = nullptr;
-    float *x = nullptr, *qkv = nullptr, *att = nullptr, *q = nullptr, *mlp = nullptr, *logits = nullptr, *xsplit = nullptr;
+    wlk_step_ws ws;                      // the activations of the step chain
     GroupBlock* blk_dev = nullptr;
     int* pick_dev = nullptr;             // [R][token | log-probability]
     GroupResults* results_dev = nullptr; // a call of more than one chain: every row's picks and step count
@@ -123,32 +138,26 @@ struct wlk_group {
     // stacked word alignment (wlk_group_find_alignment): nothing of it exists before the first such call
     wlk_prefill_ws align_ws;             // the stacked decoder pass over 8 x 256 rows
     bool align_ready = false;
-    char* align_buf = nullptr;           // grown on demand: [hidden | logits | w | cost | results | trace_t | trace]
-    size_t align_cap = 0;
+    GrowBuf align_buf;                   // [hidden | logits | w | cost | results | trace_t | trace]
     char* align_up_dev = nullptr;        // [AlignWin x 8 | targets int x 8 x 256]
     char* align_pinned = nullptr;        // [upload block | results: starts and token probabilities of all windows]
     // draft verification (wlk_group_verify): shares the stacked decoder pass's workspace; nothing of it exists before the
     // first such call
-    char* verify_buf = nullptr;          // grown on demand: [hidden (n_d + 2) x d | logits (n_d + 2) x V] of the longest draft
-    size_t verify_cap = 0;
+    GrowBuf verify_buf;                  // [hidden (n_d + 2) x d | logits (n_d + 2) x V] of the longest draft
     int* verify_dev = nullptr;           // [drafts int x 8 x 256 | picks int x 8 x 257 x 3 | results int x 8 x 8]
     int* verify_pinned = nullptr;        // [drafts | results]
 
     ~wlk_group() {
         (void)hipSetDevice(m->device);
         if (stream) (void)hipStreamSynchronize(stream);
-        float* fl[] = {x, qkv, att, q, mlp, logits, xsplit};
-        for (float* p : fl)
-            if (p) (void)hipFree(p);
+        wlk_step_ws_free(ws);
         if (blk_dev) (void)hipFree(blk_dev);
         if (pick_dev) (void)hipFree(pick_dev);
         if (results_dev) (void)hipFree(results_dev);
         if (pinned) (void)hipHostFree(pinned);
         if (align_ready) wlk_prefill_ws_free(align_ws);
-        if (align_buf) (void)hipFree(align_buf);
         if (align_up_dev) (void)hipFree(align_up_dev);
         if (align_pinned) (void)hipHostFree(align_pinned);
-        if (verify_buf) (void)hipFree(verify_buf);
         if (verify_dev) (void)hipFree(verify_dev);
         if (verify_pinned) (void)hipHostFree(verify_pinned);
         for (hipEvent_t e : joined)
@@ -156,67 +165,49 @@ struct wlk_group {
         if (stream) (void)hipStreamDestroy(stream);
     }
 
-    void enqueue_step(int R);
+    // embed .. logits of R rows + every row's pick
+    void enqueue_step(int R) {
+        const LaunchCtx c{stream, nullptr};
+        wlk_enqueue_step_rows(m, c, ws, blk_dev->rows, R);
+        launch_rules_pick_rows(c, ws.logits, m->D.n_vocab, R, blk_dev->pick, pick_dev);
+    }
+    // what session s's own stream has queued (encode, prefill, its earlier steps) is done before this stream touches its caches
+    void join(int r, const wlk_session* s) {
+        WLK_HIP(hipEventRecord(joined[r], s->stream));
+        WLK_HIP(hipStreamWaitEvent(stream, joined[r], 0));
+    }
+    void stacked_ws_ready();             // the stacked decoder pass's workspace, allocated by the first call that needs it
     int run_pick(wlk_session* const* sessions, const int64_t* tokens, const wlk_pick_params* p, const int32_t* max_steps, int n,
                  int burst, int32_t* tokens_out, float* logprobs_out, int32_t* steps_out);
 };
 
-// embed .. logits of R rows + every row's pick: wlk_engine::enqueue_decoder's operators in its order (see the file comment)
-void wlk_group::enqueue_step(int R) {
-    const wlk_dims& D = m->D;
-    const int d = D.n_text_state, T = D.n_audio_ctx, H = D.n_text_head, V = D.n_vocab, ctx_len = D.n_text_ctx;
-    const LaunchCtx c{stream, nullptr};
-    const float scale = std::pow((float)kHeadDim, -0.25f);
-    const StepRow* rows_dev = blk_dev->rows;
-    launch_embed_rows(c, rows_dev, m->w_tok_emb, m->w_dec_pos, x, R, d);
-    float* sc = xsplit;
-    float* pm = sc + (size_t)8 * H * T;
-    float* pl = pm + (size_t)8 * H * 8;
-    float* po = pl + (size_t)8 * H * 8;
-    for (int i = 0; i < D.n_text_layer; ++i) {
-        const LayerW& L = m->dec_layers[i];
-        const long layer_off = (long)i * ctx_len * d;       // beam 1: [L][ctx][d]
-        GemmArgs g;
-        g.A = x; g.lda = d; g.W = L.qkvw; g.bias = L.qkvb; g.C = qkv; g.ldc = 3 * d; g.M = R; g.N = 3 * d; g.K = d;
-        g.flags = kGemmScaleCols; g.scale = scale; g.scale_cols = 2 * d;
-        g.ln_gamma = L.ln1w; g.ln_beta = L.ln1b;
-        g.kv_rows = rows_dev; g.kv_layer_off = layer_off; g.kv_d = d; g.kv_ctx = ctx_len;
-        launch_gemv(c, g, "dec_ln1_qkv_kv");
-        launch_decoder_self_attention_rows(c, qkv, rows_dev, layer_off, att, R, d, H, ctx_len);
-        GemmArgs o;
-        o.A = att; o.lda = d; o.W = L.outw; o.bias = L.outb; o.C = x; o.ldc = d; o.M = R; o.N = d; o.K = d;
-        o.flags = kGemmResidual; o.R = x; o.ldr = d;
-        launch_gemv(c, o, "dec_out");
-        GemmArgs qq;
-        qq.A = x; qq.lda = d; qq.W = L.xqw; qq.bias = L.xqb; qq.C = q; qq.ldc = d; qq.M = R; qq.N = d; qq.K = d;
-        qq.flags = kGemmScaleCols; qq.scale = scale; qq.scale_cols = d; qq.ln_gamma = L.lnxw; qq.ln_beta = L.lnxb;
-        launch_gemv(c, qq, "dec_lnx_xq");
-        CrossAttnArgs ca{};
-        ca.q = q; ca.k = nullptr; ca.v = nullptr; ca.ldkv = (long)D.n_text_layer * 2 * d; ca.out = att;
-        ca.rows = R; ca.d = d; ca.n_head = H; ca.T = T;
-        ca.head_rank = m->n_align > 0 ? m->head_rank + (size_t)i * H : nullptr;
-        ca.ring = nullptr; ca.ring_row = nullptr; ca.beam_of_row = nullptr;
-        ca.ring_rows = ctx_len + kAlignWindow; ca.n_beam = 1; ca.qk_debug = nullptr;
-        ca.step_rows = rows_dev; ca.kv_off = (long)i * 2 * d;
-        launch_decoder_cross_attention_split(c, ca, sc, pm, pl, po, true);
-        GemmArgs xo;
-        xo.A = att; xo.lda = d; xo.W = L.xoutw; xo.bias = L.xoutb; xo.C = x; xo.ldc = d; xo.M = R; xo.N = d; xo.K = d;
-        xo.flags = kGemmResidual; xo.R = x; xo.ldr = d;
-        launch_gemv(c, xo, "dec_xout");
-        GemmArgs f1;
-        f1.A = x; f1.lda = d; f1.W = L.fc1w; f1.bias = L.fc1b; f1.C = mlp; f1.ldc = 4 * d; f1.M = R; f1.N = 4 * d; f1.K = d;
-        f1.flags = kGemmGelu; f1.ln_gamma = L.ln2w; f1.ln_beta = L.ln2b;
-        launch_gemv(c, f1, "dec_ln2_fc1");
-        GemmArgs f2;
-        f2.A = mlp; f2.lda = 4 * d; f2.W = L.fc2w; f2.bias = L.fc2b; f2.C = x; f2.ldc = d; f2.M = R; f2.N = d; f2.K = 4 * d;
-        f2.flags = kGemmResidual; f2.R = x; f2.ldr = d;
-        launch_gemv(c, f2, "dec_fc2");
-    }
-    GemmArgs lg;
-    lg.A = x; lg.lda = d; lg.W = m->w_tok_emb; lg.C = logits; lg.ldc = V; lg.M = R; lg.N = V; lg.K = d;
-    lg.ln_gamma = m->w_ln_w; lg.ln_beta = m->w_ln_b;
-    launch_gemv(c, lg, "dec_lnf_logits");
-    launch_rules_pick_rows(c, logits, V, R, blk_dev->pick, pick_dev);
+// The host checks of one listed session that every entry point makes before anything is launched (a refused call touches
+// nothing), in the order each entry point has always made them.  own_arg_error: the verdict on the row's other arguments,
+// which ranks behind the session's own argument errors and before its state.  The stacked decoder pass of an alignment or
+// a verify call takes plain sessions only; a verify pass, as a prefill, none that keeps raw alignment scores.
+enum GateCall { kGateStep, kGateAlign, kGateVerify };
+static int gate_session(const wlk_group* g, const wlk_session* s, bool listed_before, GateCall call,
+                        const char* own_arg_error = nullptr) {
+    static const char* const kName[] = {"window group step", "find_alignment", "verify"};
+    const char* name = kName[call];
+    if (!s) return fail(WLK_ERR_ARG, "window group: NULL session");
+    if (listed_before) return fail(WLK_ERR_ARG, "window group: a session is listed twice");
+    if (s->m != g->m) return fail(WLK_ERR_ARG, "window group: a session of another model");
+    if (s->beam != 1) return fail(WLK_ERR_ARG, std::string(name) + " needs a beam-1 session");
+    if (own_arg_error) return fail(WLK_ERR_ARG, own_arg_error);
+    if (s->engine) return fail(WLK_ERR_STATE, "window group: the session is attached to the batch engine");
+    if (!s->encoded) return fail(WLK_ERR_STATE, std::string(name) + " before an encode");
+    if (call == kGateVerify && !s->rules_mask) return fail(WLK_ERR_STATE, "verify before wlk_rules_set");
+    if (call != kGateStep && (s->debug || s->prof_on || (call == kGateVerify && s->align_raw_scores)))
+        return fail(WLK_ERR_STATE, "window group: not a plain beam-1 session");
+    return WLK_OK;
+}
+// the stacked pass overwrites the session's caches and score window: whatever happens from there on, its next decode must be
+// a prefill (as after wlk_find_alignment)
+static void next_decode_is_prefill(wlk_session* s) {
+    s->n_steps = 0;
+    s->self_len = 0;
+    s->have_sot = false;
 }
 
 static bool pick_params_ok(const wlk_pick_params& p, int V) {
@@ -241,17 +232,9 @@ int wlk_group_create(wlk_model* m, int max_rows, wlk_group** out) {
         g->m = m;
         g->max_rows = max_rows;
         WLK_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-        const wlk_dims& D = m->D;
-        const size_t R = kGroupMaxRows, d = D.n_text_state, T = D.n_audio_ctx, V = D.n_vocab;
-        g->x = dev_alloc<float>(R * d);
-        g->qkv = dev_alloc<float>(R * 3 * d);
-        g->att = dev_alloc<float>(R * d);
-        g->q = dev_alloc<float>(R * d);
-        g->mlp = dev_alloc<float>(R * 4 * d);
-        g->logits = dev_alloc<float>(R * V);
-        g->xsplit = dev_alloc<float>(cross_split_scratch_floats(8, D.n_text_head, (int)T));
+        wlk_step_ws_alloc(m, g->ws);
         g->blk_dev = reinterpret_cast<GroupBlock*>(dev_alloc<char>(sizeof(GroupBlock)));
-        g->pick_dev = dev_alloc<int>(2 * R);
+        g->pick_dev = dev_alloc<int>(2 * kGroupMaxRows);
         g->results_dev = reinterpret_cast<GroupResults*>(dev_alloc<char>(sizeof(GroupResults)));
         WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&g->pinned), sizeof(GroupBlock) + sizeof(GroupResults), hipHostMallocDefault));
         std::memset(g->pinned, 0, sizeof(GroupBlock) + sizeof(GroupResults));
@@ -293,16 +276,12 @@ int wlk_group::run_pick(wlk_session* const* sessions, const int64_t* tokens, con
     // every session is checked on the host before anything is launched: a refused call has advanced nobody
     for (int r = 0; r < n; ++r) {
         const wlk_session* s = sessions[r];
-        if (!s) return fail(WLK_ERR_ARG, "window group: NULL session");
-        for (int j = 0; j < r; ++j)
-            if (sessions[j] == s) return fail(WLK_ERR_ARG, "window group: a session is listed twice");
-        if (s->m != g->m) return fail(WLK_ERR_ARG, "window group: a session of another model");
-        if (s->beam != 1) return fail(WLK_ERR_ARG, "window group: only sessions of one row");
-        if (tokens[r] < 0 || tokens[r] >= D.n_vocab) return fail(WLK_ERR_ARG, "token id out of range");
-        if (!pick_params_ok(p[r], D.n_vocab)) return fail(WLK_ERR_ARG, "rule parameters out of range");
-        if (max_steps && max_steps[r] < 1) return fail(WLK_ERR_ARG, "window group: a row's step budget is at least 1");
-        if (s->engine) return fail(WLK_ERR_STATE, "window group: the session is attached to the batch engine (its steps belong to the engine's loops)");
-        if (!s->encoded || s->n_steps < 1) return fail(WLK_ERR_STATE, "window group: step before the session's prefill");
+        const char* own = tokens[r] < 0 || tokens[r] >= D.n_vocab ? "token id out of range"
+                          : !pick_params_ok(p[r], D.n_vocab)      ? "rule parameters out of range"
+                          : max_steps && max_steps[r] < 1         ? "window group: a row's step budget is at least 1"
+                                                                  : nullptr;
+        if (const int rc = gate_session(g, s, std::find(sessions, sessions + r, s) != sessions + r, kGateStep, own)) return rc;
+        if (s->n_steps < 1) return fail(WLK_ERR_STATE, "window group: step before the session's prefill");
         if (!s->rules_mask) return fail(WLK_ERR_STATE, "window group: step before wlk_rules_set");
         if (s->self_len + 1 > D.n_text_ctx) return fail(WLK_ERR_STATE, "text context exceeded");
     }
@@ -317,9 +296,7 @@ int wlk_group::run_pick(wlk_session* const* sessions, const int64_t* tokens, con
             blk->pick[r] = PickRowEntry{s->rules_mask, pick_rules_of(p[r])};
             const int limit = std::min(std::min(max_steps ? (int)max_steps[r] : 1, burst), (int)D.n_text_ctx - s->self_len);
             blk->burst[r] = BurstRow{1, 0, limit, s->n_steps, s->self_len, s->prefill_rows};
-            // encode, prefill and an earlier step of the session's own chain have finished before this stream touches its caches
-            WLK_HIP(hipEventRecord(g->joined[r], s->stream));
-            WLK_HIP(hipStreamWaitEvent(g->stream, g->joined[r], 0));
+            g->join(r, s);
         }
         uint64_t rows_taken = 0;
         if (burst == 1) {
@@ -391,6 +368,12 @@ std::string align_shape_refusal(const wlk_model* m, int P, int num_frames) {
 }
 }  // namespace
 
+void wlk_group::stacked_ws_ready() {
+    if (align_ready) return;
+    wlk_prefill_ws_alloc(m, align_ws, kGroupMaxRows, align_session_rows(m));
+    align_ready = true;
+}
+
 extern "C" {
 
 int wlk_group_align_fits(wlk_group* g, int32_t n_tokens, int32_t num_frames, int32_t* fits) {
@@ -409,13 +392,8 @@ int wlk_group_find_alignment(wlk_group* g, const wlk_align_window* w, int n) {
         const wlk_align_window& a = w[r];
         const wlk_session* s = a.s;
         if (!s || !a.tokens || !a.starts || !a.token_probs) return fail(WLK_ERR_ARG, "window group: NULL argument in an alignment window");
-        for (int j = 0; j < r; ++j)
-            if (w[j].s == s) return fail(WLK_ERR_ARG, "window group: a session is listed twice");
-        if (s->m != m) return fail(WLK_ERR_ARG, "window group: a session of another model");
-        if (s->beam != 1) return fail(WLK_ERR_ARG, "find_alignment needs a beam-1 session");
-        if (s->engine) return fail(WLK_ERR_STATE, "window group: the session is attached to the batch engine");
-        if (!s->encoded) return fail(WLK_ERR_STATE, "find_alignment before an encode");
-        if (s->debug || s->prof_on) return fail(WLK_ERR_STATE, "window group: not a plain beam-1 session");
+        const bool twice = std::any_of(w, w + r, [s](const wlk_align_window& o) { return o.s == s; });
+        if (const int rc = gate_session(g, s, twice, kGateAlign)) return rc;
         const int P = a.n_tokens, n_text = P - a.n_sot - 2;
         if (a.n_sot < 1 || n_text < 1) return fail(WLK_ERR_ARG, "find_alignment: need [sot sequence, notimestamps, >= 1 text token, eot]");
         if (a.eot < 1 || a.eot > D.n_vocab) return fail(WLK_ERR_ARG, "find_alignment: eot out of range");
@@ -431,10 +409,7 @@ int wlk_group_find_alignment(wlk_group* g, const wlk_align_window* w, int n) {
         WLK_HIP(hipSetDevice(m->device));
         const LaunchCtx c{g->stream, nullptr};
         const int d = D.n_text_state, T = D.n_audio_ctx;
-        if (!g->align_ready) {
-            wlk_prefill_ws_alloc(m, g->align_ws, kGroupMaxRows, align_session_rows(m));
-            g->align_ready = true;
-        }
+        g->stacked_ws_ready();
         if (!g->align_up_dev) {
             g->align_up_dev = dev_alloc<char>(kAlignUpBytes);
             WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&g->align_pinned), kAlignUpBytes + kAlignResBytes, hipHostMallocDefault));
@@ -450,17 +425,10 @@ int wlk_group_find_alignment(wlk_group* g, const wlk_align_window* w, int n) {
             n_res += (size_t)N + n_text;
         }
         const size_t res_b = up16(n_res * 4);
-        const size_t need = hid_b + log_b + wc_b + res_b + 2 * tr_b;
-        if (need > g->align_cap) {
-            WLK_HIP(hipStreamSynchronize(g->stream));
-            if (g->align_buf) WLK_HIP(hipFree(g->align_buf));
-            g->align_buf = nullptr; g->align_cap = 0;
-            g->align_buf = dev_alloc<char>(need);
-            g->align_cap = need;
-        }
-        float* hid = reinterpret_cast<float*>(g->align_buf);
-        float* logits = reinterpret_cast<float*>(g->align_buf + hid_b);
-        char* at = g->align_buf + hid_b + log_b;
+        g->align_buf.reserve(hid_b + log_b + wc_b + res_b + 2 * tr_b, g->stream);
+        float* hid = reinterpret_cast<float*>(g->align_buf.p);
+        float* logits = reinterpret_cast<float*>(g->align_buf.p + hid_b);
+        char* at = g->align_buf.p + hid_b + log_b;
         int* res_dev = reinterpret_cast<int*>(at + wc_b);
         signed char* trace_t0 = reinterpret_cast<signed char*>(at + wc_b + res_b);
         signed char* trace0 = trace_t0 + tr_b;
@@ -499,14 +467,8 @@ int wlk_group_find_alignment(wlk_group* g, const wlk_align_window* w, int n) {
             items[r].s = s; items[r].tokens = w[r].tokens; items[r].n_tok = P; items[r].sot_index = 0;
             stack[r] = &items[r];
             if (s->ring_rows != w[0].s->ring_rows) throw std::logic_error("window group: score windows of different heights");
-            // the chain overwrites the session's caches and score window: whatever happens from here on, its next decode
-            // must be a prefill (as after wlk_find_alignment)
-            s->n_steps = 0;
-            s->self_len = 0;
-            s->have_sot = false;
-            // what the session's own stream has queued (encode, its window's steps) is done before this stream touches it
-            WLK_HIP(hipEventRecord(g->joined[r], s->stream));
-            WLK_HIP(hipStreamWaitEvent(g->stream, g->joined[r], 0));
+            next_decode_is_prefill(s);
+            g->join(r, s);
         }
         WLK_HIP(hipMemcpyAsync(g->align_up_dev, g->align_pinned, kAlignUpBytes, hipMemcpyHostToDevice, g->stream));
 
@@ -581,14 +543,8 @@ int wlk_group_verify(wlk_group* g, const wlk_verify_window* w, int n) {
         const wlk_verify_window& a = w[r];
         const wlk_session* s = a.s;
         if (!s || !a.tokens || !a.result) return fail(WLK_ERR_ARG, "window group: NULL argument in a verify window");
-        for (int j = 0; j < r; ++j)
-            if (w[j].s == s) return fail(WLK_ERR_ARG, "window group: a session is listed twice");
-        if (s->m != m) return fail(WLK_ERR_ARG, "window group: a session of another model");
-        if (s->beam != 1) return fail(WLK_ERR_ARG, "verify needs a beam-1 session");
-        if (s->engine) return fail(WLK_ERR_STATE, "window group: the session is attached to the batch engine");
-        if (!s->encoded) return fail(WLK_ERR_STATE, "verify before an encode");
-        if (!s->rules_mask) return fail(WLK_ERR_STATE, "verify before wlk_rules_set");
-        if (s->debug || s->prof_on || s->align_raw_scores) return fail(WLK_ERR_STATE, "window group: not a plain beam-1 session");
+        const bool twice = std::any_of(w, w + r, [s](const wlk_verify_window& o) { return o.s == s; });
+        if (const int rc = gate_session(g, s, twice, kGateVerify)) return rc;
         const int P0 = a.n_initial, P = a.n_tokens, n_d = P - P0;
         if (n_d < 1) return fail(WLK_ERR_ARG, "verify: an empty draft");
         const std::string shape = verify_shape_refusal(m, P0, n_d);
@@ -608,10 +564,7 @@ int wlk_group_verify(wlk_group* g, const wlk_verify_window* w, int n) {
         WLK_HIP(hipSetDevice(m->device));
         const LaunchCtx c{g->stream, nullptr};
         const int d = D.n_text_state, T = D.n_audio_ctx;
-        if (!g->align_ready) {
-            wlk_prefill_ws_alloc(m, g->align_ws, kGroupMaxRows, align_session_rows(m));
-            g->align_ready = true;
-        }
+        g->stacked_ws_ready();
         if (!g->verify_dev) {
             g->verify_dev = dev_alloc<int>(kVerifyDraftInts + kVerifyPickInts + kVerifyResAll);
             WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&g->verify_pinned), (kVerifyDraftInts + kVerifyResAll) * sizeof(int),
@@ -620,16 +573,10 @@ int wlk_group_verify(wlk_group* g, const wlk_verify_window* w, int n) {
         // ---- workspace: [hidden | logits] of the longest window: its n_d + 1 candidate rows and the sot row behind them
         int rows_max = 0;
         for (int r = 0; r < n; ++r) rows_max = std::max(rows_max, w[r].n_tokens - w[r].n_initial + 2);
-        const size_t hid_b = up16((size_t)rows_max * d * 4), need = hid_b + up16((size_t)rows_max * V * 4);
-        if (need > g->verify_cap) {
-            WLK_HIP(hipStreamSynchronize(g->stream));
-            if (g->verify_buf) WLK_HIP(hipFree(g->verify_buf));
-            g->verify_buf = nullptr; g->verify_cap = 0;
-            g->verify_buf = dev_alloc<char>(need);
-            g->verify_cap = need;
-        }
-        float* hid = reinterpret_cast<float*>(g->verify_buf);
-        float* logits = reinterpret_cast<float*>(g->verify_buf + hid_b);
+        const size_t hid_b = up16((size_t)rows_max * d * 4);
+        g->verify_buf.reserve(hid_b + up16((size_t)rows_max * V * 4), g->stream);
+        float* hid = reinterpret_cast<float*>(g->verify_buf.p);
+        float* logits = reinterpret_cast<float*>(g->verify_buf.p + hid_b);
         int* draft_dev = g->verify_dev;
         int* picks_dev = draft_dev + kVerifyDraftInts;
         int* res_dev = picks_dev + kVerifyPickInts;
@@ -644,14 +591,8 @@ int wlk_group_verify(wlk_group* g, const wlk_verify_window* w, int n) {
             for (int i = 0; i < n_d; ++i) draft_h[(size_t)r * kMaxDraft + i] = (int)w[r].tokens[P0 + i];
             items[r].s = s; items[r].tokens = w[r].tokens; items[r].n_tok = w[r].n_tokens; items[r].sot_index = w[r].sot_index;
             stack[r] = &items[r];
-            // the chain overwrites the session's caches and score window: should anything fail from here on, its next
-            // decode must be a prefill
-            s->n_steps = 0;
-            s->self_len = 0;
-            s->have_sot = false;
-            // what the session's own stream has queued (encode, an earlier window's steps) is done before this stream touches it
-            WLK_HIP(hipEventRecord(g->joined[r], s->stream));
-            WLK_HIP(hipStreamWaitEvent(g->stream, g->joined[r], 0));
+            next_decode_is_prefill(s);
+            g->join(r, s);
         }
         WLK_HIP(hipMemcpyAsync(draft_dev, draft_h, (size_t)n * kMaxDraft * sizeof(int), hipMemcpyHostToDevice, g->stream));
         WLK_HIP(hipMemsetAsync(res_dev, 0, kVerifyResAll * sizeof(int), g->stream));
@@ -748,7 +689,7 @@ int wlk_group_export_logits(wlk_group* g, int row, float* host, uint64_t capacit
     return guarded([&]() {
         WLK_HIP(hipSetDevice(g->m->device));
         WLK_HIP(hipStreamSynchronize(g->stream));
-        copy_sync(host, g->logits + (size_t)row * V, V * sizeof(float), hipMemcpyDeviceToHost);
+        copy_sync(host, g->ws.logits + (size_t)row * V, V * sizeof(float), hipMemcpyDeviceToHost);
         return WLK_OK;
     });
 }
@@ -765,32 +706,18 @@ int wlk_diag_pick_rows(const float* logits_host, int n_vocab, const uint8_t* mas
             return fail(WLK_ERR_ARG, "pick rows: mask index or rule parameters out of range");
     return guarded([&]() {
         const size_t V = (size_t)n_vocab;
-        float* logits = dev_alloc<float>(V * n);
-        unsigned char* masks = dev_alloc<unsigned char>(V * n_masks);
-        PickRowEntry* table = reinterpret_cast<PickRowEntry*>(dev_alloc<char>(sizeof(PickRowEntry) * kGroupMaxRows));
-        int* out = dev_alloc<int>(2 * kGroupMaxRows);
-        auto release = [&] {
-            (void)hipFree(logits); (void)hipFree(masks); (void)hipFree(table); (void)hipFree(out);
-        };
-        try {
-            PickRowEntry host[kGroupMaxRows];
-            for (int r = 0; r < n; ++r) host[r] = PickRowEntry{masks + V * mask_of_row[r], pick_rules_of(p[r])};
-            copy_sync(logits, logits_host, V * n * sizeof(float), hipMemcpyHostToDevice);
-            copy_sync(masks, masks_host, V * n_masks, hipMemcpyHostToDevice);
-            copy_sync(table, host, sizeof(PickRowEntry) * n, hipMemcpyHostToDevice);
-            launch_rules_pick_rows(LaunchCtx{nullptr, nullptr}, logits, n_vocab, n, table, out);
-            int res[2 * kGroupMaxRows];
-            WLK_HIP(hipStreamSynchronize(nullptr));
-            copy_sync(res, out, (size_t)8 * n, hipMemcpyDeviceToHost);
-            for (int r = 0; r < n; ++r) {
-                tokens_out[r] = res[2 * r];
-                std::memcpy(&logprobs_out[r], &res[2 * r + 1], 4);
-            }
-        } catch (...) {
-            release();
-            throw;
+        DevBytes logits(V * n * sizeof(float), logits_host), masks(V * n_masks, masks_host), out(8 * n);
+        PickRowEntry host[kGroupMaxRows];
+        for (int r = 0; r < n; ++r) host[r] = PickRowEntry{masks.as<unsigned char>() + V * mask_of_row[r], pick_rules_of(p[r])};
+        DevBytes table(sizeof(PickRowEntry) * n, host);
+        launch_rules_pick_rows(LaunchCtx{nullptr, nullptr}, logits.f(), n_vocab, n, table.as<PickRowEntry>(), out.i());
+        int res[2 * kGroupMaxRows];
+        WLK_HIP(hipStreamSynchronize(nullptr));
+        out.back(res);
+        for (int r = 0; r < n; ++r) {
+            tokens_out[r] = res[2 * r];
+            std::memcpy(&logprobs_out[r], &res[2 * r + 1], 4);
         }
-        release();
         return WLK_OK;
     });
 }
@@ -803,33 +730,17 @@ int wlk_diag_pick_advance(const wlk_pick_params* p, const int32_t* tokens, int n
     return guarded([&]() {
         std::vector<PickRules> host(n);
         for (int i = 0; i < n; ++i) host[i] = pick_rules_of(p[i]);
-        PickRules* in_dev = reinterpret_cast<PickRules*>(dev_alloc<char>(sizeof(PickRules) * n));
-        PickRules* out_dev = nullptr;
-        int* tok_dev = nullptr;
-        auto release = [&] {
-            (void)hipFree(in_dev);
-            if (out_dev) (void)hipFree(out_dev);
-            if (tok_dev) (void)hipFree(tok_dev);
-        };
-        try {
-            out_dev = reinterpret_cast<PickRules*>(dev_alloc<char>(sizeof(PickRules) * n));
-            tok_dev = dev_alloc<int>(n);
-            copy_sync(in_dev, host.data(), sizeof(PickRules) * n, hipMemcpyHostToDevice);
-            copy_sync(tok_dev, tokens, sizeof(int) * (size_t)n, hipMemcpyHostToDevice);
-            hipLaunchKernelGGL(pick_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, in_dev, tok_dev, n, out_dev);
-            WLK_HIP(hipGetLastError());
-            WLK_HIP(hipStreamSynchronize(nullptr));
-            copy_sync(host.data(), out_dev, sizeof(PickRules) * n, hipMemcpyDeviceToHost);
-            for (int i = 0; i < n; ++i) {
-                const PickRules& q = host[i];
-                out[i] = wlk_pick_params{q.first_step, q.without_timestamps, q.timestamp_begin, q.eot, q.no_timestamps, q.ts_mode,
-                                         q.ts_bound, q.max_initial};
-            }
-        } catch (...) {
-            release();
-            throw;
+        DevBytes in_dev(sizeof(PickRules) * n, host.data()), out_dev(sizeof(PickRules) * n), tok_dev(sizeof(int) * (size_t)n, tokens);
+        hipLaunchKernelGGL(pick_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, in_dev.as<const PickRules>(),
+                           tok_dev.as<const int>(), n, out_dev.as<PickRules>());
+        WLK_HIP(hipGetLastError());
+        WLK_HIP(hipStreamSynchronize(nullptr));
+        out_dev.back(host.data());
+        for (int i = 0; i < n; ++i) {
+            const PickRules& q = host[i];
+            out[i] = wlk_pick_params{q.first_step, q.without_timestamps, q.timestamp_begin, q.eot, q.no_timestamps, q.ts_mode,
+                                     q.ts_bound, q.max_initial};
         }
-        release();
         return WLK_OK;
     });
 }
@@ -844,42 +755,23 @@ int wlk_diag_draft_pick(const float* logits_host, int n_vocab, const uint8_t* ma
     if (!pick_params_ok(*p0, n_vocab)) return fail(WLK_ERR_ARG, "draft pick: rule parameters out of range");
     return guarded([&]() {
         const size_t V = (size_t)n_vocab, n_pos = (size_t)n_draft + 1;
-        float* logits = dev_alloc<float>(V * n_pos);
-        unsigned char* mask = nullptr;
-        int* ints = nullptr;                    // [draft n_draft | picks n_pos x 3 | result 4]
-        auto release = [&] {
-            (void)hipFree(logits);
-            if (mask) (void)hipFree(mask);
-            if (ints) (void)hipFree(ints);
-        };
-        try {
-            mask = dev_alloc<unsigned char>(V);
-            ints = dev_alloc<int>((size_t)n_draft + n_pos * 3 + 4);
-            int* picks = ints + n_draft;
-            int* res = picks + n_pos * 3;
-            copy_sync(logits, logits_host, V * n_pos * sizeof(float), hipMemcpyHostToDevice);
-            copy_sync(mask, mask_host, V, hipMemcpyHostToDevice);
-            copy_sync(ints, draft, sizeof(int) * (size_t)n_draft, hipMemcpyHostToDevice);
-            launch_draft_pick(LaunchCtx{nullptr, nullptr}, logits, n_vocab, mask, pick_rules_of(*p0), ints, n_draft, ended ? 1 : 0,
-                              picks, res, nullptr);
-            WLK_HIP(hipStreamSynchronize(nullptr));
-            std::vector<int> host(n_pos * 3 + 4);
-            copy_sync(host.data(), picks, host.size() * sizeof(int), hipMemcpyDeviceToHost);
-            for (size_t j = 0; j < n_pos; ++j) {
-                tokens_out[j] = host[3 * j];
-                std::memcpy(&logprobs_out[j], &host[3 * j + 1], 4);
-            }
-            const int* r4 = host.data() + n_pos * 3;
-            result->accepted = r4[0];
-            result->next_token = r4[1];
-            std::memcpy(&result->next_logprob, &r4[2], 4);
-            std::memcpy(&result->sum_logprob, &r4[3], 4);
-            result->no_speech_prob = NAN;
-        } catch (...) {
-            release();
-            throw;
+        DevBytes logits(V * n_pos * sizeof(float), logits_host), mask(V, mask_host), drafts(sizeof(int) * (size_t)n_draft, draft),
+            picks((n_pos * 3 + 4) * sizeof(int));          // [picks n_pos x 3 | result 4]
+        launch_draft_pick(LaunchCtx{nullptr, nullptr}, logits.f(), n_vocab, mask.as<unsigned char>(), pick_rules_of(*p0), drafts.i(),
+                          n_draft, ended ? 1 : 0, picks.i(), picks.i() + n_pos * 3, nullptr);
+        WLK_HIP(hipStreamSynchronize(nullptr));
+        std::vector<int> host(n_pos * 3 + 4);
+        picks.back(host.data());
+        for (size_t j = 0; j < n_pos; ++j) {
+            tokens_out[j] = host[3 * j];
+            std::memcpy(&logprobs_out[j], &host[3 * j + 1], 4);
         }
-        release();
+        const int* r4 = host.data() + n_pos * 3;
+        result->accepted = r4[0];
+        result->next_token = r4[1];
+        std::memcpy(&result->next_logprob, &r4[2], 4);
+        std::memcpy(&result->sum_logprob, &r4[3], 4);
+        result->no_speech_prob = NAN;
         return WLK_OK;
     });
 }
