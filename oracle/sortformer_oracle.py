@@ -26,18 +26,23 @@ import torch
 
 
 def nemo_log_mel(pcm: np.ndarray, filters: np.ndarray, n_fft: int = 512, win_length: int = 400, hop: int = 160,
-                 preemph: float = 0.97, log_guard: float = 2.0 ** -24, seq_len_plus_one: bool = False) -> np.ndarray:
+                 preemph: float = 0.97, log_guard: float = 2.0 ** -24, seq_len_plus_one: bool = False,
+                 double: bool = False) -> np.ndarray:
     """-> [n_frames, n_mels], n_frames = len(pcm) // hop + 1 = what the centred STFT yields and ``get_features`` hands
     back; FilterbankFeatures.get_seq_len counts len(pcm) // hop of them as valid and the forward fills the rest with
-    pad_value 0 (``seq_len_plus_one``: the rule of NeMo < 2.0, every frame valid)."""
-    x = torch.from_numpy(np.asarray(pcm, np.float32)).unsqueeze(0)
+    pad_value 0 (``seq_len_plus_one``: the rule of NeMo < 2.0, every frame valid).  ``double``: the tests' high-precision
+    form - the same float32 samples, window, filters and constants, the arithmetic in float64."""
+    dt = torch.float64 if double else torch.float32
+    x = torch.from_numpy(np.array(pcm, dtype=np.float32)).to(dt).unsqueeze(0)
+    if double:
+        preemph, log_guard = float(np.float32(preemph)), float(np.float32(log_guard))
     x = torch.cat((x[:, :1], x[:, 1:] - preemph * x[:, :-1]), dim=1)
-    window = torch.hann_window(win_length, periodic=False)
+    window = torch.hann_window(win_length, periodic=False).to(dt)
     spec = torch.stft(x, n_fft=n_fft, hop_length=hop, win_length=win_length, center=True, window=window,
                       return_complex=True, pad_mode="constant")
     mag = torch.sqrt(torch.view_as_real(spec).pow(2).sum(-1))
     power = mag.pow(2.0)
-    mel = torch.matmul(torch.from_numpy(np.asarray(filters, np.float32)), power)
+    mel = torch.matmul(torch.from_numpy(np.array(filters, dtype=np.float32)).to(dt), power)
     out = torch.log(mel + log_guard)
     n_frames = x.shape[1] // hop + 1
     res = out[0, :, :n_frames].transpose(0, 1).contiguous().numpy()

@@ -40,14 +40,15 @@ def to_torch_state_dict(sd) -> Dict[str, torch.Tensor]:
 # ---------------------------------------------------------------------------------------
 
 def log_mel_spectrogram(audio: torch.Tensor, filters: torch.Tensor, padding: int = 0) -> torch.Tensor:
-    """``filters`` is the [n_mels, 201] filterbank (audio.py:91-107)."""
-    audio = audio.float()
+    """``filters`` is the [n_mels, 201] filterbank (audio.py:91-107).  A float64 ``audio`` - the tests' high-precision
+    form - stays float64: the same float32 window and filters, the arithmetic in double."""
+    audio = _f32(audio)
     if padding > 0:
         audio = F.pad(audio, (0, padding))                                   # audio.py:145-146
-    window = torch.hann_window(N_FFT)                                        # audio.py:147
+    window = torch.hann_window(N_FFT).to(audio.dtype)                        # audio.py:147
     stft = torch.stft(audio, N_FFT, HOP, window=window, return_complex=True)  # audio.py:148
     power = stft[..., :-1].abs() ** 2                                        # audio.py:149
-    mel = filters @ power                                                    # audio.py:152
+    mel = filters.to(power.dtype) @ power                                    # audio.py:152
     log_spec = torch.clamp(mel, min=1e-10).log10()                           # audio.py:154
     log_spec = torch.maximum(log_spec, log_spec.max() - 8.0)                 # audio.py:155
     return (log_spec + 4.0) / 4.0                                            # audio.py:156
