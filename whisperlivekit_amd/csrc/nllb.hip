@@ -166,11 +166,12 @@ void launch_nllb_align_readout(const LaunchCtx& ctx, const float* probs, int n_a
 
 using namespace wlk;
 
-struct wlk_nllb_session {
-    wlk_nllb* m = nullptr;
+struct wlk_nllb_session : NlOwner {
+    // graphs[]: the plain, ancestry and align step, each per kv_cur; every one is re-recorded on another k / source length
+    // (NlGraphSlot), the align pair also on another head set
+    enum { kStepGraph = 0, kBeamGraph = 2, kAlignGraph = 4, kGraphs = 6 };
+    wlk_nllb_session() : NlOwner(kGraphs) {}
     int rows = 1;
-    hipStream_t stream = nullptr;
-    std::vector<void*> owned;
     // encoder
     float *ex = nullptr, *eh = nullptr, *eqkv = nullptr, *eatt = nullptr, *ewide = nullptr, *enc_out = nullptr, *cross_kv = nullptr;
     int src_len = 0;
@@ -178,7 +179,8 @@ struct wlk_nllb_session {
     // decoder
     float *kcache[2] = {nullptr, nullptr}, *vcache[2] = {nullptr, nullptr};
     int kv_cur = 0;
-    float *dx = nullptr, *dh = nullptr, *dqkv = nullptr, *datt = nullptr, *dq = nullptr, *dwide = nullptr, *hsel = nullptr, *logits = nullptr;
+    NlDecWs ws{};
+    float *hsel = nullptr, *logits = nullptr;
     int *tokens_dev = nullptr, *offset_dev = nullptr, *src_rows_dev = nullptr;
     float* top_vals = nullptr;
     int* top_ids = nullptr;
@@ -192,20 +194,11 @@ struct wlk_nllb_session {
     int* step_ids_host = nullptr;
     float* step_vals_dev = nullptr;
     int* step_ids_dev = nullptr;
-    int step_k = 1;
-    hipGraphExec_t step_exec[2] = {nullptr, nullptr};
-    int step_exec_k[2] = {0, 0};
-    int step_exec_src[2] = {0, 0};     // the source length a captured step was recorded with: the cross-attention launch carries it
-                                       // by value, so a sentence of another length needs a new recording (round 5: a session
-                                       // that translated a 5-token and then a 7-token source replayed the 5-token graph)
     // ancestry steps (wlk_nllb_step_beam): the step block continues [... | src rows | fresh]; no cache row moves
     unsigned char* anc = nullptr;      // [rows][max_tgt]: physical cache row that holds position t of hypothesis b
     void* topk_wide_scratch = nullptr;
     bool anc_live = false;             // an ancestry step has run since the last decode(first=1) / encode
     uint64_t ancestry_steps = 0;
-    hipGraphExec_t beam_exec[2] = {nullptr, nullptr};      // per kv_cur, re-recorded on another k / source length (as step_exec)
-    int beam_exec_k[2] = {0, 0};
-    int beam_exec_src[2] = {0, 0};
     // AlignAtt steps (wlk_nllb_step_align): selected heads' softmax rows [n_align][rows][src_len] -> read-out
     int n_align = 0;
     int* head_rank_dev = nullptr;      // [dec_layers][heads]: rank of the (layer, head) pair or -1
@@ -216,160 +209,94 @@ struct wlk_nllb_session {
     int* align_host_dev = nullptr;
     bool have_align = false;           // align_p holds a step of the current source
     uint64_t align_steps = 0, align_captures = 0;
-    hipGraphExec_t align_exec[2] = {nullptr, nullptr};     // per kv_cur, re-recorded on another k / source length / head set
-    int align_exec_k[2] = {0, 0};
-    int align_exec_src[2] = {0, 0};
-    template <typename T>
-    T* alloc(size_t n) {
-        void* p = nullptr;
-        WLK_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-        owned.push_back(p);
-        return static_cast<T*>(p);
-    }
-    LaunchCtx ctx() const { return LaunchCtx{stream, nullptr}; }
-    ~wlk_nllb_session() {        // also the clean-up of a half-built session (an allocation that threw in session_create)
-        if (m) (void)hipSetDevice(m->device);
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (void* p : owned) (void)hipFree(p);
-        for (auto& e : step_exec) if (e) (void)hipGraphExecDestroy(e);
-        for (auto& e : beam_exec) if (e) (void)hipGraphExecDestroy(e);
-        for (auto& e : align_exec) if (e) (void)hipGraphExecDestroy(e);
-        if (step_host) (void)hipHostFree(step_host);
-        if (step_vals_host) (void)hipHostFree(step_vals_host);
-        if (step_ids_host) (void)hipHostFree(step_ids_host);
-        if (align_host) (void)hipHostFree(align_host);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace wlk {
 
-static void nl_encode(wlk_nllb_session* s, int S) {
-    wlk_nllb* m = s->m;
-    const wlk_nllb_dims& D = m->D;
-    const LaunchCtx c = s->ctx();
-    const int d = D.d_model, H = D.heads, f = D.ffn;
-    const float q_scale = 0.125f;                      // 64^-0.5, exact
-    hipLaunchKernelGGL(nllb_embed_kernel, dim3(S), dim3(256), 0, s->stream, s->tokens_dev, m->emb, m->pos, D.embed_scale,
-                       D.pad_id + 1, (const int*)nullptr, S, d, s->ex);
-    WLK_HIP(hipGetLastError());
-    for (int l = 0; l < D.enc_layers; ++l) {
-        const NlLayer& L = m->enc[l];
-        launch_layernorm(c, s->ex, d, L.ln1w, L.ln1b, s->eh, d, S, d, "nllb_ln1");
-        nl_linear(c, s->eh, d, L.qkvw, L.qkvb, s->eqkv, 3 * d, S, 3 * d, d, kGemmScaleCols, nullptr, 0, "nllb_enc_qkv", q_scale, d);
-        SfAttnArgs a;
-        a.q = s->eqkv; a.k = s->eqkv + d; a.v = s->eqkv + 2 * d; a.ldq = a.ldk = a.ldv = 3 * d;
-        a.out = s->eatt; a.ldo = d; a.T = S; a.n_head = H; a.dh = 64; a.scale = 1.f;
-        launch_sf_attention(c, a);
-        nl_linear(c, s->eatt, d, L.outw, L.outb, s->ex, d, S, d, d, kGemmResidual, s->ex, d, "nllb_enc_out");
-        nl_ffn(c, L, s->ex, s->eh, s->ewide, S, d, f);
+// Session addressing of the decoder layers: the current dense caches [layer][row][ctx][d] at *offset_dev, one cross K/V and
+// one source length for every row; anc / align as nl_decode's anc_step / align_step
+struct NlSessionAddr {
+    const wlk_nllb_session* s;
+    int n_tok;
+    bool anc, align;
+    const wlk_nllb_dims& D() const { return s->m->D; }
+    size_t cache_at(int l) const { return (size_t)l * s->rows * D().max_tgt * D().d_model; }
+    float* kc(int l) const { return s->kcache[s->kv_cur] + cache_at(l); }
+    float* vc(int l) const { return s->vcache[s->kv_cur] + cache_at(l); }
+    void kv_rider(GemmArgs& g, int l) const {
+        g.kcache = kc(l); g.vcache = vc(l); g.kv_pos = s->offset_dev; g.kv_d = D().d_model; g.kv_ctx = D().max_tgt;
     }
-    launch_layernorm(c, s->ex, d, m->enc_lnw, m->enc_lnb, s->enc_out, d, S, d, "nllb_enc_ln");
-    // cross-attention keys / values of every decoder layer: [S][dec_layers][k | v]
-    const long ld = (long)D.dec_layers * 2 * d;
-    for (int l = 0; l < D.dec_layers; ++l) {
-        const NlLayer& L = m->dec[l];
-        nl_linear(c, s->enc_out, d, L.xkvw, L.xkvb, s->cross_kv + (size_t)l * 2 * d, ld, S, 2 * d, d, 0, nullptr, 0, "nllb_xkv");
+    void append(const LaunchCtx& c, const float* qkv, int l) const {
+        launch_kv_append(c, qkv, kc(l), vc(l), s->rows, n_tok, s->offset_dev, D().d_model, D().max_tgt);
     }
-}
-
-// anc_step (n_tok == 1, graph replay): row b continues hypothesis src[b] of the previous step WITHOUT moving the cache - the
-// table update runs in front of the layers and the self-attention reads keys / values through the table (DESIGN 20)
-// align_step (n_tok == 1, graph replay): the selected heads leave their softmax rows in align_probs and the read-out follows
-// the top-k (DESIGN 21)
-static void nl_decode(wlk_nllb_session* s, int n_tok, bool graph_step = false, bool anc_step = false, bool align_step = false) {
-    wlk_nllb* m = s->m;
-    const wlk_nllb_dims& D = m->D;
-    const LaunchCtx c = s->ctx();
-    const int d = D.d_model, H = D.heads, f = D.ffn, rows = s->rows, R = rows * n_tok, ctx_len = D.max_tgt, S = s->src_len;
-    const float q_scale = 0.125f;
-    const bool fused = n_tok == 1 && gemv_applicable(R, d);
-    if (anc_step && (!fused || !graph_step || !s->anc)) throw std::logic_error("NLLB decode: the ancestry step needs the fused graph step");
-    if (align_step && (n_tok != 1 || !graph_step || anc_step || s->n_align < 1))
-        throw std::logic_error("NLLB decode: the alignment step is a single-token graph step with heads set");
-    if (graph_step)
-        hipLaunchKernelGGL(nllb_embed_step_kernel, dim3(R), dim3(256), 0, s->stream, s->step_host_dev, rows, m->emb, m->pos,
-                           D.embed_scale, D.pad_id + 1, d, s->offset_dev, s->dx);
-    else
-        hipLaunchKernelGGL(nllb_embed_kernel, dim3(R), dim3(256), 0, s->stream, s->tokens_dev, m->emb, m->pos, D.embed_scale,
-                           D.pad_id + 1, s->offset_dev, n_tok, d, s->dx);
-    WLK_HIP(hipGetLastError());
-    if (anc_step) launch_anc_update_block(c, s->anc, s->step_host_dev, rows, ctx_len);
-    const size_t cache_layer = (size_t)rows * ctx_len * d;
-    const long ldkv = (long)D.dec_layers * 2 * d;
-    for (int l = 0; l < D.dec_layers; ++l) {
-        const NlLayer& L = m->dec[l];
-        float* kc = s->kcache[s->kv_cur] + l * cache_layer;
-        float* vc = s->vcache[s->kv_cur] + l * cache_layer;
-        if (fused) {      // single-token steps: LayerNorm and the cache append ride in the weight-streaming GEMV
-            GemmArgs g;
-            g.A = s->dx; g.lda = d; g.W = L.qkvw; g.bias = L.qkvb; g.C = s->dqkv; g.ldc = 3 * d; g.M = R; g.N = 3 * d; g.K = d;
-            g.flags = kGemmScaleCols; g.scale = q_scale; g.scale_cols = d;
-            g.ln_gamma = L.ln1w; g.ln_beta = L.ln1b;
-            g.kcache = kc; g.vcache = vc; g.kv_pos = s->offset_dev; g.kv_d = d; g.kv_ctx = ctx_len;
-            launch_gemv(c, g, "nllb_ln1_qkv_kv");
-        } else {
-            launch_layernorm(c, s->dx, d, L.ln1w, L.ln1b, s->dh, d, R, d, "nllb_ln1");
-            nl_linear(c, s->dh, d, L.qkvw, L.qkvb, s->dqkv, 3 * d, R, 3 * d, d, kGemmScaleCols, nullptr, 0, "nllb_dec_qkv", q_scale, d);
-            launch_kv_append(c, s->dqkv, kc, vc, rows, n_tok, s->offset_dev, d, ctx_len);
-        }
-        if (anc_step) launch_decoder_self_attention_anc(c, s->dqkv, kc, vc, s->anc, s->datt, rows, s->offset_dev, d, H, ctx_len);
-        else launch_decoder_self_attention(c, s->dqkv, kc, vc, s->datt, rows, n_tok, s->offset_dev, d, H, ctx_len);
-        nl_linear(c, s->datt, d, L.outw, L.outb, s->dx, d, R, d, d, kGemmResidual, s->dx, d, "nllb_dec_out");
-
-        if (fused) {
-            GemmArgs q;
-            q.A = s->dx; q.lda = d; q.W = L.xqw; q.bias = L.xqb; q.C = s->dq; q.ldc = d; q.M = R; q.N = d; q.K = d;
-            q.flags = kGemmScaleCols; q.scale = q_scale; q.scale_cols = d; q.ln_gamma = L.lnxw; q.ln_beta = L.lnxb;
-            launch_gemv(c, q, "nllb_lnx_xq");
-        } else {
-            launch_layernorm(c, s->dx, d, L.lnxw, L.lnxb, s->dh, d, R, d, "nllb_lnx");
-            nl_linear(c, s->dh, d, L.xqw, L.xqb, s->dq, d, R, d, d, kGemmScaleCols, nullptr, 0, "nllb_dec_xq", q_scale, d);
-        }
+    void self_attention(const LaunchCtx& c, const float* qkv, float* att, int l) const {
+        if (anc) launch_decoder_self_attention_anc(c, qkv, kc(l), vc(l), s->anc, att, s->rows, s->offset_dev, D().d_model, D().heads, D().max_tgt);
+        else launch_decoder_self_attention(c, qkv, kc(l), vc(l), att, s->rows, n_tok, s->offset_dev, D().d_model, D().heads, D().max_tgt);
+    }
+    void cross_attention(const LaunchCtx& c, const float* q, float* att, int l) const {
+        const int d = D().d_model, H = D().heads, rows = s->rows;
         CrossAttnArgs ca{};
-        ca.q = s->dq;
+        ca.q = q;
         ca.k = s->cross_kv + (size_t)l * 2 * d;
         ca.v = ca.k + d;
-        ca.ldkv = ldkv;
-        ca.out = s->datt;
-        ca.rows = R; ca.d = d; ca.n_head = H; ca.T = S;
+        ca.ldkv = (long)D().dec_layers * 2 * d;
+        ca.out = att;
+        ca.rows = rows * n_tok; ca.d = d; ca.n_head = H; ca.T = s->src_len;
         ca.head_rank = nullptr; ca.ring = nullptr; ca.ring_row = nullptr; ca.beam_of_row = nullptr;
         ca.ring_rows = 0; ca.n_beam = 1; ca.qk_debug = nullptr;
-        if (align_step) {     // window [n_align][rows][1][S]: row r is "beam" r, ring row 0
+        if (align) {          // window [n_align][rows][1][S]: row r is "beam" r, ring row 0
             ca.head_rank = s->head_rank_dev + (size_t)l * H;
             ca.ring = s->align_probs; ca.ring_row = s->align_rows_dev; ca.beam_of_row = s->align_rows_dev + rows;
             ca.ring_rows = 1; ca.n_beam = rows;
         }
         launch_decoder_cross_attention(c, ca);
-        nl_linear(c, s->datt, d, L.xoutw, L.xoutb, s->dx, d, R, d, d, kGemmResidual, s->dx, d, "nllb_dec_xout");
-        if (fused) {
-            GemmArgs g;
-            g.A = s->dx; g.lda = d; g.W = L.fc1w; g.bias = L.fc1b; g.C = s->dwide; g.ldc = f; g.M = R; g.N = f; g.K = d;
-            g.flags = kGemmRelu; g.ln_gamma = L.ln2w; g.ln_beta = L.ln2b;
-            launch_gemv(c, g, "nllb_ln2_fc1");
-            nl_linear(c, s->dwide, f, L.fc2w, L.fc2b, s->dx, d, R, d, f, kGemmResidual, s->dx, d, "nllb_fc2");
-        } else {
-            nl_ffn(c, L, s->dx, s->dh, s->dwide, R, d, f);
-        }
     }
-    // final LayerNorm + tied vocabulary projection of the last fed position of every row
-    if (fused) {
-        GemmArgs lg;
-        lg.A = s->dx; lg.lda = d; lg.W = m->emb; lg.C = s->logits; lg.ldc = D.vocab; lg.M = rows; lg.N = D.vocab; lg.K = d;
-        lg.ln_gamma = m->dec_lnw; lg.ln_beta = m->dec_lnb;
-        launch_gemv(c, lg, "nllb_lnf_logits");
-    } else {
-        launch_layernorm(c, s->dx + (size_t)(n_tok - 1) * d, (long)n_tok * d, m->dec_lnw, m->dec_lnb, s->hsel, d, rows, d, "nllb_dec_ln");
-        nl_linear(c, s->hsel, d, m->emb, nullptr, s->logits, D.vocab, rows, D.vocab, d, 0, nullptr, 0, "nllb_logits");
-    }
-    if (graph_step && s->step_k > 8)     // (ancestry steps only: wlk_nllb_step stops at 8)
-        launch_logsoftmax_topk_wide(c, s->logits, D.vocab, rows, s->step_k, s->step_vals_dev, s->step_ids_dev, s->topk_wide_scratch);
+};
+
+static void nl_encode(wlk_nllb_session* s, int S) {
+    wlk_nllb* m = s->m;
+    const wlk_nllb_dims& D = m->D;
+    hipLaunchKernelGGL(nllb_embed_kernel, dim3(S), dim3(256), 0, s->stream, s->tokens_dev, m->emb, m->pos, D.embed_scale,
+                       D.pad_id + 1, (const int*)nullptr, S, D.d_model, s->ex);
+    WLK_HIP(hipGetLastError());
+    SfAttnArgs one;
+    one.T = S;
+    nl_encoder_layers(s->ctx(), m, s->ex, s->eh, s->eqkv, s->eatt, s->ewide, s->enc_out, s->cross_kv, S, one);
+}
+
+// graph_k > 0: a single-token step replayed from a graph - tokens and offset come from the host-coherent step block and
+// the graph_k best continuations of every row go straight back into host-coherent memory
+// anc_step (n_tok == 1, graph replay): row b continues hypothesis src[b] of the previous step WITHOUT moving the cache - the
+// table update runs in front of the layers and the self-attention reads keys / values through the table (DESIGN 20)
+// align_step (n_tok == 1, graph replay): the selected heads leave their softmax rows in align_probs and the read-out follows
+// the top-k (DESIGN 21)
+static void nl_decode(wlk_nllb_session* s, int n_tok, int graph_k = 0, bool anc_step = false, bool align_step = false) {
+    wlk_nllb* m = s->m;
+    const wlk_nllb_dims& D = m->D;
+    const LaunchCtx c = s->ctx();
+    const int d = D.d_model, rows = s->rows, R = rows * n_tok;
+    const bool graph_step = graph_k > 0, fused = n_tok == 1 && gemv_applicable(R, d);
+    if (anc_step && (!fused || !graph_step || !s->anc)) throw std::logic_error("NLLB decode: the ancestry step needs the fused graph step");
+    if (align_step && (n_tok != 1 || !graph_step || anc_step || s->n_align < 1))
+        throw std::logic_error("NLLB decode: the alignment step is a single-token graph step with heads set");
+    if (graph_step)
+        hipLaunchKernelGGL(nllb_embed_step_kernel, dim3(R), dim3(256), 0, s->stream, s->step_host_dev, rows, m->emb, m->pos,
+                           D.embed_scale, D.pad_id + 1, d, s->offset_dev, s->ws.x);
+    else
+        hipLaunchKernelGGL(nllb_embed_kernel, dim3(R), dim3(256), 0, s->stream, s->tokens_dev, m->emb, m->pos, D.embed_scale,
+                           D.pad_id + 1, s->offset_dev, n_tok, d, s->ws.x);
+    WLK_HIP(hipGetLastError());
+    if (anc_step) launch_anc_update_block(c, s->anc, s->step_host_dev, rows, D.max_tgt);
+    nl_decoder_layers(c, m, s->ws, R, fused, NlSessionAddr{s, n_tok, anc_step, align_step});
+    nl_logits(c, m, fused, s->ws.x, rows, n_tok, s->hsel, s->logits);
+    if (graph_k > 8)     // (ancestry steps only: wlk_nllb_step stops at 8)
+        launch_logsoftmax_topk_wide(c, s->logits, D.vocab, rows, graph_k, s->step_vals_dev, s->step_ids_dev, s->topk_wide_scratch);
     else if (graph_step)      // results straight into the host-coherent block: no copy node behind the graph either
-        launch_logsoftmax_topk(c, s->logits, D.vocab, rows, s->step_k, s->step_vals_dev, s->step_ids_dev, s->topk_scratch, nullptr,
+        launch_logsoftmax_topk(c, s->logits, D.vocab, rows, graph_k, s->step_vals_dev, s->step_ids_dev, s->topk_scratch, nullptr,
                                nullptr, nullptr, 0);
     if (align_step) {
         float* res = reinterpret_cast<float*>(s->align_host_dev + 3);
-        launch_nllb_align_readout(c, s->align_probs, s->n_align, rows, S, s->align_host_dev, s->align_p, s->align_host_dev + 3,
+        launch_nllb_align_readout(c, s->align_probs, s->n_align, rows, s->src_len, s->align_host_dev, s->align_p, s->align_host_dev + 3,
                                   res + rows, res + 2 * rows);
     }
 }
@@ -501,8 +428,8 @@ int wlk_nllb_session_create(wlk_nllb* m, int rows, wlk_nllb_session** out) {
             s->kcache[i] = s->alloc<float>((size_t)D.dec_layers * rows * Tt * d);
             s->vcache[i] = s->alloc<float>((size_t)D.dec_layers * rows * Tt * d);
         }
-        s->dx = s->alloc<float>(Rmax * d); s->dh = s->alloc<float>(Rmax * d); s->dqkv = s->alloc<float>(Rmax * 3 * d);
-        s->datt = s->alloc<float>(Rmax * d); s->dq = s->alloc<float>(Rmax * d); s->dwide = s->alloc<float>(Rmax * f);
+        s->ws = NlDecWs{s->alloc<float>(Rmax * d), s->alloc<float>(Rmax * d), s->alloc<float>(Rmax * 3 * d), s->alloc<float>(Rmax * d),
+                        s->alloc<float>(Rmax * d), s->alloc<float>(Rmax * f)};
         s->hsel = s->alloc<float>((size_t)rows * d);
         s->logits = s->alloc<float>((size_t)rows * D.vocab);
         s->tokens_dev = s->alloc<int>(std::max(S, Rmax));
@@ -516,12 +443,9 @@ int wlk_nllb_session_create(wlk_nllb* m, int rows, wlk_nllb_session** out) {
         WLK_HIP(hipMemsetAsync(s->anc, 0, (size_t)rows * Tt, s->stream));
         WLK_HIP(hipStreamSynchronize(s->stream));
         // [tokens rows | offset] for wlk_nllb_step, continued by [src rows | fresh] for wlk_nllb_step_beam
-        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->step_host), (size_t)(2 * rows + 2) * sizeof(int), hipHostMallocMapped));
-        WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->step_host_dev), s->step_host, 0));
-        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->step_vals_host), (size_t)rows * 16 * sizeof(float), hipHostMallocMapped));
-        WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->step_vals_dev), s->step_vals_host, 0));
-        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->step_ids_host), (size_t)rows * 16 * sizeof(int), hipHostMallocMapped));
-        WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->step_ids_dev), s->step_ids_host, 0));
+        s->mapped((size_t)(2 * rows + 2), &s->step_host, &s->step_host_dev);
+        s->mapped((size_t)rows * 16, &s->step_vals_host, &s->step_vals_dev);
+        s->mapped((size_t)rows * 16, &s->step_ids_host, &s->step_ids_dev);
         *out = s.release();
         return WLK_OK;
     });
@@ -534,12 +458,8 @@ int wlk_nllb_session_destroy(wlk_nllb_session* s) {
 
 static int nl_stage_tokens(wlk_nllb_session* s, const int64_t* ids, int n, std::vector<int>& stage) {
     const wlk_nllb_dims& D = s->m->D;
-    stage.resize(n);
-    for (int i = 0; i < n; ++i) {
-        if (ids[i] < 0 || ids[i] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
-        if (ids[i] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sequence is not supported (one sentence per call)");
-        stage[i] = (int)ids[i];
-    }
+    if (int rc = nl_check_tokens(D, ids, n, "padding inside a sequence is not supported (one sentence per call)")) return rc;
+    stage.assign(ids, ids + n);
     return WLK_OK;
 }
 
@@ -600,25 +520,13 @@ int wlk_nllb_step(wlk_nllb_session* s, const int64_t* tokens, int32_t n_rows, in
     const wlk_nllb_dims& D = s->m->D;
     if (s->self_len + 1 > D.max_tgt) return nl_fail(WLK_ERR_CAPACITY, "target context exceeded");
     if (!gemv_applicable(n_rows, D.d_model)) return nl_fail(WLK_ERR_ARG, "wlk_nllb_step: too many rows for the single-token path");
-    for (int r = 0; r < n_rows; ++r) {
-        if (tokens[r] < 0 || tokens[r] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
-        if (tokens[r] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sequence is not supported");
-    }
+    if (int rc = nl_check_tokens(D, tokens, n_rows)) return rc;
     return nl_guarded([&]() {
         WLK_HIP(hipSetDevice(s->m->device));
         WLK_HIP(hipStreamSynchronize(s->stream));           // the previous step's readers of the host block are done
         for (int r = 0; r < n_rows; ++r) s->step_host[r] = (int)tokens[r];
         s->step_host[n_rows] = s->self_len;
-        hipGraphExec_t& exec = s->step_exec[s->kv_cur];
-        if (!exec || s->step_exec_k[s->kv_cur] != k || s->step_exec_src[s->kv_cur] != s->src_len) {
-            if (exec) { WLK_HIP(hipGraphExecDestroy(exec)); exec = nullptr; }
-            s->step_k = k;
-            capture_step_graph(s->stream, exec, [&] { nl_decode(s, 1, /*graph_step=*/true); });
-            s->step_exec_k[s->kv_cur] = k;
-            s->step_exec_src[s->kv_cur] = s->src_len;
-        }
-        WLK_HIP(hipGraphLaunch(exec, s->stream));
-        WLK_HIP(hipStreamSynchronize(s->stream));
+        nl_replay(s->stream, s->graphs[s->kStepGraph + s->kv_cur], k, s->src_len, [&] { nl_decode(s, 1, k); });
         std::memcpy(logprobs, s->step_vals_host, (size_t)n_rows * k * sizeof(float));
         std::memcpy(ids, s->step_ids_host, (size_t)n_rows * k * sizeof(int));
         s->self_len += 1;
@@ -639,8 +547,7 @@ int wlk_nllb_step_beam(wlk_nllb_session* s, const int64_t* tokens, const int32_t
     if (k > 8 && !topk_wide_applicable(D.vocab, k)) return nl_fail(WLK_ERR_ARG, "wlk_nllb_step_beam: k > 8 needs a vocabulary of at most 262144");
     if (s->self_len + 1 > D.max_tgt) return nl_fail(WLK_ERR_CAPACITY, "target context exceeded");
     for (int r = 0; r < n_rows; ++r) {
-        if (tokens[r] < 0 || tokens[r] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
-        if (tokens[r] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sequence is not supported");
+        if (int rc = nl_check_tokens(D, tokens + r, 1)) return rc;
         if (source_rows[r] < 0 || source_rows[r] >= n_rows) return nl_fail(WLK_ERR_ARG, "source row out of range");
     }
     return nl_guarded([&]() {
@@ -652,16 +559,8 @@ int wlk_nllb_step_beam(wlk_nllb_session* s, const int64_t* tokens, const int32_t
         }
         s->step_host[n_rows] = s->self_len;
         s->step_host[2 * n_rows + 1] = s->anc_live ? 0 : 1;      // fresh: every physical row still holds its own history
-        hipGraphExec_t& exec = s->beam_exec[s->kv_cur];
-        if (!exec || s->beam_exec_k[s->kv_cur] != k || s->beam_exec_src[s->kv_cur] != s->src_len) {
-            if (exec) { WLK_HIP(hipGraphExecDestroy(exec)); exec = nullptr; }
-            s->step_k = k;
-            capture_step_graph(s->stream, exec, [&] { nl_decode(s, 1, /*graph_step=*/true, /*anc_step=*/true); });
-            s->beam_exec_k[s->kv_cur] = k;
-            s->beam_exec_src[s->kv_cur] = s->src_len;
-        }
-        WLK_HIP(hipGraphLaunch(exec, s->stream));
-        WLK_HIP(hipStreamSynchronize(s->stream));
+        nl_replay(s->stream, s->graphs[s->kBeamGraph + s->kv_cur], k, s->src_len,
+                  [&] { nl_decode(s, 1, k, /*anc_step=*/true); });
         std::memcpy(logprobs, s->step_vals_host, (size_t)n_rows * k * sizeof(float));
         std::memcpy(ids, s->step_ids_host, (size_t)n_rows * k * sizeof(int));
         s->self_len += 1;
@@ -682,18 +581,12 @@ int wlk_nllb_session_set_align(wlk_nllb_session* s, const int32_t* layer_head_pa
     if (!s || (n > 0 && !layer_head_pairs)) return nl_fail(WLK_ERR_ARG, "NULL argument");
     if (n < 0 || n > kNlMaxAlign) return nl_fail(WLK_ERR_ARG, "wlk_nllb_session_set_align: 0..64 (layer, head) pairs");
     const wlk_nllb_dims& D = s->m->D;
-    std::vector<int> rank((size_t)D.dec_layers * D.heads, -1);
-    for (int i = 0; i < n; ++i) {
-        const int l = layer_head_pairs[2 * i], h = layer_head_pairs[2 * i + 1];
-        if (l < 0 || l >= D.dec_layers || h < 0 || h >= D.heads) return nl_fail(WLK_ERR_ARG, "alignment head: layer or head out of range");
-        if (rank[(size_t)l * D.heads + h] >= 0) return nl_fail(WLK_ERR_ARG, "alignment head: duplicate (layer, head) pair");
-        rank[(size_t)l * D.heads + h] = i;
-    }
+    std::vector<int> rank;
+    if (int rc = nl_head_rank(D, layer_head_pairs, n, rank)) return rc;
     return nl_guarded([&]() {
         WLK_HIP(hipSetDevice(s->m->device));
         WLK_HIP(hipStreamSynchronize(s->stream));
-        for (auto& e : s->align_exec)        // a recording carries the head count by value
-            if (e) { WLK_HIP(hipGraphExecDestroy(e)); e = nullptr; }
+        for (int i = 0; i < 2; ++i) s->graphs[s->kAlignGraph + i].drop();        // a recording carries the head count by value
         s->have_align = false;
         s->n_align = 0;
         if (n == 0) return WLK_OK;
@@ -703,8 +596,7 @@ int wlk_nllb_session_set_align(wlk_nllb_session* s, const int32_t* layer_head_pa
             s->align_rows_dev = s->alloc<int>(2 * (size_t)rows);
             s->align_probs = s->alloc<float>((size_t)kNlMaxAlign * rows * D.max_src);
             s->align_p = s->alloc<float>((size_t)rows * D.max_src);
-            WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->align_host), (size_t)(3 + 3 * rows) * sizeof(int), hipHostMallocMapped));
-            WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->align_host_dev), s->align_host, 0));
+            s->mapped((size_t)(3 + 3 * rows), &s->align_host, &s->align_host_dev);
             std::vector<int> rr(2 * (size_t)rows, 0);
             for (int r = 0; r < rows; ++r) rr[rows + r] = r;
             copy_sync(s->align_rows_dev, rr.data(), rr.size() * sizeof(int), hipMemcpyHostToDevice);
@@ -727,27 +619,16 @@ static int nl_step_align(wlk_nllb_session* s, const int64_t* tokens, int n_rows,
     const wlk_nllb_dims& D = s->m->D;
     if (s->self_len + 1 > D.max_tgt) return nl_fail(WLK_ERR_CAPACITY, "target context exceeded");
     if (!gemv_applicable(n_rows, D.d_model)) return nl_fail(WLK_ERR_ARG, "wlk_nllb_step_align: too many rows for the single-token path");
-    for (int r = 0; r < n_rows; ++r) {
-        if (tokens[r] < 0 || tokens[r] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
-        if (tokens[r] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sequence is not supported");
-    }
+    if (int rc = nl_check_tokens(D, tokens, n_rows)) return rc;
     return nl_guarded([&]() {
         WLK_HIP(hipSetDevice(s->m->device));
         WLK_HIP(hipStreamSynchronize(s->stream));           // the previous step's readers of the host blocks are done
         for (int r = 0; r < n_rows; ++r) s->step_host[r] = (int)tokens[r];
         s->step_host[n_rows] = s->self_len;
         s->align_host[0] = lo; s->align_host[1] = hi; s->align_host[2] = limit;
-        hipGraphExec_t& exec = s->align_exec[s->kv_cur];
-        if (!exec || s->align_exec_k[s->kv_cur] != k || s->align_exec_src[s->kv_cur] != s->src_len) {
-            if (exec) { WLK_HIP(hipGraphExecDestroy(exec)); exec = nullptr; }
-            s->step_k = k;
-            capture_step_graph(s->stream, exec, [&] { nl_decode(s, 1, /*graph_step=*/true, /*anc_step=*/false, /*align_step=*/true); });
-            s->align_exec_k[s->kv_cur] = k;
-            s->align_exec_src[s->kv_cur] = s->src_len;
+        if (nl_replay(s->stream, s->graphs[s->kAlignGraph + s->kv_cur], k, s->src_len,
+                      [&] { nl_decode(s, 1, k, /*anc_step=*/false, /*align_step=*/true); }))
             s->align_captures += 1;
-        }
-        WLK_HIP(hipGraphLaunch(exec, s->stream));
-        WLK_HIP(hipStreamSynchronize(s->stream));
         s->self_len += 1;
         s->have_logits = true;
         s->have_align = true;

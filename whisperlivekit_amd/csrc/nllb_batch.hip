@@ -13,8 +13,8 @@
 //                                segment (launch_sf_attention's n_seg: no score crosses a sentence), cross K/V projected
 //                                over all rows and copied into each slot's own buffer.  Slots not named are untouched -
 //                                they may be in the middle of a decode; that is what lets a new sentence take a freed slot.
-//   step((slot, token) x R)      one decoder pass over R rows, any subset of the slots in any order: nl_decode's fused
-//                                branch (LayerNorm-fused weight-streaming GEMVs, the cache append riding in the qkv GEMV
+//   step((slot, token) x R)      one decoder pass over R rows, any subset of the slots in any order: nl_decoder_layers'
+//                                fused form (LayerNorm-fused weight-streaming GEMVs, the cache append riding in the qkv GEMV
 //                                through GemmArgs::kv_rows, launch_decoder_self_attention_rows) with every per-row scalar
 //                                (token, position, caches, cross K/V, SOURCE LENGTH) in a row table.  The host writes the
 //                                table into a host-coherent block; the chain's first kernel reads it over the bus and
@@ -22,7 +22,7 @@
 //                                host-coherent memory.  The chain is one graph per row count - and because no launch
 //                                carries a length or an offset by value, a recording serves every later mix of sentences
 //                                (the session's step graph carries the source length and is re-recorded per length:
-//                                wlk_nllb_session::step_exec_src).
+//                                NlGraphSlot::src).
 //
 // Two kernels are new: the row-table embedding and the RAGGED cross-attention (every row its own key count, 1..512, read
 // from the table).  The row table is common.h's StepRow - the type the GEMV's cache append and the self-attention
@@ -346,17 +346,18 @@ struct NlBatchSlot {
 
 using namespace wlk;
 
-struct wlk_nllb_batch {
-    wlk_nllb* m = nullptr;
+struct wlk_nllb_batch : NlOwner {
+    // graphs[]: the plain step by row count, then the align step by row count (dropped with the head set)
+    enum { kStepGraph = 0, kAlignGraph = kNlBatchMaxRows + 1, kGraphs = 2 * (kNlBatchMaxRows + 1) };
+    wlk_nllb_batch() : NlOwner(kGraphs) {}
     int n_slots = 0;
-    hipStream_t stream = nullptr;
-    std::vector<void*> owned;
     std::vector<NlBatchSlot> slots;
     // stacked encode (n_slots x max_src rows)
     float *ex = nullptr, *eh = nullptr, *eqkv = nullptr, *eatt = nullptr, *ewide = nullptr, *enc_stack = nullptr, *xkv_stack = nullptr;
     int* enc_tokens = nullptr;
-    // stacked step (up to 8 rows)
-    float *dx = nullptr, *dqkv = nullptr, *datt = nullptr, *dq = nullptr, *dwide = nullptr, *logits = nullptr;
+    // stacked step (up to 8 rows; fused only: no h)
+    NlDecWs ws{};
+    float* logits = nullptr;
     void* topk_scratch = nullptr;
     StepRow* rows_dev = nullptr;         // the device copy of the row table, written by the chain's first kernel
     StepRow* probe_rows_dev = nullptr;   // wlk_nllb_batch_cross_attention's own table
@@ -366,9 +367,6 @@ struct wlk_nllb_batch {
     int* ids_host = nullptr;
     float* vals_dev = nullptr;
     int* ids_dev = nullptr;
-    int step_k = 1;
-    hipGraphExec_t exec[kNlBatchMaxRows + 1] = {nullptr};     // by row count
-    int exec_k[kNlBatchMaxRows + 1] = {0};
     // AlignAtt steps (wlk_nllb_batch_step_align); nothing below is allocated before the first align step
     int n_align = 0;
     std::vector<int> head_rank;          // [dec_layers][heads]: rank of the (layer, head) pair or -1, as set
@@ -379,31 +377,9 @@ struct wlk_nllb_batch {
     int* align_host = nullptr;           // pinned + mapped: [8] lo | hi | limit, then [8] position, [8] probability, [8] tail mass
     int* align_host_dev = nullptr;
     uint64_t align_steps = 0, align_captures = 0;
-    hipGraphExec_t align_exec[kNlBatchMaxRows + 1] = {nullptr};   // by row count, apart from exec[]: dropped with the head set
-    int align_exec_k[kNlBatchMaxRows + 1] = {0};
     // stacked prompt prefill (wlk_nllb_batch_prefill): n_slots x max_tgt rows, allocated by the first prefill
-    float *px = nullptr, *ph = nullptr, *pqkv = nullptr, *patt = nullptr, *pq = nullptr, *pwide = nullptr;
+    NlDecWs pws{};
     StepRow *prefill_stage = nullptr, *prefill_rows = nullptr;    // the uploaded table and the copy the embedding leaves
-    template <typename T>
-    T* alloc(size_t n) {
-        void* p = nullptr;
-        WLK_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-        owned.push_back(p);
-        return static_cast<T*>(p);
-    }
-    LaunchCtx ctx() const { return LaunchCtx{stream, nullptr}; }
-    ~wlk_nllb_batch() {          // also the clean-up of a half-built batch
-        if (m) (void)hipSetDevice(m->device);
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (void* p : owned) (void)hipFree(p);
-        for (auto& e : exec) if (e) (void)hipGraphExecDestroy(e);
-        for (auto& e : align_exec) if (e) (void)hipGraphExecDestroy(e);
-        if (align_host) (void)hipHostFree(align_host);
-        if (rows_host) (void)hipHostFree(rows_host);
-        if (vals_host) (void)hipHostFree(vals_host);
-        if (ids_host) (void)hipHostFree(ids_host);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace wlk {
@@ -411,81 +387,58 @@ namespace wlk {
 static void nlb_encode(wlk_nllb_batch* b, const NlSegTable& sg, const int* len, int total) {
     wlk_nllb* m = b->m;
     const wlk_nllb_dims& D = m->D;
-    const LaunchCtx c = b->ctx();
-    const int d = D.d_model, H = D.heads, f = D.ffn, S = total;
-    const float q_scale = 0.125f;                      // 64^-0.5, exact
-    hipLaunchKernelGGL(nllb_embed_segments_kernel, dim3(S), dim3(256), 0, b->stream, b->enc_tokens, m->emb, m->pos, D.embed_scale,
-                       D.pad_id + 1, sg, d, b->ex);
+    hipLaunchKernelGGL(nllb_embed_segments_kernel, dim3(total), dim3(256), 0, b->stream, b->enc_tokens, m->emb, m->pos, D.embed_scale,
+                       D.pad_id + 1, sg, D.d_model, b->ex);
     WLK_HIP(hipGetLastError());
-    int longest = 0;
-    for (int s = 0; s < sg.n; ++s) longest = std::max(longest, len[s]);
-    for (int l = 0; l < D.enc_layers; ++l) {
-        const NlLayer& L = m->enc[l];
-        launch_layernorm(c, b->ex, d, L.ln1w, L.ln1b, b->eh, d, S, d, "nllb_ln1");
-        nl_linear(c, b->eh, d, L.qkvw, L.qkvb, b->eqkv, 3 * d, S, 3 * d, d, kGemmScaleCols, nullptr, 0, "nllb_enc_qkv", q_scale, d);
-        SfAttnArgs a;
-        a.q = b->eqkv; a.k = b->eqkv + d; a.v = b->eqkv + 2 * d; a.ldq = a.ldk = a.ldv = 3 * d;
-        a.out = b->eatt; a.ldo = d; a.T = longest; a.n_head = H; a.dh = 64; a.scale = 1.f;
-        a.n_seg = sg.n;
-        for (int s = 0; s < sg.n; ++s) { a.seg_start[s] = sg.start[s]; a.seg_T[s] = len[s]; }
-        launch_sf_attention(c, a);
-        nl_linear(c, b->eatt, d, L.outw, L.outb, b->ex, d, S, d, d, kGemmResidual, b->ex, d, "nllb_enc_out");
-        nl_ffn(c, L, b->ex, b->eh, b->ewide, S, d, f);
+    SfAttnArgs seg;
+    seg.n_seg = sg.n;
+    for (int s = 0; s < sg.n; ++s) {
+        seg.seg_start[s] = sg.start[s]; seg.seg_T[s] = len[s];
+        seg.T = std::max(seg.T, len[s]);
     }
-    launch_layernorm(c, b->ex, d, m->enc_lnw, m->enc_lnb, b->enc_stack, d, S, d, "nllb_enc_ln");
-    // cross-attention keys / values of every decoder layer over all stacked rows: [S][dec_layers][k | v]
-    const long ld = (long)D.dec_layers * 2 * d;
-    for (int l = 0; l < D.dec_layers; ++l) {
-        const NlLayer& L = m->dec[l];
-        nl_linear(c, b->enc_stack, d, L.xkvw, L.xkvb, b->xkv_stack + (size_t)l * 2 * d, ld, S, 2 * d, d, 0, nullptr, 0, "nllb_xkv");
-    }
+    nl_encoder_layers(b->ctx(), m, b->ex, b->eh, b->eqkv, b->eatt, b->ewide, b->enc_stack, b->xkv_stack, total, seg);
 }
+
+// Row-table addressing of the decoder layers: row r's caches ([dec_layers][max_tgt][d]), position, cross K/V and SOURCE
+// LENGTH come from rows[r].  align: the selected heads leave their softmax rows in align_probs.
+struct NlRowsAddr {
+    const wlk_nllb_batch* b;
+    const StepRow* rows;
+    int R;
+    bool align;
+    const wlk_nllb_dims& D() const { return b->m->D; }
+    long layer_off(int l) const { return (long)l * D().max_tgt * D().d_model; }
+    void kv_rider(GemmArgs& g, int l) const {
+        g.kv_rows = rows; g.kv_layer_off = layer_off(l); g.kv_d = D().d_model; g.kv_ctx = D().max_tgt;
+    }
+    void append(const LaunchCtx& c, const float* qkv, int l) const { launch_kv_append_rows(c, qkv, rows, layer_off(l), R, D().d_model); }
+    void self_attention(const LaunchCtx& c, const float* qkv, float* att, int l) const {
+        launch_decoder_self_attention_rows(c, qkv, rows, layer_off(l), att, R, D().d_model, D().heads, D().max_tgt);
+    }
+    void cross_attention(const LaunchCtx& c, const float* q, float* att, int l) const {
+        const int d = D().d_model, H = D().heads;
+        const long kv_off = (long)l * 2 * d, ldkv = (long)D().dec_layers * 2 * d;
+        if (align)
+            launch_nllb_cross_attention_ragged_align(c, q, rows, kv_off, ldkv, att, R, d, H, b->head_rank_dev + (size_t)l * H,
+                                                     b->align_probs, D().max_src);
+        else
+            launch_nllb_cross_attention_ragged(c, q, rows, kv_off, ldkv, att, R, d, H);
+    }
+};
 
 // embed .. logits .. top-k of R stacked rows; every per-row scalar comes from the row table.  align: the selected heads
 // leave their softmax rows in align_probs and the ragged read-out follows the top-k (windows and results in align_host)
-static void nlb_step_chain(wlk_nllb_batch* b, int R, bool align = false) {
+static void nlb_step_chain(wlk_nllb_batch* b, int R, int k, bool align = false) {
     wlk_nllb* m = b->m;
     const wlk_nllb_dims& D = m->D;
     const LaunchCtx c = b->ctx();
-    const int d = D.d_model, H = D.heads, f = D.ffn, ctx_len = D.max_tgt;
-    const float q_scale = 0.125f;
     hipLaunchKernelGGL(nllb_embed_rows_step_kernel, dim3(R), dim3(256), 0, b->stream, b->rows_host_dev, b->rows_dev, m->emb,
-                       m->pos, D.embed_scale, D.pad_id + 1, d, b->dx);
+                       m->pos, D.embed_scale, D.pad_id + 1, D.d_model, b->ws.x);
     WLK_HIP(hipGetLastError());
-    const long ldkv = (long)D.dec_layers * 2 * d;
-    for (int l = 0; l < D.dec_layers; ++l) {
-        const NlLayer& L = m->dec[l];
-        const long layer_off = (long)l * ctx_len * d;       // a slot's caches: [dec_layers][max_tgt][d]
-        GemmArgs g;
-        g.A = b->dx; g.lda = d; g.W = L.qkvw; g.bias = L.qkvb; g.C = b->dqkv; g.ldc = 3 * d; g.M = R; g.N = 3 * d; g.K = d;
-        g.flags = kGemmScaleCols; g.scale = q_scale; g.scale_cols = d;
-        g.ln_gamma = L.ln1w; g.ln_beta = L.ln1b;
-        g.kv_rows = b->rows_dev; g.kv_layer_off = layer_off; g.kv_d = d; g.kv_ctx = ctx_len;
-        launch_gemv(c, g, "nllb_ln1_qkv_kv");
-        launch_decoder_self_attention_rows(c, b->dqkv, b->rows_dev, layer_off, b->datt, R, d, H, ctx_len);
-        nl_linear(c, b->datt, d, L.outw, L.outb, b->dx, d, R, d, d, kGemmResidual, b->dx, d, "nllb_dec_out");
-        GemmArgs q;
-        q.A = b->dx; q.lda = d; q.W = L.xqw; q.bias = L.xqb; q.C = b->dq; q.ldc = d; q.M = R; q.N = d; q.K = d;
-        q.flags = kGemmScaleCols; q.scale = q_scale; q.scale_cols = d; q.ln_gamma = L.lnxw; q.ln_beta = L.lnxb;
-        launch_gemv(c, q, "nllb_lnx_xq");
-        if (align)
-            launch_nllb_cross_attention_ragged_align(c, b->dq, b->rows_dev, (long)l * 2 * d, ldkv, b->datt, R, d, H,
-                                                     b->head_rank_dev + (size_t)l * H, b->align_probs, D.max_src);
-        else
-            launch_nllb_cross_attention_ragged(c, b->dq, b->rows_dev, (long)l * 2 * d, ldkv, b->datt, R, d, H);
-        nl_linear(c, b->datt, d, L.xoutw, L.xoutb, b->dx, d, R, d, d, kGemmResidual, b->dx, d, "nllb_dec_xout");
-        GemmArgs g1;
-        g1.A = b->dx; g1.lda = d; g1.W = L.fc1w; g1.bias = L.fc1b; g1.C = b->dwide; g1.ldc = f; g1.M = R; g1.N = f; g1.K = d;
-        g1.flags = kGemmRelu; g1.ln_gamma = L.ln2w; g1.ln_beta = L.ln2b;
-        launch_gemv(c, g1, "nllb_ln2_fc1");
-        nl_linear(c, b->dwide, f, L.fc2w, L.fc2b, b->dx, d, R, d, f, kGemmResidual, b->dx, d, "nllb_fc2");
-    }
-    GemmArgs lg;
-    lg.A = b->dx; lg.lda = d; lg.W = m->emb; lg.C = b->logits; lg.ldc = D.vocab; lg.M = R; lg.N = D.vocab; lg.K = d;
-    lg.ln_gamma = m->dec_lnw; lg.ln_beta = m->dec_lnb;
-    launch_gemv(c, lg, "nllb_lnf_logits");
+    nl_decoder_layers(c, m, b->ws, R, /*fused=*/true, NlRowsAddr{b, b->rows_dev, R, align});
+    nl_logits(c, m, /*fused=*/true, b->ws.x, R, 1, nullptr, b->logits);
     // results straight into the host-coherent block: no copy node behind the graph
-    launch_logsoftmax_topk(c, b->logits, D.vocab, R, b->step_k, b->vals_dev, b->ids_dev, b->topk_scratch, nullptr, nullptr, nullptr, 0);
+    launch_logsoftmax_topk(c, b->logits, D.vocab, R, k, b->vals_dev, b->ids_dev, b->topk_scratch, nullptr, nullptr, nullptr, 0);
     if (align) {
         int* res = b->align_host_dev + 3 * kNlBatchMaxRows;
         launch_nllb_align_readout_rows(c, b->align_probs, b->n_align, (long)kNlBatchMaxRows * D.max_src, D.max_src, R, b->rows_dev,
@@ -499,27 +452,10 @@ static void nlb_step_chain(wlk_nllb_batch* b, int R, bool align = false) {
 static void nlb_prefill_chain(wlk_nllb_batch* b, int N) {
     wlk_nllb* m = b->m;
     const wlk_nllb_dims& D = m->D;
-    const LaunchCtx c = b->ctx();
-    const int d = D.d_model, H = D.heads, f = D.ffn, ctx_len = D.max_tgt;
-    const float q_scale = 0.125f;
     hipLaunchKernelGGL(nllb_embed_rows_step_kernel, dim3(N), dim3(256), 0, b->stream, b->prefill_stage, b->prefill_rows, m->emb,
-                       m->pos, D.embed_scale, D.pad_id + 1, d, b->px);
+                       m->pos, D.embed_scale, D.pad_id + 1, D.d_model, b->pws.x);
     WLK_HIP(hipGetLastError());
-    const long ldkv = (long)D.dec_layers * 2 * d;
-    for (int l = 0; l < D.dec_layers; ++l) {
-        const NlLayer& L = m->dec[l];
-        const long layer_off = (long)l * ctx_len * d;
-        launch_layernorm(c, b->px, d, L.ln1w, L.ln1b, b->ph, d, N, d, "nllb_ln1");
-        nl_linear(c, b->ph, d, L.qkvw, L.qkvb, b->pqkv, 3 * d, N, 3 * d, d, kGemmScaleCols, nullptr, 0, "nllb_dec_qkv", q_scale, d);
-        launch_kv_append_rows(c, b->pqkv, b->prefill_rows, layer_off, N, d);
-        launch_decoder_self_attention_rows(c, b->pqkv, b->prefill_rows, layer_off, b->patt, N, d, H, ctx_len);
-        nl_linear(c, b->patt, d, L.outw, L.outb, b->px, d, N, d, d, kGemmResidual, b->px, d, "nllb_dec_out");
-        launch_layernorm(c, b->px, d, L.lnxw, L.lnxb, b->ph, d, N, d, "nllb_lnx");
-        nl_linear(c, b->ph, d, L.xqw, L.xqb, b->pq, d, N, d, d, kGemmScaleCols, nullptr, 0, "nllb_dec_xq", q_scale, d);
-        launch_nllb_cross_attention_ragged(c, b->pq, b->prefill_rows, (long)l * 2 * d, ldkv, b->patt, N, d, H);
-        nl_linear(c, b->patt, d, L.xoutw, L.xoutb, b->px, d, N, d, d, kGemmResidual, b->px, d, "nllb_dec_xout");
-        nl_ffn(c, L, b->px, b->ph, b->pwide, N, d, f);
-    }
+    nl_decoder_layers(b->ctx(), m, b->pws, N, /*fused=*/false, NlRowsAddr{b, b->prefill_rows, N, false});
 }
 
 static StepRow nlb_row(const wlk_nllb_batch* b, int slot, int token) {
@@ -570,19 +506,15 @@ int wlk_nllb_batch_create(wlk_nllb* m, int n_slots, wlk_nllb_batch** out) {
         b->eatt = b->alloc<float>(Smax * d); b->ewide = b->alloc<float>(Smax * f); b->enc_stack = b->alloc<float>(Smax * d);
         b->xkv_stack = b->alloc<float>(Smax * L * 2 * d);
         b->enc_tokens = b->alloc<int>(Smax);
-        b->dx = b->alloc<float>(R * d); b->dqkv = b->alloc<float>(R * 3 * d); b->datt = b->alloc<float>(R * d);
-        b->dq = b->alloc<float>(R * d); b->dwide = b->alloc<float>(R * f);
+        b->ws = NlDecWs{b->alloc<float>(R * d), nullptr, b->alloc<float>(R * 3 * d), b->alloc<float>(R * d), b->alloc<float>(R * d),
+                        b->alloc<float>(R * f)};
         b->logits = b->alloc<float>(R * D.vocab);
         b->topk_scratch = b->alloc<char>(topk_scratch_bytes(R));
         b->rows_dev = b->alloc<StepRow>(R);
         b->probe_rows_dev = b->alloc<StepRow>(R);
-        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->rows_host), R * sizeof(StepRow), hipHostMallocMapped));
-        WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->rows_host_dev), b->rows_host, 0));
-        std::memset(b->rows_host, 0, R * sizeof(StepRow));
-        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->vals_host), R * 8 * sizeof(float), hipHostMallocMapped));
-        WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->vals_dev), b->vals_host, 0));
-        WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->ids_host), R * 8 * sizeof(int), hipHostMallocMapped));
-        WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->ids_dev), b->ids_host, 0));
+        b->mapped(R, &b->rows_host, &b->rows_host_dev);
+        b->mapped(R * 8, &b->vals_host, &b->vals_dev);
+        b->mapped(R * 8, &b->ids_host, &b->ids_dev);
         *out = b.release();
         return WLK_OK;
     });
@@ -609,12 +541,8 @@ int wlk_nllb_batch_encode(wlk_nllb_batch* b, const int32_t* slots, const int64_t
         len[i] = (int)li;
     }
     const int total = src_offsets[n];
-    std::vector<int> stage(total);
-    for (int i = 0; i < total; ++i) {
-        if (src_ids[i] < 0 || src_ids[i] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
-        if (src_ids[i] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sentence is not supported (sentences are stacked, not padded)");
-        stage[i] = (int)src_ids[i];
-    }
+    if (int rc = nl_check_tokens(D, src_ids, total, "padding inside a sentence is not supported (sentences are stacked, not padded)")) return rc;
+    const std::vector<int> stage(src_ids, src_ids + total);
     return nl_guarded([&]() {
         WLK_HIP(hipSetDevice(b->m->device));
         WLK_HIP(hipStreamSynchronize(b->stream));
@@ -654,22 +582,13 @@ int wlk_nllb_batch_step(wlk_nllb_batch* b, const int32_t* slots, const int64_t* 
         const NlBatchSlot& s = b->slots[slots[r]];
         if (!s.encoded) return nl_fail(WLK_ERR_STATE, "NLLB batch step on a slot that is not encoded");
         if (s.self_len + 1 > D.max_tgt) return nl_fail(WLK_ERR_CAPACITY, "target context exceeded");
-        if (tokens[r] < 0 || tokens[r] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
-        if (tokens[r] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sequence is not supported");
+        if (int rc = nl_check_tokens(D, tokens + r, 1)) return rc;
     }
     return nl_guarded([&]() {
         WLK_HIP(hipSetDevice(b->m->device));
         WLK_HIP(hipStreamSynchronize(b->stream));           // the previous step's readers of the host block are done
         for (int r = 0; r < n_rows; ++r) b->rows_host[r] = nlb_row(b, slots[r], (int)tokens[r]);
-        hipGraphExec_t& exec = b->exec[n_rows];
-        if (!exec || b->exec_k[n_rows] != k) {
-            if (exec) { WLK_HIP(hipGraphExecDestroy(exec)); exec = nullptr; }
-            b->step_k = k;
-            capture_step_graph(b->stream, exec, [&] { nlb_step_chain(b, n_rows); });
-            b->exec_k[n_rows] = k;
-        }
-        WLK_HIP(hipGraphLaunch(exec, b->stream));
-        WLK_HIP(hipStreamSynchronize(b->stream));
+        nl_replay(b->stream, b->graphs[b->kStepGraph + n_rows], k, 0, [&] { nlb_step_chain(b, n_rows, k); });
         std::memcpy(logprobs, b->vals_host, (size_t)n_rows * k * sizeof(float));
         std::memcpy(ids, b->ids_host, (size_t)n_rows * k * sizeof(int));
         for (auto& s : b->slots) s.logits_row = -1;
@@ -685,22 +604,15 @@ int wlk_nllb_batch_step(wlk_nllb_batch* b, const int32_t* slots, const int64_t* 
 int wlk_nllb_batch_set_align(wlk_nllb_batch* b, const int32_t* layer_head_pairs, int32_t n) {
     if (!b || (n > 0 && !layer_head_pairs)) return nl_fail(WLK_ERR_ARG, "NULL argument");
     if (n < 0 || n > kNlMaxAlign) return nl_fail(WLK_ERR_ARG, "wlk_nllb_batch_set_align: 0..64 (layer, head) pairs");
-    const wlk_nllb_dims& D = b->m->D;
-    std::vector<int> rank((size_t)D.dec_layers * D.heads, -1);
-    for (int i = 0; i < n; ++i) {
-        const int l = layer_head_pairs[2 * i], h = layer_head_pairs[2 * i + 1];
-        if (l < 0 || l >= D.dec_layers || h < 0 || h >= D.heads) return nl_fail(WLK_ERR_ARG, "alignment head: layer or head out of range");
-        if (rank[(size_t)l * D.heads + h] >= 0) return nl_fail(WLK_ERR_ARG, "alignment head: duplicate (layer, head) pair");
-        rank[(size_t)l * D.heads + h] = i;
-    }
+    std::vector<int> rank;
+    if (int rc = nl_head_rank(b->m->D, layer_head_pairs, n, rank)) return rc;
     return nl_guarded([&]() {
         bool recorded = false;
-        for (auto& e : b->align_exec) recorded = recorded || e;
+        for (int r = 0; r <= kNlBatchMaxRows; ++r) recorded = recorded || b->graphs[b->kAlignGraph + r].exec;
         if (recorded) {                      // a recording carries the head count by value
             WLK_HIP(hipSetDevice(b->m->device));
             WLK_HIP(hipStreamSynchronize(b->stream));
-            for (auto& e : b->align_exec)
-                if (e) { WLK_HIP(hipGraphExecDestroy(e)); e = nullptr; }
+            for (int r = 0; r <= kNlBatchMaxRows; ++r) b->graphs[b->kAlignGraph + r].drop();
         }
         for (auto& s : b->slots) s.align_row = -1;
         b->head_rank = std::move(rank);      // uploaded by the next align step: nothing is allocated here
@@ -729,8 +641,7 @@ int wlk_nllb_batch_step_align(wlk_nllb_batch* b, const int32_t* slots, const int
         if (!s.encoded) return nl_fail(WLK_ERR_STATE, "NLLB batch step on a slot that is not encoded");
         if (s.self_len == 0) return nl_fail(WLK_ERR_STATE, "wlk_nllb_batch_step_align before the slot's decoder prompt (prefill or step first)");
         if (s.self_len + 1 > D.max_tgt) return nl_fail(WLK_ERR_CAPACITY, "target context exceeded");
-        if (tokens[r] < 0 || tokens[r] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
-        if (tokens[r] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sequence is not supported");
+        if (int rc = nl_check_tokens(D, tokens + r, 1)) return rc;
         if (lo[r] < 0 || hi[r] > s.src_len || limit[r] < 0 || limit[r] > s.src_len)
             return nl_fail(WLK_ERR_ARG, "wlk_nllb_batch_step_align: needs 0 <= lo, hi <= src_len and 0 <= limit <= src_len in every row");
     }
@@ -742,9 +653,7 @@ int wlk_nllb_batch_step_align(wlk_nllb_batch* b, const int32_t* slots, const int
             b->head_rank_dev = b->alloc<int>((size_t)D.dec_layers * D.heads);
             b->align_probs = b->alloc<float>((size_t)kNlMaxAlign * R8 * D.max_src);
             b->align_p = b->alloc<float>((size_t)R8 * D.max_src);
-            WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->align_host), 6 * R8 * sizeof(int), hipHostMallocMapped));
-            WLK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->align_host_dev), b->align_host, 0));
-            std::memset(b->align_host, 0, 6 * R8 * sizeof(int));
+            b->mapped(6 * R8, &b->align_host, &b->align_host_dev);
         }
         if (b->head_rank_stale) {
             WLK_HIP(hipMemcpyAsync(b->head_rank_dev, b->head_rank.data(), b->head_rank.size() * sizeof(int), hipMemcpyHostToDevice,
@@ -756,16 +665,8 @@ int wlk_nllb_batch_step_align(wlk_nllb_batch* b, const int32_t* slots, const int
             b->rows_host[r] = nlb_row(b, slots[r], (int)tokens[r]);
             b->align_host[3 * r] = lo[r]; b->align_host[3 * r + 1] = hi[r]; b->align_host[3 * r + 2] = limit[r];
         }
-        hipGraphExec_t& exec = b->align_exec[n_rows];
-        if (!exec || b->align_exec_k[n_rows] != k) {
-            if (exec) { WLK_HIP(hipGraphExecDestroy(exec)); exec = nullptr; }
-            b->step_k = k;
-            capture_step_graph(b->stream, exec, [&] { nlb_step_chain(b, n_rows, /*align=*/true); });
-            b->align_exec_k[n_rows] = k;
+        if (nl_replay(b->stream, b->graphs[b->kAlignGraph + n_rows], k, 0, [&] { nlb_step_chain(b, n_rows, k, /*align=*/true); }))
             b->align_captures += 1;
-        }
-        WLK_HIP(hipGraphLaunch(exec, b->stream));
-        WLK_HIP(hipStreamSynchronize(b->stream));
         std::memcpy(logprobs, b->vals_host, (size_t)n_rows * k * sizeof(float));
         std::memcpy(ids, b->ids_host, (size_t)n_rows * k * sizeof(int));
         std::memcpy(align_pos, b->align_host + 3 * R8, (size_t)n_rows * sizeof(int));
@@ -805,11 +706,10 @@ int wlk_nllb_batch_prefill(wlk_nllb_batch* b, const int32_t* slots, const int64_
         if (pi > D.max_tgt - 1) return nl_fail(WLK_ERR_CAPACITY, "NLLB batch prefill: a prompt leaves no room for a step");
     }
     const int total = prompt_offsets[n];
+    if (int rc = nl_check_tokens(D, prompt_ids, total)) return rc;
     std::vector<StepRow> table((size_t)total);
     for (int i = 0; i < n; ++i)
         for (int t = prompt_offsets[i]; t < prompt_offsets[i + 1]; ++t) {
-            if (prompt_ids[t] < 0 || prompt_ids[t] >= D.vocab) return nl_fail(WLK_ERR_ARG, "token id out of range");
-            if (prompt_ids[t] == D.pad_id) return nl_fail(WLK_ERR_ARG, "padding inside a sequence is not supported");
             table[t] = nlb_row(b, slots[i], (int)prompt_ids[t]);
             table[t].offset = t - prompt_offsets[i];
         }
@@ -818,8 +718,8 @@ int wlk_nllb_batch_prefill(wlk_nllb_batch* b, const int32_t* slots, const int64_
         WLK_HIP(hipStreamSynchronize(b->stream));
         if (!b->prefill_rows) {
             const size_t d = D.d_model, N = (size_t)b->n_slots * D.max_tgt;
-            b->px = b->alloc<float>(N * d); b->ph = b->alloc<float>(N * d); b->pqkv = b->alloc<float>(N * 3 * d);
-            b->patt = b->alloc<float>(N * d); b->pq = b->alloc<float>(N * d); b->pwide = b->alloc<float>(N * D.ffn);
+            b->pws = NlDecWs{b->alloc<float>(N * d), b->alloc<float>(N * d), b->alloc<float>(N * 3 * d), b->alloc<float>(N * d),
+                             b->alloc<float>(N * d), b->alloc<float>(N * D.ffn)};
             b->prefill_stage = b->alloc<StepRow>(N);
             b->prefill_rows = b->alloc<StepRow>(N);
         }
@@ -893,11 +793,11 @@ int wlk_nllb_batch_cross_attention(wlk_nllb_batch* b, const int32_t* slots, int3
         WLK_HIP(hipSetDevice(b->m->device));
         WLK_HIP(hipStreamSynchronize(b->stream));
         WLK_HIP(hipMemcpyAsync(b->probe_rows_dev, table, (size_t)n_rows * sizeof(StepRow), hipMemcpyHostToDevice, b->stream));
-        WLK_HIP(hipMemcpyAsync(b->dq, q_host, (size_t)n_rows * d * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        WLK_HIP(hipMemcpyAsync(b->ws.q, q_host, (size_t)n_rows * d * sizeof(float), hipMemcpyHostToDevice, b->stream));
         WLK_HIP(hipStreamSynchronize(b->stream));           // `table` and q_host are pageable
-        launch_nllb_cross_attention_ragged(b->ctx(), b->dq, b->probe_rows_dev, (long)layer * 2 * d, (long)D.dec_layers * 2 * d, b->datt,
+        launch_nllb_cross_attention_ragged(b->ctx(), b->ws.q, b->probe_rows_dev, (long)layer * 2 * d, (long)D.dec_layers * 2 * d, b->ws.att,
                                            n_rows, (int)d, D.heads);
-        WLK_HIP(hipMemcpyAsync(out_host, b->datt, (size_t)n_rows * d * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+        WLK_HIP(hipMemcpyAsync(out_host, b->ws.att, (size_t)n_rows * d * sizeof(float), hipMemcpyDeviceToHost, b->stream));
         WLK_HIP(hipStreamSynchronize(b->stream));
         return WLK_OK;
     });
