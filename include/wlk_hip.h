@@ -762,6 +762,19 @@ int wlk_nllb_batch_step_align(wlk_nllb_batch* b, const int32_t* slots, const int
                               float* tail_mass /*[n_rows]*/);
 /* align steps run and align-step graphs recorded since the batch was created */
 int wlk_nllb_batch_align_stats(wlk_nllb_batch* b, uint64_t* align_steps, uint64_t* graph_captures);
+/* Draft verification (opt-in).  For n freshly encoded slots (target length 0): ids_i = ids[offsets[i] .. offsets[i+1])
+ * = [decoder start, forced first token, d_0 .. d_{n_d-1}]  (P_i = 2 + n_d >= 2, no eos among them).
+ * ONE stacked decoder pass over all sum(P_i) rows (the chain of wlk_nllb_batch_prefill), then per slot:
+ *   pick_j  = arg-max over the vocabulary of the logits of row 1 + j, j = 0 .. n_d   (lowest id on an exact tie)
+ *   k       = the first j < n_d with pick_j != d_j, n_d if there is none
+ *   accepted[i] = k,  next_token[i] = pick_k
+ * Afterwards the slot's target length is 2 + k: it continues with wlk_nllb_batch_step(next_token).
+ * State / argument rules of wlk_nllb_batch_prefill, plus WLK_ERR_ARG for P_i < 2; a refused call launches nothing and
+ * changes nothing.  Synchronous.  A batch that never verifies allocates nothing for this; no graph is recorded. */
+int wlk_nllb_batch_verify(wlk_nllb_batch* b, const int32_t* slots, const int64_t* ids, const int32_t* offsets, int32_t n,
+                          int32_t* accepted, int64_t* next_token);
+/* verify passes run, draft tokens offered and draft tokens accepted since the batch was created */
+int wlk_nllb_batch_verify_stats(wlk_nllb_batch* b, uint64_t* passes, uint64_t* draft_tokens, uint64_t* accepted_tokens);
 
 /* ---- word-timestamp alignment ------------------------------------------------------------------
  * Dynamic time warping of a [n_rows tokens, n_cols frames] fp32 cost matrix on `device`: replaces `dtw_cpu`
@@ -867,6 +880,12 @@ int wlk_diag_nllb_align(const float* probs, int32_t n_align, int32_t rows, int32
 int wlk_diag_nllb_align_rows(const float* probs, int32_t n_align, int32_t rows, int32_t stride, const int32_t* S,
                              const int32_t* lo, const int32_t* hi, const int32_t* limit, float* p_out, int32_t* pos, float* prob,
                              float* mass);
+/* The greedy pick of a draft verification alone (csrc/nllb_batch.hip: nllb_verify_pick_rows_kernel through its production
+ * launcher, then the fold of its slice partials) on host logits [n_rows][n_vocab]: picks[r] = the arg-max of row r (lowest id
+ * on a tie: rank 0 of wlk_diag_topk, form 0), match[r] = (picks[r] == targets[r]).  n_rows in [1, 128], n_vocab in
+ * [1, 2^20]; anything else returns WLK_ERR_ARG before any upload.  Synchronous, on a stream of its own. */
+int wlk_diag_nllb_verify_pick(const float* logits, int32_t n_rows, int32_t n_vocab, const int32_t* targets, int32_t* picks,
+                              int32_t* match);
 /* The decoder's attention stage (csrc/decoder.hip, the merged out projection of csrc/gemm_f32.hip, the prefill flash
  * kernel of csrc/attention.hip) on host data, through ONE chosen route.  The launchers are the ones a decode step uses,
  * unchanged.  Heads are 64 wide and d = 64 n_head.

@@ -348,6 +348,8 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_nllb_batch_prefill": (cint, [p, p, p, p, i32]),
         "wlk_nllb_batch_step_align": (cint, [p, p, p, i32, i32, p, p, p, p, p, p, p, p]),
         "wlk_nllb_batch_align_stats": (cint, [p, C.POINTER(u64), C.POINTER(u64)]),
+        "wlk_nllb_batch_verify": (cint, [p, p, p, p, i32, p, p]),
+        "wlk_nllb_batch_verify_stats": (cint, [p, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "wlk_vad_weights_floats": (cint, [C.POINTER(u64)]),
         "wlk_vad_tensor_lookup": (cint, [C.c_char_p, C.POINTER(u64), C.POINTER(u64)]),
         "wlk_vad_tensor_name": (cint, [cint, C.POINTER(C.c_char_p)]),
@@ -389,6 +391,7 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_topk": (cint, [p, i32, i32, i32, i32, p, p]),
         "wlk_diag_nllb_align": (cint, [p, i32, i32, i32, i32, i32, i32, p, p, p, p]),
         "wlk_diag_nllb_align_rows": (cint, [p, i32, i32, i32, p, p, p, p, p, p, p, p]),
+        "wlk_diag_nllb_verify_pick": (cint, [p, i32, i32, p, p, p]),
         "wlk_diag_sf_kernel": (cint, [C.POINTER(DiagSfKernelArgs)]),
         "wlk_diag_linear_ex": (cint, [C.POINTER(DiagLinearArgs)]),
         "wlk_diag_gemv_variant": (cint, [cint, cint, cint, cint, cint, C.c_char_p, cint]),
@@ -458,6 +461,7 @@ EXPORTED_SYMBOLS = (
     "wlk_group_find_alignment", "wlk_group_align_fits", "wlk_diag_dtw_starts",
     "wlk_group_run_pick", "wlk_diag_pick_advance",
     "wlk_group_verify", "wlk_group_verify_fits", "wlk_diag_draft_pick",
+    "wlk_nllb_batch_verify", "wlk_nllb_batch_verify_stats", "wlk_diag_nllb_verify_pick",
 )
 
 

@@ -719,6 +719,33 @@ int wlk_diag_nllb_align_rows(const float* probs, int32_t n_align, int32_t rows, 
     });
 }
 
+/* the greedy pick of a draft verification alone (see include/wlk_hip.h): the pick launcher a verify uses, unchanged, and the
+ * fold of its slice partials */
+int wlk_diag_nllb_verify_pick(const float* logits, int32_t n_rows, int32_t n_vocab, const int32_t* targets, int32_t* picks,
+                              int32_t* match) {
+    if (!logits || !targets || !picks || !match || n_rows < 1 || n_rows > 128 || n_vocab < 1 || n_vocab > (1 << 20)) {
+        g_diag_error = "wlk_diag_nllb_verify_pick: null pointer, n_rows outside [1, 128] or n_vocab outside [1, 2^20]";
+        return WLK_ERR_ARG;
+    }
+    return run([&]() {
+        struct Stream {
+            hipStream_t s = nullptr;
+            Stream() { WLK_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+            ~Stream() { (void)hipStreamDestroy(s); }
+        } st;
+        DevBytes L((size_t)n_rows * n_vocab * sizeof(float), logits), T((size_t)n_rows * sizeof(int), targets),
+            PARTS((size_t)n_rows * kNlPickSlices * sizeof(NlPick)), PK((size_t)n_rows * sizeof(int)), MT((size_t)n_rows * sizeof(int));
+        WLK_HIP(hipDeviceSynchronize());   // the uploads ran on the legacy stream; st does not wait for it
+        LaunchCtx ctx;
+        ctx.stream = st.s;
+        launch_nllb_verify_pick_rows(ctx, L.f(), n_vocab, n_rows, PARTS.as<NlPick>());
+        launch_nllb_verify_fold_rows(ctx, PARTS.as<NlPick>(), n_rows, T.i(), PK.i(), MT.i());
+        WLK_HIP(hipStreamSynchronize(st.s));
+        PK.back(picks);
+        MT.back(match);
+    });
+}
+
 /* The decoder's attention stage on host data through one chosen route (see include/wlk_hip.h): the launchers of a decode
  * step, unchanged.  Every shape is checked here or by its launcher before anything is launched for it. */
 int wlk_diag_dec_attention(const wlk_diag_dec_attention_args* q) {

@@ -334,6 +334,149 @@ void launch_nllb_align_readout_rows(const LaunchCtx& ctx, const float* probs, in
     WLK_HIP(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Draft verification (wlk_nllb_batch_verify): the arg-max of every candidate row, then one wave per slot that
+// compares the picks with the draft.
+//
+// nllb_verify_pick_rows_kernel: grid (kNlPickSlices, rows).  A row of 256 206 logits is 1 MB - one workgroup per row would
+// pull it through one CU - so a row is cut into kNlPickSlices slices of `per` (even) elements and workgroup (s, r) reads
+// slice s of row r ONCE: thread t owns the element pairs (u * 256 + t) of every block of 256 * kNlPickLoads pairs, issues
+// the kNlPickLoads loads of a block before it folds the first, and keeps the best (value, id) it has seen.  A greedy id
+// needs no normaliser: no expf, no candidate list.  Order: value descending, id ascending - rank 0 of
+// launch_logsoftmax_topk on the same row.
+//   kVec2    n_vocab is even: every row and every slice starts 8-byte aligned (NOT 16: 256 206 * 4 = 1 024 824), a pair
+//            is one 8-byte load.  Odd vocabularies (tests) take two 4-byte loads per pair.
+// Nothing is read at or past the slice's end: a pair beyond it re-reads the slice's first pair and is never folded.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kNlVerifyChunk = 128;        // rows of logits a verify forms at a time (131 MB at NLLB's vocabulary)
+constexpr int kNlPickLoads = 16;           // 8-byte loads a thread has in flight: 32 slices x 256 threads x 16 pairs = 262 144
+
+__device__ __forceinline__ bool nl_pick_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+// the fold of a row's partials, by one lane: all kNlPickSlices entries requested before the first comparison
+__device__ __forceinline__ NlPick nl_pick_fold(const NlPick* __restrict__ parts, long row) {
+    NlPick p[kNlPickSlices];
+#pragma unroll
+    for (int s = 0; s < kNlPickSlices; ++s) p[s] = parts[row * kNlPickSlices + s];
+    NlPick b = p[0];
+#pragma unroll
+    for (int s = 1; s < kNlPickSlices; ++s)
+        if (nl_pick_better(p[s].v, p[s].i, b.v, b.i)) b = p[s];
+    return b;
+}
+
+template <bool kVec2>
+__global__ __launch_bounds__(256) void nllb_verify_pick_rows_kernel(const float* __restrict__ logits, int n_vocab,
+                                                                    NlPick* __restrict__ parts) {
+    __shared__ float cand_v[4];
+    __shared__ int cand_i[4];
+    const int tid = threadIdx.x, slice = blockIdx.x, row = blockIdx.y;
+    const int per = (((n_vocab + kNlPickSlices - 1) / kNlPickSlices) + 1) & ~1;
+    const int lo = slice * per;
+    const int hi = min(n_vocab, lo + per);
+    const float* x = logits + (long)row * n_vocab;
+    const int safe = lo < hi ? lo : 0;                 // (an empty trailing slice reads nothing: its loop does not run)
+    float bv = -INFINITY;
+    int bi = INT_MAX;
+    for (int base = lo; base < hi; base += 2 * 256 * kNlPickLoads) {
+        float2 v[kNlPickLoads];
+#pragma unroll
+        for (int u = 0; u < kNlPickLoads; ++u) {
+            const int i = base + 2 * (u * 256 + tid);
+            if (kVec2) {
+                v[u] = *reinterpret_cast<const float2*>(x + (i < hi ? i : safe));      // hi is even: i < hi means i + 1 < hi
+            } else {
+                v[u].x = x[i < hi ? i : safe];
+                v[u].y = x[i + 1 < hi ? i + 1 : safe];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kNlPickLoads; ++u) { pin_loaded(v[u].x); pin_loaded(v[u].y); }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < kNlPickLoads; ++u) {
+            const int i = base + 2 * (u * 256 + tid);
+            if (i < hi && nl_pick_better(v[u].x, i, bv, bi)) { bv = v[u].x; bi = i; }
+            if (i + 1 < hi && nl_pick_better(v[u].y, i + 1, bv, bi)) { bv = v[u].y; bi = i + 1; }
+        }
+    }
+    wave_argmax(bv, bi);
+    if ((tid & 63) == 0) { cand_v[tid >> 6] = bv; cand_i[tid >> 6] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (nl_pick_better(cand_v[w], cand_i[w], bv, bi)) { bv = cand_v[w]; bi = cand_i[w]; }
+        NlPick out;
+        out.v = bv;
+        out.i = bi;
+        parts[(long)row * kNlPickSlices + slice] = out;
+    }
+}
+
+void launch_nllb_verify_pick_rows(const LaunchCtx& ctx, const float* logits, int n_vocab, int n_rows, NlPick* parts) {
+    if (n_vocab < 1 || n_rows < 1 || n_rows > 65535) throw std::invalid_argument("NLLB verify pick: n_vocab >= 1, 1..65535 rows");
+    KernelScope ks(ctx, "nllb_verify_pick_rows", 0.0, 4.0 * n_rows * (double)n_vocab);
+    if (n_vocab % 2 == 0)
+        hipLaunchKernelGGL(nllb_verify_pick_rows_kernel<true>, dim3(kNlPickSlices, n_rows), dim3(256), 0, ctx.stream, logits, n_vocab, parts);
+    else
+        hipLaunchKernelGGL(nllb_verify_pick_rows_kernel<false>, dim3(kNlPickSlices, n_rows), dim3(256), 0, ctx.stream, logits, n_vocab, parts);
+    WLK_HIP(hipGetLastError());
+}
+
+// diagnostics: the fold alone, one lane per row
+__global__ __launch_bounds__(64) void nllb_verify_fold_rows_kernel(const NlPick* __restrict__ parts, int n_rows,
+                                                                   const int* __restrict__ targets, int* __restrict__ picks,
+                                                                   int* __restrict__ match) {
+    const int r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= n_rows) return;
+    const NlPick b = nl_pick_fold(parts, r);
+    picks[r] = b.i;
+    match[r] = b.i == targets[r] ? 1 : 0;
+}
+
+void launch_nllb_verify_fold_rows(const LaunchCtx& ctx, const NlPick* parts, int n_rows, const int* targets, int* picks, int* match) {
+    if (n_rows < 1) throw std::invalid_argument("NLLB verify fold: rows >= 1");
+    KernelScope ks(ctx, "nllb_verify_fold_rows");
+    hipLaunchKernelGGL(nllb_verify_fold_rows_kernel, dim3((n_rows + 63) / 64), dim3(64), 0, ctx.stream, parts, n_rows, targets, picks, match);
+    WLK_HIP(hipGetLastError());
+}
+
+// One wave per slot behind the picks.  Slot i's rows are row0[i] .. row0[i] + P[i] of the stacked table (P = 2 + n_d); the
+// logits of row 1 + j predict draft token d_j = the token of row 2 + j, and the logits of the last row what follows the draft.
+//   pick_j = nl_pick_fold of row row0 + 1 + j, j = 0 .. n_d (lane = j mod 64, 64 positions a round)
+//   k      = the first j with j == n_d or pick_j != d_j: a ballot over the miss flags, the first set bit
+//   res[2 i] = k, res[2 i + 1] = pick_k - plain stores by the lane that holds position k, into host-coherent memory
+struct NlVerifySlots {
+    int n = 0;
+    int row0[kNlBatchMaxRows] = {0}, P[kNlBatchMaxRows] = {0};
+};
+__global__ __launch_bounds__(64) void nllb_verify_accept_kernel(const NlPick* __restrict__ parts, const StepRow* __restrict__ rows,
+                                                                NlVerifySlots sl, int* __restrict__ res) {
+    const int slot = blockIdx.x, lane = threadIdx.x;
+    int r0 = 0, P = 2;
+#pragma unroll
+    for (int s = 0; s < kNlBatchMaxRows; ++s)
+        if (s == slot) { r0 = sl.row0[s]; P = sl.P[s]; }
+    const int n_d = P - 2;
+    for (int base = 0; base <= n_d; base += 64) {
+        const int j = base + lane;
+        const bool live = j <= n_d;
+        const int draft = rows[r0 + (j < n_d ? 2 + j : 0)].token;
+        const NlPick pick = nl_pick_fold(parts, r0 + 1 + (live ? j : 0));
+        const bool miss = !(j < n_d && pick.i == draft);
+        const unsigned long long m = __ballot(miss);
+        if (m != 0ull) {
+            const int k = base + __ffsll((long long)m) - 1;      // k <= n_d: position n_d always misses
+            if (j == k) {
+                res[2 * slot] = k;
+                res[2 * slot + 1] = pick.i;
+            }
+            break;
+        }
+    }
+}
+
 struct NlBatchSlot {
     float *enc_out = nullptr, *cross_kv = nullptr, *kcache = nullptr, *vcache = nullptr;
     int src_len = 0, self_len = 0;
@@ -380,6 +523,11 @@ struct wlk_nllb_batch : NlOwner {
     // stacked prompt prefill (wlk_nllb_batch_prefill): n_slots x max_tgt rows, allocated by the first prefill
     NlDecWs pws{};
     StepRow *prefill_stage = nullptr, *prefill_rows = nullptr;    // the uploaded table and the copy the embedding leaves
+    // draft verification (wlk_nllb_batch_verify); nothing below is allocated before the first verify
+    float* vlogits = nullptr;            // [kNlVerifyChunk][vocab]: one chunk of candidate rows' logits, reused chunk by chunk
+    NlPick* vparts = nullptr;            // [n_slots x max_tgt][kNlPickSlices]: every candidate row's slice partials
+    int *vres_host = nullptr, *vres_dev = nullptr;      // pinned + mapped: [8] accepted | next token
+    uint64_t verify_passes = 0, verify_draft = 0, verify_accepted = 0;
 };
 
 namespace wlk {
@@ -475,6 +623,49 @@ static int nlb_check_slots(const wlk_nllb_batch* b, const int32_t* slots, int n)
         seen |= 1u << slots[i];
     }
     return WLK_OK;
+}
+
+// Host checks of a stacked prompt pass (prefill: min_len 1, verify: min_len 2) and its row table: row t = (slot, token,
+// position inside the slot's prompt).  Refuses before anything is launched or changed.
+static int nlb_prompt_table(const wlk_nllb_batch* b, const char* who, const int32_t* slots, const int64_t* ids, const int32_t* offsets,
+                            int n, int min_len, std::vector<StepRow>& table) {
+    const std::string w = who;
+    if (n < 1 || n > b->n_slots) return nl_fail(WLK_ERR_ARG, w + ": 1..n_slots prompts per call");
+    if (int rc = nlb_check_slots(b, slots, n)) return rc;
+    const wlk_nllb_dims& D = b->m->D;
+    if (offsets[0] != 0) return nl_fail(WLK_ERR_ARG, w + ": prompt_offsets must start at 0");
+    for (int i = 0; i < n; ++i) {
+        const NlBatchSlot& s = b->slots[slots[i]];
+        if (!s.encoded) return nl_fail(WLK_ERR_STATE, w + " on a slot that is not encoded");
+        if (s.self_len != 0) return nl_fail(WLK_ERR_STATE, w + " on a slot that already holds target tokens");
+        const long pi = (long)offsets[i + 1] - offsets[i];
+        if (pi < min_len) return nl_fail(WLK_ERR_ARG, w + (min_len == 1 ? ": every prompt needs at least one token"
+                                                                        : ": needs the decoder start and the forced first token in front of the draft"));
+        if (pi > D.max_tgt - 1) return nl_fail(WLK_ERR_CAPACITY, w + ": a prompt leaves no room for a step");
+    }
+    const int total = offsets[n];
+    if (int rc = nl_check_tokens(D, ids, total)) return rc;
+    table.resize((size_t)total);
+    for (int i = 0; i < n; ++i)
+        for (int t = offsets[i]; t < offsets[i + 1]; ++t) {
+            table[t] = nlb_row(b, slots[i], (int)ids[t]);
+            table[t].offset = t - offsets[i];
+        }
+    return WLK_OK;
+}
+
+// the prefill workspace (allocated by the first stacked prompt pass) and the table's upload; the stream is idle on entry
+static void nlb_prompt_upload(wlk_nllb_batch* b, const std::vector<StepRow>& table) {
+    const wlk_nllb_dims& D = b->m->D;
+    if (!b->prefill_rows) {
+        const size_t d = D.d_model, N = (size_t)b->n_slots * D.max_tgt;
+        b->pws = NlDecWs{b->alloc<float>(N * d), b->alloc<float>(N * d), b->alloc<float>(N * 3 * d), b->alloc<float>(N * d),
+                         b->alloc<float>(N * d), b->alloc<float>(N * D.ffn)};
+        b->prefill_stage = b->alloc<StepRow>(N);
+        b->prefill_rows = b->alloc<StepRow>(N);
+    }
+    WLK_HIP(hipMemcpyAsync(b->prefill_stage, table.data(), table.size() * sizeof(StepRow), hipMemcpyHostToDevice, b->stream));
+    WLK_HIP(hipStreamSynchronize(b->stream));           // `table` is pageable
 }
 
 }  // namespace wlk
@@ -693,38 +884,13 @@ int wlk_nllb_batch_align_stats(wlk_nllb_batch* b, uint64_t* align_steps, uint64_
 int wlk_nllb_batch_prefill(wlk_nllb_batch* b, const int32_t* slots, const int64_t* prompt_ids, const int32_t* prompt_offsets,
                            int32_t n) {
     if (!b || !slots || !prompt_ids || !prompt_offsets) return nl_fail(WLK_ERR_ARG, "NULL argument");
-    if (n < 1 || n > b->n_slots) return nl_fail(WLK_ERR_ARG, "NLLB batch prefill: 1..n_slots prompts per call");
-    if (int rc = nlb_check_slots(b, slots, n)) return rc;
-    const wlk_nllb_dims& D = b->m->D;
-    if (prompt_offsets[0] != 0) return nl_fail(WLK_ERR_ARG, "NLLB batch prefill: prompt_offsets must start at 0");
-    for (int i = 0; i < n; ++i) {
-        const NlBatchSlot& s = b->slots[slots[i]];
-        if (!s.encoded) return nl_fail(WLK_ERR_STATE, "NLLB batch prefill on a slot that is not encoded");
-        if (s.self_len != 0) return nl_fail(WLK_ERR_STATE, "NLLB batch prefill on a slot that already holds target tokens");
-        const long pi = (long)prompt_offsets[i + 1] - prompt_offsets[i];
-        if (pi < 1) return nl_fail(WLK_ERR_ARG, "NLLB batch prefill: every prompt needs at least one token");
-        if (pi > D.max_tgt - 1) return nl_fail(WLK_ERR_CAPACITY, "NLLB batch prefill: a prompt leaves no room for a step");
-    }
+    std::vector<StepRow> table;
+    if (int rc = nlb_prompt_table(b, "NLLB batch prefill", slots, prompt_ids, prompt_offsets, n, 1, table)) return rc;
     const int total = prompt_offsets[n];
-    if (int rc = nl_check_tokens(D, prompt_ids, total)) return rc;
-    std::vector<StepRow> table((size_t)total);
-    for (int i = 0; i < n; ++i)
-        for (int t = prompt_offsets[i]; t < prompt_offsets[i + 1]; ++t) {
-            table[t] = nlb_row(b, slots[i], (int)prompt_ids[t]);
-            table[t].offset = t - prompt_offsets[i];
-        }
     return nl_guarded([&]() {
         WLK_HIP(hipSetDevice(b->m->device));
         WLK_HIP(hipStreamSynchronize(b->stream));
-        if (!b->prefill_rows) {
-            const size_t d = D.d_model, N = (size_t)b->n_slots * D.max_tgt;
-            b->pws = NlDecWs{b->alloc<float>(N * d), b->alloc<float>(N * d), b->alloc<float>(N * 3 * d), b->alloc<float>(N * d),
-                             b->alloc<float>(N * d), b->alloc<float>(N * D.ffn)};
-            b->prefill_stage = b->alloc<StepRow>(N);
-            b->prefill_rows = b->alloc<StepRow>(N);
-        }
-        WLK_HIP(hipMemcpyAsync(b->prefill_stage, table.data(), table.size() * sizeof(StepRow), hipMemcpyHostToDevice, b->stream));
-        WLK_HIP(hipStreamSynchronize(b->stream));           // `table` is pageable
+        nlb_prompt_upload(b, table);
         nlb_prefill_chain(b, total);
         WLK_HIP(hipStreamSynchronize(b->stream));
         for (int i = 0; i < n; ++i) {
@@ -734,6 +900,68 @@ int wlk_nllb_batch_prefill(wlk_nllb_batch* b, const int32_t* slots, const int64_
         }
         return WLK_OK;
     });
+}
+
+int wlk_nllb_batch_verify(wlk_nllb_batch* b, const int32_t* slots, const int64_t* ids, const int32_t* offsets, int32_t n,
+                          int32_t* accepted, int64_t* next_token) {
+    if (!b || !slots || !ids || !offsets || !accepted || !next_token) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    std::vector<StepRow> table;
+    if (int rc = nlb_prompt_table(b, "NLLB batch verify", slots, ids, offsets, n, 2, table)) return rc;
+    const wlk_nllb_dims& D = b->m->D;
+    const int total = offsets[n];
+    NlVerifySlots sl;
+    sl.n = n;
+    for (int i = 0; i < n; ++i) { sl.row0[i] = offsets[i]; sl.P[i] = offsets[i + 1] - offsets[i]; }
+    return nl_guarded([&]() {
+        WLK_HIP(hipSetDevice(b->m->device));
+        WLK_HIP(hipStreamSynchronize(b->stream));
+        if (!b->vres_host) {                 // (the last of the three: a failed allocation is tried again by the next call)
+            b->vlogits = b->alloc<float>((size_t)kNlVerifyChunk * D.vocab);
+            b->vparts = b->alloc<NlPick>((size_t)b->n_slots * D.max_tgt * kNlPickSlices);
+            b->mapped(2 * kNlBatchMaxRows, &b->vres_host, &b->vres_dev);
+        }
+        for (int i = 0; i < n; ++i) b->vres_host[2 * i] = -1;
+        nlb_prompt_upload(b, table);
+        nlb_prefill_chain(b, total);
+        // read-out: row 0 of a slot predicts the forced token and is projected with the rest (skipping it would cost a gather)
+        const LaunchCtx c = b->ctx();
+        for (int r0 = 0; r0 < total; r0 += kNlVerifyChunk) {
+            const int rows = std::min(kNlVerifyChunk, total - r0);
+            const size_t at = (size_t)r0 * D.d_model;
+            nl_logits(c, b->m, /*fused=*/false, b->pws.x + at, rows, 1, b->pws.h + at, b->vlogits);
+            launch_nllb_verify_pick_rows(c, b->vlogits, D.vocab, rows, b->vparts + (size_t)r0 * kNlPickSlices);
+        }
+        {
+            KernelScope ks(c, "nllb_verify_accept");
+            hipLaunchKernelGGL(nllb_verify_accept_kernel, dim3(n), dim3(64), 0, b->stream, b->vparts, b->prefill_rows, sl, b->vres_dev);
+            WLK_HIP(hipGetLastError());
+        }
+        WLK_HIP(hipStreamSynchronize(b->stream));
+        for (int i = 0; i < n; ++i)          // (before any slot changes)
+            if (b->vres_host[2 * i] < 0 || b->vres_host[2 * i] > sl.P[i] - 2)
+                throw std::runtime_error("NLLB batch verify: the accept kernel left no result");
+        b->verify_passes += 1;
+        for (int i = 0; i < n; ++i) {
+            const int k = b->vres_host[2 * i];
+            accepted[i] = k;
+            next_token[i] = b->vres_host[2 * i + 1];
+            NlBatchSlot& s = b->slots[slots[i]];
+            s.self_len = 2 + k;              // the rows behind it hold the rejected draft: a step at o reads below o and writes o
+            s.logits_row = -1;
+            s.align_row = -1;
+            b->verify_draft += (uint64_t)(sl.P[i] - 2);
+            b->verify_accepted += (uint64_t)k;
+        }
+        return WLK_OK;
+    });
+}
+
+int wlk_nllb_batch_verify_stats(wlk_nllb_batch* b, uint64_t* passes, uint64_t* draft_tokens, uint64_t* accepted_tokens) {
+    if (!b || !passes || !draft_tokens || !accepted_tokens) return nl_fail(WLK_ERR_ARG, "NULL argument");
+    *passes = b->verify_passes;
+    *draft_tokens = b->verify_draft;
+    *accepted_tokens = b->verify_accepted;
+    return WLK_OK;
 }
 
 int wlk_nllb_batch_release(wlk_nllb_batch* b, int32_t slot) {

@@ -55,6 +55,19 @@ void launch_nllb_align_readout_rows(const LaunchCtx& ctx, const float* probs, in
                                     int n_rows, const StepRow* rows, const int* ctl, float* p_out, int* pos, float* prob,
                                     float* mass);
 
+// Draft verification (nllb_batch.hip): the greedy pick of every row of logits [n_rows][n_vocab] in ONE read of the
+// row.  A row is split over kNlPickSlices workgroups; each leaves its (value, id) best - order (value descending, id
+// ascending), (-inf, INT_MAX) for a slice without elements - in parts [n_rows][kNlPickSlices].  nl_pick_fold (below) folds a
+// row's partials; launch_nllb_verify_fold_rows does that for n_rows rows, one lane per row: picks[r] and
+// match[r] = (picks[r] == targets[r]) - the diagnostics' route, the accept kernel folds for itself.
+constexpr int kNlPickSlices = 32;
+struct NlPick {
+    float v;
+    int i;
+};
+void launch_nllb_verify_pick_rows(const LaunchCtx& ctx, const float* logits, int n_vocab, int n_rows, NlPick* parts);
+void launch_nllb_verify_fold_rows(const LaunchCtx& ctx, const NlPick* parts, int n_rows, const int* targets, int* picks, int* match);
+
 }  // namespace wlk
 
 struct wlk_nllb {

@@ -394,6 +394,30 @@ class HipNllbBatch:
         _lib.check(self.lib.wlk_nllb_batch_prefill(self._h, sl.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p),
                                                    off.ctypes.data_as(C.c_void_p), sl.size))
 
+    def verify(self, slots: Sequence[int], token_lists: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
+        """Draft verification of freshly encoded slots in ONE stacked decoder pass (wlk_nllb_batch_verify, DESIGN.md section
+        31): ``token_lists[i] = [decoder start, forced first token, d_0 .. d_{n-1}]`` -> ``(accepted int32 [len(slots)],
+        next_token int64 [len(slots)])``: the greedy picks agree with the first ``accepted[i]`` draft tokens, and
+        ``next_token[i]`` is the pick behind them.  The slot then holds ``2 + accepted[i]`` target tokens and continues with
+        ``step`` feeding ``next_token[i]``."""
+        if len(slots) != len(token_lists):
+            raise ValueError("verify: one token list per slot")
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        arrs = [np.asarray(t, dtype=np.int64).reshape(-1) for t in token_lists]
+        off = np.zeros(len(arrs) + 1, np.int32)
+        off[1:] = np.cumsum([a.size for a in arrs])
+        ids = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros(0, np.int64))
+        accepted, nxt = np.empty(sl.size, np.int32), np.empty(sl.size, np.int64)
+        _lib.check(self.lib.wlk_nllb_batch_verify(self._h, sl.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p),
+                                                  off.ctypes.data_as(C.c_void_p), sl.size, accepted.ctypes.data_as(C.c_void_p),
+                                                  nxt.ctypes.data_as(C.c_void_p)))
+        return accepted, nxt
+
+    def verify_stats(self) -> Dict[str, int]:
+        passes, draft, accepted = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _lib.check(self.lib.wlk_nllb_batch_verify_stats(self._h, C.byref(passes), C.byref(draft), C.byref(accepted)))
+        return {"passes": int(passes.value), "draft_tokens": int(draft.value), "accepted_tokens": int(accepted.value)}
+
     def step_align(self, slots: Sequence[int], tokens: Sequence[int], k: int, lo: Sequence[int], hi: Sequence[int],
                    limit: Sequence[int]):
         """``step`` + the alignment read-out of every row, one graph replay (wlk_nllb_batch_step_align) -> ``(logprobs
@@ -577,11 +601,29 @@ def _per_sentence(value, n: int, what: str) -> list:
     return [None if value is None else int(value)] * n
 
 
+def clamp_draft(prev_ids: Optional[Sequence[int]], max_new_tokens: int, max_tgt: Optional[int], eos: int) -> List[int]:
+    """The draft ``batch.verify`` may be handed for a sentence whose previous result of :func:`generate` was ``prev_ids``
+    (``[start, forced, y...]``, possibly ending in ``</s>``): ``prev_ids[2:]`` cut in front of its first ``</s>`` and limited to
+    ``min(max_new_tokens - 3, max_tgt - 3)`` tokens (``max_tgt`` ``None``: no context limit) - the token behind an accepted
+    draft then lands at output index <= ``max_length - 2``, never where the forced-EOS rule or the length stop decides, and
+    ``2 + len(draft) <= max_tgt - 1`` is the prefill's capacity rule.  ``[]`` = no draft."""
+    if prev_ids is None:
+        return []
+    d = [int(t) for t in list(prev_ids)[2:]]
+    if eos in d:
+        d = d[:d.index(eos)]
+    room = int(max_new_tokens) - 3
+    if max_tgt is not None:
+        room = min(room, int(max_tgt) - 3)
+    return d[:room] if room >= 1 else []
+
+
 def generate_batch(batch, sources: Sequence[Sequence[int]],
                    forced_bos_token_ids: Union[None, int, Sequence[Optional[int]]] = None, *,
                    max_new_tokens: Union[int, Sequence[int]] = 199, forced_eos_token_id: Optional[int] = None,
                    more: Optional[Callable[[], Optional[Iterable[tuple]]]] = None,
-                   done: Optional[Callable[[object, List[int]], None]] = None) -> List[List[int]]:
+                   done: Optional[Callable[[object, List[int]], None]] = None,
+                   drafts: Optional[Sequence[Optional[Sequence[int]]]] = None) -> List[List[int]]:
     """Greedy :func:`generate` for any number of sentences through the slots of one batch (``HipNllbBatch``, or anything with
     its ``n_slots`` / ``encode`` / ``step`` / ``release``): ``model.generate`` on a padded batch in ``transformers``, sentence
     by sentence the same ids as :func:`generate` alone.  ``forced_bos_token_ids`` and ``max_new_tokens`` are scalars or one
@@ -595,15 +637,36 @@ def generate_batch(batch, sources: Sequence[Sequence[int]],
     ``more`` is polled once per step (and once more before the pass would end): it may return further
     ``(source, forced_bos, max_new_tokens, ticket)`` work, which queues behind what is already waiting; the ids of such a
     sentence go to ``done(ticket, ids)`` as soon as it ends.  This is how a serving layer joins a running pass.  Returns
-    the ids of ``sources`` in input order, each including the start token."""
+    the ids of ``sources`` in input order, each including the start token.
+
+    ``drafts``: one entry (or ``None``) per sentence - a previous result of this sentence's
+    translation, e.g. of the same sentence a word shorter; ``more`` may append one as a fifth element.  The sentences admitted
+    together that have a usable draft (:func:`clamp_draft`), a forced BOS and a batch with ``verify`` share ONE
+    ``batch.verify`` behind their ``encode``: such a sentence starts as ``[start, bos] + draft[:accepted] + [next]`` and joins
+    the following ``step`` (or ends there on ``</s>``).  Greedy decoding is a function of the tokens in front of a position,
+    so a draft changes how many tokens one pass yields, never which.  A batch without ``verify`` ignores drafts."""
     cfg = batch.model.cfg
     eos, start = cfg.eos_token_id, cfg.decoder_start_token_id
     n = len(sources)
     bos, limits = _per_sentence(forced_bos_token_ids, n, "forced_bos_token_ids"), _per_sentence(max_new_tokens, n, "max_new_tokens")
+    if drafts is not None and len(drafts) != n:
+        raise ValueError("generate_batch: drafts must hold one entry (or None) per sentence")
     results: List[Optional[List[int]]] = [None] * n
-    waiting = [dict(src=sources[i], bos=bos[i], max_new=limits[i], index=i, ticket=None) for i in range(n)]
+    waiting = [dict(src=sources[i], bos=bos[i], max_new=limits[i], index=i, ticket=None,
+                    draft=None if drafts is None else drafts[i]) for i in range(n)]
     free = list(range(batch.n_slots))
     running: Dict[int, dict] = {}                      # slot -> sentence, in admission order
+    can_verify = hasattr(batch, "verify")
+    max_tgt = getattr(getattr(batch.model, "cdims", None), "max_tgt", None)
+
+    def usable_draft(item) -> List[int]:
+        if not can_verify or item.get("draft") is None or item["bos"] is None:
+            return []
+        d = clamp_draft(item["draft"], item["max_new"], max_tgt, eos)
+        for j, t in enumerate(d):                      # what the library would refuse ends the draft, not the pass
+            if t < 0 or t >= cfg.vocab_size or t == cfg.pad_token_id:
+                return d[:j]
+        return d
 
     def finish(item, slot=None):
         if slot is not None:
@@ -617,8 +680,9 @@ def generate_batch(batch, sources: Sequence[Sequence[int]],
 
     while True:
         if more is not None:
-            for src, fb, mn, ticket in (more() or ()):
-                waiting.append(dict(src=src, bos=None if fb is None else int(fb), max_new=int(mn), index=None, ticket=ticket))
+            for src, fb, mn, ticket, *rest in (more() or ()):
+                waiting.append(dict(src=src, bos=None if fb is None else int(fb), max_new=int(mn), index=None, ticket=ticket,
+                                    draft=rest[0] if rest else None))
         admitted = []
         while waiting and (free or waiting[0]["max_new"] <= 0):
             item = waiting.pop(0)
@@ -630,6 +694,14 @@ def generate_batch(batch, sources: Sequence[Sequence[int]],
         if admitted:
             batch.encode([s for s, _ in admitted], [it["src"] for _, it in admitted])
             running.update(admitted)
+            drafted = [(s, it, d) for s, it, d in ((s, it, usable_draft(it)) for s, it in admitted) if d]
+            if drafted:
+                accepted, nxt = batch.verify([s for s, _, _ in drafted], [[start, it["bos"]] + d for _, it, d in drafted])
+                for (slot, item, d), k, t in zip(drafted, accepted, nxt):
+                    item["out"] = [start, item["bos"]] + d[:int(k)] + [int(t)]
+                    if int(t) == eos:                  # (never the length stop: clamp_draft keeps len(out) < max_length)
+                        del running[slot]
+                        finish(item, slot)
         if not running:
             if waiting:
                 continue

@@ -104,6 +104,13 @@ def _common_prefix(a: Sequence[str], b: Sequence[str]) -> int:
     return n
 
 
+def resolve_draft(draft: Optional[bool]) -> bool:
+    """``HipNllbTranslationModel(draft=...)``: an explicit value wins; ``None`` reads ``WLK_NLLB_DRAFT`` (default off)."""
+    if draft is None:
+        return os.environ.get("WLK_NLLB_DRAFT", "0").strip() == "1"
+    return bool(draft)
+
+
 def resolve_stack(stack: Optional[int]) -> int:
     """``HipNllbTranslationModel(stack=...)``: an explicit value wins; ``None`` reads ``WLK_NLLB_STACK`` (default 0 = off)."""
     if stack is None:
@@ -132,13 +139,17 @@ class NllbStacker:
         self.passes = 0                            # generate_batch passes run (bench / tests)
         self.sentences = 0
 
-    def translate_many(self, requests: Sequence[Tuple[Sequence[int], Optional[int], int]]) -> List[List[int]]:
-        """``requests``: ``(source ids, forced_bos_token_id, max_new_tokens)`` per sentence -> their ids, in order."""
-        return self._submit([(list(src), bos, int(max_new)) for src, bos, max_new in requests])
+    def translate_many(self, requests: Sequence[tuple]) -> List[List[int]]:
+        """``requests``: ``(source ids, forced_bos_token_id, max_new_tokens)`` per sentence -> their ids, in order.  A request
+        may carry a fourth element, the draft ``nllb.generate_batch`` verifies (a previous result of the sentence, or ``None``)."""
+        return self._submit([(list(req[0]), req[1], int(req[2]), *req[3:4]) for req in requests])
 
     def _drive(self, more, done) -> None:
         """one pass over the batch: returns when the batch is empty and ``more`` has nothing left"""
-        nllb.generate_batch(self.batch, [], more=more, done=done)
+        def more_in_order():                       # the queue keeps the ticket last; generate_batch takes the draft behind it
+            return [it if len(it) == 4 else (it[0], it[1], it[2], it[4], it[3]) for it in (more() or ())]
+
+        nllb.generate_batch(self.batch, [], more=more_in_order, done=done)
 
     def _submit(self, requests: Sequence[tuple]) -> list:
         """queues ``requests`` (the pass's request tuples, without ticket) and waits for their outcomes, driving the pass if
@@ -224,7 +235,8 @@ class HipNllbTranslationModel:
 
     def __init__(self, model: nllb.HipNllbModel, tokenizer: Any, num_beams: int = 1, max_new_tokens: int = 199,
                  max_source_tokens: int = 200, stack: Optional[int] = None, policy: str = "local_agreement", threshold: int = 2,
-                 alignment_heads: Optional[Sequence[Tuple[int, int]]] = None, hypothesis_tail: bool = False):
+                 alignment_heads: Optional[Sequence[Tuple[int, int]]] = None, hypothesis_tail: bool = False,
+                 draft: Optional[bool] = None):
         """``policy="alignatt"`` (opt-in, greedy only): sessions are :class:`HipAlignAttTranslation`; a target token whose
         source position lies within ``threshold`` tokens of the end of the committed source is held back;
         ``alignment_heads`` = ``(decoder layer, head)`` pairs, ``None`` = ``nllb.default_alignment_heads`` - neither that
@@ -233,7 +245,12 @@ class HipNllbTranslationModel:
 
         ``policy="alignatt"`` with ``stack=n`` (or ``WLK_NLLB_STACK=n``) stacks: the model owns one batch of n slots with
         the alignment heads set and a :class:`NllbAlignAttStacker`, and the sessions submit their updates to it instead of
-        owning a device session.  (Before DESIGN.md section 22 this combination silently ran unstacked.)"""
+        owning a device session.  (Before DESIGN.md section 22 this combination silently ran unstacked.)
+
+        ``draft`` (opt-in; ``None`` reads ``WLK_NLLB_DRAFT``, default off): every session hands the
+        ids of the open sentence's previous hypothesis to its next update as a draft, verified in one stacked decoder pass.
+        Needs ``stack >= 1``, ``num_beams == 1`` and ``policy="local_agreement"`` (``ValueError`` otherwise); the texts are
+        those of ``draft=False``."""
         if policy not in ("local_agreement", "alignatt"):
             raise ValueError("policy must be 'local_agreement' or 'alignatt'")
         if policy == "alignatt" and int(num_beams) != 1:
@@ -249,6 +266,11 @@ class HipNllbTranslationModel:
         # opt-in: one batch of `stack` slots shared by every session (greedy decoding only; beams keep their own sessions)
         self.stack = resolve_stack(stack) if self.num_beams == 1 else 0
         self.batch = model.new_batch(self.stack) if self.stack else None
+        self.draft = resolve_draft(draft)
+        if self.draft and not (self.stack >= 1 and self.num_beams == 1 and policy == "local_agreement"):
+            if self.batch is not None:
+                self.batch.close()
+            raise ValueError("draft verification needs stack >= 1, num_beams = 1 and policy='local_agreement'")
         self.stacker = None
         if self.batch is not None and policy == "alignatt":
             heads = self.alignment_heads if self.alignment_heads is not None else nllb.default_alignment_heads(model.cfg)
@@ -326,6 +348,8 @@ class HipOnlineTranslation:
         self._closed: List[_Segment] = []          # sentences that ended (punctuation) and await their final translation
         self._validated_words: List[str] = []      # target words of the open segment already handed out
         self._previous: List[str] = []             # previous hypothesis of the open segment (target words)
+        self._previous_ids: Optional[List[int]] = None   # ... and its ids, the next update's draft (draft serving only)
+        self._hyp_ids: Optional[List[int]] = None  # draft serving: the ids of this call's hypothesis of the open segment
         self._buffer_words: List[str] = []
         self._dirty = False
         self._last_end: Optional[float] = None     # end time of the last validated piece
@@ -362,6 +386,7 @@ class HipOnlineTranslation:
             pieces += words[keep:]
             end = seg.end
             self._validated_words, self._previous, self._buffer_words = [], [], []
+            self._previous_ids = None
         self._closed = []
         if self._segment.tokens and self._dirty:      # the open sentence: local agreement of two successive hypotheses
             hyp = self._translate(self._segment)
@@ -376,6 +401,7 @@ class HipOnlineTranslation:
                 self._validated_words = hyp[:agreed]
                 end = self._segment.end
             self._previous = hyp
+            self._previous_ids = self._hyp_ids
             self._buffer_words = hyp[len(self._validated_words):] if hyp[:len(self._validated_words)] == self._validated_words else []
         self._dirty = False
         new = None
@@ -399,6 +425,7 @@ class HipOnlineTranslation:
             self._last_end = validated.end
         self._segment = _Segment()
         self._validated_words, self._previous, self._buffer_words = [], [], []
+        self._previous_ids = None
         self._dirty = False
         return validated, TimedText()
 
@@ -423,9 +450,14 @@ class HipOnlineTranslation:
 
     def _translate_many(self, segs: Sequence[_Segment]) -> List[List[str]]:
         m = self.shared
-        outs = m.stacker.translate_many([(m.encode(seg.text(), self.source_language), self.target_id, m.max_new_tokens)
-                                         for seg in segs])
+        requests = [(m.encode(seg.text(), self.source_language), self.target_id, m.max_new_tokens) for seg in segs]
+        if getattr(m, "draft", False) and segs:
+            # the open sentence's last hypothesis is the draft of whatever continues that sentence: its next update (the
+            # open segment itself) or, when punctuation closed it, its final translation (the first closed segment)
+            requests[0] = (*requests[0], self._previous_ids)
+        outs = m.stacker.translate_many(requests)
         self.translations += len(outs)
+        self._hyp_ids = list(outs[-1]) if getattr(m, "draft", False) and segs and segs[-1] is self._segment else None
         return [m.decode(out).split() for out in outs]
 
     def _translate(self, seg: _Segment) -> List[str]:
