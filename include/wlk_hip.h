@@ -805,6 +805,16 @@ int wlk_encode_mel(wlk_session* s, const float* mel, int32_t n_frames);
  * needs a new prefill afterwards (its alignment window holds this call's scores). */
 int wlk_find_alignment(wlk_session* s, const int64_t* tokens, int32_t n_tokens, int32_t n_sot, int32_t eot,
                        int32_t num_frames, float qk_scale, float* cost, int8_t* trace, float* token_probs);
+/* The alignment-head survey for a checkpoint without a head table (the reference's scripts/determine_alignment_heads.py:
+ * 125-160) on an encoded beam-1 session: one teacher-forced decoder pass over `tokens` (n_tokens ids, the caller's
+ * [sot sequence, <|notimestamps|>, transcript, <|endoftext|>]), and for EVERY decoder layer, head and token row
+ * peak[l][h][p] = max softmax(scores[:num_frames / 2]) = 1 / sum_f exp(s_f - max s) and frame[l][h][p] = the lowest position
+ * that attains the maximum (NULL: not wanted); [n_text_layer][n_text_head][n_tokens] each.  The scores are never stored.
+ * Does not depend on the model's alignment heads (none set is fine).  WLK_ERR_ARG: NULL argument, beam != 1, n_tokens < 1,
+ * num_frames / 2 outside 1 .. n_audio_ctx, a token id out of range; WLK_ERR_CAPACITY: n_tokens > n_text_ctx; WLK_ERR_STATE:
+ * not encoded, attached to the batch engine, debug or profiling session - all before anything is launched.  The session
+ * needs a new prefill afterwards.  Means and votes over the rows are the host's (whisperlivekit_amd/alignment_heads.py). */
+int wlk_head_survey(wlk_session* s, const int64_t* tokens, int32_t n_tokens, int32_t num_frames, float* peak, int32_t* frame);
 
 /* kernel-tuning probe: average microseconds per launch over `reps` back-to-back launches of one linear layer on
  * device-resident pseudo-random operands (same `force_gemv` meaning as wlk_diag_linear) */
@@ -1118,6 +1128,23 @@ typedef struct wlk_diag_word_align_args {
     int8_t* trace;                  /* in / out, or NULL */
 } wlk_diag_word_align_args;
 int wlk_diag_word_align(const wlk_diag_word_align_args* args);
+/* The kernel of wlk_head_survey (csrc/head_survey.hip) on host data, through its launcher launch_head_survey, unchanged:
+ * q [n_layer][P] rows of ldq floats (the scaled queries, head h in columns 64 h ..), k = Tk rows of ldkv >= n_layer x 2 x 64
+ * n_head floats with layer l's keys at column l x 2 x 64 n_head (the session's cross K|V layout); for every (layer, head,
+ * row) over the first F <= Tk keys peak = 1 / sum_f exp(s_f - max s) and frame = the lowest arg-max, [n_layer][n_head][P]
+ * each (frame may be NULL).  k_splits forces that many key ranges (whole 128-key trips; more than there are trips: clamped);
+ * 0 = the launcher's own choice.  The inputs must be finite in the first F key rows.  Buffers, refusals and
+ * synchronisation as wlk_diag_word_align. */
+typedef struct wlk_diag_head_survey_args {
+    int32_t n_layer, n_head, P, F, Tk, k_splits;
+    int64_t ldq, ldkv;
+    int64_t q_floats, k_floats, peak_floats, frame_n;
+    float* q;                       /* in / out */
+    float* k;                       /* in / out */
+    float* peak;                    /* in / out */
+    int32_t* frame;                 /* in / out, or NULL */
+} wlk_diag_head_survey_args;
+int wlk_diag_head_survey(const wlk_diag_head_survey_args* args);
 /* NLLB's ragged decoder cross-attention (csrc/nllb_batch.hip) on host data through launch_nllb_cross_attention_ragged
  * (align = 0) or launch_nllb_cross_attention_ragged_align (align = 1), unchanged: q [n_rows][d], d = 64 n_head; row r
  * attends to the lengths[r] (1 .. 512) key rows of its block kv + kv_at[r], which holds kv_rows[r] >= lengths[r] rows of

@@ -138,6 +138,13 @@ class DiagWordAlignArgs(C.Structure):
         (n, C.c_void_p) for n in ("ring", "logits", "targets", "w", "cost", "probs", "trace")]
 
 
+class DiagHeadSurveyArgs(C.Structure):
+    """wlk_diag_head_survey_args (include/wlk_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("n_layer", "n_head", "P", "F", "Tk", "k_splits")] + [
+        (n, C.c_int64) for n in ("ldq", "ldkv", "q_floats", "k_floats", "peak_floats", "frame_n")] + [
+        (n, C.c_void_p) for n in ("q", "k", "peak", "frame")]
+
+
 class DiagNllbCrossRaggedArgs(C.Structure):
     """wlk_diag_nllb_cross_ragged_args (include/wlk_hip.h)"""
     _fields_ = [(n, C.c_int32) for n in ("n_rows", "d", "n_head", "align", "n_rank", "align_stride")] + [
@@ -399,6 +406,8 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_enc_op": (cint, [C.POINTER(DiagEncOpArgs)]),
         "wlk_diag_x3_plan": (cint, [cint, cint, cint, cint, cint, C.c_char_p, cint]),
         "wlk_diag_word_align": (cint, [C.POINTER(DiagWordAlignArgs)]),
+        "wlk_diag_head_survey": (cint, [C.POINTER(DiagHeadSurveyArgs)]),
+        "wlk_head_survey": (cint, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
         "wlk_diag_nllb_cross_ragged": (cint, [C.POINTER(DiagNllbCrossRaggedArgs)]),
         "wlk_model_set_cif": (cint, [p, p, cint, C.c_float]),
         "wlk_cif_result": (cint, [p, C.POINTER(CifOut)]),
@@ -439,7 +448,7 @@ EXPORTED_SYMBOLS = (
     "wlk_vad_stream_create", "wlk_vad_stream_reset", "wlk_vad_stream_run", "wlk_vad_stream_state",
     "wlk_vad_stream_destroy", "wlk_vad_stream_run_pcm16", "wlk_vad_group_create", "wlk_vad_group_run",
     "wlk_vad_group_destroy",
-    "wlk_dtw", "wlk_encode_mel", "wlk_log_mel", "wlk_find_alignment",
+    "wlk_dtw", "wlk_encode_mel", "wlk_log_mel", "wlk_find_alignment", "wlk_head_survey",
     "wlk_nllb_arena_floats", "wlk_nllb_tensor_lookup", "wlk_nllb_tensor_name", "wlk_nllb_create", "wlk_nllb_upload",
     "wlk_nllb_finalize", "wlk_nllb_destroy", "wlk_nllb_session_create", "wlk_nllb_session_destroy", "wlk_nllb_encode",
     "wlk_nllb_decode", "wlk_nllb_step", "wlk_nllb_kv_reorder", "wlk_nllb_topk", "wlk_nllb_export", "wlk_nllb_sync",
@@ -454,7 +463,7 @@ EXPORTED_SYMBOLS = (
     "wlk_diag_encoder_attention_x3", "wlk_diag_encoder_attention_x3_time", "wlk_diag_qkv_x3_attention",
     "wlk_diag_select", "wlk_diag_dec_attention", "wlk_diag_topk", "wlk_diag_sf_kernel", "wlk_diag_nllb_align",
     "wlk_diag_nllb_align_rows", "wlk_diag_linear_ex", "wlk_diag_gemv_variant", "wlk_diag_gemm_plan", "wlk_diag_enc_op",
-    "wlk_diag_x3_plan", "wlk_diag_word_align", "wlk_diag_nllb_cross_ragged",
+    "wlk_diag_x3_plan", "wlk_diag_word_align", "wlk_diag_head_survey", "wlk_diag_nllb_cross_ragged",
     "wlk_model_set_cif", "wlk_cif_result", "wlk_diag_cif",
     "wlk_group_create", "wlk_group_destroy", "wlk_group_step_pick", "wlk_group_stats", "wlk_group_export_logits",
     "wlk_diag_pick_rows",

@@ -15,12 +15,13 @@ from __future__ import annotations
 
 import logging
 import re
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
 from . import policy as P
 from .align_att import HipAlignAttStandalone, make_alignatt_class
+from .alignment_heads import resolve_custom_heads
 from .dims import default_alignment_heads, ALIGNMENT_HEADS, MODEL_DIMS, ModelDims
 from .engine import HipWhisperModel
 
@@ -66,7 +67,7 @@ class HipSimulStreamingASR:
     def __init__(self, model_size: str = "base.en", *, device: int = 0, model_path: Optional[str] = None,
                  state_dict=None, dims: Optional[ModelDims] = None, alignment_heads=None,
                  synthetic_seed: Optional[int] = None, hip_model: Optional[HipWhisperModel] = None,
-                 custom_alignment_heads: Optional[Sequence[Tuple[int, int]]] = None,
+                 custom_alignment_heads: Union[None, str, Sequence[Tuple[int, int]]] = None,
                  hw_queues: Optional[int] = None, lora_path: Optional[str] = None, cif_device: Optional[bool] = None,
                  **cfg_kwargs):
         if hw_queues is not None:     # explicit deployment knob (process-wide, see _lib.configure_hw_queues); default: off
@@ -78,7 +79,10 @@ class HipSimulStreamingASR:
         self.use_full_mlx = False
         self.mlx_encoder = self.fw_encoder = self.mlx_model = None
         self.fast_encoder = False
-        heads = custom_alignment_heads or alignment_heads
+        # custom heads: (layer, head) pairs, or the base85 dump the reference's --custom-alignment-heads carries
+        # (whisper/__init__.py:549-551; alignment_heads.py writes one) - decoded once the checkpoint's dims are known
+        def heads_for(d):
+            return resolve_custom_heads(custom_alignment_heads, d) or alignment_heads
         if lora_path is not None and (model_path is None or hip_model is not None):
             # the adapter is merged while the checkpoint is read (checkpoint.load_whisper_checkpoint); a ready model, a state dict
             # or synthetic weights would silently serve the un-adapted model (the reference merges it for every load)
@@ -94,11 +98,11 @@ class HipSimulStreamingASR:
             # simul_whisper/backend.py:530-539 hands load_model the path, not the size name): custom heads, else the pairs the
             # checkpoint carries (MLX exports), else Whisper.__init__'s default - every head of the upper half of the decoder
             # layers.  The per-size tables (dims.ALIGNMENT_HEADS) belong to the official NAMES the reference downloads.
-            self.hip_model = HipWhisperModel.from_state_dict(d, sd, heads or own_heads or default_alignment_heads(d), device)
+            self.hip_model = HipWhisperModel.from_state_dict(d, sd, heads_for(d) or own_heads or default_alignment_heads(d), device)
         elif state_dict is not None:
             d = dims or MODEL_DIMS[model_size]
             self.hip_model = HipWhisperModel.from_state_dict(
-                d, state_dict, heads or ALIGNMENT_HEADS.get(model_size), device)
+                d, state_dict, heads_for(d) or ALIGNMENT_HEADS.get(model_size), device)
         elif synthetic_seed is not None:
             self.hip_model = HipWhisperModel.synthetic(model_size, synthetic_seed, device)
         else:

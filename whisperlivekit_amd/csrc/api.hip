@@ -546,6 +546,7 @@ int wlk_session_destroy(wlk_session* s) {
     if (s->enc_out3) (void)hipFree(s->enc_out3);
     if (s->emlp3) (void)hipFree(s->emlp3);
     if (s->wa_buf) (void)hipFree(s->wa_buf);
+    if (s->survey_buf) (void)hipFree(s->survey_buf);
     if (s->pinned) (void)hipHostFree(s->pinned);
     if (s->dec_stage) (void)hipHostFree(s->dec_stage);
     if (s->audio_stage) (void)hipHostFree(s->audio_stage);
@@ -1042,6 +1043,8 @@ static void enqueue_decode(wlk_session* s, const LaunchCtx& c, int n_rows, int n
     const float scale = std::pow((float)kHeadDim, -0.25f);
     const size_t cache_layer = (size_t)s->beam * ctx_len * d;
     bool scores_dumped = false;   // prefill: raw alignment-head scores are waiting in the window rows
+    // find_alignment and the head survey: the flash branch whatever the row count, its q never folded, no window softmax
+    const bool raw_pass = s->align_raw_scores || s->survey;
     for (int i = 0; i < D.n_text_layer; ++i) {
         const LayerW& L = m->dec_layers[i];
         float* kc = s->kcache[s->kv_cur] + i * cache_layer;
@@ -1076,11 +1079,12 @@ static void enqueue_decode(wlk_session* s, const LaunchCtx& c, int n_rows, int n
         GemmArgs q;
         q.lda = d; q.W = L.xqw; q.bias = L.xqb; q.C = s->dq; q.ldc = d; q.M = R; q.N = d; q.K = d;
         q.flags = kGemmScaleCols; q.scale = scale; q.scale_cols = d;
+        if (s->survey) q.C = s->survey_buf + (size_t)i * R * d;   // head survey: every layer's queries are kept
         // decode steps: the split cross-attention kernel derives its head's query values itself (same arithmetic) - one
         // launch less per layer
         // (the fold leaves s->dq unwritten, so it must never meet the flash branch below, which reads it: that branch is
-        // taken for align_raw_scores - excluded here, not merely "never fed with R == 1 today")
-        const bool fold_xq = fused && R == 1 && !s->debug && !s->align_raw_scores && cross_split_folds_query(d);   // one row: saves a launch; several rows would each re-stream Wq
+        // taken for align_raw_scores and survey - excluded here, not merely "never fed with R == 1 today")
+        const bool fold_xq = fused && R == 1 && !s->debug && !raw_pass && cross_split_folds_query(d);   // one row: saves a launch; several rows would each re-stream Wq
         if (fold_xq) {
         } else if (fused) {
             q.A = s->dx; q.ln_gamma = L.lnxw; q.ln_beta = L.lnxb;
@@ -1093,11 +1097,11 @@ static void enqueue_decode(wlk_session* s, const LaunchCtx& c, int n_rows, int n
         const int* ranks_l = m->n_align > 0 ? m->head_rank + (size_t)i * H : nullptr;
         bool merged_xout = false;
         GemmArgs xo_mg;   // carries the split-form operand description to the out projection when merged_xout
-        if ((R > 8 || s->align_raw_scores) && !s->debug) {
+        if ((R > 8 || raw_pass) && !s->debug) {
             // prefill: MFMA flash kernel shares every K/V tile between 32 query rows
             if (fold_xq) throw std::logic_error("decode: the folded query projection left no q for the flash kernel");
             FlashArgs fa;
-            fa.q = s->dq; fa.ldq = d;
+            fa.q = q.C; fa.ldq = d;
             fa.k = s->cross_kv + (size_t)i * 2 * d; fa.v = fa.k + d; fa.ldkv = (long)D.n_text_layer * 2 * d;
             fa.out = s->datt; fa.ldo = d; fa.Tq = R; fa.Tk = T; fa.n_head = H;
             fa.head_rank = ranks_l; fa.ring = s->ring; fa.ring_row = s->ring_row;
@@ -1154,7 +1158,7 @@ static void enqueue_decode(wlk_session* s, const LaunchCtx& c, int n_rows, int n
         launch_linear(c, xo, "dec_xout");
         transformer_mlp(c, L, s->dx, s->dh, s->dmlp, R, d, "dec_ln2", "dec_fc1", "dec_fc2");
     }
-    if (scores_dumped && m->n_align > 0 && !s->align_raw_scores)     // find_alignment normalises the raw scores itself
+    if (scores_dumped && m->n_align > 0 && !raw_pass)     // find_alignment normalises the raw scores itself, the survey reads none
         launch_ring_softmax(c, s->ring, s->ring_row, s->beam_of_row, m->all_ranks, m->n_align, R, s->ring_rows, s->beam, T);
     // final LayerNorm + vocabulary projection only for the rows the policy reads
     GemmArgs lg;
@@ -1232,7 +1236,7 @@ extern "C++" std::string wlk_prefill_precheck(const wlk_prefill_item& it, const 
     const wlk_dims& D = s->m->D;
     const int P = it.n_tok, d = D.n_text_state;
     if (!s->encoded) return "wlk_decode before wlk_encode";
-    if (s->beam != 1 || s->debug || s->prof_on || s->align_raw_scores) return "not a plain beam-1 session";
+    if (s->beam != 1 || s->debug || s->prof_on || s->align_raw_scores || s->survey) return "not a plain beam-1 session";
     if (it.sot_index < 0 || it.sot_index >= P) return "sot_index out of range";
     if (P > D.n_text_ctx) return "text context exceeded";
     for (int i = 0; i < P; ++i)

@@ -370,6 +370,27 @@ void launch_encoder_attention_x3(const LaunchCtx& ctx, const unsigned short* qk3
 void enc_attention_x3_check(long ldqk, long vt_ld, long ldo, int T, int d, int n_head, bool x3_out);   // throws for what the launcher refuses
 void launch_x3_pack_qkv(const LaunchCtx& ctx, const float* qkv, unsigned short* out, int T, int d, long vt_off, long vt_ld);
 
+// ---- head_survey.hip ---------------------------------------------------------------------------
+// Softmax peak and arg-max frame of every (layer, head, token row) over the first F keys: peak = 1 / sum_f exp(s_f - max s),
+// s_f = q . k_f (the queries arrive scaled), frame = the lowest f that attains the maximum.  Heads are 64 wide.  Plain
+// strides in floats / words, no session: q of layer l, row p, head h at q + l q_layer + p ldq + 64 h; key f at
+// k + l k_layer + f ldkv + 64 h; results at peak / frame + l out_layer + h out_head + p.  Inputs must be finite.
+struct HeadSurveyArgs {
+    const float* q = nullptr;
+    long ldq = 0, q_layer = 0;
+    const float* k = nullptr;
+    long ldkv = 0, k_layer = 0;
+    float* peak = nullptr;
+    int* frame = nullptr;               // or null
+    long out_layer = 0, out_head = 0;
+    float* part = nullptr;              // head_survey_scratch_floats(a) floats; may be null when that is 0
+    int n_layer = 0, n_head = 0, P = 0, F = 0;
+    int k_splits = 0;                   // key ranges (whole 128-key trips, clamped to their count); 0 = the launcher's choice
+};
+void head_survey_check(const HeadSurveyArgs& a);            // throws std::invalid_argument for what the launcher refuses
+int head_survey_splits(const HeadSurveyArgs& a);            // the key ranges the launcher takes
+size_t head_survey_scratch_floats(const HeadSurveyArgs& a);
+void launch_head_survey(const LaunchCtx& ctx, const HeadSurveyArgs& a);
 // ---- word_align.hip ---------------------------------------------------------------------------
 // The device half of find_alignment behind the decoder pass: token probabilities, softmax over the first F frames, z-score
 // over the P token rows, median of 7 + head mean of the rows n_sot .. P - 2, dtw.  n_text = P - n_sot - 2 rows of logits.

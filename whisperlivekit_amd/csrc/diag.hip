@@ -1665,6 +1665,61 @@ int wlk_diag_word_align(const wlk_diag_word_align_args* q) {
     }
 }
 
+/* The alignment-head survey kernel on host data, through launch_head_survey, unchanged (see include/wlk_hip.h).  What a
+ * buffer cannot hold, and what head_survey_check refuses (its own text), is WLK_ERR_ARG before anything is uploaded. */
+int wlk_diag_head_survey(const wlk_diag_head_survey_args* q) {
+    struct Refuse : std::invalid_argument {
+        using std::invalid_argument::invalid_argument;
+    };
+    try {
+        auto need = [](bool ok, const char* what) {
+            if (!ok) throw Refuse(std::string("wlk_diag_head_survey: ") + what);
+        };
+        need(q != nullptr, "null arguments");
+        need(q->q && q->k && q->peak, "null q, k or peak");
+        const int64_t LIM = 1 << 20;
+        need(q->n_layer >= 1 && q->n_layer <= 256 && q->n_head >= 1 && q->n_head <= 256 && q->P >= 1 && q->P <= LIM && q->F >= 1 &&
+                 q->F <= LIM && q->Tk >= 1 && q->Tk <= LIM && q->ldq >= 1 && q->ldq <= (LIM << 4) && q->ldkv >= 1 && q->ldkv <= (LIM << 4),
+             "n_layer, n_head in [1, 256], P, F, Tk in [1, 2^20], ldq, ldkv in [1, 2^24]");
+        need(q->F <= q->Tk, "F beyond the Tk key rows");
+        need(q->k_splits >= 0, "negative key split");
+        const int64_t d = 64 * (int64_t)q->n_head, rows = (int64_t)q->n_layer * q->n_head * q->P;
+        need(q->ldkv >= q->n_layer * 2 * d, "key rows shorter than n_layer x 2 x 64 n_head");
+        HeadSurveyArgs a;
+        a.ldq = q->ldq; a.q_layer = (long)q->P * q->ldq; a.ldkv = q->ldkv; a.k_layer = 2 * d;
+        a.out_head = q->P; a.out_layer = (long)q->n_head * q->P;
+        a.n_layer = q->n_layer; a.n_head = q->n_head; a.P = q->P; a.F = q->F; a.k_splits = q->k_splits;
+        {   // the launcher's own refusals, by its own function, on stand-in pointers
+            float* const base = reinterpret_cast<float*>(uintptr_t(1) << 20);
+            a.q = a.k = base; a.peak = a.part = base; a.frame = q->frame ? reinterpret_cast<int*>(base) : nullptr;
+            head_survey_check(a);
+        }
+        need(((int64_t)q->n_layer * q->P - 1) * q->ldq + d <= q->q_floats, "the query rows lie past q");
+        need(((int64_t)q->Tk - 1) * q->ldkv + (q->n_layer - 1) * 2 * d + d <= q->k_floats, "the Tk key rows lie past k");
+        need(rows <= q->peak_floats, "peak holds fewer than n_layer x n_head x P floats");
+        need(!q->frame || rows <= q->frame_n, "frame holds fewer than n_layer x n_head x P entries");
+        DevBytes Q, K, PEAK, FRAME, PART;
+        Q.mirror(q->q, (size_t)q->q_floats * 4);
+        K.mirror(q->k, (size_t)q->k_floats * 4);
+        PEAK.mirror(q->peak, (size_t)q->peak_floats * 4);
+        if (q->frame) FRAME.mirror(q->frame, (size_t)q->frame_n * 4);
+        PART.alloc(head_survey_scratch_floats(a) * 4);
+        a.q = Q.f(); a.k = K.f(); a.peak = PEAK.f(); a.frame = q->frame ? FRAME.i() : nullptr; a.part = PART.f();
+        LaunchCtx ctx;
+        WLK_HIP(hipDeviceSynchronize());
+        launch_head_survey(ctx, a);
+        WLK_HIP(hipDeviceSynchronize());
+        Q.back(); K.back(); PEAK.back(); FRAME.back();
+        return WLK_OK;
+    } catch (const std::invalid_argument& e) {      // Refuse, or the launcher's own refusal: nothing was uploaded or launched
+        g_diag_error = e.what();
+        return WLK_ERR_ARG;
+    } catch (const std::exception& e) {
+        g_diag_error = e.what();
+        return WLK_ERR_HIP;
+    }
+}
+
 int wlk_diag_x3_plan(int m, int n, int k, int batch, int cus, char* out_text, int cap) {
     if (!out_text || cap < 1) return WLK_ERR_ARG;
     char text[256];

@@ -304,7 +304,12 @@ struct wlk_session {
     bool align_raw_scores = false;
     float* wa_buf = nullptr;
     size_t wa_cap = 0;
-    wlk_engine* engine = nullptr;   // set by wlk_engine_attach: single-token steps run batched with the other attached sessions
+    // alignment-head survey (head_survey.hip): while set, the prefill behaves as under align_raw_scores and layer i's scaled
+    // cross-attention queries go to slot i of survey_buf ([n_layer][P][d], then the results; grown on demand)
+    bool survey = false;
+    float* survey_buf = nullptr;
+    size_t survey_cap = 0;
+    wlk_engine* engine = nullptr;  // set by wlk_engine_attach: single-token steps run batched with the other attached sessions
     // CIF head on the device (cif.hip): allocated by the first encode that finds a head on the model (or at creation when
     // it is already set), for any beam count
     float* cif_alpha = nullptr;                                  // [n_audio_ctx]

@@ -198,7 +198,7 @@ static int gate_session(const wlk_group* g, const wlk_session* s, bool listed_be
     if (s->engine) return fail(WLK_ERR_STATE, "window group: the session is attached to the batch engine");
     if (!s->encoded) return fail(WLK_ERR_STATE, std::string(name) + " before an encode");
     if (call == kGateVerify && !s->rules_mask) return fail(WLK_ERR_STATE, "verify before wlk_rules_set");
-    if (call != kGateStep && (s->debug || s->prof_on || (call == kGateVerify && s->align_raw_scores)))
+    if (call != kGateStep && (s->debug || s->prof_on || (call == kGateVerify && (s->align_raw_scores || s->survey))))
         return fail(WLK_ERR_STATE, "window group: not a plain beam-1 session");
     return WLK_OK;
 }

@@ -356,6 +356,19 @@ class HipSession:
             trace.ctypes.data_as(C.POINTER(C.c_int8)), probs.ctypes.data_as(C.POINTER(C.c_float))))
         return trace, probs, cost
 
+    def head_survey(self, tokens: Sequence[int], num_frames: int = 3000) -> Tuple[np.ndarray, np.ndarray]:
+        """One teacher-forced decoder pass over ``tokens`` on the encoded session; for EVERY decoder layer and head the peak
+        of softmax(cross-attention scores[:num_frames // 2]) of every token row and the position that attains it
+        (wlk_head_survey; scripts/determine_alignment_heads.py:149-168 of the reference).
+        -> (peaks [n_text_layer, n_text_head, P] float32, frames [same] int32).  The session needs a new prefill afterwards."""
+        toks = np.ascontiguousarray(np.asarray(tokens, dtype=np.int64).reshape(-1))
+        d = self.model.dims
+        shape = (d.n_text_layer, d.n_text_head, max(len(toks), 1))
+        peaks, frames = np.empty(shape, np.float32), np.empty(shape, np.int32)
+        _lib.check(self.lib.wlk_head_survey(self._h, toks.ctypes.data_as(C.POINTER(C.c_int64)), len(toks), int(num_frames),
+                                            peaks.ctypes.data_as(C.POINTER(C.c_float)), frames.ctypes.data_as(C.POINTER(C.c_int32))))
+        return peaks, frames
+
     def decode(self, tokens: np.ndarray, first: bool, sot_index: int = 0) -> None:
         t = np.ascontiguousarray(tokens, dtype=np.int64)
         if t.ndim != 2:
