@@ -261,6 +261,18 @@ int wlk_diag_dtw_starts(const float* costs, const int64_t* offsets, const int32_
  * masks[mask_of_row[r]] and p[r]; n in 1..8.  Synchronous. */
 int wlk_diag_pick_rows(const float* logits_host, int n_vocab, const uint8_t* masks_host, int n_masks, const int32_t* mask_of_row,
                        const wlk_pick_params* p /* [n] */, int n, int32_t* tokens_out, float* logprobs_out);
+/* Diagnostic (tests): the one-row pick kernel behind wlk_pick_greedy alone on host data - one logits row [n_vocab], one rule
+ * mask [n_vocab] and one parameter block; token_out [1], logprob_bits_out [1] = the bits of the log-probability.  And the
+ * top-k kernel behind wlk_pick_topk: logits [n_rows][n_vocab] (n_rows in 1..8), one rule mask, p [n_rows], k in 1..8;
+ * logprobs_out / ids_out [n_rows][k], ordered and filled up as wlk_pick_topk's.  WLK_ERR_ARG, before anything is uploaded,
+ * for a NULL pointer, a count out of range or a parameter block wlk_group_step_pick would refuse.  On the device the logits
+ * and the masks of these two entries, of wlk_diag_pick_rows and of wlk_diag_draft_pick are followed by one guard entry (+inf,
+ * allowed): a kernel that reads past the last row returns token n_vocab.
+ * Run on the current device; need no model.  Synchronous. */
+int wlk_diag_pick_one(const float* logits_host, int n_vocab, const uint8_t* mask_host, const wlk_pick_params* p, int32_t* token_out,
+                      uint32_t* logprob_bits_out);
+int wlk_diag_pick_topk(const float* logits_host, int n_vocab, const uint8_t* mask_host, const wlk_pick_params* p /* [n_rows] */,
+                       int n_rows, int k, float* logprobs_out /* [n_rows][k] */, int32_t* ids_out /* [n_rows][k] */);
 /* Diagnostic (tests): the device form of the rule transition of wlk_group_run_pick alone - out[i] = the parameter block of
  * the step after tokens[i] was picked under p[i].  Needs no model; any n >= 1.  Synchronous. */
 int wlk_diag_pick_advance(const wlk_pick_params* p /* [n] */, const int32_t* tokens /* [n] */, int n, wlk_pick_params* out /* [n] */);

@@ -9,7 +9,10 @@ Per row, over the logits of the last decode step:
   result       the k best of what is left by (value descending, index ascending), as log_softmax over what is left;
                (-inf, -1) where fewer than k entries are left.
 
-`near_ties` says where float64 itself is too close to call: the only places a float32 implementation may answer differently."""
+`near_ties` says where float64 itself is too close to call: the only places a float32 implementation may answer differently.
+`exact_ties` tells the ties the contract itself decides (gap 0: the lower id ranks first) from those.  `history_state` is
+what ApplyTimestampRules.apply reads from a sampled history, as the fields of wlk_pick_params; `rules_topk_f32` restates the
+contract in float32 numpy, to measure what float32 alone costs against float64 (tests/test_gpu_rules_pick.py)."""
 import numpy as np
 
 NEAR_TIE = 1e-4
@@ -68,8 +71,14 @@ def _row(logits, mask, st, k):
             if lse_ts > text:
                 x[:tb] = -np.inf
                 norm = lse_ts
-    order = np.lexsort((np.arange(V), -x))[:k + 1]          # value descending, index ascending
+    if V > k + 1:                                           # only what reaches the k + 1st largest value (ties with it included)
+        cand = np.flatnonzero(x >= np.partition(x, V - (k + 1))[V - (k + 1)])
+    else:
+        cand = np.arange(V)
+    order = cand[np.lexsort((cand, -x[cand]))][:k + 1]      # value descending, index ascending
     vals = x[order]
+    if len(vals) < k + 1:                                   # a vocabulary of no more than k entries: the ranking ends in -inf
+        vals = np.concatenate([vals, np.full(k + 1 - len(vals), -np.inf)])
     lp = np.full(k, -np.inf)
     ids = np.full(k, -1, np.int32)
     n = min(k, int(np.isfinite(vals[:k]).sum()))
@@ -99,4 +108,78 @@ def near_ties(logits, mask, states, k, eps=NEAR_TIE):
         close = np.nan_to_num(gap, nan=np.inf) <= eps
         out[r, :len(close)] |= close[:k]
         out[r, 1:] |= close[:k - 1]
+    return out
+
+
+def exact_ties(logits, mask, states, k):
+    """[rows, k] bool: entries whose value is bit-equal to a neighbour's in the ranking (the k + 1st included).  Such a tie is
+    no near-tie: float64 and float32 see the same two numbers, and the contract ranks the lower id first."""
+    out = np.zeros((len(states), k), bool)
+    for r in range(len(states)):
+        _, _, _, vals = _row(np.asarray(logits[r]), mask, states[r], k)
+        with np.errstate(invalid="ignore"):
+            same = np.isfinite(vals[:-1]) & (np.diff(vals) == 0.0)
+        out[r, :len(same)] |= same[:k]
+        out[r, 1:] |= same[:k - 1]
+    return out
+
+
+def unplanted_near_ties(logits, mask, states, k, eps=NEAR_TIE):
+    """[rows, k] bool: `near_ties` without the entries that are close to a neighbour ONLY because they equal it: a gap in
+    (0, eps] to either neighbour, or a decision margin within eps, still counts."""
+    out = np.zeros((len(states), k), bool)
+    for r in range(len(states)):
+        _, _, margin, vals = _row(np.asarray(logits[r]), mask, states[r], k)
+        if margin <= eps:
+            out[r] = True
+            continue
+        with np.errstate(invalid="ignore"):
+            gap = np.nan_to_num(np.abs(np.diff(vals)), nan=np.inf)
+        close = (gap <= eps) & (gap > 0.0)
+        out[r, :len(close)] |= close[:k]
+        out[r, 1:] |= close[:k - 1]
+    return out
+
+
+def history_state(history, tb, eot, no_timestamps, max_initial, without_timestamps):
+    """The wlk_pick_params of the pick that follows the sampled tokens `history` (whisper/decoding.py:441-499 reads the whole
+    history: the last token, the one before it, and the last timestamp anywhere in it)."""
+    h = [int(t) for t in history]
+    last_ts = len(h) >= 1 and h[-1] >= tb
+    before_last_ts = len(h) < 2 or h[-2] >= tb
+    stamps = [t for t in h if t >= tb]
+    bound = tb
+    if stamps:
+        bound = stamps[-1] if (last_ts and not before_last_ts) else stamps[-1] + 1
+    return dict(first_step=int(len(h) == 0), without_timestamps=int(bool(without_timestamps)), timestamp_begin=int(tb), eot=int(eot),
+                no_timestamps=int(no_timestamps), ts_mode=0 if not last_ts else (1 if before_last_ts else 2), ts_bound=int(bound),
+                max_initial=int(max_initial))
+
+
+def rules_topk_f32(logits, mask, states, ids):
+    """The contract in float32 numpy, evaluated at the float64 ranking `ids` [rows, k]: max, sum exp(x - max) and
+    (x - max) - log(sum) in float32, the decision as logsumexp(timestamps) > max(text).  -> log-probabilities [rows, k]
+    float32 (-inf where ids is -1).  Only a yardstick for the error float32 arithmetic has on a case."""
+    f = np.float32
+    out = np.full(np.shape(ids), -np.inf, f)
+    for r in range(len(states)):
+        st, row = states[r], np.asarray(logits[r], f)
+        x = np.where(allowed(mask, st, row.shape[0]), row, f(-np.inf))
+        tb = st["timestamp_begin"]
+
+        def fold(v):
+            m = v.max() if v.size else f(-np.inf)
+            if not np.isfinite(m):
+                return m, f(0)
+            return m, np.exp(v - m, dtype=f).sum(dtype=f)
+        m_all, s_all = fold(x)
+        mx, logsum = m_all, np.log(s_all, dtype=f)
+        if not st["without_timestamps"]:
+            m_ts, s_ts = fold(x[tb:])
+            text = x[:tb].max() if tb > 0 else f(-np.inf)
+            if np.isfinite(m_ts) and f(m_ts + np.log(s_ts, dtype=f)) > text:
+                mx, logsum = m_ts, np.log(s_ts, dtype=f)
+        for j, v in enumerate(np.asarray(ids[r])):
+            if v >= 0:
+                out[r, j] = f(f(x[v] - mx) - logsum)
     return out

@@ -259,6 +259,8 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_group_stats": (cint, [p, C.POINTER(u64), C.POINTER(u64)]),
         "wlk_group_export_logits": (cint, [p, cint, p, u64, C.POINTER(u64)]),
         "wlk_diag_pick_rows": (cint, [p, cint, p, cint, p, p, cint, p, p]),
+        "wlk_diag_pick_one": (cint, [p, cint, p, p, p, p]),
+        "wlk_diag_pick_topk": (cint, [p, cint, p, p, cint, cint, p, p]),
         "wlk_group_find_alignment": (cint, [p, C.POINTER(AlignWindow), cint]),
         "wlk_group_align_fits": (cint, [p, i32, i32, C.POINTER(i32)]),
         "wlk_diag_dtw_starts": (cint, [p, p, p, p, cint, p, p]),
@@ -466,7 +468,7 @@ EXPORTED_SYMBOLS = (
     "wlk_diag_x3_plan", "wlk_diag_word_align", "wlk_diag_head_survey", "wlk_diag_nllb_cross_ragged",
     "wlk_model_set_cif", "wlk_cif_result", "wlk_diag_cif",
     "wlk_group_create", "wlk_group_destroy", "wlk_group_step_pick", "wlk_group_stats", "wlk_group_export_logits",
-    "wlk_diag_pick_rows",
+    "wlk_diag_pick_rows", "wlk_diag_pick_one", "wlk_diag_pick_topk",
     "wlk_group_find_alignment", "wlk_group_align_fits", "wlk_diag_dtw_starts",
     "wlk_group_run_pick", "wlk_diag_pick_advance",
     "wlk_group_verify", "wlk_group_verify_fits", "wlk_diag_draft_pick",

@@ -694,6 +694,22 @@ int wlk_group_export_logits(wlk_group* g, int row, float* host, uint64_t capacit
     });
 }
 
+// The logits and the masks of the pick entries below (wlk_diag_pick_rows, _pick_one, _pick_topk, _draft_pick) are followed by
+// one guard entry each - a logit of +inf under a mask byte that allows it: a sweep that reads one entry past the last row
+// picks token n_vocab, which no reference names.
+static void upload_guarded(DevBytes& d, const void* host, size_t bytes, const void* guard, size_t guard_bytes) {
+    d.alloc(bytes + guard_bytes);
+    WLK_HIP(hipMemcpy(d.p, host, bytes, hipMemcpyHostToDevice));
+    WLK_HIP(hipMemcpy(d.p + bytes, guard, guard_bytes, hipMemcpyHostToDevice));
+}
+static void upload_guarded_row(DevBytes& logits, const float* logits_host, size_t n_floats, DevBytes& mask, const uint8_t* mask_host,
+                               size_t mask_bytes) {
+    const float inf = INFINITY;
+    const uint8_t allow = 0;
+    upload_guarded(logits, logits_host, n_floats * sizeof(float), &inf, sizeof(float));
+    upload_guarded(mask, mask_host, mask_bytes, &allow, 1);
+}
+
 // Tests: rules_pick_rows_kernel on logits rows, rule masks (bit 0 = always suppressed, bit 1 = blank, as wlk_rules_set
 // builds them) and parameters given from the host - so that one and the same row can be put through it and through
 // wlk_pick_greedy.  Row r uses masks[mask_of_row[r]].
@@ -706,7 +722,8 @@ int wlk_diag_pick_rows(const float* logits_host, int n_vocab, const uint8_t* mas
             return fail(WLK_ERR_ARG, "pick rows: mask index or rule parameters out of range");
     return guarded([&]() {
         const size_t V = (size_t)n_vocab;
-        DevBytes logits(V * n * sizeof(float), logits_host), masks(V * n_masks, masks_host), out(8 * n);
+        DevBytes logits, masks, out(8 * n);
+        upload_guarded_row(logits, logits_host, V * n, masks, masks_host, V * n_masks);
         PickRowEntry host[kGroupMaxRows];
         for (int r = 0; r < n; ++r) host[r] = PickRowEntry{masks.as<unsigned char>() + V * mask_of_row[r], pick_rules_of(p[r])};
         DevBytes table(sizeof(PickRowEntry) * n, host);
@@ -718,6 +735,53 @@ int wlk_diag_pick_rows(const float* logits_host, int n_vocab, const uint8_t* mas
             tokens_out[r] = res[2 * r];
             std::memcpy(&logprobs_out[r], &res[2 * r + 1], 4);
         }
+        return WLK_OK;
+    });
+}
+
+// Tests: rules_pick_kernel, the one-row pick behind wlk_pick_greedy, on one host logits row, one rule mask and one parameter
+// block.  logprob_bits_out receives the bits of the float the kernel wrote.
+int wlk_diag_pick_one(const float* logits_host, int n_vocab, const uint8_t* mask_host, const wlk_pick_params* p, int32_t* token_out,
+                      uint32_t* logprob_bits_out) {
+    if (!logits_host || !mask_host || !p || !token_out || !logprob_bits_out) return fail(WLK_ERR_ARG, "NULL argument");
+    if (n_vocab < 1) return fail(WLK_ERR_ARG, "pick one: n_vocab >= 1");
+    if (!pick_params_ok(*p, n_vocab)) return fail(WLK_ERR_ARG, "pick one: rule parameters out of range");
+    return guarded([&]() {
+        const size_t V = (size_t)n_vocab;
+        DevBytes logits, mask, out(8);
+        upload_guarded_row(logits, logits_host, V, mask, mask_host, V);
+        launch_rules_pick(LaunchCtx{nullptr, nullptr}, logits.f(), n_vocab, mask.as<unsigned char>(), pick_rules_of(*p), out.i(),
+                          reinterpret_cast<float*>(out.i() + 1));
+        int res[2];
+        WLK_HIP(hipStreamSynchronize(nullptr));
+        out.back(res);
+        token_out[0] = res[0];
+        std::memcpy(logprob_bits_out, &res[1], 4);
+        return WLK_OK;
+    });
+}
+
+// Tests: rules_topk_kernel, the rules + log-softmax + k best behind wlk_pick_topk, on host logits [n_rows][n_vocab], one rule
+// mask and one parameter block per row.  logprobs_out / ids_out [n_rows][k].
+int wlk_diag_pick_topk(const float* logits_host, int n_vocab, const uint8_t* mask_host, const wlk_pick_params* p, int n_rows, int k,
+                       float* logprobs_out, int32_t* ids_out) {
+    if (!logits_host || !mask_host || !p || !logprobs_out || !ids_out) return fail(WLK_ERR_ARG, "NULL argument");
+    if (n_rows < 1 || n_rows > kMaxPickRows || k < 1 || k > 8 || n_vocab < 1) return fail(WLK_ERR_ARG, "pick top-k: 1..8 rows, k in [1, 8]");
+    for (int r = 0; r < n_rows; ++r)
+        if (!pick_params_ok(p[r], n_vocab)) return fail(WLK_ERR_ARG, "pick top-k: rule parameters out of range");
+    return guarded([&]() {
+        const size_t V = (size_t)n_vocab, n_out = (size_t)n_rows * k;
+        DevBytes logits, mask, out(8 * n_out);   // [log-probs | ids]
+        upload_guarded_row(logits, logits_host, V * n_rows, mask, mask_host, V);
+        PickRulesRows rules{};
+        for (int r = 0; r < n_rows; ++r) rules.r[r] = pick_rules_of(p[r]);
+        launch_rules_topk(LaunchCtx{nullptr, nullptr}, logits.f(), n_vocab, n_rows, mask.as<unsigned char>(), rules, k, out.f(),
+                          out.i() + n_out);
+        std::vector<int> host(2 * n_out);
+        WLK_HIP(hipStreamSynchronize(nullptr));
+        out.back(host.data());
+        std::memcpy(logprobs_out, host.data(), 4 * n_out);
+        std::memcpy(ids_out, host.data() + n_out, 4 * n_out);
         return WLK_OK;
     });
 }
@@ -755,8 +819,8 @@ int wlk_diag_draft_pick(const float* logits_host, int n_vocab, const uint8_t* ma
     if (!pick_params_ok(*p0, n_vocab)) return fail(WLK_ERR_ARG, "draft pick: rule parameters out of range");
     return guarded([&]() {
         const size_t V = (size_t)n_vocab, n_pos = (size_t)n_draft + 1;
-        DevBytes logits(V * n_pos * sizeof(float), logits_host), mask(V, mask_host), drafts(sizeof(int) * (size_t)n_draft, draft),
-            picks((n_pos * 3 + 4) * sizeof(int));          // [picks n_pos x 3 | result 4]
+        DevBytes logits, mask, drafts(sizeof(int) * (size_t)n_draft, draft), picks((n_pos * 3 + 4) * sizeof(int));   // [picks n_pos x 3 | result 4]
+        upload_guarded_row(logits, logits_host, V * n_pos, mask, mask_host, V);
         launch_draft_pick(LaunchCtx{nullptr, nullptr}, logits.f(), n_vocab, mask.as<unsigned char>(), pick_rules_of(*p0), drafts.i(),
                           n_draft, ended ? 1 : 0, picks.i(), picks.i() + n_pos * 3, nullptr);
         WLK_HIP(hipStreamSynchronize(nullptr));

@@ -711,6 +711,39 @@ def pick_rows(logits: np.ndarray, masks: np.ndarray, mask_of_row: Sequence[int],
     return out, lp
 
 
+def pick_one(logits: np.ndarray, mask: np.ndarray, state: dict) -> Tuple[int, np.float32]:
+    """wlk_diag_pick_one (tests): the one-row pick kernel of ``HipSession.pick_greedy`` on a host logits row [V], one rule
+    mask [V] uint8 and one rule state.  -> (token, log-probability with the kernel's bits)."""
+    lib = _lib.load()
+    lg = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1)
+    mk = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+    if mk.size != lg.size:
+        raise ValueError("pick_one: a logits row [V] and a mask [V]")
+    prm = np.asarray([int(state[f]) for f in HipSession.PICK_FIELDS], dtype=np.int32)
+    tok = np.empty(1, np.int32)
+    lp = np.empty(1, np.uint32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.wlk_diag_pick_one(vp(lg), lg.size, vp(mk), vp(prm), vp(tok), vp(lp)))
+    return int(tok[0]), lp.view(np.float32)[0]
+
+
+def pick_topk_rows(logits: np.ndarray, mask: np.ndarray, states: Sequence[dict], k: int) -> Tuple[np.ndarray, np.ndarray]:
+    """wlk_diag_pick_topk (tests): the top-k kernel of ``HipSession.pick_topk`` on host logits [n, V], one rule mask [V]
+    uint8 and one rule state per row.  -> (log-probabilities [n, k], ids [n, k])."""
+    lib = _lib.load()
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    mk = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+    prm = np.asarray([[int(st[f]) for f in HipSession.PICK_FIELDS] for st in states], dtype=np.int32).reshape(-1, 8)
+    if lg.ndim != 2 or lg.shape[0] != prm.shape[0] or mk.size != lg.shape[1]:
+        raise ValueError("pick_topk_rows: logits [n, V], a mask [V] and n states")
+    n, kk = lg.shape[0], max(int(k), 0)
+    lp = np.empty((n, kk), np.float32)
+    ids = np.empty((n, kk), np.int32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.wlk_diag_pick_topk(vp(lg), lg.shape[1], vp(mk), vp(prm), n, int(k), vp(lp), vp(ids)))
+    return lp, ids
+
+
 def draft_pick(logits: np.ndarray, mask: np.ndarray, state: dict, draft: Sequence[int], ended: bool = False
                ) -> Tuple[np.ndarray, np.ndarray, dict]:
     """wlk_diag_draft_pick (tests): the two kernels behind ``HipWindowGroup.verify``'s decoder pass on host logits
