@@ -15,6 +15,7 @@
 
 #include "../../include/wlk_hip.h"
 #include "common.h"
+#include "decoder_chain.h"
 #include "internal.h"
 
 namespace wlk {
@@ -714,28 +715,6 @@ int wlk_audio_len(wlk_session* s, int* n) {
 }
 
 // ---- encode ---------------------------------------------------------------------------------
-// pre-LN MLP block: x += fc2(gelu(fc1(LN(x)))).  For decode steps (GEMV path) the LayerNorm is folded into the
-// fc1 launch; for many rows it is its own kernel (folding it into the MFMA GEMM's tile staging was measured
-// slower: every workgroup re-derives the row statistics)
-static void transformer_mlp(const LaunchCtx& c, const LayerW& L, float* x, float* h, float* mlp, int rows, int d,
-                            const char* t_ln, const char* t_fc1, const char* t_fc2) {
-    GemmArgs g;
-    g.lda = d; g.W = L.fc1w; g.bias = L.fc1b; g.C = mlp; g.ldc = 4 * d; g.M = rows; g.N = 4 * d; g.K = d;
-    g.flags = kGemmGelu;
-    if (gemv_applicable(rows, d)) {
-        g.A = x; g.ln_gamma = L.ln2w; g.ln_beta = L.ln2b;
-        launch_gemv(c, g, "dec_ln2_fc1");
-    } else {
-        launch_layernorm(c, x, d, L.ln2w, L.ln2b, h, d, rows, d, t_ln);
-        g.A = h;
-        launch_gemm(c, g, t_fc1);
-    }
-    GemmArgs g2;
-    g2.A = mlp; g2.lda = 4 * d; g2.W = L.fc2w; g2.bias = L.fc2b; g2.C = x; g2.ldc = d; g2.M = rows; g2.N = d;
-    g2.K = 4 * d; g2.flags = kGemmResidual; g2.R = x; g2.ldr = d;
-    launch_linear(c, g2, t_fc2);
-}
-
 // One encode of every session of `group` (1..kMaxBatch sessions of one model) as ONE launch chain: the log-mel of each
 // session (its own kernels: the frame counts differ), then every encoder operator once with grid.y = sessions - shared
 // weights, per-session activation buffers through pointer tables.  A group of one is the plain per-session encode.
@@ -827,7 +806,7 @@ extern "C++" void wlk_encode_group(const std::vector<wlk_session*>& group, const
         gemm(g, table([](wlk_session* s) { return (const float*)s->x1p; }, [](wlk_session* s) { return s->ex; },
                       [&](wlk_session*) { return pos; }), "enc_conv2");
     }
-    const float scale = std::pow((float)kHeadDim, -0.25f);
+    const float scale = qk_scale();
     const PtrTable z_ex_eh = table([](wlk_session* s) { return (const float*)s->ex; }, [](wlk_session* s) { return s->eh; }, none);
     const PtrTable z_eh_qkv = table([](wlk_session* s) { return (const float*)s->eh; }, [](wlk_session* s) { return s->eqkv; }, none);
     const PtrTable z_qkv_att = table([](wlk_session* s) { return (const float*)s->eqkv; }, [](wlk_session* s) { return s->eatt; }, none);
@@ -1006,387 +985,80 @@ int wlk_session::flash_splits() {
 // ---- decode ---------------------------------------------------------------------------------
 constexpr size_t kAncStageOffset = 65536 - 64;   // [source rows 0..6 | fresh] of an ancestry step, at the end of dec_stage
 
-// Enqueue one decoder forward on the session stream.  Everything that changes from call to call
-// (tokens, alignment-window row map, cache offset) is read from the pinned staging block through
-// memcpy nodes / device scalars, so the single-token form of this sequence can be captured once
-// into a hipGraph and replayed.
-static void enqueue_decode(wlk_session* s, const LaunchCtx& c, int n_rows, int n_tok, bool first, int sot_index,
-                           bool step_block = false, const AlignArgs* side_align = nullptr, int side_blocks = 0, int side_zf = 0,
-                           bool ancestry = false) {
-    wlk_model* m = s->m;
-    const wlk_dims& D = m->D;
-    const int ctx_len = D.n_text_ctx;
-    const int R = n_rows * n_tok;
-    const int d = D.n_text_state, T = D.n_audio_ctx, H = D.n_text_head, V = D.n_vocab;
-    // one host->device copy: [tokens | alignment-window row | beam of row | cache offset]
-    // (wlk_step_select: the embedding kernel reads the step's inputs from the host-coherent block itself)
-    if (!step_block)
-        WLK_HIP(hipMemcpyAsync(s->step_in, s->dec_stage, (size_t)(3 * s->max_rows + 1) * sizeof(int), hipMemcpyHostToDevice,
-                               s->stream));
-    // decode steps (<= 8 rows): LayerNorm and the KV-cache append are fused into the weight-streaming
-    // GEMV launches; prefill keeps them as separate kernels in front of the MFMA GEMMs
+// One decoder forward on the session stream: enqueue_prefill (the prompt, n_tok tokens per beam) or enqueue_step (one token
+// per beam).  Everything that changes from call to call (tokens, alignment-window row map, cache offset) is read from the
+// pinned staging block through memcpy nodes / device scalars, so a step can be captured once into a hipGraph and replayed.
+struct wlk_decode_opts {
+    bool step_block = false;                  // wlk_step_select: the embedding kernel reads the step's inputs from the host-coherent block itself
+    const AlignArgs* side_align = nullptr;    // riders of the vocabulary GEMV (GemmArgs::side_align): the early z-score
+    int side_blocks = 0, side_zf = 0;
+    bool ancestry = false;                    // wlk_beam_step: the table update in front of the layers, the self-attention through it
+};
+
+// Embedding and layers of n_tok tokens for each of n_rows beams.  Decode steps (<= 8 rows, one token each) fuse LayerNorm and
+// the KV-cache append into the weight-streaming GEMV launches (returns true); a prompt keeps them as kernels in front of the
+// MFMA GEMMs.  Raw scores a flash pass left in the window are softmaxed in place behind the last layer, all alignment heads
+// in one launch - unless this is a raw pass: find_alignment normalises them itself, the survey reads none.
+static bool session_forward(wlk_session* s, const LaunchCtx& c, int n_rows, int n_tok, const wlk_decode_opts& o = wlk_decode_opts{}) {
+    const wlk_model* m = s->m;
+    const int R = n_rows * n_tok, d = m->D.n_text_state;
     const bool fused = gemv_applicable(R, d) && n_tok == 1;
-    if (ancestry) {
+    if (!o.step_block)      // one host->device copy: [tokens | alignment-window row | beam of row | cache offset]
+        WLK_HIP(hipMemcpyAsync(s->step_in, s->dec_stage, (size_t)(3 * s->max_rows + 1) * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    if (o.ancestry) {
         // beam step over the ancestry table (wlk_beam_step): [source rows | fresh] ride behind the staging block; the table
         // is brought up to date in front of the layers, which append position `offset` to every physical row
-        if (!fused || step_block || !s->anc) throw std::logic_error("decode: the ancestry step needs the fused beam step");
+        if (!fused || o.step_block || !s->anc) throw std::logic_error("decode: the ancestry step needs the fused beam step");
         WLK_HIP(hipMemcpyAsync(s->src_rows, static_cast<char*>(s->dec_stage) + kAncStageOffset, 8 * sizeof(int),
                                hipMemcpyHostToDevice, s->stream));
-        launch_anc_update(c, s->anc, s->src_rows, s->d_offset, n_rows, ctx_len);
+        launch_anc_update(c, s->anc, s->src_rows, s->d_offset, n_rows, m->D.n_text_ctx);
     }
-
-    if (step_block)
+    if (o.step_block)
         launch_embed_step(c, s->step_host_dev, s->step_dev, s->tokens_dev, s->ring_row, s->beam_of_row, s->d_offset,
                           m->w_tok_emb, m->w_dec_pos, s->dx, d);
     else
         launch_embed(c, s->tokens_dev, m->w_tok_emb, m->w_dec_pos, s->dx, n_rows, n_tok, s->d_offset, d);
-    const float scale = std::pow((float)kHeadDim, -0.25f);
-    const size_t cache_layer = (size_t)s->beam * ctx_len * d;
-    bool scores_dumped = false;   // prefill: raw alignment-head scores are waiting in the window rows
-    // find_alignment and the head survey: the flash branch whatever the row count, its q never folded, no window softmax
-    const bool raw_pass = s->align_raw_scores || s->survey;
-    for (int i = 0; i < D.n_text_layer; ++i) {
-        const LayerW& L = m->dec_layers[i];
-        float* kc = s->kcache[s->kv_cur] + i * cache_layer;
-        float* vc = s->vcache[s->kv_cur] + i * cache_layer;
-        GemmArgs g;
-        g.W = L.qkvw; g.bias = L.qkvb; g.C = s->dqkv; g.ldc = 3 * d; g.M = R; g.N = 3 * d;
-        g.K = d; g.flags = kGemmScaleCols; g.scale = scale; g.scale_cols = 2 * d; g.lda = d;
-        if (fused) {
-            g.A = s->dx; g.ln_gamma = L.ln1w; g.ln_beta = L.ln1b;
-            g.kcache = kc; g.vcache = vc; g.kv_pos = s->d_offset; g.kv_d = d; g.kv_ctx = ctx_len;
-            launch_gemv(c, g, "dec_ln1_qkv_kv");
-        } else {
-            launch_layernorm(c, s->dx, d, L.ln1w, L.ln1b, s->dh, d, R, d, "dec_ln1");
-            g.A = s->dh;
-            if (!gemv_applicable(R, d) && gemm_takes_kwave(R, 3 * d, d)) {   // k/v also land in the caches
-                g.kcache = kc; g.vcache = vc; g.kv_pos = s->d_offset; g.kv_d = d; g.kv_ctx = ctx_len; g.kv_ntok = n_tok;
-                launch_gemm(c, g, "dec_qkv");
-            } else {
-                launch_linear(c, g, "dec_qkv");
-                launch_kv_append(c, s->dqkv, kc, vc, n_rows, n_tok, s->d_offset, d, ctx_len);
-            }
-        }
-        if (ancestry)
-            launch_decoder_self_attention_anc(c, s->dqkv, kc, vc, s->anc, s->datt, n_rows, s->d_offset, d, H, ctx_len);
-        else
-            launch_decoder_self_attention(c, s->dqkv, kc, vc, s->datt, n_rows, n_tok, s->d_offset, d, H, ctx_len);
-        GemmArgs o;
-        o.A = s->datt; o.lda = d; o.W = L.outw; o.bias = L.outb; o.C = s->dx; o.ldc = d; o.M = R; o.N = d; o.K = d;
-        o.flags = kGemmResidual; o.R = s->dx; o.ldr = d;
-        launch_linear(c, o, "dec_out");
-
-        GemmArgs q;
-        q.lda = d; q.W = L.xqw; q.bias = L.xqb; q.C = s->dq; q.ldc = d; q.M = R; q.N = d; q.K = d;
-        q.flags = kGemmScaleCols; q.scale = scale; q.scale_cols = d;
-        if (s->survey) q.C = s->survey_buf + (size_t)i * R * d;   // head survey: every layer's queries are kept
-        // decode steps: the split cross-attention kernel derives its head's query values itself (same arithmetic) - one
-        // launch less per layer
-        // (the fold leaves s->dq unwritten, so it must never meet the flash branch below, which reads it: that branch is
-        // taken for align_raw_scores and survey - excluded here, not merely "never fed with R == 1 today")
-        const bool fold_xq = fused && R == 1 && !s->debug && !raw_pass && cross_split_folds_query(d);   // one row: saves a launch; several rows would each re-stream Wq
-        if (fold_xq) {
-        } else if (fused) {
-            q.A = s->dx; q.ln_gamma = L.lnxw; q.ln_beta = L.lnxb;
-            launch_gemv(c, q, "dec_lnx_xq");
-        } else {
-            launch_layernorm(c, s->dx, d, L.lnxw, L.lnxb, s->dh, d, R, d, "dec_lnx");
-            q.A = s->dh;
-            launch_linear(c, q, "dec_xq");
-        }
-        const int* ranks_l = m->n_align > 0 ? m->head_rank + (size_t)i * H : nullptr;
-        bool merged_xout = false;
-        GemmArgs xo_mg;   // carries the split-form operand description to the out projection when merged_xout
-        if ((R > 8 || raw_pass) && !s->debug) {
-            // prefill: MFMA flash kernel shares every K/V tile between 32 query rows
-            if (fold_xq) throw std::logic_error("decode: the folded query projection left no q for the flash kernel");
-            FlashArgs fa;
-            fa.q = q.C; fa.ldq = d;
-            fa.k = s->cross_kv + (size_t)i * 2 * d; fa.v = fa.k + d; fa.ldkv = (long)D.n_text_layer * 2 * d;
-            fa.out = s->datt; fa.ldo = d; fa.Tq = R; fa.Tk = T; fa.n_head = H;
-            fa.head_rank = ranks_l; fa.ring = s->ring; fa.ring_row = s->ring_row;
-            fa.beam_of_row = s->beam_of_row; fa.ring_rows = s->ring_rows; fa.n_beam = s->beam;
-            if (((R + 31) / 32) * H < 256) {   // few query tiles: spread the 1500 keys over more workgroups
-                fa.k_splits = wlk_session::flash_splits();
-                fa.part_o = s->fsplit;
-                fa.part_m = fa.part_o + (size_t)s->max_rows * H * fa.k_splits * 64;
-                fa.part_l = fa.part_m + (size_t)s->max_rows * H * fa.k_splits;
-            }
-            launch_prefill_cross_attention(c, fa);
-            scores_dumped = true;   // softmaxed in place behind the last layer, all alignment heads in one launch
-        } else {
-            CrossAttnArgs ca;
-            ca.q = s->dq;
-            ca.k = s->cross_kv + (size_t)i * 2 * d;
-            ca.v = ca.k + d;
-            ca.ldkv = (long)D.n_text_layer * 2 * d;
-            ca.out = s->datt;
-            ca.rows = R; ca.d = d; ca.n_head = H; ca.T = T;
-            ca.head_rank = ranks_l;
-            ca.ring = s->ring;
-            ca.ring_row = s->ring_row;
-            ca.beam_of_row = s->beam_of_row;
-            ca.ring_rows = s->ring_rows;
-            ca.n_beam = s->beam;
-            ca.qk_debug = s->debug ? s->qk_debug + (size_t)i * s->max_rows * H * T : nullptr;
-            if (fold_xq) {
-                ca.xq_x = s->dx; ca.xq_w = L.xqw; ca.xq_b = L.xqb; ca.xq_gamma = L.lnxw; ca.xq_beta = L.lnxb; ca.xq_scale = scale;
-            }
-            if (R <= 8 && !s->debug) {
-                float* sc = s->xsplit;
-                float* pm = sc + (size_t)8 * H * T;
-                float* pl = pm + (size_t)8 * H * 8;
-                float* po = pl + (size_t)8 * H * 8;
-                // beam-1 steps: the merge of the key splits is the A-operand load of the out projection below
-                merged_xout = fused && R == 1 && gemv1_folds_merge(d);
-                launch_decoder_cross_attention_split(c, ca, sc, pm, pl, po, !merged_xout);
-                if (merged_xout) {
-                    xo_mg.mg_pm = pm; xo_mg.mg_pl = pl; xo_mg.mg_po = po; xo_mg.mg_scores = sc;
-                    xo_mg.mg_head_rank = ranks_l; xo_mg.mg_ring = s->ring; xo_mg.mg_ring_row = s->ring_row;
-                    xo_mg.mg_side_heads = m->layer_heads + (size_t)i * H;
-                    xo_mg.mg_beam_of_row = s->beam_of_row; xo_mg.mg_heads = H; xo_mg.mg_T = T;
-                    xo_mg.mg_ring_rows = s->ring_rows; xo_mg.mg_n_beam = s->beam;
-                    xo_mg.mg_side_blocks = ranks_l ? m->layer_rank_count[i] : 0;
-                }
-            } else {
-                launch_decoder_cross_attention(c, ca);
-            }
-        }
-        GemmArgs xo = xo_mg;
-        xo.A = s->datt; xo.lda = d; xo.W = L.xoutw; xo.bias = L.xoutb; xo.C = s->dx; xo.ldc = d; xo.M = R; xo.N = d;
-        xo.K = d; xo.flags = kGemmResidual; xo.R = s->dx; xo.ldr = d;
-        launch_linear(c, xo, "dec_xout");
-        transformer_mlp(c, L, s->dx, s->dh, s->dmlp, R, d, "dec_ln2", "dec_fc1", "dec_fc2");
-    }
-    if (scores_dumped && m->n_align > 0 && !raw_pass)     // find_alignment normalises the raw scores itself, the survey reads none
-        launch_ring_softmax(c, s->ring, s->ring_row, s->beam_of_row, m->all_ranks, m->n_align, R, s->ring_rows, s->beam, T);
-    // final LayerNorm + vocabulary projection only for the rows the policy reads
-    GemmArgs lg;
-    lg.lda = d; lg.W = m->w_tok_emb; lg.C = s->logits_last; lg.ldc = V; lg.M = n_rows; lg.N = V; lg.K = d;
-    if (side_align && !fused) throw std::logic_error("decode: side workgroups need the fused step");
-    if (fused) {   // n_tok == 1: the last row of beam b is row b
-        lg.A = s->dx; lg.ln_gamma = m->w_ln_w; lg.ln_beta = m->w_ln_b;
-        // graph-replayed steps: the alignment window is complete behind the last layer's cross-attention, so its z-score
-        // rides in this launch (gemv_f32_kernel's side workgroups) instead of in front of the step's last two
-        lg.side_align = side_align; lg.side_blocks = side_blocks; lg.side_zf = side_zf;
-        launch_gemv(c, lg, "dec_lnf_logits");
-    } else if (first && n_rows == 1 && gemv_applicable(2, d) && getenv("WLK_NO_PREFILL_MERGE") == nullptr) {
-        // beam-1 prefill: the last row and the sot row (no-speech probability) normalised by one launch (a negative
-        // row stride walks from the last row back to the sot row) and projected by one M = 2 pass over the 51864 x d
-        // weights; per-row arithmetic of both kernels does not depend on the row count
-        launch_layernorm(c, s->dx + (size_t)(n_tok - 1) * d, (long)(sot_index - (n_tok - 1)) * d, m->w_ln_w, m->w_ln_b,
-                         s->hsel, d, 2, d, "dec_ln_f");
-        lg.A = s->hsel; lg.M = 2;   // C row 1 = logits_sot (same allocation, V floats further)
-        launch_linear(c, lg, "dec_logits");
-        return;
-    } else {
-        launch_layernorm(c, s->dx + (size_t)(n_tok - 1) * d, (long)n_tok * d, m->w_ln_w, m->w_ln_b, s->hsel, d,
-                         n_rows, d, "dec_ln_f");
-        lg.A = s->hsel;
-        launch_linear(c, lg, "dec_logits");
-    }
-    if (first) {
-        float* hs = s->hsel + (size_t)n_rows * d;
-        launch_layernorm(c, s->dx + (size_t)sot_index * d, (long)n_tok * d, m->w_ln_w, m->w_ln_b, hs, d, n_rows, d,
-                         "dec_ln_f");
-        GemmArgs ls = lg;
-        ls.ln_gamma = ls.ln_beta = nullptr;
-        ls.A = hs; ls.C = s->logits_sot;
-        launch_linear(c, ls, "dec_logits");
-    }
+    const DecSessionAddr addr{s, n_rows, n_tok, o.ancestry};
+    wlk_decoder_layers(c, m, dec_ws(s), R, fused ? DecForm::kFused : DecForm::kLinear, addr);
+    if (addr.cross_route(R) == CrossRoute::kFlash && m->n_align > 0 && !addr.raw_pass())
+        launch_ring_softmax(c, s->ring, s->ring_row, s->beam_of_row, m->all_ranks, m->n_align, R, s->ring_rows, s->beam,
+                            m->D.n_audio_ctx);
+    return fused;
 }
 
-// ---- stacked prefills (see internal.h) -----------------------------------------------------------------------------------
-extern "C++" void wlk_prefill_ws_alloc(const wlk_model* m, wlk_prefill_ws& ws, int max_sessions, int session_rows) {
-    const wlk_dims& D = m->D;
-    const size_t d = D.n_text_state, V = D.n_vocab, H = D.n_text_head;
-    ws.cap_session_rows = session_rows;
-    ws.cap_rows = max_sessions * ((session_rows + 31) / 32 * 32);
-    const size_t R = ws.cap_rows;
-    ws.dx = dev_alloc<float>(R * d);
-    ws.dh = dev_alloc<float>(R * d);
-    ws.dqkv = dev_alloc<float>(R * 3 * d);
-    ws.datt = dev_alloc<float>(R * d);
-    ws.dq = dev_alloc<float>(R * d);
-    ws.dmlp = dev_alloc<float>(R * 4 * d);
-    ws.hsel = dev_alloc<float>((size_t)2 * max_sessions * d);
-    ws.logits = dev_alloc<float>((size_t)8 * V);
-    ws.part = dev_alloc<float>(flash_split_scratch_floats((int)R, (int)H, wlk_session::kFlashSplitsMax));
-    ws.rows_dev = reinterpret_cast<StepRow*>(dev_alloc<char>(R * sizeof(StepRow)));
-    ws.tiles_dev = reinterpret_cast<StepRow*>(dev_alloc<char>(R / 32 * sizeof(StepRow)));
-    ws.ring_row_dev = dev_alloc<int>(R);
-    ws.zeros_dev = dev_alloc<int>(R);
-    memset_sync(ws.zeros_dev, 0, R * sizeof(int));
-    ws.pinned_bytes = R * sizeof(StepRow) + R / 32 * sizeof(StepRow) + R * sizeof(int);
-    WLK_HIP(hipHostMalloc(reinterpret_cast<void**>(&ws.pinned), ws.pinned_bytes, hipHostMallocDefault));
+// final LayerNorm + vocabulary projection only for the rows the policy reads: M rows of s->dx from `row` on, `stride` apart
+static void session_logits(wlk_session* s, const LaunchCtx& c, long row, long stride, int M, float* hsel, float* logits) {
+    const int d = s->m->D.n_text_state;
+    launch_layernorm(c, s->dx + row * d, stride * d, s->m->w_ln_w, s->m->w_ln_b, hsel, d, M, d, "dec_ln_f");
+    launch_linear(c, logits_gemm(s->m, hsel, M, logits), "dec_logits");
+}
+// ... of the last fed row of every beam
+static void session_logits_last(wlk_session* s, const LaunchCtx& c, int n_rows, int n_tok, bool fused,
+                                const wlk_decode_opts& o = wlk_decode_opts{}) {
+    if (o.side_align && !fused) throw std::logic_error("decode: side workgroups need the fused step");
+    if (!fused) return session_logits(s, c, n_tok - 1, n_tok, n_rows, s->hsel, s->logits_last);
+    GemmArgs lg = logits_gemm(s->m, s->dx, n_rows, s->logits_last);      // n_tok == 1: the last row of beam b is row b
+    lg.ln_gamma = s->m->w_ln_w; lg.ln_beta = s->m->w_ln_b;
+    // graph-replayed steps: the alignment window is complete behind the last layer's cross-attention, so its z-score
+    // rides in this launch (gemv_f32_kernel's side workgroups) instead of in front of the step's last two
+    lg.side_align = o.side_align; lg.side_blocks = o.side_blocks; lg.side_zf = o.side_zf;
+    launch_gemv(c, lg, "dec_lnf_logits");
 }
 
-extern "C++" void wlk_prefill_ws_free(wlk_prefill_ws& ws) {
-    void* dev[] = {ws.dx, ws.dh, ws.dqkv, ws.datt, ws.dq, ws.dmlp, ws.hsel, ws.logits, ws.part, ws.rows_dev, ws.tiles_dev,
-                   ws.ring_row_dev, ws.zeros_dev};
-    for (void* p : dev)
-        if (p) (void)hipFree(p);
-    if (ws.pinned) (void)hipHostFree(ws.pinned);
-    ws = wlk_prefill_ws{};
+static void enqueue_prefill(wlk_session* s, const LaunchCtx& c, int n_rows, int n_tok, int sot_index) {
+    const int d = s->m->D.n_text_state;
+    const bool fused = session_forward(s, c, n_rows, n_tok);
+    // beam-1 prefill: the last row and the sot row (no-speech probability) normalised by one launch (a negative row
+    // stride walks from the last row back to the sot row) and projected by one M = 2 pass over the 51864 x d weights (C row
+    // 1 = logits_sot: same allocation, V floats further); per-row arithmetic of both kernels does not depend on the row count
+    if (!fused && n_rows == 1 && gemv_applicable(2, d) && getenv("WLK_NO_PREFILL_MERGE") == nullptr)
+        return session_logits(s, c, n_tok - 1, sot_index - (n_tok - 1), 2, s->hsel, s->logits_last);
+    session_logits_last(s, c, n_rows, n_tok, fused);
+    session_logits(s, c, sot_index, n_tok, n_rows, s->hsel + (size_t)n_rows * d, s->logits_sot);
 }
 
-extern "C++" std::string wlk_prefill_precheck(const wlk_prefill_item& it, const wlk_prefill_ws& ws) {
-    const wlk_session* s = it.s;
-    if (!s || !it.tokens) return "prefill: NULL argument";
-    const wlk_dims& D = s->m->D;
-    const int P = it.n_tok, d = D.n_text_state;
-    if (!s->encoded) return "wlk_decode before wlk_encode";
-    if (s->beam != 1 || s->debug || s->prof_on || s->align_raw_scores || s->survey) return "not a plain beam-1 session";
-    if (it.sot_index < 0 || it.sot_index >= P) return "sot_index out of range";
-    if (P > D.n_text_ctx) return "text context exceeded";
-    for (int i = 0; i < P; ++i)
-        if (it.tokens[i] < 0 || it.tokens[i] >= D.n_vocab) return "token id out of range";
-    const std::string shape = wlk_prefill_shape_check(s->m, P, ws.cap_session_rows);
-    if (!shape.empty()) return shape;
-    if (!gemv_applicable(8, d)) return "model too wide for the stacked vocabulary projection";
-    return std::string();
-}
-
-extern "C++" std::string wlk_prefill_shape_check(const wlk_model* m, int P, int cap_session_rows) {
-    const wlk_dims& D = m->D;
-    const int d = D.n_text_state;
-    // the stack runs every GEMM on the k-wave kernel and the cross-attention with key splits: only prompts whose own
-    // prefill would make exactly these choices ride in it (bit-identical results either way)
-    if (P <= 8 || P > cap_session_rows) return "prompt length outside the stacked range";
-    if (!gemm_takes_kwave(P, 3 * d, d) || !gemm_takes_kwave(P, d, d) || !gemm_takes_kwave(P, 4 * d, d) ||
-        !gemm_takes_kwave(P, d, 4 * d))
-        return "prompt too long for the k-wave GEMMs";
-    if (((P + 31) / 32) * D.n_text_head >= 256) return "prompt too long for the key-split cross-attention";
-    return std::string();
-}
-
-// The stacked chain up to the last layer's output: tables, embedding, the L layers - the flash cross-attention leaves the
-// alignment heads' raw scores in rows 0 .. P-1 of each session's score window.  The one statement of it for the stacked
-// prefills (wlk_prefill_group: read-out tail behind it) and the stacked alignment pass (wlk_group_find_alignment).
-// row0[i] = first stacked row of items[i] in ws.dx; touches no session bookkeeping.
-extern "C++" void wlk_prefill_chain(const std::vector<wlk_prefill_item*>& items, const LaunchCtx& c, wlk_prefill_ws& ws,
-                                    std::vector<int>& row0) {
-    wlk_model* m = items[0]->s->m;
-    const wlk_dims& D = m->D;
-    const int d = D.n_text_state, T = D.n_audio_ctx, H = D.n_text_head, L = D.n_text_layer;
-    const int B = (int)items.size();
-    // ---- tables: one StepRow per stacked row; a session's rows are padded to whole 32-row tiles with copies of its
-    // row 0 (same token, position, destinations: every write of a copy repeats row 0's write with the same value)
-    StepRow* rows_h = reinterpret_cast<StepRow*>(ws.pinned);
-    std::vector<int> padded(B);
-    row0.assign(B, 0);
-    int R = 0;
-    for (int i = 0; i < B; ++i) {
-        row0[i] = R;
-        padded[i] = (items[i]->n_tok + 31) / 32 * 32;
-        R += padded[i];
-    }
-    if (R > ws.cap_rows) throw std::length_error("stacked prefill: more rows than the workspace holds");
-    StepRow* tiles_h = rows_h + R;
-    int* ring_row_h = reinterpret_cast<int*>(tiles_h + R / 32);
-    for (int i = 0; i < B; ++i) {
-        wlk_session* s = items[i]->s;
-        for (int p = 0; p < padded[i]; ++p) {
-            const int src = p < items[i]->n_tok ? p : 0;
-            StepRow r{};
-            r.kcache = s->kcache[s->kv_cur];
-            r.vcache = s->vcache[s->kv_cur];
-            r.cross_kv = s->cross_kv;
-            r.ring = s->ring;
-            r.token = (int)items[i]->tokens[src];
-            r.offset = src;
-            r.ring_row = src;
-            rows_h[row0[i] + p] = r;
-            ring_row_h[row0[i] + p] = src;
-            if (p % 32 == 0) tiles_h[(row0[i] + p) / 32] = r;
-        }
-    }
-    WLK_HIP(hipMemcpyAsync(ws.rows_dev, rows_h, (size_t)R * sizeof(StepRow), hipMemcpyHostToDevice, c.stream));
-    WLK_HIP(hipMemcpyAsync(ws.tiles_dev, tiles_h, (size_t)(R / 32) * sizeof(StepRow), hipMemcpyHostToDevice, c.stream));
-    WLK_HIP(hipMemcpyAsync(ws.ring_row_dev, ring_row_h, (size_t)R * sizeof(int), hipMemcpyHostToDevice, c.stream));
-
-    // ---- the chain: enqueue_decode's prefill branch (rows > 8, not fused) with stacked rows
-    launch_embed_rows(c, ws.rows_dev, m->w_tok_emb, m->w_dec_pos, ws.dx, R, d);
-    const float scale = std::pow((float)kHeadDim, -0.25f);
-    const size_t cache_layer = (size_t)D.n_text_ctx * d;       // beam 1
-    auto linear = [&](const float* A, long lda, const float* W, const float* bias, float* C, long ldc, int N, int K, int flags,
-                      const float* Rs, float sc, int sc_cols, const char* tag) {
-        GemmArgs g;
-        g.A = A; g.lda = lda; g.W = W; g.bias = bias; g.C = C; g.ldc = ldc; g.M = R; g.N = N; g.K = K;
-        g.flags = flags; g.R = Rs; g.ldr = ldc; g.scale = sc; g.scale_cols = sc_cols;
-        g.force_kwave = true;
-        launch_gemm(c, g, tag);
-    };
-    // LayerNorm + projection, as in a session's own prefill
-    auto ln_linear = [&](const float* gamma, const float* beta, const float* W, const float* bias, float* C, long ldc, int N,
-                         int flags, float sc, int sc_cols, const char* t_ln, const char* tag) {
-        launch_layernorm(c, ws.dx, d, gamma, beta, ws.dh, d, R, d, t_ln);
-        linear(ws.dh, d, W, bias, C, ldc, N, d, flags, nullptr, sc, sc_cols, tag);
-    };
-    for (int i = 0; i < L; ++i) {
-        const LayerW& W = m->dec_layers[i];
-        ln_linear(W.ln1w, W.ln1b, W.qkvw, W.qkvb, ws.dqkv, 3 * d, 3 * d, kGemmScaleCols, scale, 2 * d, "dec_ln1", "dec_qkv");
-        launch_kv_append_rows(c, ws.dqkv, ws.rows_dev, (long)(i * cache_layer), R, d);
-        launch_decoder_self_attention_rows(c, ws.dqkv, ws.rows_dev, (long)(i * cache_layer), ws.datt, R, d, H, D.n_text_ctx);
-        linear(ws.datt, d, W.outw, W.outb, ws.dx, d, d, d, kGemmResidual, ws.dx, 1.f, 0, "dec_out");
-        ln_linear(W.lnxw, W.lnxb, W.xqw, W.xqb, ws.dq, d, d, kGemmScaleCols, scale, d, "dec_lnx", "dec_xq");
-        FlashArgs fa;
-        fa.q = ws.dq; fa.ldq = d;
-        fa.k = nullptr; fa.v = nullptr; fa.ldkv = (long)L * 2 * d;
-        fa.tile_rows = ws.tiles_dev; fa.tile_kv_off = (long)i * 2 * d; fa.tile_v_off = d;
-        fa.out = ws.datt; fa.ldo = d; fa.Tq = R; fa.Tk = T; fa.n_head = H;
-        fa.head_rank = m->n_align > 0 ? m->head_rank + (size_t)i * H : nullptr;
-        fa.ring = nullptr; fa.ring_row = ws.ring_row_dev; fa.beam_of_row = ws.zeros_dev;
-        fa.ring_rows = items[0]->s->ring_rows; fa.n_beam = 1;
-        fa.k_splits = wlk_session::flash_splits();
-        fa.part_o = ws.part;
-        fa.part_m = fa.part_o + (size_t)R * H * fa.k_splits * 64;
-        fa.part_l = fa.part_m + (size_t)R * H * fa.k_splits;
-        launch_prefill_cross_attention(c, fa);
-        linear(ws.datt, d, W.xoutw, W.xoutb, ws.dx, d, d, d, kGemmResidual, ws.dx, 1.f, 0, "dec_xout");
-        ln_linear(W.ln2w, W.ln2b, W.fc1w, W.fc1b, ws.dmlp, 4 * d, 4 * d, kGemmGelu, 1.f, 0, "dec_ln2", "dec_fc1");
-        linear(ws.dmlp, 4 * d, W.fc2w, W.fc2b, ws.dx, d, d, 4 * d, kGemmResidual, ws.dx, 1.f, 0, "dec_fc2");
-    }
-}
-
-extern "C++" void wlk_prefill_group(const std::vector<wlk_prefill_item*>& items, const LaunchCtx& c, wlk_prefill_ws& ws) {
-    if (items.empty()) return;
-    wlk_model* m = items[0]->s->m;
-    const wlk_dims& D = m->D;
-    const int d = D.n_text_state, T = D.n_audio_ctx, V = D.n_vocab;
-    const int B = (int)items.size();
-    std::vector<int> row0;
-    wlk_prefill_chain(items, c, ws, row0);
-    // ---- per session: the alignment heads' raw scores softmaxed in place; final LayerNorm of the last and the sot row
-    for (int i = 0; i < B; ++i) {
-        wlk_session* s = items[i]->s;
-        const int P = items[i]->n_tok;
-        if (m->n_align > 0)
-            launch_ring_softmax(c, s->ring, ws.ring_row_dev + row0[i], ws.zeros_dev, m->all_ranks, m->n_align, P, s->ring_rows, 1, T);
-        launch_layernorm(c, ws.dx + (size_t)(row0[i] + P - 1) * d, (long)(items[i]->sot_index - (P - 1)) * d, m->w_ln_w, m->w_ln_b,
-                         ws.hsel + (size_t)2 * i * d, d, 2, d, "dec_ln_f");
-    }
-    // ---- vocabulary projection: [last, sot] rows of up to four sessions per pass over the embedding (the <= 8-row
-    // weight-streaming kernel, whose per-row arithmetic does not depend on the row count), then out to the sessions
-    for (int lo = 0; lo < B; lo += 4) {
-        const int nb = std::min(4, B - lo);
-        GemmArgs lg;
-        lg.A = ws.hsel + (size_t)2 * lo * d; lg.lda = d; lg.W = m->w_tok_emb; lg.C = ws.logits; lg.ldc = V; lg.M = 2 * nb; lg.N = V;
-        lg.K = d;
-        launch_gemv(c, lg, "dec_logits");
-        for (int i = 0; i < nb; ++i)
-            WLK_HIP(hipMemcpyAsync(items[lo + i]->s->logits_last, ws.logits + (size_t)2 * i * V, (size_t)2 * V * sizeof(float),
-                                   hipMemcpyDeviceToDevice, c.stream));
-    }
-    for (int i = 0; i < B; ++i) {
-        wlk_session* s = items[i]->s;
-        s->self_len = items[i]->n_tok;
-        s->n_steps = 1;
-        s->have_sot = true;
-        s->prefill_rows = items[i]->n_tok;
-        s->last_rows = 1;
-        s->last_ntok = items[i]->n_tok;
-    }
+static void enqueue_step(wlk_session* s, const LaunchCtx& c, int n_rows, const wlk_decode_opts& o = wlk_decode_opts{}) {
+    session_logits_last(s, c, n_rows, 1, session_forward(s, c, n_rows, 1, o), o);
 }
 
 int wlk_decode(wlk_session* s, const int64_t* tokens, int n_rows, int n_tok, int first, int sot_index) {
@@ -1437,16 +1109,17 @@ int wlk_decode(wlk_session* s, const int64_t* tokens, int n_rows, int n_tok, int
                                !s->prof_on && s->use_graph;
         if (graphable) {
             hipGraphExec_t& exec = s->step_exec[s->kv_cur];
-            if (!exec) capture_step_graph(s->stream, exec, [&] { enqueue_decode(s, c, n_rows, n_tok, false, sot_index); });
+            if (!exec) capture_step_graph(s->stream, exec, [&] { enqueue_step(s, c, n_rows); });
             WLK_HIP(hipGraphLaunch(exec, s->stream));
+        } else if (!first) {
+            enqueue_step(s, c, n_rows);
         } else {
-            enqueue_decode(s, c, n_rows, n_tok, first != 0, sot_index);
+            enqueue_prefill(s, c, n_rows, n_tok, sot_index);
             // timing probe only (scripts/eight_stream_probe.py): the prefill chain enqueued again - same inputs, same
             // buffers, same results - to measure what one prefill chain costs under load (the bound on what
             // stacking the sessions' prefills could save)
             static const int prefill_repeat = [] { const char* e = getenv("WLK_PROBE_PREFILL_REPEAT"); return e ? atoi(e) : 1; }();
-            if (first)
-                for (int rep = 1; rep < prefill_repeat; ++rep) enqueue_decode(s, c, n_rows, n_tok, true, sot_index);
+            for (int rep = 1; rep < prefill_repeat; ++rep) enqueue_prefill(s, c, n_rows, n_tok, sot_index);
         }
         WLK_HIP(hipEventRecord(s->dec_stage_ev, s->stream));
         s->dec_stage_used = true;
@@ -1695,8 +1368,9 @@ extern "C++" int wlk_step_select(wlk_session* s, int64_t token, const int32_t* a
                 a.part = s->z + (size_t)s->beam * std::max(m->n_align, 1) * D.n_audio_ctx;
                 // the vocabulary projection's weights are a (V / 4 / 4 > 2048 workgroups) stream long enough to hide the z-score
                 const bool early_z = select_early_z_enabled() && D.n_vocab >= 16384;
-                if (early_z) enqueue_decode(s, c, 1, 1, false, 0, true, s->step_align_dev, zf_blocks * a.n_align * a.n_beam, zf_blocks);
-                else enqueue_decode(s, c, 1, 1, false, 0, true);
+                wlk_decode_opts o; o.step_block = true;
+                if (early_z) { o.side_align = s->step_align_dev; o.side_blocks = zf_blocks * a.n_align * a.n_beam; o.side_zf = zf_blocks; }
+                enqueue_step(s, c, 1, o);
                 StepHostOut ho;
                 ho.result = s->result_host_dev;
                 ho.n_adj = &s->step_dev->n_adj;
@@ -1806,7 +1480,8 @@ extern "C++" int wlk_beam_step(wlk_session* s, const int64_t* tokens, const int3
         // one capture per KV buffer, as step_exec: the chain's nodes carry kcache / vcache[kv_cur], and a wlk_kv_reorder of
         // an infer that ran without ancestry steps (debug / profiling fallback, the per-token hooks) flips kv_cur
         hipGraphExec_t& exec = s->bstep_exec[s->kv_cur];
-        if (!exec) capture_step_graph(s->stream, exec, [&] { enqueue_decode(s, c, B, 1, false, 0, false, nullptr, 0, 0, true); });
+        if (!exec)
+            capture_step_graph(s->stream, exec, [&] { wlk_decode_opts o; o.ancestry = true; enqueue_step(s, c, B, o); });
         WLK_HIP(hipGraphLaunch(exec, s->stream));
         WLK_HIP(hipEventRecord(s->dec_stage_ev, s->stream));
         s->dec_stage_used = true;

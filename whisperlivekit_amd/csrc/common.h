@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <mutex>
@@ -15,6 +16,7 @@ constexpr int kNFreq = 201;
 constexpr int kMelFrames = 3000;     // frames fed to the encoder (30 s)
 constexpr int kPadSamples = 480000;  // zero padding the streaming path appends (simul_whisper.py:346)
 constexpr int kHeadDim = 64;         // every Whisper size uses 64-wide heads
+inline float qk_scale() { return std::pow((float)kHeadDim, -0.25f); }   // what q and k each carry (their product: 64^-0.5)
 constexpr int kAlignWindow = 16;     // decode steps kept for AlignAtt (align_att_base.py:223)
 
 struct HipError : std::runtime_error {
@@ -554,6 +556,12 @@ struct FlashArgs {
         __builtin_amdgcn_sched_barrier(0);                                                                                 \
     } while (0)
 size_t flash_split_scratch_floats(int rows, int n_head, int k_splits);
+// that scratch as the partials of a launch of a.k_splits key ranges over a.n_head heads: [part_o | part_m | part_l] for `rows` rows
+inline void flash_split_partition(FlashArgs& a, float* part, int rows) {
+    a.part_o = part;
+    a.part_m = a.part_o + (size_t)rows * a.n_head * a.k_splits * 64;
+    a.part_l = a.part_m + (size_t)rows * a.n_head * a.k_splits;
+}
 // encoder self-attention over qkv[T][3d] (q and k pre-scaled), out[T][d]
 void launch_encoder_attention(const LaunchCtx& ctx, const float* qkv, float* out, int T, int d, int n_head);
 // encoder self-attention of `batch` sessions in one launch: qkv = z.in[i] ([T][3d]), out = z.out[i]
@@ -619,6 +627,12 @@ void launch_decoder_cross_attention_split(const LaunchCtx& ctx, const CrossAttnA
                                           float* pl, float* po, bool merge = true);
 constexpr int kCrossSplitWays = 8;   // == kCrossSplit of decoder.hip (checked there)
 size_t cross_split_scratch_floats(int rows, int n_head, int T);
+struct CrossSplitScratch { float *scores, *pm, *pl, *po; };
+inline CrossSplitScratch cross_split_partition(float* base, int rows, int n_head, int T) {
+    float* pm = base + (size_t)rows * n_head * T;
+    const size_t n = (size_t)rows * n_head * kCrossSplitWays;
+    return CrossSplitScratch{base, pm, pm + n, pm + 2 * n};
+}
 void launch_kv_gather(const LaunchCtx& ctx, const float* src, float* dst, const int* source_rows, int n_rows,
                       int len, int d, int ctx_len, int n_layer);
 

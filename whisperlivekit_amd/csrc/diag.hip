@@ -10,6 +10,7 @@
 
 #include "../../include/wlk_hip.h"
 #include "common.h"
+#include "decoder_chain.h"
 #include "internal.h"
 #include "nllb_internal.h"
 #include "wave_ops.h"
@@ -970,9 +971,7 @@ int wlk_diag_dec_attention(const wlk_diag_dec_attention_args* q) {
             if (q->k_splits == 0) {
                 fa.k_splits = wlk_session::flash_splits();
                 PART.alloc(flash_split_scratch_floats(R, H, fa.k_splits) * F);
-                fa.part_o = PART.f();
-                fa.part_m = fa.part_o + (size_t)R * H * fa.k_splits * 64;
-                fa.part_l = fa.part_m + (size_t)R * H * fa.k_splits;
+                flash_split_partition(fa, PART.f(), R);
             }
             launch_prefill_cross_attention(ctx, fa);
             // (a session softmaxes every rank behind its last layer; this is one layer, so: the ranks of its heads)

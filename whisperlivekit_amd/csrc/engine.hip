@@ -13,7 +13,6 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cmath>
 #include <condition_variable>
 #include <cstring>
 #include <deque>
@@ -21,6 +20,7 @@
 #include <thread>
 
 #include "common.h"
+#include "decoder_chain.h"
 #include "internal.h"
 #include "loop.h"
 
@@ -119,88 +119,6 @@ struct wlk_engine {
     bool step_batched_one_replay(std::vector<EngineJob*>& group, std::vector<EngineJob*>& finished);
     void enqueue_select(int R, int n_adj);  // logit adjustments + log-softmax top-2 + AlignAtt read-out per row
 };
-
-// ---- the step chain ------------------------------------------------------------------------------------------
-void wlk_step_ws_alloc(const wlk_model* m, wlk_step_ws& ws) {
-    const wlk_dims& D = m->D;
-    const size_t R = 8, d = D.n_text_state, V = D.n_vocab;
-    ws.x = dev_alloc<float>(R * d);
-    ws.qkv = dev_alloc<float>(R * 3 * d);
-    ws.att = dev_alloc<float>(R * d);
-    ws.q = dev_alloc<float>(R * d);
-    ws.mlp = dev_alloc<float>(R * 4 * d);
-    ws.logits = dev_alloc<float>(R * V);
-    ws.xsplit = dev_alloc<float>(cross_split_scratch_floats(8, D.n_text_head, D.n_audio_ctx));
-}
-
-void wlk_step_ws_free(wlk_step_ws& ws) {
-    float* fl[] = {ws.x, ws.qkv, ws.att, ws.q, ws.mlp, ws.logits, ws.xsplit};
-    for (float* p : fl)
-        if (p) (void)hipFree(p);
-    ws = wlk_step_ws{};
-}
-
-void wlk_enqueue_step_rows(const wlk_model* m, const LaunchCtx& c, const wlk_step_ws& ws, const StepRow* rows_dev, int R,
-                           const wlk_step_opts& o) {
-    const wlk_dims& D = m->D;
-    const int d = D.n_text_state, T = D.n_audio_ctx, H = D.n_text_head, V = D.n_vocab, ctx_len = D.n_text_ctx;
-    const float scale = std::pow((float)kHeadDim, -0.25f);
-    float *x = ws.x, *att = ws.att;
-    // C[R][N] = A[R][K] W^T + bias, both operands dense
-    auto gemm = [R](const float* A, int K, const float* W, const float* bias, float* C, int N) {
-        GemmArgs g;
-        g.A = A; g.lda = K; g.W = W; g.bias = bias; g.C = C; g.ldc = N; g.M = R; g.N = N; g.K = K;
-        return g;
-    };
-    auto residual_gemv = [&](GemmArgs g, const char* tag) {       // x += ...
-        g.flags = kGemmResidual; g.R = x; g.ldr = d;
-        launch_gemv(c, g, tag);
-    };
-    if (o.block_host) launch_embed_rows_step(c, o.block_host, o.block_dev, m->w_tok_emb, m->w_dec_pos, x, R, d);
-    else launch_embed_rows(c, rows_dev, m->w_tok_emb, m->w_dec_pos, x, R, d);
-    float* sc = ws.xsplit;
-    float* pm = sc + (size_t)8 * H * T;
-    float* pl = pm + (size_t)8 * H * 8;
-    float* po = pl + (size_t)8 * H * 8;
-    for (int i = 0; i < D.n_text_layer; ++i) {
-        const LayerW& L = m->dec_layers[i];
-        const long layer_off = (long)i * ctx_len * d;       // beam 1: [L][ctx][d]
-        GemmArgs g = gemm(x, d, L.qkvw, L.qkvb, ws.qkv, 3 * d);
-        g.flags = kGemmScaleCols; g.scale = scale; g.scale_cols = 2 * d;
-        g.ln_gamma = L.ln1w; g.ln_beta = L.ln1b;
-        g.kv_rows = rows_dev; g.kv_layer_off = layer_off; g.kv_d = d; g.kv_ctx = ctx_len;
-        launch_gemv(c, g, "dec_ln1_qkv_kv");
-        launch_decoder_self_attention_rows(c, ws.qkv, rows_dev, layer_off, att, R, d, H, ctx_len);
-        residual_gemv(gemm(att, d, L.outw, L.outb, x, d), "dec_out");
-        GemmArgs qq = gemm(x, d, L.xqw, L.xqb, ws.q, d);
-        qq.flags = kGemmScaleCols; qq.scale = scale; qq.scale_cols = d; qq.ln_gamma = L.lnxw; qq.ln_beta = L.lnxb;
-        // batched steps keep the query projection as ONE multi-row GEMV (weights streamed once for all rows): folded into the
-        // split cross-attention every row's 64 workgroups would stream Wq again (19 us per launch at 8 streams,
-        // profiles/r04_trace8_busy.txt) - the fold only pays for a single row, where it saves a launch
-        const bool fold_xq = o.fold_one_row_query && R == 1 && cross_split_folds_query(d);
-        if (!fold_xq) launch_gemv(c, qq, "dec_lnx_xq");
-        CrossAttnArgs ca{};
-        ca.q = ws.q; ca.k = nullptr; ca.v = nullptr; ca.ldkv = (long)D.n_text_layer * 2 * d; ca.out = att;
-        ca.rows = R; ca.d = d; ca.n_head = H; ca.T = T;
-        ca.head_rank = m->n_align > 0 ? m->head_rank + (size_t)i * H : nullptr;
-        ca.ring = nullptr; ca.ring_row = nullptr; ca.beam_of_row = nullptr;
-        ca.ring_rows = ctx_len + kAlignWindow; ca.n_beam = 1; ca.qk_debug = nullptr;
-        ca.step_rows = rows_dev; ca.kv_off = (long)i * 2 * d;
-        if (fold_xq) {
-            ca.xq_x = x; ca.xq_w = L.xqw; ca.xq_b = L.xqb; ca.xq_gamma = L.lnxw; ca.xq_beta = L.lnxb; ca.xq_scale = scale;
-        }
-        launch_decoder_cross_attention_split(c, ca, sc, pm, pl, po, true);
-        residual_gemv(gemm(att, d, L.xoutw, L.xoutb, x, d), "dec_xout");
-        GemmArgs f1 = gemm(x, d, L.fc1w, L.fc1b, ws.mlp, 4 * d);
-        f1.flags = kGemmGelu; f1.ln_gamma = L.ln2w; f1.ln_beta = L.ln2b;
-        launch_gemv(c, f1, "dec_ln2_fc1");
-        residual_gemv(gemm(ws.mlp, 4 * d, L.fc2w, L.fc2b, x, d), "dec_fc2");
-    }
-    GemmArgs lg = gemm(x, d, m->w_tok_emb, nullptr, ws.logits, V);
-    lg.ln_gamma = m->w_ln_w; lg.ln_beta = m->w_ln_b;
-    lg.side_align = o.side_align; lg.side_blocks = o.side_blocks; lg.side_zf = o.side_zf;   // fused replay: the rows' z-scores ride here
-    launch_gemv(c, lg, "dec_lnf_logits");
-}
 
 // ---- one batched step ----------------------------------------------------------------------------------------
 void wlk_engine::enqueue_decoder(int R, bool from_block, const AlignArgs* side_align, int side_blocks, int side_zf) {

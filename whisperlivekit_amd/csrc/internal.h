@@ -129,26 +129,6 @@ struct wlk_engine;
 struct wlk_session;
 struct wlk_model;
 
-// ---- stacked prefills (api.hip: wlk_prefill_group; engine.hip: the prefill lane) -----------------------------------
-// Workspace of one stacked prefill chain: activations of all stacked rows, the row / tile tables, read-out staging.
-struct wlk_prefill_ws {
-    int cap_rows = 0;             // stacked rows (each session padded to whole 32-row query tiles) the buffers hold
-    int cap_session_rows = 0;     // longest prompt of one session taken into a stack
-    float *dx = nullptr, *dh = nullptr, *dqkv = nullptr, *datt = nullptr, *dq = nullptr, *dmlp = nullptr, *hsel = nullptr,
-          *logits = nullptr, *part = nullptr;
-    wlk::StepRow *rows_dev = nullptr, *tiles_dev = nullptr;
-    int *ring_row_dev = nullptr, *zeros_dev = nullptr;
-    char* pinned = nullptr;       // host staging of the tables
-    size_t pinned_bytes = 0;
-};
-struct wlk_prefill_item {
-    wlk_session* s = nullptr;
-    const int64_t* tokens = nullptr;
-    int n_tok = 0, sot_index = 0;
-    int rc = 0;
-    std::string err;
-};
-
 // ------------------------------------------------------------------------------------------------
 // model
 // ------------------------------------------------------------------------------------------------
@@ -398,51 +378,12 @@ void wlk_encode_group(const std::vector<wlk_session*>& group, const wlk::LaunchC
 // this per request before it stacks requests into one chain.
 std::string wlk_encode_precheck(const wlk_session* s, const wlk_model* m);
 
-// The prefills (first decoder pass of an infer: all prompt tokens at once) of several beam-1 sessions of one model as
-// ONE launch chain on c.stream: rows of all sessions stacked for the LayerNorms and GEMMs (shared weights), per-row
-// session pointers for the cache append / self-attention, per-query-tile session pointers for the cross-attention.
-// Every row goes through the kernels and the arithmetic of a prefill of its session alone (wlk_decode, first = 1), so the
-// results are bit-identical to it.  wlk_prefill_precheck: empty = this request can ride in a stack (otherwise the
-// caller runs wlk_decode).  Leaves each session as wlk_decode(first = 1) leaves it; throws on launch failures.
-std::string wlk_prefill_precheck(const wlk_prefill_item& it, const wlk_prefill_ws& ws);
-void wlk_prefill_group(const std::vector<wlk_prefill_item*>& items, const wlk::LaunchCtx& c, wlk_prefill_ws& ws);
-// the chain of wlk_prefill_group without its read-out tail and bookkeeping (api.hip); items must not be empty
-void wlk_prefill_chain(const std::vector<wlk_prefill_item*>& items, const wlk::LaunchCtx& c, wlk_prefill_ws& ws,
-                       std::vector<int>& row0);
-// the shape conditions of wlk_prefill_precheck alone: empty = a prompt of P tokens can ride in a stacked chain of model m
-std::string wlk_prefill_shape_check(const wlk_model* m, int P, int cap_session_rows);
-void wlk_prefill_ws_alloc(const wlk_model* m, wlk_prefill_ws& ws, int max_sessions, int session_rows);
-void wlk_prefill_ws_free(wlk_prefill_ws& ws);
-
 // cif.hip
 void wlk_cif_session_prepare(wlk_session* s);
 void wlk_cif_session_free(wlk_session* s);
 void wlk_cif_enqueue(const std::vector<wlk_session*>& group, const wlk::LaunchCtx& c, const std::vector<int>& content);
 
 // engine.hip
-// ---- the single-token step of up to 8 rows over a StepRow table: the batch engine's steps and the window group's --------
-// Activations of one such step, 8 rows each (xsplit: the split cross-attention's scratch).
-struct wlk_step_ws {
-    float *x = nullptr, *qkv = nullptr, *att = nullptr, *q = nullptr, *mlp = nullptr, *logits = nullptr, *xsplit = nullptr;
-};
-void wlk_step_ws_alloc(const wlk_model* m, wlk_step_ws& ws);
-void wlk_step_ws_free(wlk_step_ws& ws);
-// what a caller's chain may differ in
-struct wlk_step_opts {
-    // embedding: the tokens and offsets come out of the host-coherent block `block_host` (its device-side address), which the
-    // first kernel also copies into `block_dev`, whose `rows` is then the table (launch_embed_rows_step); nullptr = the table
-    const wlk::EngineBlock* block_host = nullptr;
-    wlk::EngineBlock* block_dev = nullptr;
-    // riders of the vocabulary GEMV (GemmArgs::side_align): the rows' z-scores of a fused replay
-    const wlk::AlignArgs* side_align = nullptr;
-    int side_blocks = 0, side_zf = 0;
-    // a step of ONE row folds the cross-attention's query projection into the attention kernel where that kernel can
-    bool fold_one_row_query = false;
-};
-// embed .. logits of R rows on c.stream: the one statement of the chain, whoever takes the step
-void wlk_enqueue_step_rows(const wlk_model* m, const wlk::LaunchCtx& c, const wlk_step_ws& ws, const wlk::StepRow* rows_dev, int R,
-                           const wlk_step_opts& o = wlk_step_opts{});
-
 // the prefill of an attached session through the engine's prefill lane (stacked with the prefills other sessions have
 // waiting); 1 = not taken (the caller runs wlk_decode itself); blocks until this session's prefill is done
 int wlk_engine_prefill(wlk_session* s, const int64_t* tokens, int n_tok, int sot_index);

@@ -15,11 +15,11 @@
 // (group_advance_rows_kernel) derives it on the device between two chains.  The host enqueues `burst` chains back to back,
 // reads the picks and the per-row step counts back once and synchronises once.  wlk_group_step_pick is its one-step case.
 //
-// The layer chain is the batch engine's, wlk_enqueue_step_rows (engine.hip), without the one-row fold of the
+// The layer chain is the batch engine's, wlk_enqueue_step_rows (decoder_chain.hip), without the one-row fold of the
 // cross-attention's query projection: a row goes through the same kernels whether it steps alone or beside seven others.
 //
 // The same group also aligns the words of up to 8 windows in one call (wlk_group_find_alignment): one stacked
-// teacher-forced decoder pass (api.hip: wlk_prefill_chain), the token probabilities per window, the ragged normalisation
+// teacher-forced decoder pass (decoder_chain.hip: wlk_prefill_chain), the token probabilities per window, the ragged normalisation
 // (word_align.hip), the warping recurrences side by side and the path walk on the device (dtw.hip), one read-back of the
 // starts and probabilities.  Its workspace is allocated by the first such call.
 //
@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "common.h"
+#include "decoder_chain.h"
 #include "internal.h"
 
 using namespace wlk;
