@@ -1196,6 +1196,15 @@ int wlk_diag_layernorm_x3(const float* x, const float* gamma, const float* beta,
  * its timing probe */
 int wlk_diag_encoder_attention_x3(const float* qkv, int t, int d, int n_head, float* out);
 int wlk_diag_encoder_attention_x3_time(int t, int d, int n_head, int reps, float* us_per_launch);
+/* Every 16-byte request that workgroup (head, q_tile) of the X3 attention kernel makes on the operand image of t rows of a
+ * d-wide model, computed on the host by the functions the kernel itself calls (no launch, needs no device).  src_off[i]: byte
+ * offset from the start of the image; lds_off[i]: the byte of the 3 x 49 152 byte LDS ring it lands at, or -1 for a load into
+ * registers.  Order: the Q fragments [thread 0 .. 511][feature step 0 / 1][plane 0 .. 2], then the LDS-DMA requests
+ * [ring step 0 .. n_steps + 1][wave 0 .. 7][piece 0 .. 5][lane 0 .. 63] (n_steps = pairs of 32-key tiles; the last two steps
+ * re-fetch the last pair).  At most cap entries are written, *n_out is their full count, *image_bytes (may be NULL) the size of
+ * the image.  WLK_ERR_ARG for a shape the launcher refuses or a workgroup the grid does not have. */
+int wlk_diag_attn_x3_addresses(int t, int d, int n_head, int head, int q_tile, int64_t* src_off, int32_t* lds_off, int64_t cap,
+                               int64_t* n_out, int64_t* image_bytes);
 /* the production operand route of that attention (qkv projection with the X3 epilogue -> attention) against the diagnostic
  * one (fp32 projection -> x3 pack -> attention) on x [t][d], w [3 d][d], bias [3 d]: the two outputs [t][d] must be equal
  * bit for bit */

@@ -395,6 +395,8 @@ def _declare(lib: C.CDLL) -> None:
         "wlk_diag_encoder_attention_x3": (cint, [p, cint, cint, cint, p]),
         "wlk_diag_encoder_attention_x3_time": (cint, [cint, cint, cint, cint, C.POINTER(C.c_float)]),
         "wlk_diag_qkv_x3_attention": (cint, [p, p, p, cint, cint, cint, C.c_float, p, p]),
+        "wlk_diag_attn_x3_addresses": (cint, [cint, cint, cint, cint, cint, p, p, C.c_int64, C.POINTER(C.c_int64),
+                                              C.POINTER(C.c_int64)]),
         "wlk_diag_select": (cint, [C.POINTER(DiagSelectArgs)]),
         "wlk_diag_dec_attention": (cint, [C.POINTER(DiagDecAttentionArgs)]),
         "wlk_diag_topk": (cint, [p, i32, i32, i32, i32, p, p]),
@@ -463,6 +465,7 @@ EXPORTED_SYMBOLS = (
     "wlk_diag_encoder_attention", "wlk_diag_encoder_attention_time", "wlk_diag_wave_ops", "wlk_diag_env_refresh",
     "wlk_diag_linear_x3", "wlk_diag_linear_x3_time", "wlk_diag_layernorm_x3",
     "wlk_diag_encoder_attention_x3", "wlk_diag_encoder_attention_x3_time", "wlk_diag_qkv_x3_attention",
+    "wlk_diag_attn_x3_addresses",
     "wlk_diag_select", "wlk_diag_dec_attention", "wlk_diag_topk", "wlk_diag_sf_kernel", "wlk_diag_nllb_align",
     "wlk_diag_nllb_align_rows", "wlk_diag_linear_ex", "wlk_diag_gemv_variant", "wlk_diag_gemm_plan", "wlk_diag_enc_op",
     "wlk_diag_x3_plan", "wlk_diag_word_align", "wlk_diag_head_survey", "wlk_diag_nllb_cross_ragged",

@@ -46,9 +46,11 @@ __device__ __forceinline__ void ax_static_for(F&& f) {
         ax_static_for<N, I + 1>(f);
     }
 }
-__device__ __forceinline__ void ax_read12(af32x4 (&f)[12], const unsigned (&addr)[12], unsigned off) {
-#pragma unroll
-    for (int t = 0; t < 12; ++t) asm volatile("ds_read_b128 %0, %1" : "=v"(f[t]) : "v"(addr[t] + off));
+// one fragment read: the lane's base register plus a compile-time byte offset in the instruction's 16-bit offset field
+template <int OFF>
+__device__ __forceinline__ void ax_read(af32x4& f, unsigned base) {
+    static_assert(OFF >= 0 && OFF < 65536, "ds_read_b128 offset field");
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f) : "v"(base), "n"(OFF));
 }
 __device__ __forceinline__ void ax_wait12(af32x4 (&f)[12]) {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]));
@@ -67,6 +69,78 @@ __device__ __forceinline__ void ax_split8(const float (&v)[8], bf16x8 (&out)[3])
 // key row (relative to the start of its 32-key group) of element e of stored chunk u of V^T: a lane of group u = lane >> 4
 // holds, after S^T = K Q^T with 16 x 16 MFMAs, the probabilities of keys 4 u .. 4 u + 3 and 16 + 4 u .. 16 + 4 u + 3
 __host__ __device__ inline int ax_vt_key(int u, int e) { return 4 * u + (e & 3) + 16 * (e >> 2); }
+
+// ---- the address sequence of a workgroup, stated once: the kernel and wlk_diag_attn_x3_addresses both call these ------------
+// All offsets are bytes from the start of the operand image (qk3).
+struct AxGeom {
+    int T, n_tiles, n_steps;     // n_steps pairs of 32-key tiles: stream 0 takes tile 2 j, stream 1 tile 2 j + 1
+    long row_qk, row_vt;         // bytes of one X3 row of q | k and of V^T
+    long q_base;                 // this head's first q chunk in row 0
+    long k_base;                 // this head's first k chunk in row 0
+    long vt_base;                // V^T row head * 64, stored key chunk 0
+};
+__host__ __device__ inline int ax_min(int a, int b) { return a < b ? a : b; }
+__host__ __device__ inline AxGeom ax_geom(int T, int d, int head, long ldqk, long vt_off, long vt_ld) {
+    AxGeom g;
+    g.T = T;
+    g.n_tiles = (T + AX_KT - 1) / AX_KT;
+    g.n_steps = (g.n_tiles + 1) / 2;
+    g.row_qk = 3 * ldqk * 2;
+    g.row_vt = 3 * vt_ld * 2;
+    g.q_base = (long)(head * 8) * 48;
+    g.k_base = (long)(d / 8 + head * 8) * 48;
+    g.vt_base = 2 * vt_off + (long)(head * 64) * g.row_vt;
+    return g;
+}
+// Q fragment (kstep, plane p) of the lane with query column c and chunk group g of query block qs of the tile at q0
+__host__ __device__ inline long ax_q_src(const AxGeom& G, int q0, int qs, int c, int g, int kstep, int p) {
+    return G.q_base + (long)ax_min(q0 + 16 * qs + c, G.T - 1) * G.row_qk + ((4 * kstep + g) * 3 + p) * 16;
+}
+// DMA piece i of wave `wave` covers bytes [1024 j, 1024 j + 1024) of a slot, j = wave + 8 i; lane l moves 16 of them
+__host__ __device__ inline int ax_piece_lds(int wave, int lane, int i) { return (wave + 8 * i) * 1024 + 16 * lane; }
+// a piece lies inside one of the four 12 KiB regions of a slot: [stream 0: K | V^T][stream 1: K | V^T]
+__host__ __device__ inline bool ax_piece_is_k(int wave, int i) { return ((wave + 8 * i) / (AX_K_BYTES / 1024)) % 2 == 0; }
+// what that lane fetches for key pair sc (0 <= sc < n_steps); the bank swizzle lives in the source address (K: chunk ^
+// (row & 7), V^T: chunk ^ ((row >> 1) & 3), planes in place).  The clamps act on the last pair only: keys past T - 1 read row
+// T - 1 (masked in the scores), and a second stream without a tile (odd tile count) re-reads its last real tile.
+__host__ __device__ inline long ax_piece_src(const AxGeom& G, int wave, int lane, int i, int sc) {
+    const int byte = ax_piece_lds(wave, lane, i);
+    const int stream = byte / AX_TILE_BYTES, in_tile = byte - stream * AX_TILE_BYTES;
+    if (in_tile < AX_K_BYTES) {
+        const int row = in_tile / AX_K_ROW;
+        const int up = (in_tile - row * AX_K_ROW) >> 4;
+        const int unit = ((up / 3) ^ (row & 7)) * 3 + up % 3;
+        const int key = ax_min((2 * sc + stream) * AX_KT + row, G.T - 1);
+        return G.k_base + unit * 16 + (long)key * G.row_qk;
+    }
+    const int off = in_tile - AX_K_BYTES;
+    const int row = off / AX_V_ROW;
+    const int up = (off - row * AX_V_ROW) >> 4;
+    const int unit = ((up / 3) ^ ((row >> 1) & 3)) * 3 + up % 3;
+    const int pair = ax_min(sc, (G.n_tiles - 1 - stream) / 2);
+    return G.vt_base + (long)row * G.row_vt + unit * 16 + (long)(2 * pair + stream) * (AX_KT / 8) * 48;
+}
+// Before the last pair no clamp acts, and a piece's source moves by a wave-uniform stride per step: two tiles of K rows, or
+// eight stored chunks of a V^T row
+__host__ __device__ inline long ax_piece_stride(const AxGeom& G, int wave, int i) {
+    return ax_piece_is_k(wave, i) ? 2L * AX_KT * G.row_qk : 2L * (AX_KT / 8) * 48;
+}
+// The request of ring step `step` (0 .. n_steps + 1; the two past the end re-fetch the last pair into a free slot), as the
+// kernel forms it: a pointer that advances while step < n_steps - 1, the last pair's own pointer from then on
+__host__ __device__ inline long ax_piece_src_at_step(const AxGeom& G, int wave, int lane, int i, int step) {
+    return step < G.n_steps - 1 ? ax_piece_src(G, wave, lane, i, 0) + step * ax_piece_stride(G, wave, i)
+                                : ax_piece_src(G, wave, lane, i, G.n_steps - 1);
+}
+// Fragment reads, relative to the slot: lane (c = lane & 15, g = lane >> 4) of key stream ks reads K fragment (kb, kstep, p) at
+// ax_k_frag(ks, c, g, kstep) + kb * AX_K_KB + p * 16 and V^T fragment (db, p) at ax_v_frag(ks, c, g) + db * AX_V_DB + p * 16:
+// neither swizzle term, row & 7 nor (row >> 1) & 3, changes with kb or db (rows 16 kb + c, 16 db + c)
+constexpr int AX_K_KB = 16 * AX_K_ROW, AX_V_DB = 16 * AX_V_ROW;
+__host__ __device__ inline unsigned ax_k_frag(int ks, int c, int g, int kstep) {
+    return (unsigned)(ks * AX_TILE_BYTES + c * AX_K_ROW + (((4 * kstep + g) ^ (c & 7)) * 3) * 16);
+}
+__host__ __device__ inline unsigned ax_v_frag(int ks, int c, int g) {
+    return (unsigned)(ks * AX_TILE_BYTES + AX_K_BYTES + c * AX_V_ROW + ((g ^ ((c >> 1) & 3)) * 3) * 16);
+}
 }  // namespace
 
 struct AttnX3Args {
@@ -102,94 +176,58 @@ __global__ __launch_bounds__(512) void enc_attention_x3_kernel(AttnX3Args a) {
     const int T = a.T;
     const int head = blockIdx.x % a.n_head;          // head == XCD for 8 heads: a head's K / V stay in one L2
     const int q0 = (blockIdx.x / a.n_head) * AX_QT;
-    const int n_tiles = (T + AX_KT - 1) / AX_KT;
-    const int n_steps = (n_tiles + 1) / 2;            // pairs of key tiles: stream 0 takes tile 2 j, stream 1 tile 2 j + 1
-    const long row_qk = 3 * a.ldqk * 2, row_vt = 3 * a.vt_ld * 2;    // bytes
+    const AxGeom G = ax_geom(T, a.d, head, a.ldqk, a.vt_off, a.vt_ld);
+    const int n_tiles = G.n_tiles, n_steps = G.n_steps;
     const int qs = wave & 3, ks = wave >> 2;
     const int c = lane & 15, g = lane >> 4;
+    const char* const image = reinterpret_cast<const char*>(qk3);
 
     // Q fragments (B operand of S^T = K Q^T): query q0 + 16 qs + c, feature chunk 4 kstep + g, plane p - first in the queue
     bf16x8 qf[6];
-    {
-        const int q = min(q0 + 16 * qs + c, T - 1);
-        const char* qp = reinterpret_cast<const char*>(qk3) + (long)q * row_qk + (long)(head * 8) * 48;
 #pragma unroll
-        for (int kstep = 0; kstep < 2; ++kstep)
+    for (int kstep = 0; kstep < 2; ++kstep)
 #pragma unroll
-            for (int p = 0; p < 3; ++p)
-                qf[kstep * 3 + p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const x3_u32x4*>(qp + ((4 * kstep + g) * 3 + p) * 16));
-    }
-    // ---- DMA sources: piece j of a slot covers its bytes [1024 j, 1024 j + 1024): [stream 0: K | V^T][stream 1: K | V^T];
-    // the bank swizzle lives in the source address (K: chunk ^ (row & 7), V^T: chunk ^ ((row >> 1) & 3), planes in place) --
-    const char* src[AX_NPW];
-    long adv[AX_NPW];
-    int key_row[AX_NPW];      // K pieces: the key this lane fetches relative to the tile's first key (-1: V^T piece)
-    int stream_of[AX_NPW];
+        for (int p = 0; p < 3; ++p)
+            qf[kstep * 3 + p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const x3_u32x4*>(image + ax_q_src(G, q0, qs, c, g, kstep, p)));
+    // ---- DMA sources (ax_piece_src_at_step): each of the wave's six pieces keeps a per-lane pointer that a wave-uniform
+    // stride advances once per step, and the pointer of the last pair - the only one the clamps act on -, which also serves
+    // the two tail fetches.  Nothing is multiplied in the key loop. ---------------------------------------------------------
+    const char* cur[AX_NPW];
+    const char* last[AX_NPW];
+    long stride[AX_NPW];
 #pragma unroll
     for (int i = 0; i < AX_NPW; ++i) {
-        const int j = wave + 8 * i;
-        const int byte = 1024 * j + 16 * lane;
-        const int stream = byte / AX_TILE_BYTES, in_tile = byte - stream * AX_TILE_BYTES;
-        stream_of[i] = stream;
-        if (in_tile < AX_K_BYTES) {
-            const int row = in_tile / AX_K_ROW;
-            const int up = (in_tile - row * AX_K_ROW) >> 4;
-            const int unit = ((up / 3) ^ (row & 7)) * 3 + up % 3;
-            key_row[i] = row;
-            src[i] = reinterpret_cast<const char*>(qk3) + (long)(a.d / 8 + head * 8) * 48 + unit * 16;    // + key * row_qk
-            adv[i] = 0;
-        } else {
-            const int off = in_tile - AX_K_BYTES;
-            const int row = off / AX_V_ROW;
-            const int up = (off - row * AX_V_ROW) >> 4;
-            const int unit = ((up / 3) ^ ((row >> 1) & 3)) * 3 + up % 3;
-            key_row[i] = -1;
-            src[i] = reinterpret_cast<const char*>(qk3 + a.vt_off) + (long)(head * 64 + row) * row_vt + unit * 16 +
-                     (long)stream * (AX_KT / 8) * 48;
-            adv[i] = 2L * (AX_KT / 8) * 48;          // two tiles of 32 keys = 8 stored chunks further
-        }
+        cur[i] = image + ax_piece_src(G, wave, lane, i, 0);
+        last[i] = image + ax_piece_src(G, wave, lane, i, n_steps - 1);
+        stride[i] = ax_piece_stride(G, wave, i);
     }
+    unsigned dma_slot = 0;                              // byte offset of the slot the next issue fills: a counter, not step % 3
     auto issue_step = [&](int step) {
-        const int sc = min(step, n_steps - 1);         // the tail re-fetches the last pair into a free slot
-        const int slot = step % AX_NB;
-        ax_static_for<AX_NPW>([&](auto I) {
-            constexpr int i = decltype(I)::value;
-            const char* p;
-            if (key_row[i] >= 0) {
-                const int key = min((2 * sc + stream_of[i]) * AX_KT + key_row[i], T - 1);   // rows past T: clamped, masked below
-                p = src[i] + (long)key * row_qk;
-            } else {
-                // a second stream without a tile (odd tile count) re-reads its last real tile
-                p = src[i] + (long)min(sc, (n_tiles - 1 - stream_of[i]) / 2) * adv[i];
-            }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)p,
-                                             (__attribute__((address_space(3))) void*)(lds + slot * AX_SLOT_BYTES + (wave + 8 * i) * 1024),
-                                             16, 0, 0);
-        });
+        const unsigned dst = dma_slot;
+        dma_slot = dma_slot == (AX_NB - 1) * AX_SLOT_BYTES ? 0u : dma_slot + AX_SLOT_BYTES;
+        if (step < n_steps - 1) {                       // wave-uniform
+            ax_static_for<AX_NPW>([&](auto I) {
+                constexpr int i = decltype(I)::value;
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)cur[i],
+                                                 (__attribute__((address_space(3))) void*)(lds + dst + (wave + 8 * i) * 1024), 16, 0, 0);
+                cur[i] += stride[i];
+            });
+        } else {
+            ax_static_for<AX_NPW>([&](auto I) {
+                constexpr int i = decltype(I)::value;
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)last[i],
+                                                 (__attribute__((address_space(3))) void*)(lds + dst + (wave + 8 * i) * 1024), 16, 0, 0);
+            });
+        }
     };
     issue_step(0);
     issue_step(1);
 
-    // ---- fragment addresses of this wave's stream --------------------------------------------------------------------
+    // ---- fragment addresses of this wave's stream: two base registers for K (kstep 0 / 1) and one for V^T; kb, db and the
+    // plane are immediates of the reads --------------------------------------------------------------------------------
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
-    const unsigned tile_base = lds_base + (unsigned)ks * AX_TILE_BYTES;
-    unsigned k_addr[12], v_addr[12];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int kstep = 0; kstep < 2; ++kstep)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {       // key 16 kb + c, feature chunk 4 kstep + g
-                const int row = 16 * kb + c;
-                k_addr[kb * 6 + kstep * 3 + p] = tile_base + (unsigned)(row * AX_K_ROW) + (unsigned)((((4 * kstep + g) ^ (row & 7)) * 3 + p) * 16);
-            }
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {           // feature 16 db + c, stored key chunk g
-            const int row = 16 * db + c;
-            v_addr[db * 3 + p] = tile_base + AX_K_BYTES + (unsigned)(row * AX_V_ROW) + (unsigned)(((g ^ ((row >> 1) & 3)) * 3 + p) * 16);
-        }
+    const unsigned k_base0 = lds_base + ax_k_frag(ks, c, g, 0), k_base1 = lds_base + ax_k_frag(ks, c, g, 1);
+    const unsigned v_base = lds_base + ax_v_frag(ks, c, g);
     af32x4 o[4];
 #pragma unroll
     for (int db = 0; db < 4; ++db) o[db] = af32x4{0.f, 0.f, 0.f, 0.f};
@@ -200,10 +238,22 @@ __global__ __launch_bounds__(512) void enc_attention_x3_kernel(AttnX3Args a) {
     // MFMAs: 60.8 us instead of 48.9.  What the two waves of a SIMD share is issue bandwidth, not just the matrix pipe.)
     af32x4 vf[12];
     float s[8];
-    auto phase_s = [&](int tile, unsigned off) {          // fragments of `tile` -> registers, s = K Q^T
+    auto phase_s = [&](int tile, unsigned off, int next) {   // fragments of `tile` (slot at byte `off`) -> registers, pair `next` requested, s = K Q^T
         af32x4 kf[12];
-        ax_read12(kf, k_addr, off);
-        ax_read12(vf, v_addr, off);
+        const unsigned k0 = k_base0 + off, k1 = k_base1 + off, vb = v_base + off;
+        ax_static_for<12>([&](auto X) {
+            constexpr int t = decltype(X)::value;
+            constexpr int kb = t / 6, kstep = (t / 3) % 2, p = t % 3;
+            ax_read<kb * AX_K_KB + p * 16>(kf[t], kstep ? k1 : k0);
+        });
+        ax_static_for<12>([&](auto X) {
+            constexpr int t = decltype(X)::value;
+            constexpr int db = t / 3, p = t % 3;
+            ax_read<db * AX_V_DB + p * 16>(vf[t], vb);
+        });
+        // The DMA of pair `next` goes out here, behind the reads and in front of the wait for them: its issue cost hides in the
+        // LDS latency (measured against the top of the step, between S and P V, and the end of the step: DESIGN section 12)
+        issue_step(next);
         ax_wait12(kf);
         // key blocks 0 / 1 are two independent accumulator chains
         af32x4 s2[2] = {af32x4{0.f, 0.f, 0.f, 0.f}, af32x4{0.f, 0.f, 0.f, 0.f}};
@@ -256,15 +306,20 @@ __global__ __launch_bounds__(512) void enc_attention_x3_kernel(AttnX3Args a) {
     };
 
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // the Q fragments and this wave's pieces of pair 0
+    // the Q fragments are in their registers from here on: said to the compiler outside the loop, or it waits for them - and
+    // with them for every DMA piece in flight - in front of the first MFMA of every step
+    asm volatile("" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3]), "+v"(qf[4]), "+v"(qf[5]));
     __builtin_amdgcn_s_barrier();
+    unsigned off = 0;                          // byte offset of the slot of pair st
     for (int st = 0; st < n_steps; ++st) {
-        issue_step(st + AX_DT);
-        const unsigned off = (unsigned)(st % AX_NB) * (unsigned)AX_SLOT_BYTES;
         const int tile = 2 * st + ks;
         if (tile < n_tiles) {      // wave-uniform
-            phase_s(tile, off);
+            phase_s(tile, off, st + AX_DT);
             phase_pv();
+        } else {
+            issue_step(st + AX_DT);      // a second stream without a tile still feeds the ring
         }
+        off = off == (AX_NB - 1) * AX_SLOT_BYTES ? 0u : off + AX_SLOT_BYTES;
         asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");   // this wave's pieces of pair st + 1 have landed
         __builtin_amdgcn_s_barrier();          // pair st + 1 readable; everybody is done with pair st's LDS image
     }
@@ -369,6 +424,32 @@ void enc_attention_x3_check(long ldqk, long vt_ld, long ldo, int T, int d, int n
     if (d != n_head * 64 || ldqk % 8 != 0 || vt_ld % 32 != 0 || vt_ld < ((T + 31) / 32) * 32 || T < 64)
         throw std::invalid_argument("x3 attention: unsupported shape");
     if (x3_out && ldo % 8 != 0) throw std::invalid_argument("x3 attention: X3 result rows need ldo % 8 == 0");
+}
+
+long enc_attention_x3_addresses(int T, int d, int n_head, int head, int q_tile, long* src, int* dst, long cap) {
+    enc_attention_x3_check(2L * d, x3_attn_vt_ld(T), d, T, d, n_head, false);
+    if (head < 0 || head >= n_head || q_tile < 0 || q_tile >= (T + AX_QT - 1) / AX_QT)
+        throw std::invalid_argument("x3 attention addresses: no such workgroup");
+    const AxGeom G = ax_geom(T, d, head, 2L * d, x3_attn_vt_off(T, d), x3_attn_vt_ld(T));
+    long n = 0;
+    auto put = [&](long s, int l) {
+        if (n < cap) { src[n] = s; dst[n] = l; }
+        ++n;
+    };
+    for (int tid = 0; tid < 512; ++tid) {
+        const int lane = tid & 63, wave = tid >> 6;
+        for (int kstep = 0; kstep < 2; ++kstep)
+            for (int p = 0; p < 3; ++p) put(ax_q_src(G, q_tile * AX_QT, wave & 3, lane & 15, lane >> 4, kstep, p), -1);
+    }
+    int slot = 0;                                       // the kernel's counter: issue_step fills slot 0, 1, 2, 0, ...
+    for (int step = 0; step < G.n_steps + AX_DT; ++step) {
+        for (int wave = 0; wave < 8; ++wave)
+            for (int i = 0; i < AX_NPW; ++i)
+                for (int lane = 0; lane < 64; ++lane)
+                    put(ax_piece_src_at_step(G, wave, lane, i, step), slot * AX_SLOT_BYTES + ax_piece_lds(wave, lane, i));
+        slot = slot == AX_NB - 1 ? 0 : slot + 1;
+    }
+    return n;
 }
 
 void launch_encoder_attention_x3(const LaunchCtx& ctx, const unsigned short* qk3, long ldqk, long vt_off, long vt_ld, float* out,

@@ -371,6 +371,12 @@ void launch_encoder_attention_x3(const LaunchCtx& ctx, const unsigned short* qk3
                                  long ldo, int T, int d, int n_head, const PtrTable* z, int batch, bool x3_out = false);
 void enc_attention_x3_check(long ldqk, long vt_ld, long ldo, int T, int d, int n_head, bool x3_out);   // throws for what the launcher refuses
 void launch_x3_pack_qkv(const LaunchCtx& ctx, const float* qkv, unsigned short* out, int T, int d, long vt_off, long vt_ld);
+// Every 16-byte request workgroup (head, q_tile) of enc_attention_x3_kernel makes on the image of T rows of a d-wide model
+// (x3_attn_vt_off, x3_attn_vt_ld), from the functions the kernel itself calls; host only, no device.  src: byte offset from
+// the image start; dst: byte of the LDS ring it lands at, -1 for a load into registers.  Order: the Q fragments [thread 0 ..
+// 511][kstep][plane], then the DMA [ring step 0 .. n_steps + 1][wave][piece 0 .. 5][lane].  Fills at most cap entries;
+// returns how many there are.  Throws for what the launcher refuses.
+long enc_attention_x3_addresses(int T, int d, int n_head, int head, int q_tile, long* src, int* dst, long cap);
 
 // ---- head_survey.hip ---------------------------------------------------------------------------
 // Softmax peak and arg-max frame of every (layer, head, token row) over the first F keys: peak = 1 / sum_f exp(s_f - max s),

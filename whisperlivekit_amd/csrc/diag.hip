@@ -470,6 +470,22 @@ int wlk_diag_encoder_attention_x3_time(int t, int d, int n_head, int reps, float
     });
 }
 
+/* the address sequence of one workgroup of that kernel, from the kernel's own host / device functions (see include/wlk_hip.h);
+ * no launch, no device */
+int wlk_diag_attn_x3_addresses(int t, int d, int n_head, int head, int q_tile, int64_t* src_off, int32_t* lds_off, int64_t cap,
+                               int64_t* n_out, int64_t* image_bytes) {
+    try {
+        if (!n_out || cap < 0 || (cap > 0 && (!src_off || !lds_off))) throw std::invalid_argument("wlk_diag_attn_x3_addresses: null arguments");
+        static_assert(sizeof(long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "address buffers");
+        *n_out = enc_attention_x3_addresses(t, d, n_head, head, q_tile, reinterpret_cast<long*>(src_off), reinterpret_cast<int*>(lds_off), (long)cap);
+        if (image_bytes) *image_bytes = (int64_t)(x3_attn_image_elems(t, d) * sizeof(unsigned short));
+        return WLK_OK;
+    } catch (const std::exception& e) {
+        g_diag_error = e.what();
+        return WLK_ERR_ARG;
+    }
+}
+
 /* Token selection and AlignAtt read-out (select.hip) on host data through one chosen route: the launchers a decode step
  * uses, unchanged, on caller-chosen logits, adjustments and alignment window (see include/wlk_hip.h) */
 int wlk_diag_select(const wlk_diag_select_args* q) {
